@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: full-graph HAN train epochs/s + node-attention (K2) bandwidth.
 
-    python bench.py --gpus N --steps K --warmup W [--workload syn-1m]
+    python bench.py --gpus N --steps K --warmup W [--workload syn-1m] [--full] [--dump-outputs DIR]
 
 One "step" is one reference epoch (ex_acm3025.py:171-218): one full-graph
 fwd+bwd+Adam step with dropout 0.6/0.6 plus one eval forward.  The workload is
 BASELINE.json's configs[3] (SYN-1M: 1M nodes, 4 meta-paths, deg 50, 256-d feats,
 8 heads x 8), synthetic data, random-init weights, node-partitioned over N GPUs
 (strong scaling: the graph is fixed, each rank owns N/G rows).
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given (dump_outputs) and prints the line.  The legs that take runs of
+their own -- live PMC traffic, the HBM-regime re-timing, the power-law variant and the
+CPU baseline -- run only with --full.
 
 Rank 0 prints ONE JSON line.  `roofline` prices the K2 (node-attention) kernel with the
 largest total time in the timed region from the bytes it requests per launch (`moved`:
@@ -17,7 +22,7 @@ measured with HIP events on the launch stream inside the timed region; `roofline
 has all three K2 kernels.  At SYN-1M the 256 MB gather table sits in the 256 MiB Infinity
 Cache, so those rates are cache-path rates; `roofline_hbm_regime` re-times the same three
 kernels in the same run on one meta-path of N = 10M rows (2.56 GB table): THAT is the HBM
-fraction.  `cpu_baseline` is the torch-CPU port of the reference algorithm
+fraction (--full).  `cpu_baseline` (--full) is the torch-CPU port of the reference algorithm
 (oracle/han_oracle_torch.py, CSR form) timed on this host on a bounded sample, with all
 usable cores and with one thread on the same sample (`cores_effective` = the measured ratio).
 """
@@ -505,6 +510,28 @@ def cpu_baseline(workload_name, n_full, sample_n):
     return out
 
 
+# --------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, last, model):
+    """What the last timed epoch computed, as float32 DIR/<name>.npy: the four device scalars HANTrainer.epoch()
+    returns (this rank's share of train loss / acc and val loss / acc) and the state it left in the model --
+    `params` (model.flat after the Adam step) and `grads` (model.flat_grad, the gradient that step applied), both
+    flat in model.param_shapes() order.  Returns {name: shape}."""
+    import numpy as np
+    arrays = dict(zip(("train_loss", "train_acc", "val_loss", "val_acc"), last))
+    arrays.update(params=model.flat, grads=model.flat_grad)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {k: a.shape for k, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -513,23 +540,30 @@ def main():
     ap.add_argument("--replicate", default="auto", choices=["auto", "all", "eval", "none"],
                     help="multi-GPU: which forward passes project the whole H table on every rank instead of "
                          "exchanging it (auto: both up to 4 ranks, the eval forward beyond)")
-    ap.add_argument("--traffic", choices=("live", "static", "off"), default="live",
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: live PMC traffic, the HBM-regime re-timing "
+                         "(--hbm-regime-nodes), the power-law variant (--skew-steps) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(float32, rank 0; see dump_outputs)")
+    ap.add_argument("--traffic", choices=("live", "static", "off"), default=None,
                     help="roofline.traffic: live = PMC passes (rocprofv3 child runs of one epoch) in this run, "
                          "N = 1 on the syn-1m family; static = the committed profiles/k2_traffic.json when it "
-                         "matches the kernel sources; off = null")
+                         "matches the kernel sources; off = null (default: live with --full, static otherwise)")
     ap.add_argument("--workload", default="syn-1m")
     ap.add_argument("--nodes", type=int, default=0, help="override N (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--graph", action="store_true",
                     help="capture the epoch into a hipGraph and replay it (single GPU; small graphs)")
     ap.add_argument("--cpu-sample", type=int, default=50000,
-                    help="nodes of the CPU-baseline sample (timed with all usable cores AND with one thread)")
+                    help="nodes of the CPU-baseline sample (timed with all usable cores AND with one thread; --full)")
     ap.add_argument("--hbm-regime-nodes", type=int, default=10_000_000,
                     help="rows of the extra single-meta-path table on which the K2 kernels are re-timed in the "
-                         "HBM-served regime after the timed region (0 = skip; single GPU only)")
+                         "HBM-served regime after the timed region (0 = skip; single GPU only; --full)")
     ap.add_argument("--skew-steps", type=int, default=5,
                     help="epochs timed on the power-law variant of the headline workload (syn-1m-skew, same N / E / F / P) "
-                         "in the same process after the timed region; reported as `skew` (0 = skip; N = 1, syn-1m only)")
+                         "in the same process after the timed region; reported as `skew` (0 = skip; N = 1, syn-1m only; "
+                         "--full)")
     ap.add_argument("--masked-backward", action="store_true",
                     help="ALSO time the opt-in masked backward (HANTrainer.set_masked_backward: destinations outside the "
                          "train mask are skipped in the transposed-graph pass and, under a partition, only the live rows "
@@ -553,6 +587,10 @@ def main():
                     help="storage of X and of the H/g gather tables (bf16 = the 10M-node config's "
                          "'bf16 feats'); accumulation is fp32 either way")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.traffic is None:
+        args.traffic = "live" if args.full else "static"
     if os.environ.get("HAN_DEBUG_HANG"):      # dump every thread's Python stack periodically (rehearsal debugging)
         import faulthandler
         faulthandler.dump_traceback_later(int(os.environ["HAN_DEBUG_HANG"]), repeat=True)
@@ -692,6 +730,8 @@ def main():
         print("[diag] allocator in the timed region:", {k: ms1.get(k, 0) - ms0.get(k, 0) for k in keys},
               "reserved GB %.1f allocated peak GB %.1f" % (ms1["reserved_bytes.all.current"] / 1e9,
                                                             ms1["allocated_bytes.all.peak"] / 1e9), file=sys.stderr)
+    if args.dump_outputs and rank == 0:       # before anything below runs another epoch
+        dump_outputs(args.dump_outputs, last, model)
     timing, ops.K2_TIMING = ops.K2_TIMING or [], None
     # the training step runs dW of meta-path p on a second stream beside the backward gather of meta-path p + 1
     # (HANTrainer(side_stream=...)): the gather's launch time in the timed region includes that company.  Two more
@@ -782,7 +822,7 @@ def main():
         r["traffic_source"] = traffic_src
     hbm = None
     skew = None
-    if rank == 0 and world == 1 and args.hbm_regime_nodes > 0 and not use_graph and table_mb < 600 \
+    if args.full and rank == 0 and world == 1 and args.hbm_regime_nodes > 0 and not use_graph and table_mb < 600 \
             and args.workload.startswith("syn-1m"):      # the headline family; other workloads are not priced against HBM
         del trainer, model
         torch.cuda.empty_cache()
@@ -790,7 +830,7 @@ def main():
         for tag, r in roofs.items():                     # the HBM fraction of the same kernel, same run
             if "hbm_frac" in r and tag in hbm:
                 r["hbm_frac"] = hbm[tag]["frac"]
-    if rank == 0 and world == 1 and args.skew_steps > 0 and not use_graph and args.workload == "syn-1m" \
+    if args.full and rank == 0 and world == 1 and args.skew_steps > 0 and not use_graph and args.workload == "syn-1m" \
             and not args.nodes:
         skew = skew_variant(dev, args, tdt, esz)
 
@@ -864,7 +904,7 @@ def main():
             # the >= 50 % HBM target of BASELINE.json is read off THIS object: same kernels, same run,
             # a table 10x larger than the Infinity Cache
             out["roofline_hbm_regime"] = hbm
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(args.workload, n, min(args.cpu_sample, n))
             out["cpu_baseline"] = cb
             out["vs_cpu_baseline"] = round(out["value"] / cb["value"], 1)

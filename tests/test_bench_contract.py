@@ -219,3 +219,27 @@ def test_round4_lines_meet_what_they_claim():
     for name, dd in lines.items():
         assert CONTRACT_KEYS <= set(dd) | {"roofline"}, name
         assert dd["unit"] == "epochs/s" and dd["data"] == "synthetic" and "workload" in dd["config"]
+
+
+def test_dump_outputs_writes_the_last_step_as_float32(tmp_path):
+    """--dump-outputs: the four metric scalars epoch() returns and the model's flat parameters / gradients, as float32
+    DIR/<name>.npy, within the 64 MB limit (an output above it is refused, not truncated)."""
+    import types
+
+    import numpy as np
+    import torch
+    last = tuple(torch.tensor(v, dtype=torch.float32) for v in (1.25, 0.5, 1.5, 0.25))
+    model = types.SimpleNamespace(flat=torch.arange(10, dtype=torch.float32), flat_grad=torch.ones(10))
+    shapes = bench.dump_outputs(str(tmp_path / "out"), last, model)
+    assert shapes == {"train_loss": (), "train_acc": (), "val_loss": (), "val_acc": (), "params": (10,), "grads": (10,)}
+    z = {k: np.load(tmp_path / "out" / f"{k}.npy") for k in shapes}
+    assert all(a.dtype == np.float32 for a in z.values())
+    assert float(z["val_loss"]) == 1.5 and np.array_equal(z["params"], np.arange(10, dtype=np.float32))
+    big = types.SimpleNamespace(flat=torch.zeros(bench.DUMP_LIMIT_BYTES // 4), flat_grad=torch.zeros(1))
+    try:
+        bench.dump_outputs(str(tmp_path / "big"), last, big)
+    except SystemExit as e:
+        assert "limit" in str(e)
+    else:
+        raise AssertionError("an output above the limit was written")
+    assert not (tmp_path / "big").exists()

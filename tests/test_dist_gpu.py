@@ -169,13 +169,13 @@ def test_bench_gpus_2_starts_two_ranks_by_itself(dev):
 
 
 def test_bench_default_path_prints_one_complete_line(dev):
-    """The line the driver records: `python bench.py` on one GPU, every leg of the default path switched on (live
-    K2 rooflines, the HBM-regime probe that releases the trainer first, the CPU baseline leg; the skew variant only
-    runs at the full size) at a small size -- one JSON line with the contract's keys, the roofline and cpu_baseline objects."""
+    """`python bench.py --full` on one GPU, every leg switched on (live K2 rooflines, the HBM-regime probe that releases
+    the trainer first, the CPU baseline leg; the skew variant only runs at the full size) at a small size -- one JSON
+    line with the contract's keys, the roofline and cpu_baseline objects."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nodes", "60000", "--steps", "2", "--warmup", "1",
-                        "--hbm-regime-nodes", "100000", "--cpu-sample", "2000", "--traffic", "static"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--nodes", "60000", "--steps", "2",
+                        "--warmup", "1", "--hbm-regime-nodes", "100000", "--cpu-sample", "2000", "--traffic", "static"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -190,3 +190,31 @@ def test_bench_default_path_prints_one_complete_line(dev):
     assert d["roofline"]["peak"] == 8000.0 and d["roofline"]["frac"] > 0
     assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["cores"] >= 1
     assert "roofline_hbm_regime" in d
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(dev, tmp_path):
+    """`python bench.py` without --full: the headline line only (no CPU baseline, HBM-regime probe or power-law
+    variant), exactly --steps timed epochs, and --dump-outputs writes the last timed epoch's outputs -- the same
+    numbers from two runs with the same arguments, and the same losses as the line's `final`."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nodes", "20000", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(out)],
+                           env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-3
+        assert not {"cpu_baseline", "roofline_hbm_regime", "skew"} & set(d)
+        z = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+        assert set(z) == {"train_loss", "train_acc", "val_loss", "val_acc", "params", "grads"}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in z.values())
+        for k in ("train_loss", "train_acc", "val_loss", "val_acc"):
+            assert abs(float(z[k]) - d["final"][k]) < 1e-5, k
+        dumps.append(z)
+    for k, a in dumps[0].items():
+        np.testing.assert_allclose(dumps[1][k], a, rtol=1e-5, atol=1e-6, err_msg=k)
