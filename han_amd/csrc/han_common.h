@@ -245,3 +245,69 @@ static inline int han_grid_for(int64_t items, int per_block, int cap) {
     if (b > cap) b = cap;
     return (int)b;
 }
+
+// ---------------------------------------------------------------------------
+// Host-side launch helpers
+// ---------------------------------------------------------------------------
+// head widths F' = HAN_D / K of the K1 / K2 kernels
+static inline bool han_fp_supported(int K, int FP) {
+    return K * FP == HAN_D && (FP == 4 || FP == 8 || FP == 16 || FP == 32 || FP == 64);
+}
+
+// runs the statement(s) with `constexpr int FPC` = FPV (4, 8, 16, 32; anything else: 64)
+#define HAN_DISPATCH_FP(FPV, ...)                                \
+    switch (FPV) {                                               \
+        case 4: { constexpr int FPC = 4; __VA_ARGS__; } break;   \
+        case 8: { constexpr int FPC = 8; __VA_ARGS__; } break;   \
+        case 16: { constexpr int FPC = 16; __VA_ARGS__; } break; \
+        case 32: { constexpr int FPC = 32; __VA_ARGS__; } break; \
+        default: { constexpr int FPC = 64; __VA_ARGS__; } break; \
+    }
+
+// HAN_DISPATCH_FP plus `constexpr bool BF` = BFV (a bf16 table)
+#define HAN_DISPATCH_FP_BF(FPV, BFV, ...)                                             \
+    do {                                                                              \
+        if (BFV) { constexpr bool BF = true; HAN_DISPATCH_FP(FPV, __VA_ARGS__) }      \
+        else { constexpr bool BF = false; HAN_DISPATCH_FP(FPV, __VA_ARGS__) }         \
+    } while (0)
+
+// meta-path counts of the K3 kernels that keep a node's P rows inside 16-lane groups
+static inline bool han_pow2_p(int P) { return P == 1 || P == 2 || P == 4 || P == 8 || P == 16; }
+
+// runs the statement(s) with `constexpr int PC` = PV (1, 2, 4, 8; anything else: 16)
+#define HAN_DISPATCH_P(PV, ...)                                 \
+    switch (PV) {                                               \
+        case 1: { constexpr int PC = 1; __VA_ARGS__; } break;   \
+        case 2: { constexpr int PC = 2; __VA_ARGS__; } break;   \
+        case 4: { constexpr int PC = 4; __VA_ARGS__; } break;   \
+        case 8: { constexpr int PC = 8; __VA_ARGS__; } break;   \
+        default: { constexpr int PC = 16; __VA_ARGS__; } break; \
+    }
+
+// a launch with `lds` bytes of dynamic LDS: beyond 64 KiB the kernel is first allowed that size; returns the HIP error
+template <typename... KArgs, typename... Args>
+static inline hipError_t han_launch_lds(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                                        Args... args) {
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    kernel<<<grid, block, lds, st>>>(args...);
+    return hipGetLastError();
+}
+
+// keep threshold of a dropout probability (HAN_KEEP_ALL: no draw drops anything)
+static inline uint32_t han_drop_threshold(float drop) {
+    return drop > 0.f ? han_keep_threshold(1.f - drop) : HAN_KEEP_ALL;
+}
+
+// the key of one dropout site of an argument struct: seed halves, device seed word, keep threshold and inverse keep
+template <typename Args>
+static inline void han_set_dropout(Args &a, uint64_t seed, const uint64_t *seed_dev, float drop, uint32_t &thr,
+                                   float &inv_keep) {
+    a.seed_lo = (uint32_t)seed;
+    a.seed_hi = (uint32_t)(seed >> 32);
+    a.seed_dev = seed_dev;
+    thr = han_drop_threshold(drop);
+    inv_keep = 1.f / (1.f - drop);
+}

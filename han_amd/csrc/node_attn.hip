@@ -1692,10 +1692,6 @@ __global__ __launch_bounds__(256) void csr_to_bitmask_kernel(const int64_t *rowp
 
 constexpr int kReduceBlocks = 1024;
 
-bool fp_supported(int K, int FP) {
-    return K * FP == HAN_D && (FP == 4 || FP == 8 || FP == 16 || FP == 32 || FP == 64);
-}
-
 // Launch geometry: 256-thread blocks, 4 waves each; cap the grid and grid-stride.
 int attn_grid(int64_t units) { return han_grid_for(units, 4, 256 * 8 * 4); }
 
@@ -1715,18 +1711,6 @@ bool split_ok(const han_row_split_t *sp, int64_t n_rows) {
 }
 
 }  // namespace
-
-#define HAN_DISPATCH_FP(FPV, ...)                                \
-    switch (FPV) {                                               \
-        case 4: { constexpr int FPC = 4; __VA_ARGS__; } break;   \
-        case 8: { constexpr int FPC = 8; __VA_ARGS__; } break;   \
-        case 16: { constexpr int FPC = 16; __VA_ARGS__; } break; \
-        case 32: { constexpr int FPC = 32; __VA_ARGS__; } break; \
-        default: { constexpr int FPC = 64; __VA_ARGS__; } break; \
-    }
-
-// bf16 tables: every head shape (the configs[4] shape 8 x 8 is the tuned one)
-#define HAN_BF16_OK(FPV) (true)
 
 // One launch over the rows `a.rows[0 .. a.n_work)` (or 0 .. n_work-1): a 16-lane group per row (short) or a wave per row.
 template <int FPC, bool BF, bool VAL>
@@ -1762,8 +1746,9 @@ static void launch_fwd_rows(const FwdArgs &a, bool train, bool short_rows, hipSt
             if constexpr (DD_OK) node_attn_fwd_kernel<FPC, true, 1, 4, BF, VAL, true, true, true><<<grid, 256, 0, st>>>(a);
         } else if (train && fast) node_attn_fwd_kernel<FPC, true, 1, 4, BF, VAL, true, true><<<grid, 256, 0, st>>>(a);
         else if (train) node_attn_fwd_kernel<FPC, true, 1, 4, BF, VAL, false, true><<<grid, 256, 0, st>>>(a);
-        else if (BF && a.deep) node_attn_fwd_kernel<FPC, false, 1, 8, BF, VAL, false, BF><<<grid, 256, 0, st>>>(a);      // HAN_FLAG_K2_DEEP
-        else node_attn_fwd_kernel<FPC, false, 1, UE, BF, VAL, false, BF><<<grid, 256, 0, st>>>(a);
+        else if (BF && a.deep) {      // HAN_FLAG_K2_DEEP: bf16 tables only
+            if constexpr (BF) node_attn_fwd_kernel<FPC, false, 1, 8, BF, VAL, false, BF><<<grid, 256, 0, st>>>(a);
+        } else node_attn_fwd_kernel<FPC, false, 1, UE, BF, VAL, false, BF><<<grid, 256, 0, st>>>(a);
     }
 }
 
@@ -1878,8 +1863,23 @@ static void launch_bwd_cols(const BwdColsArgs &a, bool low, bool has_split, cons
     else launch_bwd_cols_v<FPC, BF, false>(a, low, has_split, bins, st);
 }
 
-static bool dtype_ok(int dt, int FP) {
-    return dt == HAN_DTYPE_F32 || (dt == HAN_DTYPE_BF16 && HAN_BF16_OK(FP));
+// bf16 tables: every head shape (the configs[4] shape 8 x 8 is the tuned one)
+static bool dtype_ok(int dt) { return dt == HAN_DTYPE_F32 || dt == HAN_DTYPE_BF16; }
+
+// the long-row fields of a launch (han_row_split_t); true when the launch has long rows
+template <typename Args>
+static bool fill_split(Args &a, const han_row_split_t *sp) {
+    const bool has_split = sp && sp->n_long > 0;
+    a.split_deg = has_split ? sp->split_deg : INT64_MAX;
+    a.n_long = has_split ? sp->n_long : 0;
+    a.n_chunks = has_split ? sp->n_chunks : 0;
+    a.long_rows = has_split ? sp->long_rows : nullptr;
+    a.long_ptr = has_split ? sp->long_ptr : nullptr;
+    a.chunk_long = has_split ? sp->chunk_long : nullptr;
+    a.chunk_start = has_split ? sp->chunk_start : nullptr;
+    a.chunk_end = has_split ? sp->chunk_end : nullptr;
+    a.split_ws = has_split ? (float *)sp->workspace : nullptr;
+    return has_split;
 }
 
 extern "C" int han_node_attn_fwd(const int64_t *rowptr, const int32_t *colidx, const float *edge_val,
@@ -1896,32 +1896,20 @@ extern "C" int han_node_attn_fwd(const int64_t *rowptr, const int32_t *colidx, c
     if (!rowptr || (!colidx && E > 0) || !H || !f1 || !a2 || !b2 || !c || !out || N < 0 || E < 0 || out_stride < HAN_D)
         return HAN_E_BADARG;
     if (!split_ok(split, N)) return HAN_E_BADARG;
-    if (!fp_supported(K, FP) || !dtype_ok(table_dtype, FP)) return HAN_E_UNSUPPORTED;
+    if (!han_fp_supported(K, FP) || !dtype_ok(table_dtype)) return HAN_E_UNSUPPORTED;
     if ((flags & HAN_FLAG_LEAN) && !f2_src) return HAN_E_BADARG;      // the lean kernels read the scores from the table
     const bool train = pre || lse || aggp || tsum;
     if (train && !(lse && aggp && tsum)) return HAN_E_BADARG;      // pre is optional: the backward works from `out`
     if (coef_drop < 0.f || coef_drop >= 1.f || fts_drop < 0.f || fts_drop >= 1.f) return HAN_E_BADARG;
     if ((coef_drop > 0.f || fts_drop > 0.f) && !train) return HAN_E_BADARG;
-    if (N == 0) return 0;
     FwdArgs a;
     a.rowptr = rowptr; a.colidx = colidx; a.edge_val = edge_val; a.H = H; a.gid = table_gid; a.lsb_mask = fts_drop > 0.f; a.f1 = f1; a.f2g = f2_src; a.a2 = a2; a.b2 = b2; a.c = c; a.res = res;
     a.out = out; a.out_stride = out_stride; a.pre = pre; a.lse = lse; a.aggp = aggp; a.tsum = tsum;
     a.N = N; a.rows = nullptr; a.n_work = N; a.only_if = nullptr; a.deep = (flags & HAN_FLAG_K2_DEEP) ? 1 : 0; a.shared_hash = (flags & HAN_FLAG_K2_SHARED_HASH) ? 1 : 0; a.slope = slope;
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.seed_dev = seed_dev;
-    a.thr_coef = coef_drop > 0.f ? han_keep_threshold(1.f - coef_drop) : HAN_KEEP_ALL;
-    a.inv_keep_coef = 1.f / (1.f - coef_drop);
+    han_set_dropout(a, seed, seed_dev, coef_drop, a.thr_coef, a.inv_keep_coef);
     a.inv_keep_fts = 1.f / (1.f - fts_drop);
     a.row_offset = row_offset; a.activation = activation; a.xcd_order = (flags & HAN_FLAG_XCD_ORDER) ? 1 : 0;
-    const bool has_split = split && split->n_long > 0;
-    a.split_deg = has_split ? split->split_deg : INT64_MAX;
-    a.n_long = has_split ? split->n_long : 0;
-    a.n_chunks = has_split ? split->n_chunks : 0;
-    a.long_rows = has_split ? split->long_rows : nullptr;
-    a.long_ptr = has_split ? split->long_ptr : nullptr;
-    a.chunk_long = has_split ? split->chunk_long : nullptr;
-    a.chunk_start = has_split ? split->chunk_start : nullptr;
-    a.chunk_end = has_split ? split->chunk_end : nullptr;
-    a.split_ws = has_split ? (float *)split->workspace : nullptr;
+    const bool has_split = fill_split(a, split);
     hipStream_t st = (hipStream_t)stream;
     const bool low = (double)E < kLowDegree * (double)N;
     if (dense && dense->bits) {
@@ -1952,11 +1940,7 @@ extern "C" int han_node_attn_fwd(const int64_t *rowptr, const int32_t *colidx, c
         return 0;
     }
     const RowBins bins = bins_of(split);
-    if (table_dtype == HAN_DTYPE_BF16) {
-        HAN_DISPATCH_FP(FP, { launch_fwd<FPC, true>(a, train, low, has_split, bins, st); })
-    } else {
-        HAN_DISPATCH_FP(FP, { launch_fwd<FPC, false>(a, train, low, has_split, bins, st); })
-    }
+    HAN_DISPATCH_FP_BF(FP, table_dtype == HAN_DTYPE_BF16, launch_fwd<FPC, BF>(a, train, low, has_split, bins, st));
     HAN_CHECK_LAUNCH();
     return 0;
 }
@@ -1966,7 +1950,7 @@ extern "C" size_t han_row_split_workspace(int64_t n_chunks) {
 }
 
 extern "C" size_t han_gs_row_bytes(int K, int FP, int table_dtype) {
-    if (!fp_supported(K, FP) || !dtype_ok(table_dtype, FP)) return 0;
+    if (!han_fp_supported(K, FP) || !dtype_ok(table_dtype)) return 0;
     const size_t g_bytes = (size_t)HAN_D * (table_dtype == HAN_DTYPE_BF16 ? 2 : 4);
     return ((g_bytes + 16 * (size_t)K + 127) / 128) * 128;
 }
@@ -1985,7 +1969,7 @@ extern "C" int han_node_attn_bwd_rows(const float *dOut, int64_t dout_stride, co
     if (!dOut || !out || !aggp || !tsum || !f1 || !lse || !c || !gs || !df1 || !dc || !workspace ||
         N < 0 || dout_stride < HAN_D || out_stride < HAN_D)
         return HAN_E_BADARG;
-    if (!fp_supported(K, FP) || !dtype_ok(table_dtype, FP)) return HAN_E_UNSUPPORTED;
+    if (!han_fp_supported(K, FP) || !dtype_ok(table_dtype)) return HAN_E_UNSUPPORTED;
     if (workspace_bytes < han_node_attn_bwd_workspace(N, K, FP)) return HAN_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     BwdRowsArgs a;
@@ -1993,11 +1977,7 @@ extern "C" int han_node_attn_bwd_rows(const float *dOut, int64_t dout_stride, co
     a.f1 = f1; a.lse = lse; a.c = c; a.res = res; a.gs = gs; a.df1 = df1;
     a.slab = (float *)workspace; a.N = N; a.activation = activation;
     const int grid = han_grid_for(N, 16, kReduceBlocks);
-    if (table_dtype == HAN_DTYPE_BF16) {
-        HAN_DISPATCH_FP(FP, { node_attn_bwd_rows_kernel<FPC, true><<<grid, 256, 0, st>>>(a); })
-    } else {
-        HAN_DISPATCH_FP(FP, { node_attn_bwd_rows_kernel<FPC, false><<<grid, 256, 0, st>>>(a); })
-    }
+    HAN_DISPATCH_FP_BF(FP, table_dtype == HAN_DTYPE_BF16, node_attn_bwd_rows_kernel<FPC, BF><<<grid, 256, 0, st>>>(a));
     HAN_CHECK_LAUNCH();
     hipError_t e = han_reduce_slabs((const float *)workspace, grid, 64, 64, han_reduce_to(dc, 64), st);
     if (e != hipSuccess) return (int)e;
@@ -2015,30 +1995,19 @@ extern "C" int han_node_attn_bwd_cols(const int64_t *colptr, const int32_t *rowi
     if (!colptr || (!rowidx && E > 0) || !gs || !H || !f2 || !df1 || !a1 || !a2 || !dH || !df2 || NS < 0 || E < 0)
         return HAN_E_BADARG;
     if (!split_ok(split, NS)) return HAN_E_BADARG;
-    if (!fp_supported(K, FP) || !dtype_ok(table_dtype, FP)) return HAN_E_UNSUPPORTED;
+    if (!han_fp_supported(K, FP) || !dtype_ok(table_dtype)) return HAN_E_UNSUPPORTED;
     if (coef_drop < 0.f || coef_drop >= 1.f || fts_drop < 0.f || fts_drop >= 1.f) return HAN_E_BADARG;
     if (NS == 0) return 0;
     BwdColsArgs a;
     a.colptr = colptr; a.rowidx = rowidx; a.edge_val = edge_val; a.gs = gs; a.gid = table_gid; a.H = H; a.lsb_mask = fts_drop > 0.f; a.f2 = f2;
     a.df1 = df1; a.a1 = a1; a.a2 = a2; a.dH = dH; a.df2 = df2; a.NS = NS; a.rows = nullptr; a.n_work = NS; a.slope = slope;
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.seed_dev = seed_dev;
-    a.thr_coef = coef_drop > 0.f ? han_keep_threshold(1.f - coef_drop) : HAN_KEEP_ALL;
-    a.inv_keep_coef = 1.f / (1.f - coef_drop);
+    han_set_dropout(a, seed, seed_dev, coef_drop, a.thr_coef, a.inv_keep_coef);
     a.inv_keep_fts = 1.f / (1.f - fts_drop);
     a.src_offset = src_offset; a.dst_offset = dst_offset; a.xcd_order = (flags & HAN_FLAG_XCD_ORDER) ? 1 : 0;
     a.masked = (flags & HAN_FLAG_MASKED_EDGES) ? 1 : 0;
     a.lean = (flags & HAN_FLAG_LEAN) ? 1 : 0;
     a.only_if = nullptr;
-    const bool has_split = split && split->n_long > 0;
-    a.split_deg = has_split ? split->split_deg : INT64_MAX;
-    a.n_long = has_split ? split->n_long : 0;
-    a.n_chunks = has_split ? split->n_chunks : 0;
-    a.long_rows = has_split ? split->long_rows : nullptr;
-    a.long_ptr = has_split ? split->long_ptr : nullptr;
-    a.chunk_long = has_split ? split->chunk_long : nullptr;
-    a.chunk_start = has_split ? split->chunk_start : nullptr;
-    a.chunk_end = has_split ? split->chunk_end : nullptr;
-    a.split_ws = has_split ? (float *)split->workspace : nullptr;
+    const bool has_split = fill_split(a, split);
     hipStream_t st = (hipStream_t)stream;
     const bool low = (double)E < kLowDegree * (double)NS;
     if (dense && dense->bits) {
@@ -2056,11 +2025,7 @@ extern "C" int han_node_attn_bwd_cols(const int64_t *colptr, const int32_t *rowi
         a.only_if = reinterpret_cast<const int *>(d.hdr) + 16;
     }
     const RowBins bins = bins_of(split);
-    if (table_dtype == HAN_DTYPE_BF16) {
-        HAN_DISPATCH_FP(FP, { launch_bwd_cols<FPC, true>(a, low, has_split, bins, st); })
-    } else {
-        HAN_DISPATCH_FP(FP, { launch_bwd_cols<FPC, false>(a, low, has_split, bins, st); })
-    }
+    HAN_DISPATCH_FP_BF(FP, table_dtype == HAN_DTYPE_BF16, launch_bwd_cols<FPC, BF>(a, low, has_split, bins, st));
     HAN_CHECK_LAUNCH();
     return 0;
 }
@@ -2074,19 +2039,12 @@ extern "C" int han_score_param_bwd(const void *H, int table_dtype, const float *
                                    float *da1, float *da2, float *db1, float *db2, void *workspace,
                                    size_t workspace_bytes, int64_t N, int K, int FP, void *stream) {
     if (!H || !df1 || !df2 || !da1 || !da2 || !db1 || !db2 || !workspace || N < 0) return HAN_E_BADARG;
-    if (!fp_supported(K, FP) || !dtype_ok(table_dtype, FP)) return HAN_E_UNSUPPORTED;
+    if (!han_fp_supported(K, FP) || !dtype_ok(table_dtype)) return HAN_E_UNSUPPORTED;
     if (workspace_bytes < han_score_param_bwd_workspace(N, K, FP)) return HAN_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int grid = han_grid_for(N, 16, kReduceBlocks);
-    if (table_dtype == HAN_DTYPE_BF16) {
-        HAN_DISPATCH_FP(FP, {
-            score_param_bwd_kernel<FPC, true><<<grid, 256, 0, st>>>(H, df1, df2, (float *)workspace, N);
-        })
-    } else {
-        HAN_DISPATCH_FP(FP, {
-            score_param_bwd_kernel<FPC, false><<<grid, 256, 0, st>>>(H, df1, df2, (float *)workspace, N);
-        })
-    }
+    HAN_DISPATCH_FP_BF(FP, table_dtype == HAN_DTYPE_BF16,
+                       score_param_bwd_kernel<FPC, BF><<<grid, 256, 0, st>>>(H, df1, df2, (float *)workspace, N));
     HAN_CHECK_LAUNCH();
     HanReduceOut o = han_reduce_to(da1, 128 + 2 * K);
     o.ptr[1] = da2; o.ptr[2] = db1; o.ptr[3] = db2;
@@ -2103,15 +2061,13 @@ extern "C" int han_node_attn_coefs(const int64_t *rowptr, const int32_t *colidx,
                                    float coef_drop, uint64_t seed, const uint64_t *seed_dev, int64_t row_offset,
                                    void *stream) {
     if (!rowptr || (!colidx && E > 0) || !f1 || !f2 || (!coef && E > 0) || N < 0 || E < 0) return HAN_E_BADARG;
-    if (!fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
+    if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
     if (coef_drop < 0.f || coef_drop >= 1.f) return HAN_E_BADARG;
     if (N == 0 || E == 0) return 0;
     CoefArgs a;
     a.rowptr = rowptr; a.colidx = colidx; a.edge_val = edge_val; a.gid = table_gid; a.f1 = f1; a.f2 = f2;
     a.coef = coef; a.N = N; a.slope = slope; a.mean_heads = mean_heads;
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.seed_dev = seed_dev;
-    a.thr_coef = coef_drop > 0.f ? han_keep_threshold(1.f - coef_drop) : HAN_KEEP_ALL;
-    a.inv_keep_coef = 1.f / (1.f - coef_drop);
+    han_set_dropout(a, seed, seed_dev, coef_drop, a.thr_coef, a.inv_keep_coef);
     a.row_offset = row_offset;
     const int grid = attn_grid(N);
     hipStream_t st = (hipStream_t)stream;

@@ -157,11 +157,11 @@ __device__ __forceinline__ float4_t load_x4_tail(const void *X, int bf, int64_t 
 template <int FP>
 struct HeadsPerTile { static constexpr int value = FP >= 16 ? 1 : 16 / FP; };
 
-// MT = 16-row MFMA tiles per wave (block = 64*MT rows); VEC = 16-byte X loads
-// (needs F % 4 == 0, ldx % 4 == 0 and a 16-byte aligned X).  With dropout every
-// head a tile covers gets its own accumulator: the A fragment is masked per head
-// and the columns of the other heads are simply not read back.
-template <int FP, bool DROP, int MT, bool VEC>
+// MT = 16-row MFMA tiles per wave (block = 64*MT rows); X is loaded in quads of 4
+// elements (load_x4_tail).  With dropout every head a tile covers gets its own
+// accumulator: the A fragment is masked per head and the columns of the other
+// heads are simply not read back.
+template <int FP, bool DROP, int MT>
 __global__ __launch_bounds__(256) void project_fwd_kernel(const ProjFwdArgs a_in) {
     ProjFwdArgs a = a_in;
     han_resolve_seed(a.seed_lo, a.seed_hi, a.seed_dev);
@@ -190,25 +190,15 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(const ProjFwdArgs a_in
     float xr[XL];
     float4_t wr4[2];
     auto load_tile = [&](int k0) {
-        if (VEC) {
 #pragma unroll
-            for (int i = 0; i < XL / 4; ++i) {
-                const int idx = tid + 256 * i;
-                const int r = idx >> 3, c4 = (idx & 7) * 4;
-                const int64_t row = row0 + r;
-                float4_t v = {0.f, 0.f, 0.f, 0.f};
-                if (row < a.N && k0 + c4 < k_end) v = load_x4_tail(a.X, a.x_bf16, row * a.ldx + k0 + c4, k_end - (k0 + c4));
+        for (int i = 0; i < XL / 4; ++i) {
+            const int idx = tid + 256 * i;
+            const int r = idx >> 3, c4 = (idx & 7) * 4;
+            const int64_t row = row0 + r;
+            float4_t v = {0.f, 0.f, 0.f, 0.f};
+            if (row < a.N && k0 + c4 < k_end) v = load_x4_tail(a.X, a.x_bf16, row * a.ldx + k0 + c4, k_end - (k0 + c4));
 #pragma unroll
-                for (int e = 0; e < 4; ++e) xr[4 * i + e] = v[e];
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < XL; ++i) {
-                const int idx = tid + 256 * i;
-                const int r = idx >> 5, cc = idx & 31;
-                const int64_t row = row0 + r;
-                xr[i] = (row < a.N && k0 + cc < k_end) ? load_x1(a.X, a.x_bf16, row * a.ldx + k0 + cc) : 0.f;
-            }
+            for (int e = 0; e < 4; ++e) xr[4 * i + e] = v[e];
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -221,20 +211,12 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(const ProjFwdArgs a_in
     load_tile(k_begin);
     for (int k0 = k_begin; k0 < k_end; k0 += BK) {
         __syncthreads();   // previous tile's fragment reads are done
-        if (VEC) {
 #pragma unroll
-            for (int i = 0; i < XL / 4; ++i) {
-                const int idx = tid + 256 * i;
-                float *dst = Xs + (idx >> 3) * XS_LD + (idx & 7) * 4;
+        for (int i = 0; i < XL / 4; ++i) {
+            const int idx = tid + 256 * i;
+            float *dst = Xs + (idx >> 3) * XS_LD + (idx & 7) * 4;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) dst[e] = xr[4 * i + e];
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < XL; ++i) {
-                const int idx = tid + 256 * i;
-                Xs[(idx >> 5) * XS_LD + (idx & 31)] = xr[i];
-            }
+            for (int e = 0; e < 4; ++e) dst[e] = xr[4 * i + e];
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -925,9 +907,9 @@ struct ProjBwdArgs {
 };
 
 // MT = 16-row (f) MFMA tiles per wave: the block owns 64*MT rows of dW, so dH is
-// re-read F/(64*MT) times; VEC = 16-byte fp32 X loads.  With dropout every head a
-// column tile covers has its own accumulator (A masked per head), as in the forward.
-template <int FP, bool DROP, int MT, bool VEC>
+// re-read F/(64*MT) times; X is loaded in quads of 4 elements (load_x4_tail).  With dropout
+// every head a column tile covers has its own accumulator (A masked per head), as in the forward.
+template <int FP, bool DROP, int MT>
 __global__ __launch_bounds__(256) void project_bwd_kernel(const ProjBwdArgs a_in) {
     ProjBwdArgs a = a_in;
     han_resolve_seed(a.seed_lo, a.seed_hi, a.seed_dev);
@@ -958,25 +940,15 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const ProjBwdArgs a_in
     float xr[XL];
     float4_t gr4[2];
     auto load_tile = [&](int64_t n0) {
-        if (VEC) {
 #pragma unroll
-            for (int i = 0; i < XL / 4; ++i) {
-                const int idx = tid + 256 * i;
-                const int r = idx / (BFR / 4), c4 = (idx % (BFR / 4)) * 4;
-                const int64_t row = n0 + r;
-                float4_t v = {0.f, 0.f, 0.f, 0.f};
-                if (row < n_end && f0 + c4 < a.F) v = load_x4_tail(a.X, a.x_bf16, row * a.ldx + f0 + c4, a.F - (f0 + c4));
+        for (int i = 0; i < XL / 4; ++i) {
+            const int idx = tid + 256 * i;
+            const int r = idx / (BFR / 4), c4 = (idx % (BFR / 4)) * 4;
+            const int64_t row = n0 + r;
+            float4_t v = {0.f, 0.f, 0.f, 0.f};
+            if (row < n_end && f0 + c4 < a.F) v = load_x4_tail(a.X, a.x_bf16, row * a.ldx + f0 + c4, a.F - (f0 + c4));
 #pragma unroll
-                for (int e = 0; e < 4; ++e) xr[4 * i + e] = v[e];
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < XL; ++i) {
-                const int idx = tid + 256 * i;
-                const int r = idx / BFR, cc = idx % BFR;
-                const int64_t row = n0 + r;
-                xr[i] = (row < n_end && f0 + cc < a.F) ? load_x1(a.X, a.x_bf16, row * a.ldx + f0 + cc) : 0.f;
-            }
+            for (int e = 0; e < 4; ++e) xr[4 * i + e] = v[e];
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -989,19 +961,11 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const ProjBwdArgs a_in
     load_tile(n_begin);
     for (int64_t n0 = n_begin; n0 < n_end; n0 += BN) {
         __syncthreads();
-        if (VEC) {
 #pragma unroll
-            for (int i = 0; i < XL / 4; ++i) {
-                const int idx = tid + 256 * i;
-                *reinterpret_cast<float4_t *>(Xs + (idx / (BFR / 4)) * XLD + (idx % (BFR / 4)) * 4) =
-                    (float4_t){xr[4 * i], xr[4 * i + 1], xr[4 * i + 2], xr[4 * i + 3]};
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < XL; ++i) {
-                const int idx = tid + 256 * i;
-                Xs[(idx / BFR) * XLD + (idx % BFR)] = xr[i];
-            }
+        for (int i = 0; i < XL / 4; ++i) {
+            const int idx = tid + 256 * i;
+            *reinterpret_cast<float4_t *>(Xs + (idx / (BFR / 4)) * XLD + (idx % (BFR / 4)) * 4) =
+                (float4_t){xr[4 * i], xr[4 * i + 1], xr[4 * i + 2], xr[4 * i + 3]};
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -1332,10 +1296,6 @@ __global__ __launch_bounds__(256, 4) void project_bwd_blk_kernel(const ProjBwdBl
             }
 }
 
-bool fp_ok(int K, int FP) {
-    return K * FP == HAN_D && (FP == 4 || FP == 8 || FP == 16 || FP == 32 || FP == 64);
-}
-
 constexpr int kBwdMT = 2;   // project_bwd: 128 f rows per block
 
 void bwd_geometry(int64_t N, int F, int *ftiles, int64_t *rows_per_chunk, int64_t *nchunks) {
@@ -1350,15 +1310,6 @@ void bwd_geometry(int64_t N, int F, int *ftiles, int64_t *rows_per_chunk, int64_
 }
 
 }  // namespace
-
-#define HAN_DISPATCH_FP(FPV, ...)                                 \
-    switch (FPV) {                                                \
-        case 4: { constexpr int FPC = 4; __VA_ARGS__; } break;    \
-        case 8: { constexpr int FPC = 8; __VA_ARGS__; } break;    \
-        case 16: { constexpr int FPC = 16; __VA_ARGS__; } break;  \
-        case 32: { constexpr int FPC = 32; __VA_ARGS__; } break;  \
-        default: { constexpr int FPC = 64; __VA_ARGS__; } break;  \
-    }
 
 // Forward geometry.  Long inputs: 128-row blocks, one block per row tile.  Short inputs
 // (fewer row tiles than CUs, e.g. ACM: N = 3025, F = 1870): 64-row blocks and the
@@ -1382,6 +1333,20 @@ static void fwd_geometry(int64_t N, int F, int *mt, int *nsplit, int *f_chunk) {
 static size_t wimage_bytes(int F, int P) { return (size_t)((F + 31) / 32) * (size_t)P * B6_WTILE; }
 // shapes the bf16 x 6 matrix-pipe kernels may run on (whole-F blocks of 128 rows)
 static bool b6_shape(int64_t N, int nsplit) { return nsplit == 1 && N >= 64 * 256; }
+
+// the bf16 x 6 forward of one meta-path: blocks of 8 waves, of 4 under HAN_FLAG_K1_4WAVE
+template <bool DROP, bool KEEP>
+static void launch_fwd_b6(const ProjFwdArgs &a, int flags, hipStream_t st) {
+    const dim3 g6((unsigned)((a.N + B6_ROWS - 1) / B6_ROWS));
+    if (a.x_bf16) {
+        if (flags & HAN_FLAG_K1_4WAVE) project_fwd_b6_kernel<DROP, true, KEEP, 4><<<g6, 256, 0, st>>>(a);
+        else project_fwd_b6_kernel<DROP, true, KEEP, 8><<<g6, 512, 0, st>>>(a);
+    } else if (flags & HAN_FLAG_K1_4WAVE) {
+        project_fwd_b6_kernel<DROP, false, KEEP, 4><<<g6, 256, 0, st>>>(a);
+    } else {
+        project_fwd_b6_kernel<DROP, false, KEEP, 8><<<g6, 512, 0, st>>>(a);
+    }
+}
 
 extern "C" size_t han_project_fwd_multi_workspace(int64_t N, int F, int K, int FP, int P) {
     (void)K; (void)FP;
@@ -1415,7 +1380,7 @@ extern "C" int han_project_fwd(const void *X, int x_dtype, int64_t ldx, const fl
     if (N == 0) return 0;   // nothing to do; row pointers of empty tensors may be null
     if (!X || !W || !a1 || !a2 || !b1 || !b2 || !H || !f1 || !f2 || N < 0 || F <= 0 || ldx < F)
         return HAN_E_BADARG;
-    if (!fp_ok(K, FP)) return HAN_E_UNSUPPORTED;
+    if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
     if ((x_dtype != HAN_DTYPE_F32 && x_dtype != HAN_DTYPE_BF16) ||
         (table_dtype != HAN_DTYPE_F32 && table_dtype != HAN_DTYPE_BF16))
         return HAN_E_UNSUPPORTED;
@@ -1425,15 +1390,12 @@ extern "C" int han_project_fwd(const void *X, int x_dtype, int64_t ldx, const fl
     ProjFwdArgs a;
     a.X = X; a.ldx = ldx; a.W = W; a.H = H; a.N = N; a.F = F;
     a.x_bf16 = x_dtype == HAN_DTYPE_BF16; a.h_bf16 = table_dtype == HAN_DTYPE_BF16;
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.seed_dev = seed_dev;
-    a.thr_in = in_drop > 0.f ? han_keep_threshold(1.f - in_drop) : HAN_KEEP_ALL;
-    a.thr_fts = fts_drop > 0.f ? han_keep_threshold(1.f - fts_drop) : HAN_KEEP_ALL;
+    han_set_dropout(a, seed, seed_dev, in_drop, a.thr_in, a.inv_keep_in);
+    a.thr_fts = han_drop_threshold(fts_drop);
     a.fts_stream = HAN_STREAM_FTS + 4u * (uint32_t)HAN_FLAG_FTS_SLICE_OF(flags);
-    a.inv_keep_in = 1.f / (1.f - in_drop);
     a.row_offset = row_offset;
     a.keep = in_drop > 0.f ? keep : nullptr;
     const bool vec = (F % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)X & (a.x_bf16 ? 7 : 15)) == 0);
-    const bool vec32 = true;      // the exact-fp32 kernels: quad loads at element alignment, element loads for a partial last quad
     int mt, nsplit;
     fwd_geometry(N, F, &mt, &nsplit, &a.f_chunk);
     a.partial = nullptr;
@@ -1463,46 +1425,27 @@ extern "C" int han_project_fwd(const void *X, int x_dtype, int64_t ldx, const fl
         project_wimage_kernel<<<(ktiles * 512 + 255) / 256, 256, 0, st>>>(W, (unsigned char *)workspace, F, ktiles, 1);
         HAN_CHECK_LAUNCH();
         a.wimg = (const unsigned char *)workspace;
-        const dim3 g6((unsigned)((N + B6_ROWS - 1) / B6_ROWS));
-#define HAN_LAUNCH_B6(D_, X_, K_)                                                               \
-    do {                                                                                        \
-        if (flags & HAN_FLAG_K1_4WAVE) project_fwd_b6_kernel<D_, X_, K_, 4><<<g6, 256, 0, st>>>(a); \
-        else project_fwd_b6_kernel<D_, X_, K_, 8><<<g6, 512, 0, st>>>(a);                       \
-    } while (0)
         if (in_drop > 0.f) {
-            if (a.keep) {
-                if (a.x_bf16) HAN_LAUNCH_B6(true, true, true);
-                else HAN_LAUNCH_B6(true, false, true);
-            } else {
-                if (a.x_bf16) HAN_LAUNCH_B6(true, true, false);
-                else HAN_LAUNCH_B6(true, false, false);
-            }
+            if (a.keep) launch_fwd_b6<true, true>(a, flags, st);
+            else launch_fwd_b6<true, false>(a, flags, st);
         } else {
-            if (a.x_bf16) HAN_LAUNCH_B6(false, true, false);
-            else HAN_LAUNCH_B6(false, false, false);
+            launch_fwd_b6<false, false>(a, flags, st);
         }
-#undef HAN_LAUNCH_B6
+        HAN_CHECK_LAUNCH();
+    } else {
+        const dim3 grid((unsigned)((N + 64 * mt - 1) / (64 * mt)), (unsigned)nsplit);
+        HAN_DISPATCH_FP(FP, {
+            if (mt == 2 && in_drop > 0.f) project_fwd_kernel<FPC, true, 2><<<grid, 256, 0, st>>>(a);
+            else if (mt == 2) project_fwd_kernel<FPC, false, 2><<<grid, 256, 0, st>>>(a);
+            else if (in_drop > 0.f) project_fwd_kernel<FPC, true, 1><<<grid, 256, 0, st>>>(a);
+            else project_fwd_kernel<FPC, false, 1><<<grid, 256, 0, st>>>(a);
+        })
         HAN_CHECK_LAUNCH();
     }
-    const dim3 grid((unsigned)((N + 64 * mt - 1) / (64 * mt)), (unsigned)nsplit);
-#define HAN_LAUNCH_FWD(MTC)                                                                  \
-    HAN_DISPATCH_FP(FP, {                                                                    \
-        if (in_drop > 0.f) {                                                                 \
-            if (vec32) project_fwd_kernel<FPC, true, MTC, true><<<grid, 256, 0, st>>>(a);    \
-            else project_fwd_kernel<FPC, true, MTC, false><<<grid, 256, 0, st>>>(a);         \
-        } else {                                                                             \
-            if (vec32) project_fwd_kernel<FPC, false, MTC, true><<<grid, 256, 0, st>>>(a);   \
-            else project_fwd_kernel<FPC, false, MTC, false><<<grid, 256, 0, st>>>(a);        \
-        }                                                                                    \
-    })
-    if (b6) { /* done above */ } else if (mt == 2) { HAN_LAUNCH_FWD(2) } else { HAN_LAUNCH_FWD(1) }
-#undef HAN_LAUNCH_FWD
-    HAN_CHECK_LAUNCH();
     if (nsplit > 1) {      // sums the partial tiles, stamps / rounds, and takes the scores from the stored row
         const int fgrid = han_grid_for(N, 16, 256 * 8);
         a.a1 = a1; a.a2 = a2; a.b1 = b1; a.b2 = b2;
-        if (a.h_bf16) { HAN_DISPATCH_FP(FP, { project_finish_kernel<FPC, true><<<fgrid, 256, 0, st>>>(a, nsplit, f1, f2); }) }
-        else { HAN_DISPATCH_FP(FP, { project_finish_kernel<FPC, false><<<fgrid, 256, 0, st>>>(a, nsplit, f1, f2); }) }
+        HAN_DISPATCH_FP_BF(FP, a.h_bf16, project_finish_kernel<FPC, BF><<<fgrid, 256, 0, st>>>(a, nsplit, f1, f2));
         HAN_CHECK_LAUNCH();
         return 0;
     }
@@ -1513,11 +1456,7 @@ extern "C" int han_project_fwd(const void *X, int x_dtype, int64_t ldx, const fl
     const int sgrid = han_grid_for(N, 16, 256 * 8);
     // the lane map of the scores follows the head width for both storage types (a bf16 table with F' != 8 through the
     // 8 x 8 instantiation wrote f1 / f2 out of bounds for K < 8 and a wrong layout for K = 16)
-    if (a.h_bf16) {
-        HAN_DISPATCH_FP(FP, { project_scores_kernel<FPC, true><<<sgrid, 256, 0, st>>>(s); })
-    } else {
-        HAN_DISPATCH_FP(FP, { project_scores_kernel<FPC, false><<<sgrid, 256, 0, st>>>(s); })
-    }
+    HAN_DISPATCH_FP_BF(FP, a.h_bf16, project_scores_kernel<FPC, BF><<<sgrid, 256, 0, st>>>(s));
     HAN_CHECK_LAUNCH();
     return 0;
 }
@@ -1535,17 +1474,9 @@ static int launch_multi(ProjMultiArgs m, int P, int np_max, hipStream_t st, int 
         const int groups = (P - p) / np;
         const size_t lds = xb + (size_t)3 * np * B6_WBYTES;
         m.p_first = p;
-        hipError_t e;
-        if (np == 4) {
-            e = hipFuncSetAttribute((const void *)project_fwd_b6_multi_kernel<XBF, 4, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-            project_fwd_b6_multi_kernel<XBF, 4, MT><<<dim3(tiles, groups), 512, lds, st>>>(m);
-        } else {
-            e = hipFuncSetAttribute((const void *)project_fwd_b6_multi_kernel<XBF, 2, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-            project_fwd_b6_multi_kernel<XBF, 2, MT><<<dim3(tiles, groups), 512, lds, st>>>(m);
-        }
-        HAN_CHECK_LAUNCH();
+        const hipError_t e = np == 4 ? han_launch_lds(project_fwd_b6_multi_kernel<XBF, 4, MT>, dim3(tiles, groups), 512, lds, st, m)
+                                     : han_launch_lds(project_fwd_b6_multi_kernel<XBF, 2, MT>, dim3(tiles, groups), 512, lds, st, m);
+        if (e != hipSuccess) return (int)e;
         p += groups * np;
         *done = p;      // meta-paths done; a last odd one is left to the caller
     }
@@ -1561,7 +1492,7 @@ extern "C" int han_project_fwd_multi(const void *X, int x_dtype, int64_t ldx, co
     if (P <= 0 || (in_drop > 0.f && !seeds)) return HAN_E_BADARG;
     if (N == 0) return 0;
     if (!X || !W || !a1 || !a2 || !b1 || !b2 || !H || !f1 || !f2 || N < 0 || F <= 0 || ldx < F) return HAN_E_BADARG;
-    if (!fp_ok(K, FP)) return HAN_E_UNSUPPORTED;
+    if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
     const bool x_bf16 = x_dtype == HAN_DTYPE_BF16, h_bf16 = table_dtype == HAN_DTYPE_BF16;
     const size_t hb = (size_t)N * HAN_D * (h_bf16 ? 2 : 4), kb = han_project_keep_bytes(N, F, ldx, K, FP);
     int mt, nsplit, fch;
@@ -1590,8 +1521,7 @@ extern "C" int han_project_fwd_multi(const void *X, int x_dtype, int64_t ldx, co
                 s.b1 = b1 + (size_t)p * K; s.b2 = b2 + (size_t)p * K;
                 s.f1 = f1 + (size_t)p * N * K; s.f2 = f2 + (size_t)p * N * K; s.N = N;
                 const int sgrid = han_grid_for(N, 16, 256 * 8);
-                if (h_bf16) { HAN_DISPATCH_FP(FP, { project_scores_kernel<FPC, true><<<sgrid, 256, 0, st>>>(s); }) }
-                else { HAN_DISPATCH_FP(FP, { project_scores_kernel<FPC, false><<<sgrid, 256, 0, st>>>(s); }) }
+                HAN_DISPATCH_FP_BF(FP, h_bf16, project_scores_kernel<FPC, BF><<<sgrid, 256, 0, st>>>(s));
                 HAN_CHECK_LAUNCH();
             }
         }
@@ -1620,7 +1550,7 @@ extern "C" int han_project_bwd(const void *X, int x_dtype, int64_t ldx, const fl
                                uint64_t seed, const uint64_t *seed_dev, int64_t row_offset, const uint8_t *keep,
                                void *stream) {
     if (!X || !dH || !dW || !workspace || N < 0 || F <= 0 || ldx < F) return HAN_E_BADARG;
-    if (!fp_ok(K, FP)) return HAN_E_UNSUPPORTED;
+    if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
     if (x_dtype != HAN_DTYPE_F32 && x_dtype != HAN_DTYPE_BF16) return HAN_E_UNSUPPORTED;
     if (in_drop < 0.f || in_drop >= 1.f) return HAN_E_BADARG;
     if (workspace_bytes < han_project_bwd_workspace(N, F, K, FP)) return HAN_E_WORKSPACE;
@@ -1648,23 +1578,15 @@ extern "C" int han_project_bwd(const void *X, int x_dtype, int64_t ldx, const fl
     ProjBwdArgs a;
     a.X = X; a.x_bf16 = x_bf16; a.ldx = ldx; a.dH = dH; a.slab = (float *)workspace; a.N = N; a.F = F;
     a.rows_per_chunk = rpc;
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.seed_dev = seed_dev;
-    a.thr_in = in_drop > 0.f ? han_keep_threshold(1.f - in_drop) : HAN_KEEP_ALL;
-    a.inv_keep_in = 1.f / (1.f - in_drop);
+    han_set_dropout(a, seed, seed_dev, in_drop, a.thr_in, a.inv_keep_in);
     a.row_offset = row_offset;
     dim3 grid(ftiles, (unsigned)nch);
     // (dW on the bf16 x 6 matrix pipe was built and measured in round 2 -- coalesced loads + on-chip transpose:
     // 0.55 ms without / 0.83 ms with dropout against 0.41 / 0.84 ms for this exact-fp32 kernel at SYN-1M --
     // and not kept: the transposition of both operands through LDS costs what the shorter matrix time saves.)
-    const bool vec32 = true;      // quad loads at element alignment (load_x4_tail)
     HAN_DISPATCH_FP(FP, {
-        if (in_drop > 0.f) {
-            if (vec32) project_bwd_kernel<FPC, true, kBwdMT, true><<<grid, 256, 0, st>>>(a);
-            else project_bwd_kernel<FPC, true, kBwdMT, false><<<grid, 256, 0, st>>>(a);
-        } else {
-            if (vec32) project_bwd_kernel<FPC, false, kBwdMT, true><<<grid, 256, 0, st>>>(a);
-            else project_bwd_kernel<FPC, false, kBwdMT, false><<<grid, 256, 0, st>>>(a);
-        }
+        if (in_drop > 0.f) project_bwd_kernel<FPC, true, kBwdMT><<<grid, 256, 0, st>>>(a);
+        else project_bwd_kernel<FPC, false, kBwdMT><<<grid, 256, 0, st>>>(a);
     })
     HAN_CHECK_LAUNCH();
     hipError_t e = han_reduce_slabs((const float *)workspace, (int)nch, width, width, han_reduce_to(dW, width), st);
@@ -1676,14 +1598,12 @@ extern "C" int han_project_bwd_input(const float *dH, const float *W, float *dX,
                                      int F, int K, int FP, float in_drop, uint64_t seed,
                                      const uint64_t *seed_dev, int64_t row_offset, void *stream) {
     if (!dH || !W || !dX || N < 0 || F <= 0 || ldo < F) return HAN_E_BADARG;
-    if (!fp_ok(K, FP)) return HAN_E_UNSUPPORTED;
+    if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
     if (in_drop < 0.f || in_drop >= 1.f) return HAN_E_BADARG;
     if (N == 0) return 0;
     ProjBwdInArgs a;
     a.dH = dH; a.W = W; a.dX = dX; a.ldo = ldo; a.N = N; a.F = F;
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.seed_dev = seed_dev;
-    a.thr_in = in_drop > 0.f ? han_keep_threshold(1.f - in_drop) : HAN_KEEP_ALL;
-    a.inv_keep_in = 1.f / (1.f - in_drop);
+    han_set_dropout(a, seed, seed_dev, in_drop, a.thr_in, a.inv_keep_in);
     a.row_offset = row_offset;
     hipStream_t st = (hipStream_t)stream;
     const int grid = han_grid_for((N + 15) / 16, 4, 256 * 8);

@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_kernel(const float *__restri
 // group of the accumulator layout (rows 4*l4 .. 4*l4+3), so the per-node softmax
 // and the weighted sum finish inside the group -- no LDS exchange, no barrier; each
 // wave streams its own 16-row tiles.
-template <int CA, int P, bool WREG>
+template <int CA, int P>
 __global__ __launch_bounds__(256) void sem_attn_fwd_wave_kernel(const float *__restrict__ M, const float *Wg,
                                                                 const float *bw, const float *uw, float *Z,
                                                                 float *beta, int64_t N) {
@@ -146,20 +146,11 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_wave_kernel(const float *__r
     constexpr int TA = A / 16;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
-    // Womega lives in registers for the whole kernel: B fragment of k-step ks, column
-    // tile t is W[4ks + l4][16t + l15]  (16*TA VGPRs; no LDS traffic in the MFMA loop)
+    // Womega in LDS for the whole kernel: B fragment of k-step ks, column tile t is W[4ks + l4][16t + l15]
     constexpr int WLD = A + 16;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float wf[WREG ? 16 : 1][TA];
-    if (WREG) {
-#pragma unroll
-        for (int ks = 0; ks < (WREG ? 16 : 1); ++ks)
-#pragma unroll
-            for (int t = 0; t < TA; ++t) wf[ks][t] = Wg[(4 * ks + l4) * A + 16 * t + l15];
-    } else {
-        for (int i = threadIdx.x; i < 64 * A; i += 256) smem[(i / A) * WLD + (i % A)] = Wg[i];
-        __syncthreads();
-    }
+    for (int i = threadIdx.x; i < 64 * A; i += 256) smem[(i / A) * WLD + (i % A)] = Wg[i];
+    __syncthreads();
     float bcol[TA], ucol[TA];
 #pragma unroll
     for (int t = 0; t < TA; ++t) {
@@ -200,7 +191,7 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_wave_kernel(const float *__r
         for (int ks = 0; ks < 16; ++ks) {
 #pragma unroll
             for (int t = 0; t < TA; ++t) {
-                const float bfrag = WREG ? wf[WREG ? ks : 0][t] : smem[(4 * ks + l4) * WLD + 16 * t + l15];
+                const float bfrag = smem[(4 * ks + l4) * WLD + 16 * t + l15];
                 acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(afrag[ks], bfrag, acc[t], 0, 0, 0);
             }
         }
@@ -1990,129 +1981,59 @@ size_t bwd_lds() {
 template <int CA>
 int launch_fwd(const float *M, const float *w, const float *b, const float *u, float *Z, float *beta,
                int64_t N, int P, int flags, hipStream_t st) {
-    const size_t lds = fwd_lds<CA>();
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)sem_attn_fwd_kernel<CA>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    if ((P == 1 || P == 2 || P == 4 || P == 8 || P == 16) && N * P >= 64 * 1024 && !(flags & HAN_FLAG_K3_EXACT_PIPE)) {
+    hipError_t e;
+    if (han_pow2_p(P) && N * P >= 64 * 1024 && !(flags & HAN_FLAG_K3_EXACT_PIPE)) {
         // large inputs: the contraction on the bf16 matrix pipe (exact 3-way split, fp32-class accuracy)
         const size_t blds = (size_t)3 * 64 * CA * 128;       // swizzled 128-B rows (sem_attn_fwd_wave_b6_kernel)
         const int grid = han_grid_for(N * P, 64, 256 * 3);
-        hipError_t e2 = hipSuccess;
-#define HAN_LAUNCH_FWD_B6(PV)                                                                            \
-    e2 = hipFuncSetAttribute((const void *)sem_attn_fwd_wave_b6_kernel<CA, PV>,                          \
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);                     \
-    if (e2 == hipSuccess) sem_attn_fwd_wave_b6_kernel<CA, PV><<<grid, 256, blds, st>>>(M, w, b, u, Z, beta, N);
-        switch (P) {
-            case 1: HAN_LAUNCH_FWD_B6(1) break;
-            case 2: HAN_LAUNCH_FWD_B6(2) break;
-            case 4: HAN_LAUNCH_FWD_B6(4) break;
-            case 8: HAN_LAUNCH_FWD_B6(8) break;
-            default: HAN_LAUNCH_FWD_B6(16) break;
-        }
-#undef HAN_LAUNCH_FWD_B6
-        if (e2 != hipSuccess) return (int)e2;
-        HAN_CHECK_LAUNCH();
-        return 0;
+        HAN_DISPATCH_P(P, e = han_launch_lds(sem_attn_fwd_wave_b6_kernel<CA, PC>, grid, 256, blds, st, M, w, b, u, Z, beta, N))
+    } else if (han_pow2_p(P)) {
+        const size_t wlds = (size_t)64 * (64 * CA + 16) * sizeof(float);
+        const int grid = han_grid_for(N * P, 64, 256 * 4);
+        HAN_DISPATCH_P(P, e = han_launch_lds(sem_attn_fwd_wave_kernel<CA, PC>, grid, 256, wlds, st, M, w, b, u, Z, beta, N))
+    } else {
+        const int grid = han_grid_for(N, ROWS / P, 256 * 3);
+        e = han_launch_lds(sem_attn_fwd_kernel<CA>, grid, 256, fwd_lds<CA>(), st, M, w, b, u, Z, beta, N, P);
     }
-    if (P == 1 || P == 2 || P == 4 || P == 8 || P == 16) {
-        constexpr bool WREG = false;
-        const size_t wlds = WREG ? 0 : (size_t)64 * (64 * CA + 16) * sizeof(float);
-        const int grid = han_grid_for(N * P, 64, 256 * (WREG ? 2 : 4));
-        if (P == 1) sem_attn_fwd_wave_kernel<CA, 1, WREG><<<grid, 256, wlds, st>>>(M, w, b, u, Z, beta, N);
-        else if (P == 2) sem_attn_fwd_wave_kernel<CA, 2, WREG><<<grid, 256, wlds, st>>>(M, w, b, u, Z, beta, N);
-        else if (P == 4) sem_attn_fwd_wave_kernel<CA, 4, WREG><<<grid, 256, wlds, st>>>(M, w, b, u, Z, beta, N);
-        else if (P == 8) sem_attn_fwd_wave_kernel<CA, 8, WREG><<<grid, 256, wlds, st>>>(M, w, b, u, Z, beta, N);
-        else sem_attn_fwd_wave_kernel<CA, 16, WREG><<<grid, 256, wlds, st>>>(M, w, b, u, Z, beta, N);
-        HAN_CHECK_LAUNCH();
-        return 0;
-    }
-    const int NB = ROWS / P;
-    const int grid = han_grid_for(N, NB, 256 * 3);
-    sem_attn_fwd_kernel<CA><<<grid, 256, lds, st>>>(M, w, b, u, Z, beta, N, P);
-    HAN_CHECK_LAUNCH();
-    return 0;
+    return (int)e;
 }
 
 template <int CA>
 int launch_bwd(const float *M, const float *w, const float *b, const float *u, const float *beta,
                const float *dZ, float *dM, float *slab, int64_t N, int P, int *grid_out, int flags, hipStream_t st) {
     const size_t lds = bwd_lds<CA>();
-    hipError_t e = hipFuncSetAttribute((const void *)sem_attn_bwd_kernel<CA>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    if ((P == 1 || P == 2 || P == 4 || P == 8 || P == 16) && N * P >= 64 * 1024 && !(flags & HAN_FLAG_K3_EXACT_PIPE)) {
+    hipError_t e;
+    if (han_pow2_p(P) && N * P >= 64 * 1024 && !(flags & HAN_FLAG_K3_EXACT_PIPE)) {
         const int grid = han_grid_for(N * P, 64, kSemBwdBlocks);
         *grid_out = grid;
         constexpr int A6 = 64 * CA;
         const size_t blds = (size_t)3 * A6 * SA_WLDB + (size_t)3 * 64 * (A6 * 2 + 32) + (size_t)(4 * 16 * (A6 + 4) + 2 * A6) * sizeof(float);
-        hipError_t e3 = hipSuccess;
-#define HAN_LAUNCH_BWD_B6_AS(KERNEL, THREADS)                                                            \
-    e3 = hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds); \
-    if (e3 == hipSuccess) KERNEL<<<grid, THREADS, blds, st>>>(M, w, b, u, beta, dZ, dM, slab, N);
-#define HAN_LAUNCH_BWD_B6(PV)                                                                            \
-    if (CA == 2 && (flags & HAN_FLAG_K3_PAIRS)) {                                                        \
-        HAN_LAUNCH_BWD_B6_AS((sem_attn_bwd_pair_b6_kernel<PV>), 512)                                     \
-    } else if (flags & HAN_FLAG_K3_G3_F32) {                                                             \
-        HAN_LAUNCH_BWD_B6_AS((sem_attn_bwd_wave_b6_kernel<CA, PV, false>), 256)                          \
-    } else {                                                                                             \
-        HAN_LAUNCH_BWD_B6_AS((sem_attn_bwd_wave_b6_kernel<CA, PV, true>), 256)                           \
-    }
-        switch (P) {
-            case 1: HAN_LAUNCH_BWD_B6(1) break;
-            case 2: HAN_LAUNCH_BWD_B6(2) break;
-            case 4: HAN_LAUNCH_BWD_B6(4) break;
-            case 8: HAN_LAUNCH_BWD_B6(8) break;
-            default: HAN_LAUNCH_BWD_B6(16) break;
-        }
-#undef HAN_LAUNCH_BWD_B6
-#undef HAN_LAUNCH_BWD_B6_AS
-        if (e3 != hipSuccess) return (int)e3;
-        HAN_CHECK_LAUNCH();
-        return 0;
-    }
-    if (P == 1 || P == 2 || P == 4 || P == 8 || P == 16) {
+        HAN_DISPATCH_P(P, {
+            if (CA == 2 && (flags & HAN_FLAG_K3_PAIRS))
+                e = han_launch_lds(sem_attn_bwd_pair_b6_kernel<PC>, grid, 512, blds, st, M, w, b, u, beta, dZ, dM, slab, N);
+            else if (flags & HAN_FLAG_K3_G3_F32)
+                e = han_launch_lds(sem_attn_bwd_wave_b6_kernel<CA, PC, false>, grid, 256, blds, st, M, w, b, u, beta, dZ, dM, slab, N);
+            else
+                e = han_launch_lds(sem_attn_bwd_wave_b6_kernel<CA, PC, true>, grid, 256, blds, st, M, w, b, u, beta, dZ, dM, slab, N);
+        })
+    } else if (han_pow2_p(P)) {
         const int grid = han_grid_for(N > 0 ? N * P : 1, 64, kSemBwdBlocks);
         *grid_out = grid;
-        hipError_t e2 = hipSuccess;
-#define HAN_LAUNCH_BWD_WAVE(PV)                                                                          \
-    e2 = hipFuncSetAttribute((const void *)sem_attn_bwd_wave_kernel<CA, PV>,                             \
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                      \
-    if (e2 == hipSuccess)                                                                                \
-        sem_attn_bwd_wave_kernel<CA, PV><<<grid, 256, lds, st>>>(M, w, b, u, beta, dZ, dM, slab, N);
-        switch (P) {
-            case 1: HAN_LAUNCH_BWD_WAVE(1) break;
-            case 2: HAN_LAUNCH_BWD_WAVE(2) break;
-            case 4: HAN_LAUNCH_BWD_WAVE(4) break;
-            case 8: HAN_LAUNCH_BWD_WAVE(8) break;
-            default: HAN_LAUNCH_BWD_WAVE(16) break;
-        }
-#undef HAN_LAUNCH_BWD_WAVE
-        if (e2 != hipSuccess) return (int)e2;
-        HAN_CHECK_LAUNCH();
-        return 0;
+        HAN_DISPATCH_P(P, e = han_launch_lds(sem_attn_bwd_wave_kernel<CA, PC>, grid, 256, lds, st, M, w, b, u, beta, dZ, dM, slab, N))
+    } else {
+        const int grid = han_grid_for(N > 0 ? N : 1, ROWS / P, kSemBwdBlocks);
+        *grid_out = grid;
+        e = han_launch_lds(sem_attn_bwd_kernel<CA>, grid, 256, lds, st, M, w, b, u, beta, dZ, dM, slab, N, P);
     }
-    const int NB = ROWS / P;
-    const int grid = han_grid_for(N > 0 ? N : 1, NB, kSemBwdBlocks);
-    *grid_out = grid;
-    sem_attn_bwd_kernel<CA><<<grid, 256, lds, st>>>(M, w, b, u, beta, dZ, dM, slab, N, P);
-    HAN_CHECK_LAUNCH();
-    return 0;
+    return (int)e;
 }
 
 template <int CA, int DT>
 int launch_fwd_gen(const float *M, const float *w, const float *b, const float *u, float *Z, float *beta,
                    int64_t N, int P, hipStream_t st) {
     const size_t lds = (size_t)(16 * DT * (64 * CA + 16) + 2 * ROWS) * sizeof(float);
-    hipError_t e = hipFuncSetAttribute((const void *)sem_attn_fwd_gen_kernel<CA, DT>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
     const int grid = han_grid_for(N, ROWS / P, 256 * 2);
-    sem_attn_fwd_gen_kernel<CA, DT><<<grid, 256, lds, st>>>(M, w, b, u, Z, beta, N, P);
-    HAN_CHECK_LAUNCH();
-    return 0;
+    return (int)han_launch_lds(sem_attn_fwd_gen_kernel<CA, DT>, grid, 256, lds, st, M, w, b, u, Z, beta, N, P);
 }
 
 template <int DT>
@@ -2121,14 +2042,12 @@ int launch_bwd_gen(const float *M, const float *w, const float *b, const float *
                    hipStream_t st) {
     constexpr int D = 16 * DT;
     const size_t lds = (size_t)(D * (64 + 16) + D * (64 + 2) + 4 * 16 * (64 + 2) + 4 * ROWS) * sizeof(float);
-    hipError_t e = hipFuncSetAttribute((const void *)sem_attn_bwd_gen_kernel<DT>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
     const int grid = han_grid_for(N > 0 ? N : 1, ROWS / P, kSemBwdBlocks);
     *grid_out = grid;
     for (int a_off = 0; a_off < A; a_off += 64) {      // same grid every pass: a block's slab row fills up slice by slice
-        sem_attn_bwd_gen_kernel<DT><<<grid, 256, lds, st>>>(M, w, b, u, beta, dZ, dM, slab, N, P, A, a_off);
-        HAN_CHECK_LAUNCH();
+        const hipError_t e = han_launch_lds(sem_attn_bwd_gen_kernel<DT>, grid, 256, lds, st, M, w, b, u, beta, dZ, dM,
+                                            slab, N, P, A, a_off);
+        if (e != hipSuccess) return (int)e;
     }
     return 0;
 }
