@@ -14,7 +14,7 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_uint64, c_void
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhan_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("node_attn.hip", "project.hip", "sem_attn.hip", "loss_opt.hip")
+SOURCES = ("node_attn.hip", "project.hip", "sem_attn.hip", "loss_opt.hip", "metapath.hip")
 # node_attn.hip: the dense K2 kernels (node_attn_dense.h) keep 8-16 fp32 MFMA accumulators in a rolled loop; with the
 # default AGPR form hipcc shuffles them through v_accvgpr_read / _mov / _write every iteration (each a wait for the
 # matrix pipe); the VGPR form of the MFMA destination has no such traffic
@@ -82,9 +82,12 @@ SIGNATURES = {
     "han_l2_half_sumsq": (c_int, [P, I64, P, P, c_size_t, P]),
     "han_bias_row_counts": (c_int, [P, I64, I64, P, P]),
     "han_bias_fill_csr": (c_int, [P, I64, I64, P, P, P]),
+    "han_spgemm_row_bounds": (c_int, [P, P, P, I64, I64, c_int, P, P]),
+    "han_spgemm_count": (c_int, [P, P, P, P, I64, I64, I64, P, P, I64, I64, c_int, P, P]),
+    "han_spgemm_fill": (c_int, [P, P, P, P, I64, I64, I64, P, P, I64, I64, c_int, P, P, P]),
 }
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 _lib = None
 
 

@@ -1,0 +1,145 @@
+"""Meta-path graphs from typed relations (K0): the inputs of ``HeteGAT_multi.inference``.
+
+The reference reads its meta-path graphs preprocessed (``ex_acm3025.py:57-87``: PAP, PLP, ... as dense matrices of a
+``.mat`` file) and leaves building them to the user.  Here a meta-path such as APCPA is the boolean product of the
+typed relations along it -- paper-author, paper-conference, ... edge lists --, computed on the GPU by
+``ops.csr_bool_matmul`` (``han_spgemm_*``, ``csrc/metapath.hip``).  The results are ``CSRGraph``s that go straight
+into ``bias_mat_list``::
+
+    rel = {"AP": relation(author_ids, paper_ids, n_authors, n_papers, device=dev),
+           "PC": relation(paper_ids2, conf_ids, n_papers, n_confs, device=dev)}
+    graphs = [metapath_graph(rel, mp) for mp in ("APA", "APCPA")]
+
+Node types are single letters; ``relations`` maps an ordered pair ``"XY"`` to the graph with rows = X nodes and
+columns = Y nodes, and a hop Y -> X without its own relation runs on the transpose of ``"XY"``.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import ops
+from .graph import CSRGraph
+
+
+def _ids(x, name, device):
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+    if t.dim() != 1:
+        raise ValueError(f"{name}: expected a 1-D array of node ids, got shape {tuple(t.shape)}")
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"{name}: integer node ids expected, got {t.dtype}")
+    if device is not None:
+        t = t.to(device)
+    return t.to(torch.int64)
+
+
+def _from_keys(key, n_rows, n_cols, device) -> CSRGraph:
+    """CSR of the sorted, unique entry keys row * n_cols + col."""
+    rows = key // n_cols if key.numel() else key
+    cols = key - rows * n_cols
+    rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=device)
+    torch.cumsum(torch.bincount(rows, minlength=n_rows), 0, out=rowptr[1:])
+    return CSRGraph(rowptr, cols.to(torch.int32), n_cols, validate=False)
+
+
+def relation(src, dst, n_src: int, n_dst: int, device=None) -> CSRGraph:
+    """The graph of one typed relation from its edge list: rows = `src` nodes (n_src of them), columns = `dst` nodes,
+    columns sorted and repeated edges dropped.  src / dst: numpy or torch integer arrays of equal length; the graph
+    lives on `device` (default: where `src` is).  Raises ValueError on ids outside [0, n_src) / [0, n_dst)."""
+    n_src, n_dst = int(n_src), int(n_dst)
+    if n_src < 0 or n_dst < 0 or n_dst > 2 ** 31 - 1:
+        raise ValueError(f"sizes {n_src} x {n_dst}: expected n_src >= 0 and 0 <= n_dst < 2^31 (int32 columns)")
+    s = _ids(src, "src", device)
+    d = _ids(dst, "dst", s.device)
+    if s.shape != d.shape:
+        raise ValueError(f"src has {s.numel()} ids, dst {d.numel()}")
+    if s.numel():
+        for t, n, name in ((s, n_src, "src"), (d, n_dst, "dst")):
+            lo, hi = int(t.min()), int(t.max())
+            if lo < 0 or hi >= n:
+                raise ValueError(f"{name} ids outside [0, {n}): [{lo}, {hi}]")
+    return _from_keys(torch.unique(s * n_dst + d), n_src, n_dst, s.device)
+
+
+def compose(graphs, self_loops: bool = False) -> CSRGraph:
+    """The boolean product of a chain of graphs, left to right: entry (i, j) iff a path i -> ... -> j exists
+    (graphs[k].n_cols == graphs[k+1].n_rows).  self_loops=True needs a square result and adds (i, i).  The result
+    has strictly increasing columns per row and values None.  GPU graphs only (han_amd has no CPU path)."""
+    graphs = list(graphs)
+    if not graphs:
+        raise ValueError("compose: no graphs")
+    for k, g in enumerate(graphs):
+        if not isinstance(g, CSRGraph):
+            raise ValueError(f"compose: graphs[{k}] is a {type(g)}, expected a CSRGraph")
+    for k in range(len(graphs) - 1):
+        if graphs[k].n_cols != graphs[k + 1].n_rows:
+            raise ValueError(f"compose: graphs[{k}] has {graphs[k].n_cols} columns, graphs[{k + 1}] has "
+                             f"{graphs[k + 1].n_rows} rows")
+    if self_loops and graphs[0].n_rows != graphs[-1].n_cols:
+        raise ValueError(f"compose: self_loops needs a square result, got {graphs[0].n_rows} x {graphs[-1].n_cols}")
+    for k, g in enumerate(graphs):
+        ops.require_gpu(g.rowptr, f"compose: graphs[{k}]")
+    if len(graphs) == 1:       # no product: the graph itself, sorted and unique (+ I)
+        g = graphs[0]
+        rows = torch.repeat_interleave(torch.arange(g.n_rows, device=g.device), g.degrees())
+        key = rows * g.n_cols + g.colidx.long()
+        if self_loops:
+            key = torch.cat([key, torch.arange(g.n_rows, device=g.device) * (g.n_cols + 1)])
+        return _from_keys(torch.unique(key), g.n_rows, g.n_cols, g.device)
+    c = graphs[0]
+    for k, g in enumerate(graphs[1:]):
+        c = ops.csr_bool_matmul(c, g, diag=self_loops and k == len(graphs) - 2)
+    return c
+
+
+def plan(relations: dict, metapath: str) -> dict:
+    """How `metapath` is evaluated (host only, no graph is touched): dict(hops=[(pair, transposed)] -- one per hop,
+    the relation it uses and whether that is the transpose of the reverse pair --, split = k or None, sizes = nodes per
+    type).  split = k: the path is a palindrome of odd length whose second half is made only of derived transposes,
+    so it equals H Hᵀ with H the product of its first k hops.  Raises ValueError for a pair given in both
+    directions, a missing pair, type sizes that disagree between relations, or malformed keys / paths."""
+    if not isinstance(metapath, str) or len(metapath) < 2:
+        raise ValueError(f"meta-path {metapath!r}: expected a string of at least two one-letter node types")
+    sizes = {}
+    for key, g in relations.items():
+        if not (isinstance(key, str) and len(key) == 2):
+            raise ValueError(f"relation key {key!r}: expected an ordered pair of one-letter node types such as 'PA'")
+        if not isinstance(g, CSRGraph):
+            raise ValueError(f"relations[{key!r}] is a {type(g)}, expected a CSRGraph (see relation())")
+        if key[0] != key[1] and key[::-1] in relations:
+            raise ValueError(f"relation {key!r} is given in both directions ({key!r} and {key[::-1]!r}): give one, "
+                             "the other hop runs on its transpose")
+        for t, n in ((key[0], g.n_rows), (key[1], g.n_cols)):
+            if sizes.setdefault(t, n) != n:
+                raise ValueError(f"type {t!r} has {sizes[t]} nodes in one relation and {n} in {key!r}")
+    hops = []
+    for x, y in zip(metapath, metapath[1:]):
+        if x + y in relations:
+            hops.append((x + y, False))
+        elif y + x in relations:
+            hops.append((y + x, True))
+        else:
+            raise ValueError(f"meta-path {metapath!r}: no relation between {x!r} and {y!r} (give {x + y!r} or {y + x!r})")
+    split = None
+    if len(metapath) % 2 == 1 and metapath == metapath[::-1] and all(t for _, t in hops[len(hops) // 2:]):
+        split = len(hops) // 2
+    return dict(hops=hops, split=split, sizes=sizes)
+
+
+def metapath_graph(relations: dict, metapath: str, self_loops: bool = True) -> CSRGraph:
+    """The meta-path graph of `metapath` (e.g. "APCPA") over typed `relations` ({"AP": CSRGraph, "PC": ...}):
+    entry (i, j) iff an instance of the path leads from i to j; with self_loops (the default, as adj_to_bias /
+    adj_to_graph add I) also (i, i).  A palindromic path whose second half runs on derived transposes is evaluated as
+    H Hᵀ, H = the product over its first half (AP PC for APCPA, AP for APA) -- the same graph as the chain left to
+    right, without the chain's wide intermediates; any other path left to right (compose)."""
+    p = plan(relations, metapath)
+    if self_loops and metapath[0] != metapath[-1]:
+        raise ValueError(f"meta-path {metapath!r}: self_loops needs a path that ends on the type it starts from")
+    for key, _ in p["hops"]:
+        ops.require_gpu(relations[key].rowptr, f"relations[{key!r}]")
+    graphs = [relations[k].transpose() if t else relations[k] for k, t in p["hops"]]
+    if p["split"] is None:
+        return compose(graphs, self_loops=self_loops)
+    k = p["split"]
+    h = compose(graphs[:k]) if k > 1 else graphs[0]
+    return ops.csr_bool_matmul(h, h.transpose(), diag=self_loops)

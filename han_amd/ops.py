@@ -725,3 +725,58 @@ def l2_half_sumsq(param):
     _lib.check(lib.han_l2_half_sumsq(param.data_ptr(), param.numel(), out.data_ptr(),
                                      ws.data_ptr(), ws.numel(), _stream()), "han_l2_half_sumsq")
     return out
+
+
+# ------------------------------------------------------- K0: meta-path graphs
+SPGEMM_DIAG = 1            # HAN_SPGEMM_DIAG
+SPGEMM_MAX_SHORT = 4096    # HAN_SPGEMM_MAX_SHORT
+SPGEMM_MAX_TILE = 1 << 19  # HAN_SPGEMM_MAX_TILE
+# rows with at most SPGEMM_SHORT candidates are sorted in LDS by one wave, the others marked in an LDS bit map of
+# SPGEMM_TILE columns by a workgroup (profiles/r05_metapath_sweep.jsonl)
+SPGEMM_SHORT = 1024
+SPGEMM_TILE = 1 << 17
+SPGEMM_STATS: list | None = None   # tools/metapath_bench.py: csr_bool_matmul appends one dict of counts per product
+
+
+def csr_bool_matmul(A: CSRGraph, B: CSRGraph, diag: bool = False) -> CSRGraph:
+    """Boolean product C = A B (han_spgemm_*): entry (i, j) iff some l has (i, l) in A and (l, j) in B, and with
+    diag=True also (i, i) (square products).  A and B may hold unsorted or repeated columns; their values are
+    ignored.  C has strictly increasing columns in every row and values None.  Row bounds, count and fill launches,
+    the rows binned by their bound on the device; the one host sync reads nnz(C)."""
+    lib = _lib.load()
+    for g, name in ((A, "A"), (B, "B")):
+        if not isinstance(g, CSRGraph):
+            raise ValueError(f"{name}: expected a CSRGraph, got {type(g)}")
+        require_gpu(g.rowptr, name)
+    if A.device != B.device:
+        raise ValueError(f"A on {A.device}, B on {B.device}")
+    if A.n_cols != B.n_rows:
+        raise ValueError(f"A has {A.n_cols} columns, B has {B.n_rows} rows")
+    if diag and A.n_rows != B.n_cols:
+        raise ValueError(f"diag needs a square product, got {A.n_rows} x {B.n_cols}")
+    n, dev = A.n_rows, A.device
+    if n == 0:
+        return CSRGraph(torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
+                        B.n_cols, validate=False)
+    flags = SPGEMM_DIAG if diag else 0
+    st = _stream()
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    ub = torch.empty(n, dtype=torch.int64, device=dev)
+    _lib.check(lib.han_spgemm_row_bounds(A.rowptr.data_ptr(), ptr(A.colidx), B.rowptr.data_ptr(), n, A.n_cols, flags,
+                                         ub.data_ptr(), st), "han_spgemm_row_bounds")
+    # the bins, on the device: rows by decreasing bound -- the long rows first, and the heaviest rows of each bin
+    # are the first ones its persistent blocks take
+    rows = torch.sort(ub, descending=True, stable=True).indices.to(torch.int32)
+    n_long = (ub > SPGEMM_SHORT).sum().reshape(1)
+    args = (A.rowptr.data_ptr(), ptr(A.colidx), B.rowptr.data_ptr(), ptr(B.colidx), n, A.n_cols, B.n_cols,
+            rows.data_ptr(), n_long.data_ptr(), SPGEMM_SHORT, SPGEMM_TILE, flags)
+    counts = torch.empty(n, dtype=torch.int64, device=dev)
+    _lib.check(lib.han_spgemm_count(*args, counts.data_ptr(), st), "han_spgemm_count")
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=rowptr[1:])
+    nnz = int(rowptr[-1])
+    colidx = torch.empty(nnz, dtype=torch.int32, device=dev)
+    _lib.check(lib.han_spgemm_fill(*args, rowptr.data_ptr(), ptr(colidx), st), "han_spgemm_fill")
+    if SPGEMM_STATS is not None:
+        SPGEMM_STATS.append(dict(rows=n, cols=B.n_cols, nnz_a=A.nnz, nnz=nnz, candidates=ub.sum(), n_long=n_long))
+    return CSRGraph(rowptr, colidx, B.n_cols, validate=False)

@@ -241,6 +241,84 @@ def make_graph(spec, n, seed, device, rows=None):
     raise ValueError(kind)
 
 
+HETERO = {
+    # the DBLP four-area shape (4057 authors, 14 328 papers, 20 conferences, ~8 k terms): four areas of five
+    # conferences each; every author writes one paper of its area, further author slots go to authors of the paper's
+    # area by popularity ~ rank^-0.8; 12 % of the papers appear at a conference of another area; 3-6 terms per paper,
+    # popularity ~ rank^-1.1 over all terms.  Meta-path graphs (+ I) generated on the GPU: APA / APCPA / APTPA =
+    # 10 549 / 3 951 001 / 13 876 001 entries (the data set: 11 113 / 5 000 495 / 12 924 399); on the CPU (another
+    # generator) 10 411 / 3 881 329 / 13 721 909
+    "dblp-like": dict(A=4057, P=14328, C=20, T=8000),
+    # PAP at scale: three authors per paper (a repeated draw counts once), author popularity ~ rank^-0.5
+    "pap-3m": dict(P=3_000_000, A=1_000_000),
+}
+
+
+def _zipf_cdf(n: int, s: float, device) -> torch.Tensor:
+    w = torch.arange(1, n + 1, device=device, dtype=torch.float64) ** (-s)
+    c = torch.cumsum(w, 0)
+    return c / c[-1]
+
+
+def _zipf_draw(cdf: torch.Tensor, shape, gen, device) -> torch.Tensor:
+    """Ranks 0 .. len(cdf) - 1 drawn with the probabilities `cdf` accumulates (inverse CDF)."""
+    u = torch.rand(shape, generator=gen, device=device, dtype=torch.float64)
+    return torch.searchsorted(cdf, u, right=True).clamp_(max=cdf.numel() - 1)
+
+
+def hetero_relations(name: str, seed: int = 0, device="cpu"):
+    """Typed relations of a synthetic heterogeneous graph, the input of han_amd.metapath: returns (relations,
+    sizes) -- relations maps an ordered type pair to its CSRGraph (rows = nodes of the first type), sizes the node
+    count per type.  "dblp-like": {"AP", "PC", "PT"} (APA / APCPA / APTPA as in the DBLP experiments of the
+    reference); "pap-3m": {"PA"} (PAP).  Block-seeded over the papers, like the rest of this module."""
+    from .metapath import relation
+    if name not in HETERO:
+        raise ValueError(f"unknown heterogeneous workload {name!r}: expected one of {sorted(HETERO)}")
+    cfg = HETERO[name]
+    n_p, n_a = cfg["P"], cfg["A"]
+    if name == "pap-3m":
+        cdf = _zipf_cdf(n_a, 0.5, device)
+        src, dst = [], []
+        for b, lo, hi in _blocks(0, n_p):
+            gen = _block_generator(seed, 41, b, device)
+            src.append(torch.arange(b * ROW_BLOCK + lo, b * ROW_BLOCK + hi, device=device).repeat_interleave(3))
+            dst.append(_zipf_draw(cdf, (hi - lo) * 3, gen, device))
+        return {"PA": relation(torch.cat(src), torch.cat(dst), n_p, n_a)}, dict(cfg)
+    n_c, n_t, areas = cfg["C"], cfg["T"], 4
+    per_area = (n_a + areas - 1) // areas          # author a belongs to area a % 4
+    a_cdf, t_cdf = _zipf_cdf(per_area, 0.8, device), _zipf_cdf(n_t, 1.1, device)
+    ap, pc, pt = ([], []), ([], []), ([], [])
+    for b, lo, hi in _blocks(0, n_p):
+        gen = _block_generator(seed, 42, b, device)
+        pid = torch.arange(b * ROW_BLOCK + lo, b * ROW_BLOCK + hi, device=device)
+        m = pid.numel()
+        area = torch.randint(0, areas, (m,), generator=gen, device=device)
+        first = pid < n_a                          # paper p < n_a: written by author p
+        area = torch.where(first, pid % areas, area)
+        conf = area * 5 + torch.randint(0, 5, (m,), generator=gen, device=device)
+        stray = torch.rand(m, generator=gen, device=device) < 0.12
+        conf = torch.where(stray, torch.randint(0, n_c, (m,), generator=gen, device=device), conf)
+        authors = area[:, None] + areas * _zipf_draw(a_cdf, (m, 3), gen, device)
+        authors = torch.where(authors >= n_a, authors - areas, authors)
+        authors[:, 0] = torch.where(first, pid, authors[:, 0])
+        u = torch.rand(m, generator=gen, device=device)
+        n_auth = 1 + (u < 0.17).long() + (u < 0.03).long()
+        keep = torch.arange(3, device=device)[None, :] < n_auth[:, None]
+        ap[0].append(authors[keep])
+        ap[1].append(pid[:, None].expand(m, 3)[keep])
+        pc[0].append(pid)
+        pc[1].append(conf)
+        n_terms = 3 + torch.randint(0, 4, (m,), generator=gen, device=device)
+        terms = _zipf_draw(t_cdf, (m, 6), gen, device)
+        keep = torch.arange(6, device=device)[None, :] < n_terms[:, None]
+        pt[0].append(pid[:, None].expand(m, 6)[keep])
+        pt[1].append(terms[keep])
+    rel = {"AP": relation(torch.cat(ap[0]), torch.cat(ap[1]), n_a, n_p),
+           "PC": relation(torch.cat(pc[0]), torch.cat(pc[1]), n_p, n_c),
+           "PT": relation(torch.cat(pt[0]), torch.cat(pt[1]), n_p, n_t)}
+    return rel, dict(cfg)
+
+
 def features(name: str, device="cpu", n_override: int | None = None, rows=None) -> torch.Tensor:
     """The feature rows of make_workload alone (same block generators): what a rank of a node partition
     generates when it wants the features of ALL rows for the replicated projection."""

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HAN_ABI_VERSION 6
+#define HAN_ABI_VERSION 7
 
 #define HAN_E_BADARG   (-1)   /* null pointer, negative size, inconsistent shape.  The forward
                               * entry points return 0 at once for N == 0 (empty tensors may
@@ -385,6 +385,38 @@ int han_bias_row_counts(const float *bias, int64_t N, int64_t ld, int64_t *count
                         void *stream);
 int han_bias_fill_csr(const float *bias, int64_t N, int64_t ld, const int64_t *rowptr,
                       int32_t *colidx, void *stream);
+
+/* ---- K0: meta-path graphs from typed relations ------------------------------
+ * The boolean product C = A B of two CSR graphs: entry (i, j) of C is present iff some l has (i, l) in A and (l, j)
+ * in B.  A meta-path graph (APA, APCPA, ...) is such a product along its typed relations (paper-author, paper-
+ * conference, ... edge lists; han_amd/metapath.py); the reference reads them preprocessed (ex_acm3025.py:57-87).
+ * A (n_rows x n_mid): a_rowptr (n_rows+1) int64, a_colidx int32; B (n_mid x n_cols) likewise.  Their columns need not
+ * be sorted or unique; a colidx may be NULL when its graph has no entries (c_colidx likewise).  Every row of C holds
+ * strictly increasing columns.  flags: HAN_SPGEMM_DIAG also sets (i, i) (square products, n_rows == n_cols).
+ * Three launches:
+ *   han_spgemm_row_bounds: ub (n_rows) int64, ub_i = sum over l in A_i of deg_B(l), + 1 with HAN_SPGEMM_DIAG -- the
+ *       candidates of row i, an upper bound of its entries;
+ *   the caller bins the rows by ub: `rows` (n_rows int32) lists every row once, the rows with ub > short_max first,
+ *       and the device word *n_long holds their number (the binning needs no copy to the host);
+ *   han_spgemm_count: counts (n_rows) int64, the entries of every row; the caller scans them into c_rowptr (n_rows+1)
+ *       and allocates c_colidx (c_rowptr[n_rows] entries);
+ *   han_spgemm_fill: c_colidx.
+ * Rows with ub <= short_max (<= HAN_SPGEMM_MAX_SHORT) are sorted in LDS, a wave each; the others set bits in an LDS bit
+ * map of tile_cols columns (a multiple of 32, <= HAN_SPGEMM_MAX_TILE), a workgroup each, and read their candidates
+ * once per tile of [0, n_cols).  count and fill take the same rows, n_long, short_max, tile_cols and flags.       */
+#define HAN_SPGEMM_DIAG 1
+#define HAN_SPGEMM_MAX_SHORT 4096
+#define HAN_SPGEMM_MAX_TILE (1 << 19)
+int han_spgemm_row_bounds(const int64_t *a_rowptr, const int32_t *a_colidx, const int64_t *b_rowptr,
+                          int64_t n_rows, int64_t n_mid, int flags, int64_t *ub, void *stream);
+int han_spgemm_count(const int64_t *a_rowptr, const int32_t *a_colidx, const int64_t *b_rowptr,
+                     const int32_t *b_colidx, int64_t n_rows, int64_t n_mid, int64_t n_cols, const int32_t *rows,
+                     const int64_t *n_long, int64_t short_max, int64_t tile_cols, int flags, int64_t *counts,
+                     void *stream);
+int han_spgemm_fill(const int64_t *a_rowptr, const int32_t *a_colidx, const int64_t *b_rowptr,
+                    const int32_t *b_colidx, int64_t n_rows, int64_t n_mid, int64_t n_cols, const int32_t *rows,
+                    const int64_t *n_long, int64_t short_max, int64_t tile_cols, int flags,
+                    const int64_t *c_rowptr, int32_t *c_colidx, void *stream);
 
 #ifdef __cplusplus
 }

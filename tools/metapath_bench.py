@@ -1,0 +1,154 @@
+#!/usr/bin/env python3
+"""Meta-path construction on the GPU (han_amd.metapath, K0) against scipy on the same host, in the same process.
+
+One JSON line per (preset, meta-path):
+  gpu_ms        the whole metapath_graph call (relation transposes included: every timed call gets fresh relation
+                objects), HIP events around it, 2 warm-ups, median of --reps (gpu_ms_all: every rep);
+  scipy_s       the host preprocessing it replaces: the boolean sparse products of the chain left to right (the
+                reverse hops as transposes), + I, indices sorted -- single-threaded scipy; scipy_sym_s the same
+                product in the H Hᵀ form the GPU uses for palindromes;
+  nnz, candidates = sum of the row bounds ub over every product of the call, products = their number;
+  bytes_model   what the kernels must move: per product the candidate columns read twice (count + fill, 4 B each;
+                a long row once per bit-map tile), the A entries and B row pointers behind them (4 + 16 B per A
+                entry, three passes) and the per-row words (row list, bounds, counts, row pointers: 48 B per row),
+                plus 4 B per output entry;
+  exact         GPU output == scipy output (row pointers and columns, bit for bit).
+--sweep: the GPU time alone over short-row bounds S x bit-map tiles (ops.SPGEMM_SHORT / SPGEMM_TILE).
+
+    python tools/metapath_bench.py [--out FILE]
+    python tools/metapath_bench.py --sweep [--out FILE]
+    python tools/metapath_bench.py --no-scipy            # GPU only (the rocprofv3 run)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import scipy.sparse as sp
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from han_amd import metapath, ops, synth  # noqa: E402
+from han_amd.graph import CSRGraph  # noqa: E402
+
+PRESETS = {"dblp-like": ("APA", "APCPA", "APTPA"), "pap-3m": ("PAP",)}
+
+
+def fresh(rel):
+    """New relation objects over the same device arrays: no cached transposes."""
+    return {k: CSRGraph(g.rowptr, g.colidx, g.n_cols, validate=False) for k, g in rel.items()}
+
+
+def gpu_time(rel, mp, reps):
+    ts, out = [], None
+    for i in range(2 + reps):
+        r = fresh(rel)
+        out = None
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = metapath.metapath_graph(r, mp)
+        e1.record()
+        torch.cuda.synchronize()
+        if i >= 2:
+            ts.append(e0.elapsed_time(e1))
+    return out, ts
+
+
+def stats_of(rel, mp):
+    ops.SPGEMM_STATS = []
+    try:
+        metapath.metapath_graph(fresh(rel), mp)
+        torch.cuda.synchronize()
+        st = [{k: (int(v) if isinstance(v, torch.Tensor) else v) for k, v in d.items()} for d in ops.SPGEMM_STATS]
+    finally:
+        ops.SPGEMM_STATS = None
+    tiles = -(-max(d["cols"] for d in st) // ops.SPGEMM_TILE)
+    cand = sum(d["candidates"] for d in st)
+    model = sum(8 * d["candidates"] + 60 * d["nnz_a"] + 48 * d["rows"] + 4 * d["nnz"] for d in st)
+    return dict(products=len(st), candidates=cand, n_long=[d["n_long"] for d in st], bytes_model=model,
+                max_tiles=tiles)
+
+
+def to_scipy(g):
+    return sp.csr_matrix((np.ones(g.nnz, dtype=bool), g.colidx.cpu().numpy(), g.rowptr.cpu().numpy()),
+                         shape=(g.n_rows, g.n_cols))
+
+
+def scipy_build(host, hops, n, sym):
+    t0 = time.perf_counter()
+    if sym is not None:
+        h = host[hops[0][0]]
+        for key, _ in hops[1:sym]:
+            h = h @ host[key]
+        m = h @ h.T.tocsr()
+    else:
+        m = None
+        for key, t in hops:
+            r = host[key].T.tocsr() if t else host[key]
+            m = r if m is None else m @ r
+    m = sp.csr_matrix(m + sp.identity(n, dtype=bool, format="csr"))
+    m.sort_indices()
+    return m, time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--presets", default="dblp-like,pap-3m")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--no-scipy", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    out = open(args.out, "w") if args.out else None
+
+    def emit(d):
+        line = json.dumps(d)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    for preset in args.presets.split(","):
+        rel, sizes = synth.hetero_relations(preset, device=dev)
+        host = None if (args.no_scipy or args.sweep) else {k: to_scipy(g) for k, g in rel.items()}
+        for mp in PRESETS[preset]:
+            plan = metapath.plan(rel, mp)
+            if args.sweep:
+                for S in (256, 1024, 4096):
+                    for T in (1 << 15, 1 << 17, 1 << 19):
+                        ops.SPGEMM_SHORT, ops.SPGEMM_TILE = S, T
+                        _, ts = gpu_time(rel, mp, args.reps)
+                        emit(dict(preset=preset, metapath=mp, short_max=S, tile_cols=T,
+                                  gpu_ms=round(float(np.median(ts)), 4), gpu_ms_all=[round(t, 4) for t in ts]))
+                continue
+            g, ts = gpu_time(rel, mp, args.reps)
+            med = float(np.median(ts))
+            st = stats_of(rel, mp)
+            d = dict(preset=preset, metapath=mp, form="H Ht" if plan["split"] is not None else "left to right",
+                     short_max=ops.SPGEMM_SHORT, tile_cols=ops.SPGEMM_TILE, rows=g.n_rows, nnz=g.nnz,
+                     gpu_ms=round(med, 4), gpu_ms_all=[round(t, 4) for t in ts], **st,
+                     model_GBps=round(st["bytes_model"] / med / 1e6, 1))
+            if host is not None:
+                ref, t_chain = scipy_build(host, plan["hops"], g.n_rows, None)
+                d["exact"] = bool(np.array_equal(g.rowptr.cpu().numpy(), ref.indptr.astype(np.int64)) and
+                                  np.array_equal(g.colidx.cpu().numpy(), ref.indices.astype(np.int32)))
+                del ref
+                d["scipy_s"] = round(t_chain, 3)
+                if plan["split"] is not None and plan["split"] > 1:      # (split 1: the chain IS H Hᵀ)
+                    _, t_sym = scipy_build(host, plan["hops"], g.n_rows, plan["split"])
+                    d["scipy_sym_s"] = round(t_sym, 3)
+                d["speedup_vs_scipy"] = round(t_chain * 1e3 / med, 1)
+            emit(d)
+            del g
+            torch.cuda.empty_cache()
+        del rel, host
+    if out:
+        out.close()
+
+
+if __name__ == "__main__":
+    main()
