@@ -12,11 +12,9 @@
 // fp32-MFMA ridge: HBM-bound in eval, MFMA-bound in training where the per-head
 // input dropout (layers.py:18-19 sits inside the per-head call) forces one
 // masked MFMA per head per 16-column tile.
-#include "han_common.h"
+#include "han_b6.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 64;      // rows per block (forward)
 constexpr int BK = 32;      // K-step
@@ -309,26 +307,13 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(const ProjFwdArgs a_in
 }
 
 // ---------------------------------------------------------------------------------------------
-// Forward on the bf16 matrix pipe with fp32-class accuracy ("bf16 x 6").
-//
-// An fp32 number splits EXACTLY into three bf16 terms by truncation, x = hi + mid + lo (8 + 8 + 8
-// significand bits; every subtraction below is exact).  With both operands split, the six products
-//     hi*hi' + hi*mid' + mid*hi' + hi*lo' + lo*hi' + mid*mid'
-// (each bf16 x bf16 product is exact in the fp32 accumulator) leave out only mid*lo', lo*mid', lo*lo':
-// < 2^-23 of |x w| per term, the size of an fp32 rounding -- against 6 MFMAs of
-// v_mfma_f32_16x16x32_bf16 (16 cycles each, K = 32) where the exact-fp32 pipe needs 8
-// v_mfma_f32_16x16x4_f32 of 32 cycles: 2.7x less matrix time, and the per-head input-dropout masks
-// (layers.py:18-19; two heads per 16-column tile at F' = 8, so every tile is issued twice) become
-// packed 16-bit ANDs on the A fragments instead of fp32 selects.
+// Forward on the bf16 matrix pipe with fp32-class accuracy ("bf16 x 6": the exact 3-way split and the six
+// products of han_b6.h).  The per-head input-dropout masks (layers.py:18-19; two heads per 16-column tile at
+// F' = 8, so every tile is issued twice) become packed 16-bit ANDs on the A fragments instead of fp32 selects.
 // Block: 128 rows x all 64 columns, K-step 32; X / W tiles are split while they are staged into LDS
 // (X row-major [row][k], W transposed [col][k], 96-B rows) so that a lane's 8 k-values are one
 // 16-B read.  DROP is built for F' = 8 (the reference shape); without dropout any head shape runs.
 // ---------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int B6_ROWS = 128;             // rows per block
 constexpr int B6_LDB = 64;               // bytes per LDS row: 32 bf16, NO padding, 16-byte slots XOR-swizzled (b6_swz)
 constexpr int B6_XBYTES = B6_ROWS * B6_LDB;
@@ -348,21 +333,6 @@ __device__ __forceinline__ int b6_swz(int row) { return (0x1320 >> (((row >> 2) 
 // byte offset of 16-byte slot `sl` of row `row` inside a tile
 __device__ __forceinline__ int b6_off(int row, int sl) { return row * B6_LDB + ((sl ^ b6_swz(row)) << 4); }
 
-// x == h + m + l exactly; each term has <= 8 significand bits (its low 16 bits are zero)
-__device__ __forceinline__ void b6_split(float x, uint32_t &h, uint32_t &m, uint32_t &l) {
-    h = __float_as_uint(x) & 0xFFFF0000u;
-    const float r1 = x - __uint_as_float(h);
-    m = __float_as_uint(r1) & 0xFFFF0000u;
-    l = __float_as_uint(r1 - __uint_as_float(m));
-}
-// two truncated terms -> one packed bf16 pair (element 0 in the low half)
-__device__ __forceinline__ uint32_t b6_pack(uint32_t e0, uint32_t e1) {
-    return __builtin_amdgcn_perm(e1, e0, 0x07060302u);
-}
-__device__ __forceinline__ f32x4 b6_mfma(const i32x4 &a, const i32x4 &b, const f32x4 &c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c,
-                                                   0, 0, 0);
-}
 // per 16-bit field f of w: 0xFFFF if f < thr else 0 (thr < 2^16 in both halves of `thr2`):
 // saturating thr - f is non-zero exactly when f < thr; min(.,1) -> 0/1; 0 - that -> 0 / 0xFFFF
 // (three packed 16-bit instructions for two fields)
@@ -373,6 +343,22 @@ __device__ __forceinline__ uint32_t b6_keep_masks(uint32_t w, uint32_t thr2, uin
     asm("v_pk_min_u16 %0, %1, %2" : "=v"(m) : "v"(s), "v"(one2));
     asm("v_pk_sub_u16 %0, 0, %1" : "=v"(s) : "v"(m));
     return s;
+}
+
+// X tile staging: four consecutive k-values of a row (one float4 of the tile, `idx` = row * 8 + k / 4; zeros when
+// !ok) are split, packed and stored as 8-byte pieces into the swizzled rows of the term images, `xb` bytes apart
+// (a bf16 X is its own high term: one image)
+template <bool XBF>
+__device__ __forceinline__ void b6_stage_x4(unsigned char *Xs, int xb, int idx, bool ok, const float4_t &x) {
+    const int off = b6_off(idx >> 3, (idx & 7) >> 1) + (idx & 1) * 8;
+    uint32_t h[4], m[4], l[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) han_b6_split(ok ? x[e] : 0.f, h[e], m[e], l[e]);
+    *reinterpret_cast<uint2 *>(Xs + off) = make_uint2(han_b6_pack(h[0], h[1]), han_b6_pack(h[2], h[3]));
+    if (!XBF) {
+        *reinterpret_cast<uint2 *>(Xs + xb + off) = make_uint2(han_b6_pack(m[0], m[1]), han_b6_pack(m[2], m[3]));
+        *reinterpret_cast<uint2 *>(Xs + 2 * xb + off) = make_uint2(han_b6_pack(l[0], l[1]), han_b6_pack(l[2], l[3]));
+    }
 }
 
 // W (P x F x 64 fp32) -> the LDS-ready image the bf16 x 6 kernels copy per K-step: [K-step kt][meta-path P][term 3][column 64][64 B],
@@ -392,12 +378,12 @@ __global__ __launch_bounds__(256) void project_wimage_kernel(const float *W, uns
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int k = kt * 32 + kq * 4 + j;
-        b6_split(k < F ? Wp[(int64_t)k * HAN_D + col] : 0.f, h[j], m[j], l[j]);
+        han_b6_split(k < F ? Wp[(int64_t)k * HAN_D + col] : 0.f, h[j], m[j], l[j]);
     }
     unsigned char *dst = img + ((int64_t)kt * P + p) * B6_WTILE + b6_off(col, kq >> 1) + (kq & 1) * 8;
-    *reinterpret_cast<uint2 *>(dst) = make_uint2(b6_pack(h[0], h[1]), b6_pack(h[2], h[3]));
-    *reinterpret_cast<uint2 *>(dst + B6_WBYTES) = make_uint2(b6_pack(m[0], m[1]), b6_pack(m[2], m[3]));
-    *reinterpret_cast<uint2 *>(dst + 2 * B6_WBYTES) = make_uint2(b6_pack(l[0], l[1]), b6_pack(l[2], l[3]));
+    *reinterpret_cast<uint2 *>(dst) = make_uint2(han_b6_pack(h[0], h[1]), han_b6_pack(h[2], h[3]));
+    *reinterpret_cast<uint2 *>(dst + B6_WBYTES) = make_uint2(han_b6_pack(m[0], m[1]), han_b6_pack(m[2], m[3]));
+    *reinterpret_cast<uint2 *>(dst + 2 * B6_WBYTES) = make_uint2(han_b6_pack(l[0], l[1]), han_b6_pack(l[2], l[3]));
 }
 
 // NW = waves per block (the block always owns 128 rows): 8 waves of one 16-row tile each keep the kernel
@@ -483,16 +469,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void project_fwd_b6_kerne
 #pragma unroll
         for (int i = 0; i < XV; ++i) {
             const int idx = tid + NT * i;
-            const int off = b6_off(idx >> 3, (idx & 7) >> 1) + (idx & 1) * 8;
-            const bool ok = row0 + (idx >> 3) < a.N && k0 + (idx & 7) * 4 < a.F;
-            uint32_t h[4], m[4], l[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) b6_split(ok ? xr[i][e] : 0.f, h[e], m[e], l[e]);
-            *reinterpret_cast<uint2 *>(Xs + off) = make_uint2(b6_pack(h[0], h[1]), b6_pack(h[2], h[3]));
-            if (!XBF) {
-                *reinterpret_cast<uint2 *>(Xs + B6_XBYTES + off) = make_uint2(b6_pack(m[0], m[1]), b6_pack(m[2], m[3]));
-                *reinterpret_cast<uint2 *>(Xs + 2 * B6_XBYTES + off) = make_uint2(b6_pack(l[0], l[1]), b6_pack(l[2], l[3]));
-            }
+            b6_stage_x4<XBF>(Xs, B6_XBYTES, idx, row0 + (idx >> 3) < a.N && k0 + (idx & 7) * 4 < a.F, xr[i]);
         }
 #pragma unroll
         for (int i = 0; i < WU; ++i) *reinterpret_cast<uint2 *>(Ws + 8 * (tid + NT * i)) = wq[i];      // straight copy
@@ -515,16 +492,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void project_fwd_b6_kerne
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     const i32x4 b0 = bfrag(t, 0), b1 = bfrag(t, 1), b2 = bfrag(t, 2);
-                    f32x4 c = acc[m][t][0];
-                    if (!XBF) {
-                        c = b6_mfma(af[1], b1, c);      // small terms first
-                        c = b6_mfma(af[2], b0, c);
-                        c = b6_mfma(af[1], b0, c);
-                    }
-                    c = b6_mfma(af[0], b2, c);
-                    c = b6_mfma(af[0], b1, c);
-                    c = b6_mfma(af[0], b0, c);
-                    acc[m][t][0] = c;
+                    acc[m][t][0] = han_b6_chain_k1<XBF>(af, b0, b1, b2, acc[m][t][0]);
                 }
             } else {
                 // keep masks of this lane's 8 elements (row nglob, k = k0 + 8*l4 + j), four heads at a time:
@@ -563,16 +531,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void project_fwd_b6_kerne
                             for (int s3 = 0; s3 < NX; ++s3) am[s3][i] = af[s3][i] & (int)pm;
                         }
                         const i32x4 b0 = bfrag(t, 0), b1 = bfrag(t, 1), b2 = bfrag(t, 2);
-                        f32x4 cc = acc[m][t][hh];
-                        if (!XBF) {
-                            cc = b6_mfma(am[1], b1, cc);
-                            cc = b6_mfma(am[2], b0, cc);
-                            cc = b6_mfma(am[1], b0, cc);
-                        }
-                        cc = b6_mfma(am[0], b2, cc);
-                        cc = b6_mfma(am[0], b1, cc);
-                        cc = b6_mfma(am[0], b0, cc);
-                        acc[m][t][hh] = cc;
+                        acc[m][t][hh] = han_b6_chain_k1<XBF>(am, b0, b1, b2, acc[m][t][hh]);
                     }
                 }
                 // 16 contiguous lanes hold the same 8-byte piece (k0 & 96) / 8 + l4 of 16 consecutive rows: XOR-ing the
@@ -707,16 +666,7 @@ __global__ __launch_bounds__(512) void project_fwd_b6_multi_kernel(const ProjMul
 #pragma unroll
         for (int i = 0; i < 2 * MT; ++i) {
             const int idx = tid + NT * i;
-            const int off = b6_off(idx >> 3, (idx & 7) >> 1) + (idx & 1) * 8;
-            const bool ok = row0 + (idx >> 3) < a.N && k0 + (idx & 7) * 4 < a.F;
-            uint32_t h[4], m[4], l[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) b6_split(ok ? xr[i][e] : 0.f, h[e], m[e], l[e]);
-            *reinterpret_cast<uint2 *>(Xs + off) = make_uint2(b6_pack(h[0], h[1]), b6_pack(h[2], h[3]));
-            if (!XBF) {
-                *reinterpret_cast<uint2 *>(Xs + XB + off) = make_uint2(b6_pack(m[0], m[1]), b6_pack(m[2], m[3]));
-                *reinterpret_cast<uint2 *>(Xs + 2 * XB + off) = make_uint2(b6_pack(l[0], l[1]), b6_pack(l[2], l[3]));
-            }
+            b6_stage_x4<XBF>(Xs, XB, idx, row0 + (idx >> 3) < a.N && k0 + (idx & 7) * 4 < a.F, xr[i]);
         }
 #pragma unroll
         for (int i = 0; i < WU; ++i) *reinterpret_cast<uint2 *>(Ws + 8 * (tid + NT * i)) = wq[i];      // straight copy of the images' K-step
@@ -736,18 +686,7 @@ __global__ __launch_bounds__(512) void project_fwd_b6_multi_kernel(const ProjMul
             const i32x4 b1 = *reinterpret_cast<const i32x4 *>(bp + B6_WBYTES);
             const i32x4 b2 = *reinterpret_cast<const i32x4 *>(bp + 2 * B6_WBYTES);
 #pragma unroll
-            for (int m = 0; m < MT; ++m) {
-                f32x4 c = acc[m][t];
-                if (!XBF) {
-                    c = b6_mfma(af[m][1], b1, c);      // small terms first
-                    c = b6_mfma(af[m][2], b0, c);
-                    c = b6_mfma(af[m][1], b0, c);
-                }
-                c = b6_mfma(af[m][0], b2, c);
-                c = b6_mfma(af[m][0], b1, c);
-                c = b6_mfma(af[m][0], b0, c);
-                acc[m][t] = c;
-            }
+            for (int m = 0; m < MT; ++m) acc[m][t] = han_b6_chain_k1<XBF>(af[m], b0, b1, b2, acc[m][t]);
         }
     }
     // epilogue: C/D layout col = lane & 15, row = (lane >> 4) * 4 + reg

@@ -28,11 +28,9 @@
 //
 // Roofline: MFMA fp32 (155 TF): forward 2*R*64*A flop = 65.5 GF at N = 1M, P = 4
 // (0.42 ms at peak), backward 3x that; the M / Z / dM streams are 1-2 GB (HBM, ~0.3 ms).
-#include "han_common.h"
+#include "han_b6.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float fast_tanh(float x) {
     // 1 - 2/(1+e^{2x}) with v_exp_f32 + v_rcp_f32 (a plain or "fast" division expands to
@@ -58,6 +56,88 @@ __device__ __forceinline__ float node_xmax(float v) {
     return v;
 }
 
+// b_omega / u_omega of this lane's column in each of the TA 16-column tiles from column `col` on
+template <int TA>
+__device__ __forceinline__ void load_bu(const float *bw, const float *uw, int col, float (&bcol)[TA], float (&ucol)[TA]) {
+#pragma unroll
+    for (int t = 0; t < TA; ++t) {
+        bcol[t] = bw[col + 16 * t];
+        ucol[t] = uw[col + 16 * t];
+    }
+}
+
+// Score of the accumulator's row `reg` (row 4*l4 + reg of the tile): s = sum_a u_a tanh(pre_a + b_a); every lane of
+// the 16-lane group gets the sum.
+template <int TA>
+__device__ __forceinline__ float row_score(const f32x4 (&acc)[TA], int reg, const float (&bcol)[TA],
+                                           const float (&ucol)[TA]) {
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < TA; ++t) s += fast_tanh(acc[t][reg] + bcol[t]) * ucol[t];
+    return han_row16_sum(s);
+}
+
+// The end of the wave-local forward: softmax over the P scores of a node, Z = sum_p beta_p M_p, and the Z / beta
+// stores.  sc = the scores of this lane group's rows r0 + 4*l4 .. + 3, mz = those rows (lane = features 4*l15 .. + 3).
+template <int P>
+__device__ __forceinline__ void wave_node_softmax(const float (&sc)[4], const float4_t (&mz)[4], int64_t r0, int64_t R,
+                                                  int l15, int l4, float *Z, float *beta) {
+    if constexpr (P <= 4) {
+#pragma unroll
+        for (int k = 0; k < 4 / P; ++k) {       // the 4/P nodes of this lane group
+            const int64_t row = r0 + 4 * l4 + k * P;
+            if (row < R) {
+                float mx = sc[k * P];
+#pragma unroll
+                for (int p = 1; p < P; ++p) mx = fmaxf(mx, sc[k * P + p]);
+                float e[P], den = 0.f;
+#pragma unroll
+                for (int p = 0; p < P; ++p) { e[p] = __expf(sc[k * P + p] - mx); den += e[p]; }
+                const float inv = 1.f / den;
+                float4_t z = {0.f, 0.f, 0.f, 0.f};
+                float mine = 0.f;
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    const float bp = e[p] * inv;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) z[c] += bp * mz[k * P + p][c];
+                    mine = (l15 == p) ? bp : mine;
+                }
+                const int64_t node = row / P;
+                *reinterpret_cast<float4_t *>(Z + node * 64 + 4 * l15) = z;
+                if (l15 < P) beta[node * P + l15] = mine;
+            }
+        }
+    } else {
+        // P = 8 / 16: the node's rows sit in P/4 lane groups; every lane takes part in the
+        // cross-group exchanges (nodes are aligned, so a valid node never mixes with padding)
+        float mx = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
+        mx = node_xmax<P>(mx);
+        float e[4], den = 0.f;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) { e[reg] = __expf(sc[reg] - mx); den += e[reg]; }
+        den = node_xsum<P>(den);
+        const float inv = 1.f / den;
+        float4_t z = {0.f, 0.f, 0.f, 0.f};
+        float mine = 0.f;
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            const float bp = e[reg] * inv;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) z[c] += bp * mz[reg][c];
+            mine = (l15 == reg) ? bp : mine;
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) z[c] = node_xsum<P>(z[c]);
+        const int64_t row = r0 + 4 * l4;
+        if (row < R) {
+            if (l4 % (P / 4) == 0) *reinterpret_cast<float4_t *>(Z + (row / P) * 64 + 4 * l15) = z;
+            if (l15 < 4) beta[row + l15] = mine;      // beta is (N,P) flat == row index
+        }
+    }
+}
+
+
 template <int CA>
 __global__ __launch_bounds__(256) void sem_attn_fwd_kernel(const float *__restrict__ M, const float *Wg,
                                                            const float *bw, const float *uw, float *Z,
@@ -72,11 +152,7 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_kernel(const float *__restri
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     float bcol[TA], ucol[TA];
-#pragma unroll
-    for (int t = 0; t < TA; ++t) {
-        bcol[t] = bw[16 * t + l15];
-        ucol[t] = uw[16 * t + l15];
-    }
+    load_bu<TA>(bw, uw, l15, bcol, ucol);
     __syncthreads();
     const int NB = ROWS / P;
     const int64_t nchunks = (N + NB - 1) / NB;
@@ -103,10 +179,7 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_kernel(const float *__restri
             }
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
-                float s = 0.f;
-#pragma unroll
-                for (int t = 0; t < TA; ++t) s += fast_tanh(acc[t][reg] + bcol[t]) * ucol[t];
-                s = han_row16_sum(s);
+                const float s = row_score<TA>(acc, reg, bcol, ucol);
                 if (l15 == 0) sc[buf * ROWS + 16 * w + 4 * l4 + reg] = s;
             }
         }
@@ -152,11 +225,7 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_wave_kernel(const float *__r
     for (int i = threadIdx.x; i < 64 * A; i += 256) smem[(i / A) * WLD + (i % A)] = Wg[i];
     __syncthreads();
     float bcol[TA], ucol[TA];
-#pragma unroll
-    for (int t = 0; t < TA; ++t) {
-        bcol[t] = bw[16 * t + l15];
-        ucol[t] = uw[16 * t + l15];
-    }
+    load_bu<TA>(bw, uw, l15, bcol, ucol);
     const int64_t R = N * P;
     const int64_t ntiles = (R + 15) / 16;
     const int64_t tstride = (int64_t)gridDim.x * 4;
@@ -197,112 +266,59 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_wave_kernel(const float *__r
         }
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks) afrag[ks] = anext[ks];
-        float sc[4];
+        float sc[4];      // every lane of the group holds the score of row 4*l4 + reg
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            float s = 0.f;
-#pragma unroll
-            for (int t = 0; t < TA; ++t) s += fast_tanh(acc[t][reg] + bcol[t]) * ucol[t];
-            s = han_row16_sum(s);
-            sc[reg] = s;     // every lane of the group holds the score of row 4*l4 + reg
-        }
-        if constexpr (P <= 4) {
-#pragma unroll
-            for (int k = 0; k < 4 / P; ++k) {       // the 4/P nodes of this lane group
-                const int64_t row = r0 + 4 * l4 + k * P;
-                if (row < R) {
-                    float mx = sc[k * P];
-#pragma unroll
-                    for (int p = 1; p < P; ++p) mx = fmaxf(mx, sc[k * P + p]);
-                    float e[P], den = 0.f;
-#pragma unroll
-                    for (int p = 0; p < P; ++p) { e[p] = __expf(sc[k * P + p] - mx); den += e[p]; }
-                    const float inv = 1.f / den;
-                    float4_t z = {0.f, 0.f, 0.f, 0.f};
-                    float mine = 0.f;
-#pragma unroll
-                    for (int p = 0; p < P; ++p) {
-                        const float bp = e[p] * inv;
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) z[c] += bp * mz[k * P + p][c];
-                        mine = (l15 == p) ? bp : mine;
-                    }
-                    const int64_t node = row / P;
-                    *reinterpret_cast<float4_t *>(Z + node * 64 + 4 * l15) = z;
-                    if (l15 < P) beta[node * P + l15] = mine;
-                }
-            }
-        } else {
-            // P = 8 / 16: the node's rows sit in P/4 lane groups; every lane takes part in the
-            // cross-group exchanges (nodes are aligned, so a valid node never mixes with padding)
-            float mx = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
-            mx = node_xmax<P>(mx);
-            float e[4], den = 0.f;
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) { e[reg] = __expf(sc[reg] - mx); den += e[reg]; }
-            den = node_xsum<P>(den);
-            const float inv = 1.f / den;
-            float4_t z = {0.f, 0.f, 0.f, 0.f};
-            float mine = 0.f;
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const float bp = e[reg] * inv;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) z[c] += bp * mz[reg][c];
-                mine = (l15 == reg) ? bp : mine;
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) z[c] = node_xsum<P>(z[c]);
-            const int64_t row = r0 + 4 * l4;
-            if (row < R) {
-                if (l4 % (P / 4) == 0) *reinterpret_cast<float4_t *>(Z + (row / P) * 64 + 4 * l15) = z;
-                if (l15 < 4) beta[row + l15] = mine;      // beta is (N,P) flat == row index
-            }
-        }
+        for (int reg = 0; reg < 4; ++reg) sc[reg] = row_score<TA>(acc, reg, bcol, ucol);
+        wave_node_softmax<P>(sc, mz, r0, R, l15, l4, Z, beta);
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-// The wave-local forward on the bf16 matrix pipe with fp32-class accuracy (the "bf16 x 6" scheme of
-// project.hip): M rows and Womega are split EXACTLY into three bf16 terms (truncation), six products
-// per K = 32 step replace sixteen v_mfma_f32_16x16x4_f32 per 64-deep row -- 12 MFMAs of 16 cycles
-// instead of 16 of 32 per column tile.  Womega is split once per block into LDS, transposed
-// ([term][a][k], 144-B rows) so that a lane's 8 k-values are one 16-B read; a lane loads ITS 16 k-values
-// of its row as four 16-byte loads (one tile ahead) and splits them in registers.  Everything after
-// the contraction (tanh, score dot, per-node softmax, weighted sum) is the fp32 kernel's.
+// The wave-local forward on the bf16 matrix pipe with fp32-class accuracy (the "bf16 x 6" scheme of han_b6.h):
+// M rows and Womega are split EXACTLY into three bf16 terms, six products per K = 32 step replace sixteen
+// v_mfma_f32_16x16x4_f32 per 64-deep row -- 12 MFMAs of 16 cycles instead of 16 of 32 per column tile.
+// Womega is split once per block into LDS, transposed ([term][a][k]) so that a lane's 8 k-values are one 16-B
+// read; a lane loads ITS 16 k-values of its row as four 16-byte loads (one tile ahead) and splits them in
+// registers.  Everything after the contraction (tanh, score dot, per-node softmax, weighted sum) is the fp32 kernel's.
 // ---------------------------------------------------------------------------------------------
-typedef __bf16 sa_bf16x8 __attribute__((ext_vector_type(8)));
-typedef int sa_i32x4 __attribute__((ext_vector_type(4)));
-typedef float float2_t __attribute__((ext_vector_type(2)));
 constexpr int SA_WLDB = 160;     // bytes per LDS row of the transposed, split Womega: 64 bf16 + 32 B -- with rows of
                                  // 160 B a ds_read_b128 lane group (tools/lds_banks.py) lands on 64 different banks
 
-__device__ __forceinline__ void sa_split(float x, uint32_t &h, uint32_t &m, uint32_t &l) {
-    h = __float_as_uint(x) & 0xFFFF0000u;             // x == h + m + l exactly (8 + 8 + 8 significand bits)
-    const float r1 = x - __uint_as_float(h);
-    m = __float_as_uint(r1) & 0xFFFF0000u;
-    l = __float_as_uint(r1 - __uint_as_float(m));
-}
-__device__ __forceinline__ uint32_t sa_pack(uint32_t e0, uint32_t e1) { return __builtin_amdgcn_perm(e1, e0, 0x07060302u); }
-__device__ __forceinline__ f32x4 sa_mfma(const sa_i32x4 &a, const sa_i32x4 &b, const f32x4 &c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(sa_bf16x8, a), __builtin_bit_cast(sa_bf16x8, b),
-                                                   c, 0, 0, 0);
-}
-// 8 consecutive floats -> the three packed bf16x8 fragments.  Two values at a time: the two subtractions of the
-// split are packed (v_pk_add_f32), 4.5 instead of 5.5 vector instructions per value.
-__device__ __forceinline__ void sa_split8(const float (&v)[8], sa_i32x4 &fh, sa_i32x4 &fm, sa_i32x4 &fl) {
-    typedef uint32_t sa_u32x2 __attribute__((ext_vector_type(2)));
+// Womega (64 x A, row-major [k][a]) -> the split, transposed LDS image [3][A][LDB bytes], the B operand of pre = M .
+// Womega: item (a, g) = the 8 k-values 8g..8g+7 of column a, one 16-byte chunk per term.  SWZ (rows of 128 B): chunk g
+// of row a sits at chunk g ^ ((a >> 1) & 7).
+template <int A, int NT, int LDB, bool SWZ>
+__device__ __forceinline__ void stage_w_t(const float *Wg, unsigned char *Wt) {
+    for (int it = threadIdx.x; it < A * 8; it += NT) {
+        const int acol = it % A, g = it / A;
+        float v[8];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float2_t x = {v[2 * q], v[2 * q + 1]};
-        const sa_u32x2 hb = __builtin_bit_cast(sa_u32x2, x) & 0xFFFF0000u;
-        const float2_t r1 = x - __builtin_bit_cast(float2_t, hb);
-        const sa_u32x2 mb = __builtin_bit_cast(sa_u32x2, r1) & 0xFFFF0000u;
-        const sa_u32x2 lb = __builtin_bit_cast(sa_u32x2, r1 - __builtin_bit_cast(float2_t, mb));
-        fh[q] = (int)sa_pack(hb[0], hb[1]);
-        fm[q] = (int)sa_pack(mb[0], mb[1]);
-        fl[q] = (int)sa_pack(lb[0], lb[1]);
+        for (int j = 0; j < 8; ++j) v[j] = Wg[(8 * g + j) * A + acol];
+        i32x4 f[3];
+        han_b6_split8(v, f);
+        unsigned char *dst = Wt + acol * LDB + (SWZ ? g ^ ((acol >> 1) & 7) : g) * 16;
+#pragma unroll
+        for (int s3 = 0; s3 < 3; ++s3) *reinterpret_cast<i32x4 *>(dst + s3 * A * LDB) = f[s3];
     }
+}
+// the three term fragments of a B operand in LDS: 16-byte reads `stride` bytes apart
+__device__ __forceinline__ void load_b3(const unsigned char *p, int stride, i32x4 (&b)[3]) {
+#pragma unroll
+    for (int s3 = 0; s3 < 3; ++s3) b[s3] = *reinterpret_cast<const i32x4 *>(p + s3 * stride);
+}
+// This lane's 16 k-values of its row of `tile` (row 16 tile + l15, clamped to the last row): k = 32 s + 8 l4 + j
+// (s = 0, 1; j < 8), four 16-byte loads -- and their split into the A fragments of the two K = 32 steps.
+__device__ __forceinline__ void load_arow(const float *M, int64_t tile, int64_t R, int l15, int l4, float4_t (&araw)[4]) {
+    const int64_t ra = tile * 16 + l15 < R ? tile * 16 + l15 : R - 1;
+    const float *mr = M + ra * 64 + 8 * l4;
+    araw[0] = *reinterpret_cast<const float4_t *>(mr);
+    araw[1] = *reinterpret_cast<const float4_t *>(mr + 4);
+    araw[2] = *reinterpret_cast<const float4_t *>(mr + 32);
+    araw[3] = *reinterpret_cast<const float4_t *>(mr + 36);
+}
+__device__ __forceinline__ void split_arow(const float4_t (&araw)[4], i32x4 (&af)[2][3]) {
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) han_b6_split8(araw[2 * s2], araw[2 * s2 + 1], af[s2]);
 }
 
 template <int CA, int P>
@@ -319,60 +335,23 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_wave_b6_kernel(const float *
     unsigned char *Wt = reinterpret_cast<unsigned char *>(smem);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
-    // Womega (64 x A, row-major [k][a]) -> split, transposed: item (a, g) = 8 k-values 8g..8g+7 of column a
-    for (int it = threadIdx.x; it < A * 8; it += 256) {
-        const int acol = it % A, g = it / A;
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = Wg[(8 * g + j) * A + acol];
-        sa_i32x4 fh, fm, fl;
-        sa_split8(v, fh, fm, fl);
-        unsigned char *dst = Wt + acol * FWLDB + ((g ^ ((acol >> 1) & 7)) * 16);
-        *reinterpret_cast<sa_i32x4 *>(dst) = fh;
-        *reinterpret_cast<sa_i32x4 *>(dst + A * FWLDB) = fm;
-        *reinterpret_cast<sa_i32x4 *>(dst + 2 * A * FWLDB) = fl;
-    }
+    stage_w_t<A, 256, FWLDB, true>(Wg, Wt);
     __syncthreads();
     float bcol[TA], ucol[TA];
-#pragma unroll
-    for (int t = 0; t < TA; ++t) {
-        bcol[t] = bw[16 * t + l15];
-        ucol[t] = uw[16 * t + l15];
-    }
+    load_bu<TA>(bw, uw, l15, bcol, ucol);
     const int64_t R = N * P;
     const int64_t ntiles = (R + 15) / 16;
     const int64_t tstride = (int64_t)gridDim.x * 4;
-    // this lane's 16 k-values of its row: k = 32 s + 8 l4 + j  (s = 0, 1; j < 8): four 16-byte loads
-    float4_t araw[4];
-    {
-        const int64_t t0 = (int64_t)blockIdx.x * 4 + w;
-        const int64_t ra = t0 * 16 + l15 < R ? t0 * 16 + l15 : R - 1;
-        const float *mr = M + ra * 64 + 8 * l4;
-        araw[0] = *reinterpret_cast<const float4_t *>(mr);
-        araw[1] = *reinterpret_cast<const float4_t *>(mr + 4);
-        araw[2] = *reinterpret_cast<const float4_t *>(mr + 32);
-        araw[3] = *reinterpret_cast<const float4_t *>(mr + 36);
-    }
+    float4_t araw[4];      // the contraction's A operand: this lane's 16 k-values of its row, one tile ahead
+    load_arow(M, (int64_t)blockIdx.x * 4 + w, R, l15, l4, araw);
     for (int64_t tile = (int64_t)blockIdx.x * 4 + w; tile < ntiles; tile += tstride) {
         const int64_t r0 = tile * 16;
         f32x4 acc[TA];
 #pragma unroll
         for (int t = 0; t < TA; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        sa_i32x4 af[2][3];
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const float v[8] = {araw[2 * s2][0], araw[2 * s2][1], araw[2 * s2][2], araw[2 * s2][3],
-                                araw[2 * s2 + 1][0], araw[2 * s2 + 1][1], araw[2 * s2 + 1][2], araw[2 * s2 + 1][3]};
-            sa_split8(v, af[s2][0], af[s2][1], af[s2][2]);
-        }
-        {
-            const int64_t rn = (tile + tstride) * 16 + l15;
-            const float *mr = M + (rn < R ? rn : R - 1) * 64 + 8 * l4;      // next tile, in flight under the MFMAs
-            araw[0] = *reinterpret_cast<const float4_t *>(mr);
-            araw[1] = *reinterpret_cast<const float4_t *>(mr + 4);
-            araw[2] = *reinterpret_cast<const float4_t *>(mr + 32);
-            araw[3] = *reinterpret_cast<const float4_t *>(mr + 36);
-        }
+        i32x4 af[2][3];
+        split_arow(araw, af);
+        load_arow(M, tile + tstride, R, l15, l4, araw);      // next tile, in flight under the MFMAs
         float4_t mz[4];
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
@@ -384,80 +363,17 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_wave_b6_kernel(const float *
             f32x4 c = acc[t];
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                const unsigned char *wb = Wt + (16 * t + l15) * FWLDB + (((4 * s2 + l4) ^ ((l15 >> 1) & 7)) * 16);
-                const sa_i32x4 bh = *reinterpret_cast<const sa_i32x4 *>(wb);
-                const sa_i32x4 bm = *reinterpret_cast<const sa_i32x4 *>(wb + A * FWLDB);
-                const sa_i32x4 bl = *reinterpret_cast<const sa_i32x4 *>(wb + 2 * A * FWLDB);
-                c = sa_mfma(af[s2][1], bm, c);      // small terms first
-                c = sa_mfma(af[s2][2], bh, c);
-                c = sa_mfma(af[s2][0], bl, c);
-                c = sa_mfma(af[s2][1], bh, c);
-                c = sa_mfma(af[s2][0], bm, c);
-                c = sa_mfma(af[s2][0], bh, c);
+                i32x4 b[3];
+                load_b3(Wt + (16 * t + l15) * FWLDB + (((4 * s2 + l4) ^ ((l15 >> 1) & 7)) * 16), A * FWLDB, b);
+                c = han_b6_chain_k3(af[s2], b, c);
             }
             acc[t] = c;
             __builtin_amdgcn_sched_barrier(0);      // keep one column tile's 6 fragment reads in flight, not all 48
         }
         float sc[4];
 #pragma unroll
-        for (int reg = 0; reg < 4; ++reg) {
-            float s = 0.f;
-#pragma unroll
-            for (int t = 0; t < TA; ++t) s += fast_tanh(acc[t][reg] + bcol[t]) * ucol[t];
-            s = han_row16_sum(s);
-            sc[reg] = s;
-        }
-        if constexpr (P <= 4) {
-#pragma unroll
-            for (int k = 0; k < 4 / P; ++k) {
-                const int64_t row = r0 + 4 * l4 + k * P;
-                if (row < R) {
-                    float mx = sc[k * P];
-#pragma unroll
-                    for (int p = 1; p < P; ++p) mx = fmaxf(mx, sc[k * P + p]);
-                    float e[P], den = 0.f;
-#pragma unroll
-                    for (int p = 0; p < P; ++p) { e[p] = __expf(sc[k * P + p] - mx); den += e[p]; }
-                    const float inv = 1.f / den;
-                    float4_t z = {0.f, 0.f, 0.f, 0.f};
-                    float mine = 0.f;
-#pragma unroll
-                    for (int p = 0; p < P; ++p) {
-                        const float bp = e[p] * inv;
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) z[c] += bp * mz[k * P + p][c];
-                        mine = (l15 == p) ? bp : mine;
-                    }
-                    const int64_t node = row / P;
-                    *reinterpret_cast<float4_t *>(Z + node * 64 + 4 * l15) = z;
-                    if (l15 < P) beta[node * P + l15] = mine;
-                }
-            }
-        } else {
-            float mx = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
-            mx = node_xmax<P>(mx);
-            float e[4], den = 0.f;
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) { e[reg] = __expf(sc[reg] - mx); den += e[reg]; }
-            den = node_xsum<P>(den);
-            const float inv = 1.f / den;
-            float4_t z = {0.f, 0.f, 0.f, 0.f};
-            float mine = 0.f;
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const float bp = e[reg] * inv;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) z[c] += bp * mz[reg][c];
-                mine = (l15 == reg) ? bp : mine;
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) z[c] = node_xsum<P>(z[c]);
-            const int64_t row = r0 + 4 * l4;
-            if (row < R) {
-                if (l4 % (P / 4) == 0) *reinterpret_cast<float4_t *>(Z + (row / P) * 64 + 4 * l15) = z;
-                if (l15 < 4) beta[row + l15] = mine;
-            }
-        }
+        for (int reg = 0; reg < 4; ++reg) sc[reg] = row_score<TA>(acc, reg, bcol, ucol);
+        wave_node_softmax<P>(sc, mz, r0, R, l15, l4, Z, beta);
     }
 }
 
@@ -486,10 +402,9 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_kernel(const float *__restri
     const int l15 = lane & 15, l4 = lane >> 4;
     float bcol[TA], ucol[TA], du[TA], db[TA];
     f32x4 dW[4][TA];
+    load_bu<TA>(bw, uw, l15, bcol, ucol);
 #pragma unroll
     for (int t = 0; t < TA; ++t) {
-        bcol[t] = bw[16 * t + l15];
-        ucol[t] = uw[16 * t + l15];
         du[t] = 0.f;
         db[t] = 0.f;
 #pragma unroll
@@ -661,10 +576,9 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_kernel(const float *__r
     const int l15 = lane & 15, l4 = lane >> 4;
     float bcol[TA], ucol[TA], du[TA], db[TA];
     f32x4 dW[4][TA];
+    load_bu<TA>(bw, uw, l15, bcol, ucol);
 #pragma unroll
     for (int t = 0; t < TA; ++t) {
-        bcol[t] = bw[16 * t + l15];
-        ucol[t] = uw[16 * t + l15];
         du[t] = 0.f;
         db[t] = 0.f;
 #pragma unroll
@@ -859,6 +773,33 @@ __device__ __forceinline__ int g2_col(int s, int l4) {
     else return 32 * s + 8 * l4;
 }
 
+// Womega -> the split LDS image [3][64 f][W2LDB bytes] as stored ([f][a]), the B operand of dM = dpre . Womega^T:
+// row 16 ft + i holds feature 4 i + ft, its 16-byte piece g the columns of step g / 4, lane group g % 4 (g2_col).
+template <int CA, int NT>
+__device__ __forceinline__ void stage_w_fa(const float *Wg, unsigned char *W2s) {
+    constexpr int A = 64 * CA, W2LDB = A * 2 + 32;
+    for (int it = threadIdx.x; it < 64 * (A / 8); it += NT) {
+        const int lr = it / (A / 8), g = it % (A / 8);
+        const int f = 4 * (lr & 15) + (lr >> 4);
+        const int a0 = g2_col<CA>(g >> 2, g & 3);
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = Wg[f * A + a0 + j];
+        i32x4 fr[3];
+        han_b6_split8(v, fr);
+        unsigned char *dst = W2s + lr * W2LDB + g * 16;
+#pragma unroll
+        for (int s3 = 0; s3 < 3; ++s3) *reinterpret_cast<i32x4 *>(dst + s3 * 64 * W2LDB) = fr[s3];
+    }
+}
+// G2's A fragments of K-step s2: this lane's 8 dpre values of its row of the LDS tile (`row`), columns
+// g2_col(s2, l4) .. + 7, split
+template <int CA>
+__device__ __forceinline__ void g2_afrag(const float *row, int s2, int l4, i32x4 (&a)[3]) {
+    const float *p = row + g2_col<CA>(s2, l4);
+    han_b6_split8(*reinterpret_cast<const float4_t *>(p), *reinterpret_cast<const float4_t *>(p + 4), a);
+}
+
 // The wave-local backward with G1 (recompute of pre) and G2 (dM = dpre . Womega^T) on the bf16 matrix pipe
 // (exact 3-way split, fp32-class accuracy: see sem_attn_fwd_wave_b6_kernel).  G3 (dWomega += M^T dpre) reduces over
 // ROWS, 16 per tile -- half a K = 32 step: the wave therefore works on two of its tiles per loop pass and runs G3
@@ -894,42 +835,15 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_b6_kernel(const float *
     float *bus = dp + 4 * 16 * WLD2;
     if (BU_LDS)
         for (int it = threadIdx.x; it < 2 * A; it += 256) bus[it] = it < A ? bw[it] : uw[it - A];
-    for (int it = threadIdx.x; it < A * 8; it += 256) {                 // (a, g): k-values 8g..8g+7 of column a
-        const int acol = it % A, g = it / A;
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = Wg[(8 * g + j) * A + acol];
-        sa_i32x4 fh, fm, fl;
-        sa_split8(v, fh, fm, fl);
-        unsigned char *dst = Wt + acol * SA_WLDB + g * 16;
-        *reinterpret_cast<sa_i32x4 *>(dst) = fh;
-        *reinterpret_cast<sa_i32x4 *>(dst + A * SA_WLDB) = fm;
-        *reinterpret_cast<sa_i32x4 *>(dst + 2 * A * SA_WLDB) = fl;
-    }
-    for (int it = threadIdx.x; it < 64 * (A / 8); it += 256) {          // (row, g): the g-th 16-byte piece of an LDS row
-        const int lr = it / (A / 8), g = it % (A / 8);
-        const int f = 4 * (lr & 15) + (lr >> 4);                        // row 16 ft + i holds feature 4 i + ft
-        const int a0 = g2_col<CA>(g >> 2, g & 3);                       // piece g = step g / 4, lane group g % 4
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = Wg[f * A + a0 + j];
-        sa_i32x4 fh, fm, fl;
-        sa_split8(v, fh, fm, fl);
-        unsigned char *dst = W2s + lr * W2LDB + g * 16;
-        *reinterpret_cast<sa_i32x4 *>(dst) = fh;
-        *reinterpret_cast<sa_i32x4 *>(dst + 64 * W2LDB) = fm;
-        *reinterpret_cast<sa_i32x4 *>(dst + 2 * 64 * W2LDB) = fl;
-    }
+    stage_w_t<A, 256, SA_WLDB, false>(Wg, Wt);
+    stage_w_fa<CA, 256>(Wg, W2s);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     float bcol[BU_LDS ? 1 : TA], ucol[BU_LDS ? 1 : TA], du[TA], db[TA];
     f32x4 dW[4][TA];
+    if constexpr (!BU_LDS) load_bu<TA>(bw, uw, l15, bcol, ucol);
 #pragma unroll
     for (int t = 0; t < TA; ++t) {
-        if constexpr (!BU_LDS) {
-            bcol[t] = bw[16 * t + l15];
-            ucol[t] = uw[16 * t + l15];
-        }
         du[t] = 0.f;
         db[t] = 0.f;
 #pragma unroll
@@ -972,7 +886,7 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_b6_kernel(const float *
     for (int64_t tile0 = (int64_t)blockIdx.x * 4 + w; tile0 < ntiles; tile0 += 2 * tstride) {
       f32x4 dps[TA];            // G3B: dpre of the pass's first tile, kept until the second tile's column tile t is done
       float4_t mvs[4];          // G3B: the first tile's rows
-      sa_i32x4 mf[4][3];        // G3B: G3's A fragments, M^T of both tiles (k-slot (l4, j) = tile j / 4, row 4 l4 + j % 4)
+      i32x4 mf[4][3];        // G3B: G3's A fragments, M^T of both tiles (k-slot (l4, j) = tile j / 4, row 4 l4 + j % 4)
       // the second tile of the last pass may lie past the end: its rows are clamped, beta = 0 makes every one of
       // its contributions zero and its stores are masked
 #pragma unroll
@@ -1021,7 +935,7 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_b6_kernel(const float *
             for (int ft = 0; ft < 4; ++ft) {
                 const float v[8] = {mvs[0][ft], mvs[1][ft], mvs[2][ft], mvs[3][ft],
                                     mvc[0][ft], mvc[1][ft], mvc[2][ft], mvc[3][ft]};
-                sa_split8(v, mf[ft][0], mf[ft][1], mf[ft][2]);
+                han_b6_split8(v, mf[ft]);
             }
         }
         // ---- G1: pre = M_tile . Womega
@@ -1029,12 +943,12 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_b6_kernel(const float *
 #pragma unroll
         for (int t = 0; t < TA; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
         {
-            sa_i32x4 af[2][3];     // G1's A fragments: exact 3-way bf16 split of this tile's rows
+            i32x4 af[2][3];     // G1's A fragments: exact 3-way bf16 split of this tile's rows
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 const float v[8] = {araw[2 * s2][0], araw[2 * s2][1], araw[2 * s2][2], araw[2 * s2][3],
                                     araw[2 * s2 + 1][0], araw[2 * s2 + 1][1], araw[2 * s2 + 1][2], araw[2 * s2 + 1][3]};
-                sa_split8(v, af[s2][0], af[s2][1], af[s2][2]);
+                han_b6_split8(v, af[s2][0], af[s2][1], af[s2][2]);
             }
             {
                 const int64_t rn = (tile + tstride) * 16 + l15;      // next tile's rows, in flight under the MFMAs
@@ -1054,16 +968,9 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_b6_kernel(const float *
                     f32x4 c = acc[t];
 #pragma unroll
                     for (int s2 = 0; s2 < 2; ++s2) {
-                        const unsigned char *wb = Wt + (16 * t + l15) * SA_WLDB + (32 * s2 + 8 * l4) * 2;
-                        const sa_i32x4 bh = *reinterpret_cast<const sa_i32x4 *>(wb);
-                        const sa_i32x4 bm = *reinterpret_cast<const sa_i32x4 *>(wb + A * SA_WLDB);
-                        const sa_i32x4 bl = *reinterpret_cast<const sa_i32x4 *>(wb + 2 * A * SA_WLDB);
-                        c = sa_mfma(af[s2][1], bm, c);
-                        c = sa_mfma(af[s2][2], bh, c);
-                        c = sa_mfma(af[s2][0], bl, c);
-                        c = sa_mfma(af[s2][1], bh, c);
-                        c = sa_mfma(af[s2][0], bm, c);
-                        c = sa_mfma(af[s2][0], bh, c);
+                        i32x4 b[3];
+                        load_b3(Wt + (16 * t + l15) * SA_WLDB + (32 * s2 + 8 * l4) * 2, A * SA_WLDB, b);
+                        c = han_b6_chain_k3(af[s2], b, c);
                     }
                     acc[t] = c;
                 }
@@ -1092,19 +999,10 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_b6_kernel(const float *
                     } else {
                         const float v[8] = {dps[t][0], dps[t][1], dps[t][2], dps[t][3],
                                             acc[t][0], acc[t][1], acc[t][2], acc[t][3]};
-                        sa_i32x4 dh, dm, dl;
-                        sa_split8(v, dh, dm, dl);
+                        i32x4 d[3];
+                        han_b6_split8(v, d);
 #pragma unroll
-                        for (int ft = 0; ft < 4; ++ft) {
-                            f32x4 c = dW[ft][t];
-                            c = sa_mfma(mf[ft][1], dm, c);
-                            c = sa_mfma(mf[ft][2], dh, c);
-                            c = sa_mfma(mf[ft][0], dl, c);
-                            c = sa_mfma(mf[ft][1], dh, c);
-                            c = sa_mfma(mf[ft][0], dm, c);
-                            c = sa_mfma(mf[ft][0], dh, c);
-                            dW[ft][t] = c;
-                        }
+                        for (int ft = 0; ft < 4; ++ft) dW[ft][t] = han_b6_chain_k3(mf[ft], d, dW[ft][t]);
                     }
                 } else {
 #pragma unroll
@@ -1124,25 +1022,12 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_b6_kernel(const float *
             for (int reg = 0; reg < 4; ++reg) acc2[ft][reg] = bt[reg] * dzc[reg][ft];
 #pragma unroll
         for (int s2 = 0; s2 < A / 32; ++s2) {       // K = 32 columns of the attention space per step
-            const float4_t d0 = *reinterpret_cast<const float4_t *>(mydp + l15 * WLD2 + g2_col<CA>(s2, l4));
-            const float4_t d1 = *reinterpret_cast<const float4_t *>(mydp + l15 * WLD2 + g2_col<CA>(s2, l4) + 4);
-            const float v[8] = {d0[0], d0[1], d0[2], d0[3], d1[0], d1[1], d1[2], d1[3]};
-            sa_i32x4 ah, am, al;
-            sa_split8(v, ah, am, al);
+            i32x4 a[3], b[3];
+            g2_afrag<CA>(mydp + l15 * WLD2, s2, l4, a);
 #pragma unroll
             for (int ft = 0; ft < 4; ++ft) {
-                const unsigned char *wb = W2s + (16 * ft + l15) * W2LDB + (4 * s2 + l4) * 16;
-                const sa_i32x4 bh = *reinterpret_cast<const sa_i32x4 *>(wb);
-                const sa_i32x4 bm = *reinterpret_cast<const sa_i32x4 *>(wb + 64 * W2LDB);
-                const sa_i32x4 bl = *reinterpret_cast<const sa_i32x4 *>(wb + 2 * 64 * W2LDB);
-                f32x4 c = acc2[ft];
-                c = sa_mfma(am, bm, c);
-                c = sa_mfma(al, bh, c);
-                c = sa_mfma(ah, bl, c);
-                c = sa_mfma(am, bh, c);
-                c = sa_mfma(ah, bm, c);
-                c = sa_mfma(ah, bh, c);
-                acc2[ft] = c;
+                load_b3(W2s + (16 * ft + l15) * W2LDB + (4 * s2 + l4) * 16, 64 * W2LDB, b);
+                acc2[ft] = han_b6_chain_k3(a, b, acc2[ft]);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -1215,17 +1100,19 @@ __global__ __launch_bounds__(512) void sem_attn_bwd_pair_b6_kernel(const float *
     unsigned char *Wt = reinterpret_cast<unsigned char *>(smem);        // G1 B operand: [3][A][SA_WLDB]
     unsigned char *W2s = Wt + 3 * A * SA_WLDB;                          // G2 B operand: [3][64][W2LDB]
     float *dp = reinterpret_cast<float *>(W2s + 3 * 64 * W2LDB);        // [4 pairs][16][WLD2] fp32
+    // stage_w_t / stage_w_fa written out: called from here they change this kernel's register allocation (one more
+    // spilled register at P = 2, 4) and how the compiler pairs the LDS accesses of the gradient reduction
     for (int it = threadIdx.x; it < A * 8; it += 512) {
         const int acol = it % A, g = it / A;
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = Wg[(8 * g + j) * A + acol];
-        sa_i32x4 fh, fm, fl;
-        sa_split8(v, fh, fm, fl);
+        i32x4 fh, fm, fl;
+        han_b6_split8(v, fh, fm, fl);
         unsigned char *dst = Wt + acol * SA_WLDB + g * 16;
-        *reinterpret_cast<sa_i32x4 *>(dst) = fh;
-        *reinterpret_cast<sa_i32x4 *>(dst + A * SA_WLDB) = fm;
-        *reinterpret_cast<sa_i32x4 *>(dst + 2 * A * SA_WLDB) = fl;
+        *reinterpret_cast<i32x4 *>(dst) = fh;
+        *reinterpret_cast<i32x4 *>(dst + A * SA_WLDB) = fm;
+        *reinterpret_cast<i32x4 *>(dst + 2 * A * SA_WLDB) = fl;
     }
     for (int it = threadIdx.x; it < 64 * (A / 8); it += 512) {
         const int lr = it / (A / 8), g = it % (A / 8);
@@ -1234,12 +1121,12 @@ __global__ __launch_bounds__(512) void sem_attn_bwd_pair_b6_kernel(const float *
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = Wg[f * A + a0 + j];
-        sa_i32x4 fh, fm, fl;
-        sa_split8(v, fh, fm, fl);
+        i32x4 fh, fm, fl;
+        han_b6_split8(v, fh, fm, fl);
         unsigned char *dst = W2s + lr * W2LDB + g * 16;
-        *reinterpret_cast<sa_i32x4 *>(dst) = fh;
-        *reinterpret_cast<sa_i32x4 *>(dst + 64 * W2LDB) = fm;
-        *reinterpret_cast<sa_i32x4 *>(dst + 2 * 64 * W2LDB) = fl;
+        *reinterpret_cast<i32x4 *>(dst) = fh;
+        *reinterpret_cast<i32x4 *>(dst + 64 * W2LDB) = fm;
+        *reinterpret_cast<i32x4 *>(dst + 2 * 64 * W2LDB) = fl;
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int pair = w >> 1;
@@ -1335,12 +1222,12 @@ __global__ __launch_bounds__(512) void sem_attn_bwd_pair_b6_kernel(const float *
             }
         }
         {
-            sa_i32x4 af[2][3];
+            i32x4 af[2][3];
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 const float v[8] = {araw[2 * s2][0], araw[2 * s2][1], araw[2 * s2][2], araw[2 * s2][3],
                                     araw[2 * s2 + 1][0], araw[2 * s2 + 1][1], araw[2 * s2 + 1][2], araw[2 * s2 + 1][3]};
-                sa_split8(v, af[s2][0], af[s2][1], af[s2][2]);
+                han_b6_split8(v, af[s2][0], af[s2][1], af[s2][2]);
             }
             fetch_a(tile + tstride);
 #pragma unroll
@@ -1348,16 +1235,9 @@ __global__ __launch_bounds__(512) void sem_attn_bwd_pair_b6_kernel(const float *
                 f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
-                    const unsigned char *wb = Wt + (64 * h + 16 * t + l15) * SA_WLDB + (32 * s2 + 8 * l4) * 2;
-                    const sa_i32x4 bh = *reinterpret_cast<const sa_i32x4 *>(wb);
-                    const sa_i32x4 bm = *reinterpret_cast<const sa_i32x4 *>(wb + A * SA_WLDB);
-                    const sa_i32x4 bl = *reinterpret_cast<const sa_i32x4 *>(wb + 2 * A * SA_WLDB);
-                    c = sa_mfma(af[s2][1], bm, c);
-                    c = sa_mfma(af[s2][2], bh, c);
-                    c = sa_mfma(af[s2][0], bl, c);
-                    c = sa_mfma(af[s2][1], bh, c);
-                    c = sa_mfma(af[s2][0], bm, c);
-                    c = sa_mfma(af[s2][0], bh, c);
+                    i32x4 b[3];
+                    load_b3(Wt + (64 * h + 16 * t + l15) * SA_WLDB + (32 * s2 + 8 * l4) * 2, A * SA_WLDB, b);
+                    c = han_b6_chain_k3(af[s2], b, c);
                 }
                 if (t == 0) __syncthreads();      // the pair's previous tile has been read by both of its waves
 #pragma unroll
@@ -1380,25 +1260,12 @@ __global__ __launch_bounds__(512) void sem_attn_bwd_pair_b6_kernel(const float *
         __syncthreads();                          // both halves of the pair's dpre tile are in LDS
 #pragma unroll
         for (int s2 = 0; s2 < A / 32; ++s2) {
-            const float4_t d0 = *reinterpret_cast<const float4_t *>(mydp + l15 * WLD2 + g2_col<CA>(s2, l4));
-            const float4_t d1 = *reinterpret_cast<const float4_t *>(mydp + l15 * WLD2 + g2_col<CA>(s2, l4) + 4);
-            const float v[8] = {d0[0], d0[1], d0[2], d0[3], d1[0], d1[1], d1[2], d1[3]};
-            sa_i32x4 ah, am, al;
-            sa_split8(v, ah, am, al);
+            i32x4 a[3], b[3];
+            g2_afrag<CA>(mydp + l15 * WLD2, s2, l4, a);
 #pragma unroll
             for (int f2 = 0; f2 < 2; ++f2) {
-                const unsigned char *wb = W2s + (16 * (2 * h + f2) + l15) * W2LDB + (4 * s2 + l4) * 16;
-                const sa_i32x4 bh = *reinterpret_cast<const sa_i32x4 *>(wb);
-                const sa_i32x4 bm = *reinterpret_cast<const sa_i32x4 *>(wb + 64 * W2LDB);
-                const sa_i32x4 bl = *reinterpret_cast<const sa_i32x4 *>(wb + 2 * 64 * W2LDB);
-                f32x4 c = acc2[f2];
-                c = sa_mfma(am, bm, c);
-                c = sa_mfma(al, bh, c);
-                c = sa_mfma(ah, bl, c);
-                c = sa_mfma(am, bh, c);
-                c = sa_mfma(ah, bm, c);
-                c = sa_mfma(ah, bh, c);
-                acc2[f2] = c;
+                load_b3(W2s + (16 * (2 * h + f2) + l15) * W2LDB + (4 * s2 + l4) * 16, 64 * W2LDB, b);
+                acc2[f2] = han_b6_chain_k3(a, b, acc2[f2]);
             }
         }
 #pragma unroll
@@ -1468,11 +1335,7 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_gen_kernel(const float *__re
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     float bcol[TA], ucol[TA];
-#pragma unroll
-    for (int t = 0; t < TA; ++t) {
-        bcol[t] = bw[16 * t + l15];
-        ucol[t] = uw[16 * t + l15];
-    }
+    load_bu<TA>(bw, uw, l15, bcol, ucol);
     __syncthreads();
     const int NB = ROWS / P;
     const int64_t nchunks = (N + NB - 1) / NB;
@@ -1498,10 +1361,7 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_gen_kernel(const float *__re
             }
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
-                float s = 0.f;
-#pragma unroll
-                for (int t = 0; t < TA; ++t) s += fast_tanh(acc[t][reg] + bcol[t]) * ucol[t];
-                s = han_row16_sum(s);
+                const float s = row_score<TA>(acc, reg, bcol, ucol);
                 if (l15 == 0) sc[buf * ROWS + 16 * w + 4 * l4 + reg] = s;
             }
         }
@@ -1557,10 +1417,9 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_gen_kernel(const float *__re
     const int l15 = lane & 15, l4 = lane >> 4;
     float bcol[TA], ucol[TA], du[TA], db[TA];
     f32x4 dW[DT][TA];
+    load_bu<TA>(bw, uw, a_off + l15, bcol, ucol);
 #pragma unroll
     for (int t = 0; t < TA; ++t) {
-        bcol[t] = bw[a_off + 16 * t + l15];
-        ucol[t] = uw[a_off + 16 * t + l15];
         du[t] = 0.f;
         db[t] = 0.f;
 #pragma unroll
@@ -1810,10 +1669,9 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wide_kernel(const float *__r
     const int ntile = (D - d_off) / 16 < DTC ? (D - d_off) / 16 : DTC;   // dW tiles of this chunk that exist
     float bcol[TA], ucol[TA], du[TA], db[TA];
     f32x4 dW[DTC][TA];
+    load_bu<TA>(bw, uw, a_off + l15, bcol, ucol);
 #pragma unroll
     for (int t = 0; t < TA; ++t) {
-        bcol[t] = bw[a_off + 16 * t + l15];
-        ucol[t] = uw[a_off + 16 * t + l15];
         du[t] = 0.f;
         db[t] = 0.f;
 #pragma unroll
