@@ -339,6 +339,12 @@ class MaskedBackwardPlan:
         packed = gs_local.index_select(0, self.live_idx)
         return self.part.all_gather_rows_async(packed, tag, rows_per_rank=self.per_rank)
 
+    exchange = table_async      # the table-source interface (layers.LocalTable): .graph, .gid, .exchange
+
+    @property
+    def graph(self):
+        return self.graph_t
+
 
 class HaloPlan:
     """Exchange plan of one sharded graph: which remote table rows this rank reads.
@@ -396,6 +402,8 @@ class HaloPlan:
         work = part.all_to_all_v(table[self.n_local:], packed, self.recv_splits, self.send_splits,
                                  async_op=True)
         return GatheredTable(table, work, keep=packed, comm=part.comm)
+
+    exchange = exchange_async      # the table-source interface (layers.LocalTable)
 
 
 class GatheredTable:

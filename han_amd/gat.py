@@ -90,10 +90,10 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         self.partition: NodePartition | None = None
         self.halo_plans = (None, None)        # (forward, backward) per-meta-path HaloPlan lists
         self.masked_bwd = None                # per-meta-path MaskedBackwardPlan list (HANTrainer(masked_backward=True))
-        self.path_streams = None              # one stream per meta-path (HANTrainer(use_graph=True)): layers._on_path
+        self.path_streams = None              # one stream per meta-path (HANTrainer(use_graph=True)): layers._each_path
         self.path_order = "index"             # "heavy": the per-meta-path chains of a captured epoch are issued largest graph first (layers._path_order)
         self.overlap_branch = None            # HANTrainer(overlap_eval=True): the eval forward riding in the captured training step (trainer._EvalBranch)
-        self.side_stream = None               # second stream of the eager training step on large graphs (layers._on_side):
+        self.side_stream = None               # second stream of the eager training step on large graphs (layers.NodeLevelAttention.backward):
                                               # dW of meta-path p runs beside the backward gather of meta-path p + 1
         self._graph_cache: dict = {}
         # captured-step mode (HANTrainer(use_graph=True)): a device seed word that the trainer
@@ -275,72 +275,57 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
                 self._fixed_seeds[key] = tuple(rng.next_seed() for _ in graphs)
             return self._fixed_seeds[key]
 
-        def cfg(layer, sd, **kw):
-            return {"train": train, "in_drop": float(ffd_drop), "coef_drop": float(attn_drop),
-                    "seeds": sd, "seed_dev": self.step_seed_dev if train else None,
-                    "act": act_code, "part": self.partition, "graphs_t": graphs_t, "layer": layer,
-                    "table_dtype": self.table_dtype, "plans_f": self.halo_plans[0],
-                    "plans_b": self.halo_plans[1], "xs_full": xs_full if layer == 0 else None,
-                    "masked_bwd": self.masked_bwd if (layer == 0 and train) else None,
-                    "streams": self.path_streams, "side_stream": self.side_stream, "path_order": self.path_order,
-                    "overlap": self.overlap_branch if (layer == 0 and train) else None, **kw}
+        def run(layer, sd, **kw):      # everything a node-attention call learns about how it is to run
+            first = layer == 0
+            return layers.LayerRun(
+                train=train, in_drop=float(ffd_drop), coef_drop=float(attn_drop), seeds=sd,
+                seed_dev=self.step_seed_dev if train else None, act=act_code, part=self.partition, graphs_t=graphs_t,
+                layer=layer, table_dtype=self.table_dtype, plans_f=self.halo_plans[0], plans_b=self.halo_plans[1],
+                xs_full=xs_full if first else None, masked_bwd=self.masked_bwd if (first and train) else None,
+                streams=self.path_streams, side_stream=self.side_stream, path_order=self.path_order,
+                overlap=self.overlap_branch if (first and train) else None, **kw)
 
         def layer_fwd(layer, Xin, xs_, K, FP, sink):
             """One node-attention layer: its K heads run through the 64-column K1/K2 kernels in groups of
             64 // F' heads.  A group that is not full (K*F' not a multiple of 64) is completed with
             zero-weight heads, whose output columns are exactly 0 and are cut off again; group g draws
-            its dropout masks from seed + g, head index = index inside the group."""
+            its dropout masks from seed + g, head index = index inside the group.  A head wider than a K1 / K2 row
+            (F' > 64) is a group of its own: S = ceil(F'/64) column slices (layers.WideHeadAttention)."""
             sfx = "" if layer == 0 else f"_{layer}"
             g = lambda n: getattr(self, n + sfx, None)
             W, a1, b1, a2, b2, c, Wr, br = (g(n) for n in ("W", "a1", "b1", "a2", "b2", "c", "Wr", "br"))
             sd = seeds(layer)
-            if FP > GROUP:       # heads wider than a K1 / K2 row: one head at a time, S = ceil(F'/64) column slices
-                S = -(-FP // GROUP)
-                outs, coef_acc = [], None
-                for k in range(K):
-                    cols = slice(k * FP, (k + 1) * FP)
-                    pw = lambda t: F_torch.pad(t[..., cols], (0, S * GROUP - FP)).contiguous()
-                    pa = lambda t: F_torch.pad(t[:, k], (0, S * GROUP - FP)).contiguous()
-                    gsink = [] if sink is not None else None
-                    Mk = layers.WideHeadAttention.apply(
-                        Xin, pw(W), pa(a1), b1[:, k].contiguous(), pa(a2), b2[:, k].contiguous(), pw(c),
-                        pw(Wr) if Wr is not None else None, pw(br) if br is not None else None, xs_, tuple(graphs),
-                        cfg(layer, tuple((s_ + k) & ((1 << 64) - 1) for s_ in sd), coef_sink=gsink, coef_mean=True,
-                            group=k))
-                    outs.append(Mk[:, :, :FP])
-                    if sink is not None:      # (E,) per meta-path and head
-                        coef_acc = gsink if coef_acc is None else [x + y for x, y in zip(coef_acc, gsink)]
-                if sink is not None:
-                    sink.extend(v / K for v in coef_acc)
-                return torch.cat(outs, dim=2) if len(outs) > 1 else outs[0].contiguous()
-            groups = _head_groups(K, FP)
+            wide = FP > GROUP
+            groups = [(k, k + 1) for k in range(K)] if wide else _head_groups(K, FP)
             if len(groups) == 1 and K * FP == GROUP:      # the reference shapes: no slicing, direct gradients
                 return layers.NodeLevelAttention.apply(Xin, W, a1, b1, a2, b2, c, Wr, br, xs_, tuple(graphs),
-                                                       cfg(layer, sd, coef_sink=sink, coef_mean=True))
-            FPk = _kernel_head_width(FP)          # head width the kernels run at (zero-weight columns beyond FP)
-            kg = GROUP // FPk
+                                                       run(layer, sd, coef_sink=sink, coef_mean=True))
+            fn = layers.WideHeadAttention if wide else layers.NodeLevelAttention
+            FPk = -(-FP // GROUP) * GROUP if wide else _kernel_head_width(FP)      # width a head runs at (zero-weight columns beyond FP)
+            kg = max(GROUP // FPk, 1)                                              # head slots of a group
             outs, coef_acc = [], None
             for gi, (k0, k1) in enumerate(groups):
                 nh, cols = k1 - k0, slice(k0 * FP, k1 * FP)
 
-                def pc(t):            # (..., K*FP) columns of this group -> (..., kg heads x FPk) = 64 columns
+                def pc(t):            # (..., K*FP) columns of this group -> (..., kg heads x FPk)
                     t = t[..., cols].reshape(t.shape[:-1] + (nh, FP))
-                    return F_torch.pad(t, (0, FPk - FP, 0, kg - nh)).reshape(t.shape[:-2] + (GROUP,)).contiguous()
+                    return F_torch.pad(t, (0, FPk - FP, 0, kg - nh)).reshape(t.shape[:-2] + (kg * FPk,)).contiguous()
 
-                def ph(t, per_head):  # (P,K,FP) / (P,K) -> (P,kg,FPk) / (P,kg)
-                    t = t[:, k0:k1]
+                def ph(t, per_head):  # (P,K,FP) / (P,K) -> (P,kg,FPk) / (P,kg); a wide head has no head axis
+                    if wide:
+                        return (F_torch.pad(t[:, k0], (0, FPk - FP)) if per_head else t[:, k0]).contiguous()
                     pad = (0, FPk - FP, 0, kg - nh) if per_head else (0, kg - nh)
-                    return F_torch.pad(t, pad).contiguous()
+                    return F_torch.pad(t[:, k0:k1], pad).contiguous()
                 gsink = [] if sink is not None else None
-                Mg = layers.NodeLevelAttention.apply(
+                Mg = fn.apply(
                     Xin, pc(W), ph(a1, True), ph(b1, False), ph(a2, True), ph(b2, False), pc(c),
                     pc(Wr) if Wr is not None else None, pc(br) if br is not None else None, xs_, tuple(graphs),
-                    cfg(layer, tuple((s_ + gi) & ((1 << 64) - 1) for s_ in sd), coef_sink=gsink, coef_mean=False,
+                    run(layer, tuple((s_ + gi) & ((1 << 64) - 1) for s_ in sd), coef_sink=gsink, coef_mean=wide,
                         group=gi))
                 outs.append(Mg.reshape(Mg.shape[0], Mg.shape[1], kg, FPk)[:, :, :nh, :FP]
                             .reshape(Mg.shape[0], Mg.shape[1], nh * FP))
-                if sink is not None:      # (E, kg) per meta-path -> sum over the real heads
-                    part = [v[:, :nh].sum(1) for v in gsink]
+                if sink is not None:      # (E, kg) per meta-path -> sum over the real heads; a wide head gives (E,)
+                    part = gsink if wide else [v[:, :nh].sum(1) for v in gsink]
                     coef_acc = part if coef_acc is None else [x + y for x, y in zip(coef_acc, part)]
             if sink is not None:
                 sink.extend(v / K for v in coef_acc)

@@ -17,6 +17,10 @@ There is no CPU implementation: every function raises on non-GPU tensors.
 """
 from __future__ import annotations
 
+import dataclasses
+import functools
+from typing import NamedTuple
+
 import torch
 import torch.nn.functional as F_torch
 
@@ -54,52 +58,6 @@ def _same_tensor(ts) -> bool:
                and t.dtype == t0.dtype for t in ts[1:])
 
 
-class _on_path:
-    """Run the enclosed launches of meta-path p on its own stream (cfg["streams"], single GPU): the per-meta-path
-    chains K1 -> K2 (forward) and rows -> cols -> score gradients -> dW (backward) are independent of each other,
-    and at the size of the reference's data sets every kernel is a few microseconds on a few CUs -- side by side
-    in a captured epoch they overlap instead of queueing (HANTrainer(use_graph=True)).  Scratch buffers are per path."""
-
-    def __init__(self, streams, p):
-        self.s = streams[p] if streams is not None else None
-        self.p = p
-
-    def __enter__(self):
-        if self.s is not None:
-            self.ctx = torch.cuda.stream(self.s)
-            self.ctx.__enter__()
-            self.prev, ops.WS_SUFFIX = ops.WS_SUFFIX, ops.WS_SUFFIX + f"@p{self.p}"
-
-    def __exit__(self, *exc):
-        if self.s is not None:
-            ops.WS_SUFFIX = self.prev
-            self.ctx.__exit__(*exc)
-
-
-class _on_side:
-    """Run the enclosed launches on the side stream (cfg["side_stream"]: single GPU, eager training step on large
-    graphs).  The backward's dW of meta-path p needs only dH_p, so it runs beside the transposed-graph gather of
-    meta-path p + 1: the gather is bound by the memory fabric and leaves vector / matrix issue slots that dW, bound by
-    exactly those, can use -- 2.70 + 0.52 ms one after the other, 2.95 ms side by side.  What was measured and is NOT
-    done: the forward's K1 of meta-path p + 1 beside K2 of meta-path p gains nothing (K2's blocks refill every slot
-    they free, K1's 8-wave blocks with 40 KB of LDS wait: 2.5 ms instead of 0.74, a higher stream priority changes
-    nothing, and CU masks only move the same CU time around: tools/cu_mask_probe.py); two K2 launches beside each
-    other evict each other's gather table from the Infinity Cache (four meta-path chains side by side: 40.7 ms per
-    epoch against 35.5).  Scratch buffers of the side stream are its own (ops.WS_SUFFIX)."""
-
-    def __init__(self, side):
-        self.s = side
-
-    def __enter__(self):
-        self.ctx = torch.cuda.stream(self.s)
-        self.ctx.__enter__()
-        self.prev, ops.WS_SUFFIX = ops.WS_SUFFIX, ops.WS_SUFFIX + "@side"
-
-    def __exit__(self, *exc):
-        ops.WS_SUFFIX = self.prev
-        self.ctx.__exit__(*exc)
-
-
 def _used_on(stream, *tensors):
     """Tensors allocated on one stream and read on another: tell the caching allocator, so that their memory is not
     handed out again before that stream is done with it."""
@@ -135,6 +93,20 @@ def _join(streams):
             cur.wait_stream(st)
 
 
+def _each_path(streams, order, fn):
+    """fn(p) for every meta-path, each on its own stream when there are path streams (LayerRun.streams, single GPU):
+    the per-meta-path chains K1 -> K2 (forward) and rows -> cols -> score gradients -> dW (backward) are independent of
+    each other, and at the size of the reference's data sets every kernel is a few microseconds on a few CUs -- side by
+    side in a captured epoch they overlap instead of queueing (HANTrainer(use_graph=True)).  Scratch buffers are per
+    path (ops.branch)."""
+    for p in order:
+        if streams is None:
+            fn(p)
+        else:
+            with ops.branch(streams[p], f"@p{p}"):
+                fn(p)
+
+
 class _Ready:
     """A table that needs no exchange (same interface as the async exchange handles)."""
 
@@ -145,10 +117,154 @@ class _Ready:
         return self.table
 
 
+class LocalTable:
+    """Table source of a meta-path whose gather table is the rows at hand (no node partition).  A table source has
+    .graph (the CSR graph that indexes the table), .gid (global id of each table row, or None when row i is node i)
+    and .exchange(table, tag) -> handle whose .wait() yields the gather table; the others are AllGatherTable,
+    dist.HaloPlan and dist.MaskedBackwardPlan."""
+    gid = None
+
+    def __init__(self, graph):
+        self.graph = graph
+
+    def exchange(self, table, tag):
+        return _Ready(table)
+
+
+class AllGatherTable(LocalTable):
+    """Table source of a meta-path without locality under a node partition: every rank's whole shard."""
+
+    def __init__(self, part: NodePartition, graph):
+        self.part, self.graph = part, graph
+
+    def exchange(self, table, tag):
+        return self.part.all_gather_rows_async(table, tag)
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class LayerRun:
+    """How one call of NodeLevelAttention / WideHeadAttention is to run (built by gat.HeteGAT_multi.node_level)."""
+    train: bool
+    seeds: tuple                      # one dropout seed per meta-path
+    act: int                          # kernel activation code (ops.ACT_*)
+    in_drop: float = 0.0              # as asked for; what runs is drop_in / drop_coef (0 when not training)
+    coef_drop: float = 0.0
+    seed_dev: torch.Tensor | None = None       # device seed word of a captured step (han_hip.h "Seeds")
+    part: NodePartition | None = None
+    graphs_t: tuple | None = None     # the P transposed graphs of the backward (built on demand when None)
+    layer: int = 0
+    group: int = 0                    # head group (wide heads: head) of the layer; names the exchange tables
+    table_dtype: torch.dtype = torch.float32   # storage of the H / g tables (float32 | bfloat16)
+    plans_f: list | None = None       # per meta-path dist.HaloPlan or None (all-gather): forward / backward tables
+    plans_b: list | None = None
+    xs_full: tuple | None = None      # the features of ALL rows: replicated projection under a partition
+    masked_bwd: list | None = None    # per meta-path dist.MaskedBackwardPlan, or None (the full pass)
+    streams: list | None = None       # one stream per meta-path (_each_path)
+    side_stream: torch.cuda.Stream | None = None   # dW beside the next meta-path's backward gather (NodeLevelAttention.backward)
+    path_order: str | None = None     # _path_order
+    overlap: object = None            # trainer._EvalBranch riding in this call's fork / join sections
+    coef_sink: list | None = None     # receives per meta-path the coefficients of this call as data -- (E,K), or their
+    coef_mean: bool = False           # head mean (E,) with coef_mean (return_coef of layers.py:43-44 / models/gat.py:143-172; single GPU only)
+
+    @functools.cached_property
+    def multi(self) -> bool:
+        return self.part is not None and self.part.active
+
+    @functools.cached_property
+    def row_offset(self) -> int:
+        return self.part.row_start if self.part is not None else 0
+
+    @functools.cached_property
+    def drop_in(self) -> float:
+        return float(self.in_drop) if self.train else 0.0
+
+    @functools.cached_property
+    def drop_coef(self) -> float:
+        return float(self.coef_drop) if self.train else 0.0
+
+    def tag(self, kind, p, *s):
+        """Name of the persistent exchange table of this (layer, head group, meta-path[, slice])."""
+        return (kind, self.layer, self.group, p) + s
+
+    def transposed(self, graphs):
+        return self.graphs_t or tuple(g.transpose() for g in graphs)
+
+    def _source(self, plans, p, graph):
+        if not self.multi:
+            return LocalTable(graph)
+        if plans is not None and plans[p] is not None:       # halo rows only
+            return plans[p]
+        return AllGatherTable(self.part, graph)                # the whole shard
+
+    def source_f(self, p, graph):
+        """Table source of meta-path p's forward table H."""
+        return self._source(self.plans_f, p, graph)
+
+    def source_b(self, p, graph_t, masked=True):
+        """(table source, kind of exchange tag) of meta-path p's backward table [g | stats]."""
+        if masked and self.masked_bwd is not None and self.masked_bwd[p] is not None:
+            return self.masked_bwd[p], "bm"      # opt-in: only the live rows are read / travel
+        return self._source(self.plans_b, p, graph_t), "b"
+
+
+class _SavedPath(NamedTuple):
+    """Backward state of one meta-path (NodeLevelAttention) or one column slice of it (WideHeadAttention: f1 / f2 are
+    the head's totals).  The output rows the backward inverts the activation on are not here: M is kept through
+    ctx.save_for_backward (version-checked by autograd, no reference cycle)."""
+    H: torch.Tensor
+    f1: torch.Tensor
+    f2: torch.Tensor
+    lse: torch.Tensor
+    aggp: torch.Tensor
+    tsum: torch.Tensor
+    R: torch.Tensor | None
+    keep: torch.Tensor | None = None
+
+
+def _paths_in(Xin, xs, P):
+    """(Xin, xs): layers >= 1 read meta-path p's input from the previous layer's output, Xin[:, p, :]."""
+    if Xin is None:
+        return None, xs
+    Xin = Xin.contiguous()
+    return Xin, tuple(Xin[:, p, :] for p in range(P))
+
+
+def _residual_fwd(run, x, Wr, br, a1, a2, b1, b2, seed):
+    """utils/layers.py:38-40: conv1d(seq, F', 1) of the DROPPED input -- the head's seed gives the same per-head
+    input-dropout draws as for H; the projected rows are not dropped.  (The score vectors only ride along.)"""
+    R, _, _ = ops.project_fwd(x, Wr, a1, a2, b1, b2, in_drop=run.drop_in, fts_drop=0.0, seed=seed,
+                              row_offset=run.row_offset, seed_dev=run.seed_dev)
+    return R + br
+
+
+def _residual_g(gs, K, FP, dtype):
+    """Residual: d(pre) = g, the fp32 rows of the fused backward table."""
+    return ops.gs_views(gs, K, FP, dtype)[0].to(torch.float32).contiguous()
+
+
+def _residual_bwd(run, x, g32, Wr, K, FP, seed, dWr, want_dx):
+    """g flows into Wr (written to dWr) and, with want_dx, into the input (returned)."""
+    ops.project_bwd(x, g32, K, FP, in_drop=run.drop_in, seed=seed, row_offset=run.row_offset,
+                    seed_dev=run.seed_dev, out=dWr)
+    if want_dx:
+        return ops.project_bwd_input(g32, Wr.contiguous(), K, FP, in_drop=run.drop_in, seed=seed,
+                                     row_offset=run.row_offset, seed_dev=run.seed_dev)
+
+
+def _sink_coefs(run, graph, f1, f2, seed):
+    if run.coef_sink is None:
+        return
+    if run.multi:
+        raise NotImplementedError("return_coef is not provided under a node partition")
+    run.coef_sink.append(ops.node_attn_coefs(graph, f1, f2, coef_drop=run.drop_coef, seed=seed,
+                                             row_offset=run.row_offset, mean_heads=bool(run.coef_mean),
+                                             seed_dev=run.seed_dev))
+
+
 class NodeLevelAttention(torch.autograd.Function):
     """K1 + K2 for every meta-path: (X_p, graph_p) -> M (N, P, D).
 
-    forward(Xin, W (P,F,D), a1 (P,K,F'), b1 (P,K), a2, b2, c (P,D), Wr, br, xs, graphs, cfg)
+    forward(Xin, W (P,F,D), a1 (P,K,F'), b1 (P,K), a2, b2, c (P,D), Wr, br, xs, graphs, run)
       Wr, br  None, or the residual connection of utils/layers.py:38-40 for layers whose
               input width differs from the head width: Wr (P,F,D) = the K heads'
               conv1d(seq, F', 1) kernels side by side, br (P,D) their biases; the term
@@ -159,139 +275,96 @@ class NodeLevelAttention(torch.autograd.Function):
       xs      tuple of P feature tensors (N,F) (no gradient: they are inputs);
               ignored when Xin is given
       graphs  tuple of P CSRGraph (rows = local destinations)
-      cfg     dict: train (bool), in_drop, coef_drop, seeds (tuple of P ints),
-              act (kernel activation code), part (NodePartition or None),
-              table_dtype (torch.float32 | torch.bfloat16: storage of the H / g tables),
-              graphs_t (tuple of P transposed graphs for the backward, or None),
-              plans_f / plans_b (per meta-path HaloPlan or None: halo exchange instead of
-              the all-gather, forward / backward tables),
-              coef_sink (None, or a list that receives per meta-path the coefficients
-              of this call as data -- (E,K), or their head mean (E,) with coef_mean=True;
-              return_coef of layers.py:43-44 / models/gat.py:143-172; single GPU only)
+      run     LayerRun
     """
 
     @staticmethod
-    def forward(ctx, Xin, W, a1, b1, a2, b2, c, Wr, br, xs, graphs, cfg):
+    def forward(ctx, Xin, W, a1, b1, a2, b2, c, Wr, br, xs, graphs, run):
         P = len(graphs)
-        if Xin is not None:
-            Xin = Xin.contiguous()
-            xs = tuple(Xin[:, p, :] for p in range(P))
+        Xin, xs = _paths_in(Xin, xs, P)
         K, FP = a1.shape[1], a1.shape[2]
-        part: NodePartition | None = cfg.get("part")
-        train = bool(cfg["train"])
-        in_drop = float(cfg.get("in_drop", 0.0)) if train else 0.0
-        coef_drop = float(cfg.get("coef_drop", 0.0)) if train else 0.0
+        part, multi, train = run.part, run.multi, run.train
+        in_drop, coef_drop, row_offset, seed_dev, tdt = run.drop_in, run.drop_coef, run.row_offset, run.seed_dev, run.table_dtype
         N = xs[0].shape[0]
         M = torch.empty((N, P, D), dtype=torch.float32, device=W.device)
-        row_offset = part.row_start if part is not None else 0
         saved = [None] * P
-        seed_dev = cfg.get("seed_dev")      # device seed word of a captured step (see han_hip.h "Seeds")
-        multi = part is not None and part.active
-        plans_f = cfg.get("plans_f") if multi else None      # per meta-path HaloPlan or None
-        # all projections first, each table's all-gather started as soon as it exists:
+        srcs = [run.source_f(p, graphs[p]) for p in range(P)]
+        # all projections first, each table's exchange started as soon as it exists:
         # the exchange of meta-path p+1.. overlaps the node attention of meta-path p
-        proj, proj_keep = [None] * P, [None] * P
-        xs_full = cfg.get("xs_full") if (multi and Xin is None) else None
-        tdt = cfg.get("table_dtype", torch.float32)
+        proj = [None] * P
+        xs_full = run.xs_full if (multi and Xin is None) else None
         # the reference feeds ONE feature matrix to every meta-path (ex_acm3025.py:86): all P projections then go
         # through ONE call -- the eval forward of long inputs as one fused launch that reads, splits and stages
         # every X tile once for four meta-paths (ops.project_fwd_multi)
-        replicated = [xs_full is not None and (plans_f is None or plans_f[p] is None) for p in range(P)]
+        replicated = [xs_full is not None and isinstance(s, AllGatherTable) for s in srcs]
         pj = [None] * P
-        src = xs_full if all(replicated) else (xs if not any(replicated) else None)
-        streams = cfg.get("streams") if (not multi and cfg.get("streams") is not None and len(cfg["streams"]) >= P) else None
-        # the backward runs dW beside the next meta-path's gather (_on_side); the forward stays one chain
-        side = cfg.get("side_stream") if (streams is None and not multi and train and P > 1 and W.is_cuda) else None
+        shared = xs_full if all(replicated) else (xs if not any(replicated) else None)
+        streams = run.streams if (not multi and run.streams is not None and len(run.streams) >= P) else None
+        # the backward runs dW beside the next meta-path's gather (cols_path); the forward stays one chain
+        side = run.side_stream if (streams is None and not multi and train and P > 1 and W.is_cuda) else None
         _fork(streams)
         # HANTrainer(overlap_eval=True): the eval forward's K1 + K2 as one more branch of this fork / join section
-        overlap = cfg.get("overlap") if (train and cfg.get("group", 0) == 0) else None
+        overlap = run.overlap if (train and run.group == 0) else None
         if overlap is not None:
             overlap.node_level()
-        if streams is None and P > 1 and src is not None and _same_tensor(src) and W.is_contiguous() and src[0].stride(-1) == 1:
+        if streams is None and P > 1 and shared is not None and _same_tensor(shared) and W.is_contiguous() and shared[0].stride(-1) == 1:
             full = all(replicated)
-            Hs, f1s, f2s, keeps = ops.project_fwd_multi(src[0], W, a1, a2, b1, b2, in_drop=in_drop, fts_drop=in_drop,
-                                                        seeds=[int(v) for v in cfg["seeds"]],
+            Hs, f1s, f2s, keeps = ops.project_fwd_multi(shared[0], W, a1, a2, b1, b2, in_drop=in_drop, fts_drop=in_drop,
+                                                        seeds=[int(v) for v in run.seeds],
                                                         row_offset=0 if full else row_offset, table_dtype=tdt,
                                                         seed_dev=seed_dev, want_keep=True)
             pj = [(Hs[p], f1s[p], f2s[p], keeps[p]) for p in range(P)]
 
         def project_path(p):
-            seed = int(cfg["seeds"][p])
-            plan = plans_f[p] if plans_f is not None else None
-            handle = keep = None
+            seed = int(run.seeds[p])
+            # replicated projection: every rank holds the features of ALL rows and projects the whole
+            # table itself instead of receiving (G-1)/G of it -- a point-to-point xGMI link moves a
+            # 256-B row slower than K1 recomputes it (dist.replication_policy).  Masks are keyed by
+            # global row ids, so the rows are bit-identical to what their owners compute.
+            X, off = (xs_full[p], 0) if replicated[p] else (xs[p], row_offset)
+            # training: the forward also writes the keep table of its per-head input dropout, which dW
+            # reads instead of regenerating the draws (None for shapes without a table)
+            H, f1, f2, keep = pj[p] if pj[p] is not None else ops.project_fwd(
+                X, W[p], a1[p], a2[p], b1[p], b2[p], in_drop=in_drop, fts_drop=in_drop, seed=seed,
+                row_offset=off, table_dtype=tdt, seed_dev=seed_dev, want_keep=True)
             if replicated[p]:
-                # replicated projection: every rank holds the features of ALL rows and projects the whole
-                # table itself instead of receiving (G-1)/G of it -- a point-to-point xGMI link moves a
-                # 256-B row slower than K1 recomputes it (dist.replication_policy).  Masks are keyed by
-                # global row ids, so the rows are bit-identical to what their owners compute.
-                Hf, f1f, f2f, keepf = pj[p] if pj[p] is not None else ops.project_fwd(
-                    xs_full[p], W[p], a1[p], a2[p], b1[p], b2[p], in_drop=in_drop, fts_drop=in_drop, seed=seed,
-                    row_offset=0, table_dtype=tdt, seed_dev=seed_dev, want_keep=True)
-                r0, r1 = part.row_start, part.row_end
-                H, f1, f2 = Hf[r0:r1], f1f[r0:r1], f2f[r0:r1]
-                if keepf is not None:      # the local rows of the table (+ its slack) when they form a table themselves
-                    Fw = xs_full[p].shape[1]
+                handle, r0, r1 = _Ready(H), part.row_start, part.row_end
+                H, f1, f2 = H[r0:r1], f1[r0:r1], f2[r0:r1]
+                if keep is not None:      # the local rows of the table (+ its slack) when they form a table themselves
+                    Fw = X.shape[1]
                     kb_loc = ops.keep_bytes(r1 - r0, Fw, xs[p].stride(0), K, FP)
-                    keep = keepf[r0 * Fw:r0 * Fw + kb_loc] if kb_loc and (r0 * Fw) % 8 == 0 else None
-                handle = _Ready(Hf)
+                    keep = keep[r0 * Fw:r0 * Fw + kb_loc] if kb_loc and (r0 * Fw) % 8 == 0 else None
             else:
-                # training: the forward also writes the keep table of its per-head input dropout, which dW
-                # reads instead of regenerating the draws (None for shapes without a table)
-                H, f1, f2, keep = pj[p] if pj[p] is not None else ops.project_fwd(
-                    xs[p], W[p], a1[p], a2[p], b1[p], b2[p], in_drop=in_drop, fts_drop=in_drop, seed=seed,
-                    row_offset=row_offset, table_dtype=tdt, seed_dev=seed_dev, want_keep=True)
-            if multi and handle is None:      # halo rows only (HaloPlan) or the whole shard (all-gather)
-                tag = ("f", cfg.get("layer", 0), cfg.get("group", 0), p)   # persistent exchange table of this (layer, head group, meta-path)
-                handle = plan.exchange_async(H, tag) if plan is not None else part.all_gather_rows_async(H, tag)
-            if cfg.get("coef_sink") is not None:
-                if multi:
-                    raise NotImplementedError("return_coef is not provided under a node partition")
-                cfg["coef_sink"].append(ops.node_attn_coefs(
-                    graphs[p], f1, f2, coef_drop=coef_drop, seed=seed, row_offset=row_offset,
-                    mean_heads=bool(cfg.get("coef_mean", False)), seed_dev=seed_dev))
-            R = None
-            if Wr is not None:   # same seed -> the same per-head input-dropout draws as for H
-                R, _, _ = ops.project_fwd(xs[p], Wr[p], a1[p], a2[p], b1[p], b2[p], in_drop=in_drop,
-                                          fts_drop=0.0, seed=seed, row_offset=row_offset, seed_dev=seed_dev)
-                R = R + br[p]
-            proj[p] = (H, f1, f2, handle, R)
-            proj_keep[p] = keep
+                handle = srcs[p].exchange(H, run.tag("f", p))
+            _sink_coefs(run, graphs[p], f1, f2, seed)
+            # same seed -> the same per-head input-dropout draws as for H
+            R = _residual_fwd(run, xs[p], Wr[p], br[p], a1[p], a2[p], b1[p], b2[p], seed) if Wr is not None else None
+            proj[p] = (H, f1, f2, handle, R, keep)
 
         def attend_path(p):
-            H, f1, f2, handle, R = proj[p]
-            H_tab = handle.wait() if multi else H
-            plan = plans_f[p] if plans_f is not None else None
-            _, sv = ops.node_attn_fwd(plan.graph if plan is not None else graphs[p], H_tab, f1, a2[p], b2[p],
-                                      c[p], out=M[:, p, :], train=train, coef_drop=coef_drop,
-                                      fts_drop=in_drop, seed=int(cfg["seeds"][p]), row_offset=row_offset,
-                                      activation=cfg["act"],
-                                      table_gid=plan.gid if plan is not None else None, res=R,
-                                      seed_dev=seed_dev, f2=None if multi else f2)
-            if train:
-                # sv[0] is the OUTPUT view M[:, p, :] the backward inverts the activation on: it is kept through
-                # ctx.save_for_backward(M) below (version-checked by autograd, no reference cycle), not here
-                saved[p] = (H, f1, f2, None) + sv[1:] + (R, proj_keep[p])
+            H, f1, f2, handle, R, keep = proj[p]
+            _, sv = ops.node_attn_fwd(srcs[p].graph, handle.wait(), f1, a2[p], b2[p], c[p], out=M[:, p, :], train=train,
+                                      coef_drop=coef_drop, fts_drop=in_drop, seed=int(run.seeds[p]), row_offset=row_offset,
+                                      activation=run.act, table_gid=srcs[p].gid, res=R, seed_dev=seed_dev,
+                                      f2=None if multi else f2)
+            if train:      # sv[0] is the OUTPUT view M[:, p, :]: kept through ctx.save_for_backward(M) below, not here
+                saved[p] = _SavedPath(H, f1, f2, *sv[1:], R, keep)
 
-        order = _path_order(streams, graphs, cfg.get("path_order"))
-        for p in order:
-            with _on_path(streams, p):
-                project_path(p)
-        for p in order:
-            with _on_path(streams, p):
-                attend_path(p)
+        order = _path_order(streams, graphs, run.path_order)
+        _each_path(streams, order, project_path)
+        _each_path(streams, order, attend_path)
         _join(streams)
         if overlap is not None:
             overlap.join()
         ctx.overlap = overlap
         del proj
         ctx.side = side
-        ctx.cfg, ctx.xs, ctx.graphs = cfg, xs, graphs
+        ctx.run, ctx.xs, ctx.graphs = run, xs, graphs
         ctx.xin_shape = tuple(Xin.shape) if Xin is not None else None
         ctx.saved_per_p = saved
         # the per-meta-path tensors above were allocated on these streams: the backward must run each meta-path on
-        # the SAME stream (the caching allocator ties a block to its allocation stream), whatever cfg holds by then
+        # the SAME stream (the caching allocator ties a block to its allocation stream), whatever the model holds by then
         ctx.streams = streams
-        ctx.in_drop, ctx.coef_drop = in_drop, coef_drop
         ctx.has_res = Wr is not None
         # direct-gradient mode (HANTrainer): every parameter carries a pre-bound .grad slice of
         # the flat gradient buffer and is used once per step, so the backward kernels WRITE
@@ -307,20 +380,17 @@ class NodeLevelAttention(torch.autograd.Function):
     def backward(ctx, dM):
         W, a1, b1, a2, b2, c = ctx.saved_tensors[:6]
         Wr = ctx.saved_tensors[6] if ctx.has_res else None
-        if not ctx.cfg["train"]:
+        run, xs, graphs = ctx.run, ctx.xs, ctx.graphs
+        if not run.train:
             raise RuntimeError("NodeLevelAttention was run with train=False; no backward state")
         Mout = ctx.saved_tensors[-1]
         dWr = torch.empty_like(Wr) if Wr is not None else None
         dbr = torch.empty_like(c) if Wr is not None else None
-        cfg, xs, graphs = ctx.cfg, ctx.xs, ctx.graphs
-        if not cfg["train"]:
-            raise RuntimeError("NodeLevelAttention was run with train=False; no backward state")
-        part: NodePartition | None = cfg.get("part")
         P = len(graphs)
         K, FP = a1.shape[1], a1.shape[2]
         dM = dM.contiguous()
-        graphs_t = cfg.get("graphs_t") or tuple(g.transpose() for g in graphs)
-        row_offset = part.row_start if part is not None else 0
+        graphs_t = run.transposed(graphs)
+        in_drop, coef_drop, row_offset, seed_dev = run.drop_in, run.drop_coef, run.row_offset, run.seed_dev
         direct = ctx.direct
         if direct is not None:
             dW, da1, db1, da2, db2, dc = direct[:6]
@@ -333,10 +403,7 @@ class NodeLevelAttention(torch.autograd.Function):
         dXin = None
         if ctx.xin_shape is not None and ctx.needs_input_grad[0]:
             dXin = torch.empty(ctx.xin_shape, dtype=torch.float32, device=W.device)
-        multi = part is not None and part.active
-        seed_dev = cfg.get("seed_dev")
-        plans_b = cfg.get("plans_b") if multi else None
-        masked = cfg.get("masked_bwd")        # per meta-path MaskedBackwardPlan, or None (the full pass)
+        srcs = [run.source_b(p, graphs_t[p]) for p in range(P)]
         rows = [None] * P
         dres_in = []
         streams = ctx.streams       # the streams the forward ran (and allocated) on
@@ -346,67 +413,55 @@ class NodeLevelAttention(torch.autograd.Function):
             ctx.overlap.head()
 
         def rows_path(p):      # row-local halves first; their tables go out while we continue
-            H, f1, f2, _, lse, aggp, tsum, R, _keep = ctx.saved_per_p[p]
-            gs, df1, dcp = ops.node_attn_bwd_rows(dM[:, p, :], Mout[:, p, :], aggp, tsum, f1, lse, c[p],
-                                                  activation=cfg["act"], K=K, FP=FP,
-                                                  table_dtype=H.dtype, res=R, dc_out=dc[p])
-            if Wr is not None:      # residual: d(pre) = g flows into Wr, br and the input
-                g32 = ops.gs_views(gs, K, FP, H.dtype)[0].to(torch.float32).contiguous()
-                seed_p = int(cfg["seeds"][p])
+            sv = ctx.saved_per_p[p]
+            gs, df1, dcp = ops.node_attn_bwd_rows(dM[:, p, :], Mout[:, p, :], sv.aggp, sv.tsum, sv.f1, sv.lse, c[p],
+                                                  activation=run.act, K=K, FP=FP,
+                                                  table_dtype=sv.H.dtype, res=sv.R, dc_out=dc[p])
+            if Wr is not None:
+                g32 = _residual_g(gs, K, FP, sv.H.dtype)
                 dbr[p] = dcp
-                ops.project_bwd(xs[p], g32, K, FP, in_drop=ctx.in_drop, seed=seed_p,
-                                row_offset=row_offset, seed_dev=seed_dev, out=dWr[p])
+                dx = _residual_bwd(run, xs[p], g32, Wr[p], K, FP, int(run.seeds[p]), dWr[p], dXin is not None)
                 if dXin is not None:
-                    dres_in.append(ops.project_bwd_input(g32, Wr[p], K, FP, in_drop=ctx.in_drop,
-                                                         seed=seed_p, row_offset=row_offset,
-                                                         seed_dev=seed_dev))
-            mb = masked[p] if masked is not None else None
-            if mb is not None:        # opt-in masked backward: only the live rows of [g | stats] are read / travel
-                rows[p] = (mb.table_async(gs, ("bm", cfg.get("layer", 0), cfg.get("group", 0), p)), df1)
-            elif multi:
-                plan = plans_b[p] if plans_b is not None else None
-                ex = plan.exchange_async if plan is not None else part.all_gather_rows_async
-                rows[p] = (ex(gs, ("b", cfg.get("layer", 0), cfg.get("group", 0), p)), df1)   # ONE fused [g | stats] table on the wire
-            else:
-                rows[p] = (gs, df1)
+                    dres_in.append(dx)
+            src, kind = srcs[p]
+            rows[p] = (src.exchange(gs, run.tag(kind, p)), df1)      # ONE fused [g | stats] table on the wire
 
         def cols_path(p):
-            H, f1, f2, pre, lse, aggp, tsum, R, keep = ctx.saved_per_p[p]
-            seed = int(cfg["seeds"][p])
+            sv = ctx.saved_per_p[p]
+            seed = int(run.seeds[p])
             gs_h, df1 = rows[p]
-            mb = masked[p] if masked is not None else None
-            gs_tab = gs_h.wait() if (multi or mb is not None) else gs_h
-            plan = plans_b[p] if (plans_b is not None and mb is None) else None
-            gt = mb.graph_t if mb is not None else (plan.graph if plan is not None else graphs_t[p])
-            dH, df2 = ops.node_attn_bwd_cols(gt, gs_tab, H, f2, df1, a1[p], a2[p],
-                                             coef_drop=ctx.coef_drop, fts_drop=ctx.in_drop, seed=seed,
-                                             src_offset=row_offset, dst_offset=0,
-                                             table_gid=mb.gid if mb is not None else (plan.gid if plan is not None else None),
-                                             seed_dev=seed_dev)
+            src = srcs[p][0]
+            dH, df2 = ops.node_attn_bwd_cols(src.graph, gs_h.wait(), sv.H, sv.f2, df1, a1[p], a2[p], coef_drop=coef_drop,
+                                             fts_drop=in_drop, seed=seed, src_offset=row_offset, dst_offset=0,
+                                             table_gid=src.gid, seed_dev=seed_dev)
             rows[p] = None
-            ops.score_param_bwd(H, df1, df2, K=K, FP=FP, out=(da1[p], da2[p], db1[p], db2[p]))
-            if side is not None and dXin is None:      # dW(p) beside the transposed-graph gather of meta-path p + 1
+            ops.score_param_bwd(sv.H, df1, df2, K=K, FP=FP, out=(da1[p], da2[p], db1[p], db2[p]))
+            if side is not None and dXin is None:
+                # dW(p) on the side stream (single GPU, eager training step on large graphs) beside the transposed-graph
+                # gather of meta-path p + 1: the gather is bound by the memory fabric and leaves vector / matrix issue
+                # slots that dW, bound by exactly those, can use -- 2.70 + 0.52 ms one after the other, 2.95 ms side by
+                # side.  What was measured and is NOT done: the forward's K1 of meta-path p + 1 beside K2 of meta-path p
+                # gains nothing (K2's blocks refill every slot they free, K1's 8-wave blocks with 40 KB of LDS wait:
+                # 2.5 ms instead of 0.74, a higher stream priority changes nothing, and CU masks only move the same CU
+                # time around: tools/cu_mask_probe.py); two K2 launches beside each other evict each other's gather
+                # table from the Infinity Cache (four meta-path chains side by side: 40.7 ms per epoch against 35.5).
                 side.wait_stream(torch.cuda.current_stream())
-                with _on_side(side):
-                    ops.project_bwd(xs[p], dH, K, FP, in_drop=ctx.in_drop, seed=seed,
-                                    row_offset=row_offset, seed_dev=seed_dev, out=dW[p], keep=keep)
+                with ops.branch(side, "@side"):
+                    ops.project_bwd(xs[p], dH, K, FP, in_drop=in_drop, seed=seed,
+                                    row_offset=row_offset, seed_dev=seed_dev, out=dW[p], keep=sv.keep)
                 _used_on(side, dH)
                 return
-            ops.project_bwd(xs[p], dH, K, FP, in_drop=ctx.in_drop, seed=seed,
-                            row_offset=row_offset, seed_dev=seed_dev, out=dW[p], keep=keep)
+            ops.project_bwd(xs[p], dH, K, FP, in_drop=in_drop, seed=seed,
+                            row_offset=row_offset, seed_dev=seed_dev, out=dW[p], keep=sv.keep)
             if dXin is not None:
-                ops.project_bwd_input(dH, W[p], K, FP, out=dXin[:, p, :], in_drop=ctx.in_drop,
+                ops.project_bwd_input(dH, W[p], K, FP, out=dXin[:, p, :], in_drop=in_drop,
                                       seed=seed, row_offset=row_offset, seed_dev=seed_dev)
                 if dres_in:
                     dXin[:, p, :] += dres_in[p]
 
-        order = _path_order(streams, graphs, cfg.get("path_order"))
-        for p in order:
-            with _on_path(streams, p):
-                rows_path(p)
-        for p in order:
-            with _on_path(streams, p):
-                cols_path(p)
+        order = _path_order(streams, graphs, run.path_order)
+        _each_path(streams, order, rows_path)
+        _each_path(streams, order, cols_path)
         _join(streams)
         if ctx.overlap is not None:
             ctx.overlap.join()
@@ -431,79 +486,57 @@ class WideHeadAttention(torch.autograd.Function):
     backward of the slices -- the softmax backward is linear in d alpha, so the slices' df1 / df2 add up -- with the
     totals in the places that need them (df1 into the transposed-graph pass, df2 into dH and the score gradients).
 
-    forward(Xin, W (P,F,S*64), a1 (P,S*64), b1 (P,), a2 (P,S*64), b2 (P,), c (P,S*64), Wr, br, xs, graphs, cfg) -> M (N,P,S*64);
+    forward(Xin, W (P,F,S*64), a1 (P,S*64), b1 (P,), a2 (P,S*64), b2 (P,), c (P,S*64), Wr, br, xs, graphs, run) -> M (N,P,S*64);
     columns beyond F' carry zero weights (their outputs are exactly act(0 + 0) and are cut off by the caller).
-    cfg as for NodeLevelAttention.  Under a node partition every slice's table travels like a narrow head's (halo plan or
+    run as for NodeLevelAttention.  Under a node partition every slice's table travels like a narrow head's (halo plan or
     all-gather, its own persistent exchange table) and so do the head's f2 totals (4 bytes per row); the forward is
-    never replicated (xs_full is not used) and the backward exchanges one [g | stats] table per slice."""
+    never replicated (xs_full is not used) and the backward exchanges one [g | stats] table per slice (always the full
+    pass: masked_bwd is not used)."""
 
     @staticmethod
-    def forward(ctx, Xin, W, a1, b1, a2, b2, c, Wr, br, xs, graphs, cfg):
+    def forward(ctx, Xin, W, a1, b1, a2, b2, c, Wr, br, xs, graphs, run):
         P = len(graphs)
-        if Xin is not None:
-            Xin = Xin.contiguous()
-            xs = tuple(Xin[:, p, :] for p in range(P))
-        part = cfg.get("part")
-        multi = part is not None and part.active
-        row_offset = part.row_start if part is not None else 0
-        plans_f = cfg.get("plans_f") if multi else None
-        lay, grp = cfg.get("layer", 0), cfg.get("group", 0)
+        Xin, xs = _paths_in(Xin, xs, P)
         S = W.shape[2] // D
-        train = bool(cfg["train"])
-        in_drop = float(cfg.get("in_drop", 0.0)) if train else 0.0
-        coef_drop = float(cfg.get("coef_drop", 0.0)) if train else 0.0
+        train = run.train
+        in_drop, coef_drop, row_offset, seed_dev = run.drop_in, run.drop_coef, run.row_offset, run.seed_dev
         N, dev = xs[0].shape[0], W.device
         M = torch.empty((N, P, S * D), dtype=torch.float32, device=dev)
-        seed_dev = cfg.get("seed_dev")
-        tdt = cfg.get("table_dtype", torch.float32)
         zero1 = torch.zeros(1, dtype=torch.float32, device=dev)
         saved = []
         for p in range(P):
-            seed = int(cfg["seeds"][p])
+            seed = int(run.seeds[p])
             Ws = W[p].view(-1, S, D).permute(1, 0, 2).contiguous()          # (S,F,64)
             a1s, a2s, cs = a1[p].view(S, 1, D), a2[p].view(S, 1, D), c[p].view(S, D)
-            plan = plans_f[p] if plans_f is not None else None
-            exchange = (plan.exchange_async if plan is not None else part.all_gather_rows_async) if multi else None
+            src = run.source_f(p, graphs[p])
             Hs, Htabs, f1, f2, Rs = [], [], None, None, []
             for s_ in range(S):
                 fl = ops.flag_fts_slice(s_)
                 H, f1s, f2s = ops.project_fwd(xs[p], Ws[s_], a1s[s_], a2s[s_], b1[p:p + 1] if s_ == 0 else zero1,
                                               b2[p:p + 1] if s_ == 0 else zero1, in_drop=in_drop, fts_drop=in_drop,
-                                              seed=seed, row_offset=row_offset, table_dtype=tdt, seed_dev=seed_dev, flags=fl)
+                                              seed=seed, row_offset=row_offset, table_dtype=run.table_dtype,
+                                              seed_dev=seed_dev, flags=fl)
                 Hs.append(H)
-                Htabs.append(exchange(H, ("wf", lay, grp, p, s_)) if multi else _Ready(H))
+                Htabs.append(src.exchange(H, run.tag("wf", p, s_)))
                 f1 = f1s if f1 is None else f1 + f1s
                 f2 = f2s if f2 is None else f2 + f2s
-                R = None
-                if Wr is not None:      # residual conv1d(seq, F', 1) of the DROPPED input (layers.py:38-40): same draws
-                    Wrs = Wr[p].view(-1, S, D)[:, s_, :].contiguous()
-                    R, _, _ = ops.project_fwd(xs[p], Wrs, a1s[s_], a2s[s_], zero1, zero1, in_drop=in_drop, fts_drop=0.0,
-                                              seed=seed, row_offset=row_offset, seed_dev=seed_dev)
-                    R = R + br[p].view(S, D)[s_]
-                Rs.append(R)
-            if cfg.get("coef_sink") is not None:
-                if multi:
-                    raise NotImplementedError("return_coef is not provided under a node partition")
-                cfg["coef_sink"].append(ops.node_attn_coefs(graphs[p], f1, f2, coef_drop=coef_drop, seed=seed,
-                                                            mean_heads=bool(cfg.get("coef_mean", False)),
-                                                            seed_dev=seed_dev))
-            f2_tab = exchange(f2, ("wf2", lay, grp, p)).wait() if multi else f2      # the head's scores of every table row
+                Rs.append(_residual_fwd(run, xs[p], Wr[p].view(-1, S, D)[:, s_, :].contiguous(), br[p].view(S, D)[s_],
+                                        a1s[s_], a2s[s_], zero1, zero1, seed) if Wr is not None else None)
+            _sink_coefs(run, graphs[p], f1, f2, seed)
+            f2_tab = src.exchange(f2, run.tag("wf2", p)).wait()      # the head's scores of every table row
             per_s = []
             for s_ in range(S):
-                _, sv = ops.node_attn_fwd(plan.graph if plan is not None else graphs[p], Htabs[s_].wait(), f1, a2s[s_],
-                                          b2[p:p + 1], cs[s_],
+                _, sv = ops.node_attn_fwd(src.graph, Htabs[s_].wait(), f1, a2s[s_], b2[p:p + 1], cs[s_],
                                           out=M[:, p, s_ * D:(s_ + 1) * D], train=train, coef_drop=coef_drop,
-                                          fts_drop=in_drop, seed=seed, row_offset=row_offset, activation=cfg["act"],
-                                          table_gid=plan.gid if plan is not None else None, res=Rs[s_],
-                                          seed_dev=seed_dev, f2_src=f2_tab)
-                if train:
-                    per_s.append((Hs[s_], None) + sv[1:] + (Rs[s_],))      # the output slice: ctx.save_for_backward(M)
+                                          fts_drop=in_drop, seed=seed, row_offset=row_offset, activation=run.act,
+                                          table_gid=src.gid, res=Rs[s_], seed_dev=seed_dev, f2_src=f2_tab)
+                if train:      # the output slice: ctx.save_for_backward(M)
+                    per_s.append(_SavedPath(Hs[s_], f1, f2, *sv[1:], Rs[s_]))
             if train:
-                saved.append((f1, f2, per_s))
-        ctx.cfg, ctx.xs, ctx.graphs, ctx.S = cfg, xs, graphs, S
+                saved.append(per_s)
+        ctx.run, ctx.xs, ctx.graphs, ctx.S = run, xs, graphs, S
         ctx.xin_shape = tuple(Xin.shape) if Xin is not None else None
         ctx.saved_per_p = saved
-        ctx.in_drop, ctx.coef_drop = in_drop, coef_drop
         ctx.has_res = Wr is not None
         ctx.save_for_backward(W, a1, a2, c, *((Wr,) if Wr is not None else ()), *((M,) if train else ()))
         return M
@@ -512,20 +545,15 @@ class WideHeadAttention(torch.autograd.Function):
     def backward(ctx, dM):
         W, a1, a2, c = ctx.saved_tensors[:4]
         Wr = ctx.saved_tensors[4] if ctx.has_res else None
-        cfg, xs, graphs, S = ctx.cfg, ctx.xs, ctx.graphs, ctx.S
-        if not cfg["train"]:
+        run, xs, graphs, S = ctx.run, ctx.xs, ctx.graphs, ctx.S
+        if not run.train:
             raise RuntimeError("WideHeadAttention was run with train=False; no backward state")
         Mout = ctx.saved_tensors[-1]
         P, dev = len(graphs), W.device
         Fw = W.shape[1]
         dM = dM.contiguous()
-        graphs_t = cfg.get("graphs_t") or tuple(g.transpose() for g in graphs)
-        seed_dev = cfg.get("seed_dev")
-        part = cfg.get("part")
-        multi = part is not None and part.active
-        row_offset = part.row_start if part is not None else 0
-        plans_b = cfg.get("plans_b") if multi else None
-        lay, grp = cfg.get("layer", 0), cfg.get("group", 0)
+        graphs_t = run.transposed(graphs)
+        in_drop, coef_drop, row_offset, seed_dev = run.drop_in, run.drop_coef, run.row_offset, run.seed_dev
         dW = torch.empty((P, S, Fw, D), dtype=torch.float32, device=dev)
         da1, da2, dc = torch.empty_like(a1), torch.empty_like(a2), torch.empty_like(c)
         db1 = torch.empty((P,), dtype=torch.float32, device=dev)
@@ -535,51 +563,45 @@ class WideHeadAttention(torch.autograd.Function):
         if ctx.xin_shape is not None and ctx.needs_input_grad[0]:
             dXin = torch.zeros(ctx.xin_shape, dtype=torch.float32, device=dev)
         for p in range(P):
-            f1, f2, per_s = ctx.saved_per_p[p]
-            seed = int(cfg["seeds"][p])
+            per_s = ctx.saved_per_p[p]
+            f1, f2 = per_s[0].f1, per_s[0].f2
+            seed = int(run.seeds[p])
             a1s, a2s, cs = a1[p].view(S, 1, D), a2[p].view(S, 1, D), c[p].view(S, D)
-            plan = plans_b[p] if plans_b is not None else None
-            exchange = (plan.exchange_async if plan is not None else part.all_gather_rows_async) if multi else None
+            src = run.source_b(p, graphs_t[p], masked=False)[0]
             rows, df1 = [], None
             for s_ in range(S):       # row-local halves: g, the slice's share of df1
-                H, _, lse, aggp, tsum, R = per_s[s_]
-                gs, df1s, _ = ops.node_attn_bwd_rows(dM[:, p, s_ * D:(s_ + 1) * D], Mout[:, p, s_ * D:(s_ + 1) * D], aggp,
-                                                     tsum, f1, lse, cs[s_],
-                                                     activation=cfg["act"], K=1, FP=D, table_dtype=H.dtype, res=R,
+                sv = per_s[s_]
+                gs, df1s, _ = ops.node_attn_bwd_rows(dM[:, p, s_ * D:(s_ + 1) * D], Mout[:, p, s_ * D:(s_ + 1) * D], sv.aggp,
+                                                     sv.tsum, f1, sv.lse, cs[s_],
+                                                     activation=run.act, K=1, FP=D, table_dtype=sv.H.dtype, res=sv.R,
                                                      dc_out=dc[p, s_ * D:(s_ + 1) * D])
-                rows.append(exchange(gs, ("wb", lay, grp, p, s_)) if multi else _Ready(gs))      # one [g | stats] table per slice
+                rows.append(src.exchange(gs, run.tag("wb", p, s_)))      # one [g | stats] table per slice
                 df1 = df1s if df1 is None else df1 + df1s
                 if Wr is not None:
-                    g32 = ops.gs_views(gs, 1, D, H.dtype)[0].to(torch.float32).contiguous()
-                    ops.project_bwd(xs[p], g32, 1, D, in_drop=ctx.in_drop, seed=seed, row_offset=row_offset,
-                                    seed_dev=seed_dev, out=dWr[p, s_])
+                    dx = _residual_bwd(run, xs[p], _residual_g(gs, 1, D, sv.H.dtype), Wr[p].view(-1, S, D)[:, s_, :], 1, D,
+                                       seed, dWr[p, s_], dXin is not None)
                     if dXin is not None:
-                        Wrs = Wr[p].view(-1, S, D)[:, s_, :].contiguous()
-                        dXin[:, p, :] += ops.project_bwd_input(g32, Wrs, 1, D, in_drop=ctx.in_drop, seed=seed,
-                                                               row_offset=row_offset, seed_dev=seed_dev)
+                        dXin[:, p, :] += dx
             cols, df2 = [], None
             for s_ in range(S):       # transposed-graph halves with the head's df1; each returns its share of df2
-                H = per_s[s_][0]
-                dH, df2s = ops.node_attn_bwd_cols(plan.graph if plan is not None else graphs_t[p], rows[s_].wait(), H, f2,
-                                                  df1, a1s[s_], a2s[s_],
-                                                  coef_drop=ctx.coef_drop, fts_drop=ctx.in_drop, seed=seed,
-                                                  src_offset=row_offset, dst_offset=0,
-                                                  table_gid=plan.gid if plan is not None else None, seed_dev=seed_dev)
+                dH, df2s = ops.node_attn_bwd_cols(src.graph, rows[s_].wait(), per_s[s_].H, f2, df1, a1s[s_], a2s[s_],
+                                                  coef_drop=coef_drop, fts_drop=in_drop, seed=seed, src_offset=row_offset,
+                                                  dst_offset=0, table_gid=src.gid, seed_dev=seed_dev)
                 cols.append((dH, df2s))
                 df2 = df2s if df2 is None else df2 + df2s
             for s_ in range(S):
-                H = per_s[s_][0]
+                H = per_s[s_].H
                 dH, df2s = cols[s_]
                 if S > 1:             # the kernel added its own df2 share times a2; the head's total belongs there
                     dH.addcmul_(df2 - df2s, a2s[s_])
                 o1 = torch.empty((1,), dtype=torch.float32, device=dev) if s_ else db1[p:p + 1]
                 o2 = torch.empty((1,), dtype=torch.float32, device=dev) if s_ else db2[p:p + 1]
                 ops.score_param_bwd(H, df1, df2, K=1, FP=D, out=(da1[p].view(S, 1, D)[s_], da2[p].view(S, 1, D)[s_], o1, o2))
-                ops.project_bwd(xs[p], dH, 1, D, in_drop=ctx.in_drop, seed=seed, row_offset=row_offset, seed_dev=seed_dev,
+                ops.project_bwd(xs[p], dH, 1, D, in_drop=in_drop, seed=seed, row_offset=row_offset, seed_dev=seed_dev,
                                 out=dW[p, s_])
                 if dXin is not None:
                     Ws = W[p].view(-1, S, D)[:, s_, :].contiguous()
-                    dXin[:, p, :] += ops.project_bwd_input(dH, Ws, 1, D, in_drop=ctx.in_drop, seed=seed,
+                    dXin[:, p, :] += ops.project_bwd_input(dH, Ws, 1, D, in_drop=in_drop, seed=seed,
                                                            row_offset=row_offset, seed_dev=seed_dev)
         ctx.saved_per_p = None
         fold = lambda t: t.permute(0, 2, 1, 3).reshape(P, Fw, S * D)
@@ -737,89 +759,57 @@ def _squeeze_batch(seq: torch.Tensor, name="seq") -> torch.Tensor:
 
 def _single_head(seq, out_sz, graph, activation, in_drop, coef_drop, residual, params, training,
                  seed, return_coef=False):
-    """One head of width out_sz through the D=64 kernels: the head occupies slot 0 of K = 64/F'k head
-    slots of the lane-mapped width F'k = next of 4, 8, 16, 32, 64 >= out_sz; the columns beyond out_sz
-    and the other slots have zero weights."""
+    """One head of width out_sz.  Up to 64 columns it runs through the D=64 kernels (NodeLevelAttention): the head
+    occupies slot 0 of K = 64/F'k head slots of the lane-mapped width F'k = next of 4, 8, 16, 32, 64 >= out_sz.
+    Wider, it runs as ceil(out_sz / 64) column slices that share the head's scores, coefficients and per-head
+    dropout draws (WideHeadAttention).  The columns beyond out_sz and the other slots have zero weights."""
     x = _squeeze_batch(seq)
     if out_sz < 1:
         raise ValueError("out_sz must be positive")
-    if out_sz > D:
-        return _single_wide_head(x, out_sz, graph, activation, in_drop, coef_drop, residual, params, training, seed,
-                                 return_coef)
-    fpk = next(w for w in (4, 8, 16, 32, 64) if out_sz <= w)
-    K = D // fpk
-    dev = x.device
     Fin = x.shape[1]
+    if params["W"].shape[0] != Fin:
+        raise ValueError(f"W has {params['W'].shape[0]} input features, seq has {Fin}")
+    wide = out_sz > D
+    width = D * -(-out_sz // D)      # padded width of the head's columns
 
-    def pad_last(t, width):
-        out = t.new_zeros(t.shape[:-1] + (width,))
+    def pad_last(t, w=width):
+        out = t.new_zeros(t.shape[:-1] + (w,))
         out[..., :t.shape[-1]] = t
         return out
 
-    W = pad_last(params["W"], D)[None]                                   # (1,F,D)
-    a1 = torch.cat([pad_last(params["a1"], fpk)[None], x.new_zeros(K - 1, fpk)])[None]   # (1,K,F'k)
-    a2 = torch.cat([pad_last(params["a2"], fpk)[None], x.new_zeros(K - 1, fpk)])[None]
-    b1 = pad_last(params["b1"].reshape(1), K)[None]
-    b2 = pad_last(params["b2"].reshape(1), K)[None]
-    c = pad_last(params["c"], D)[None]
-    if W.shape[1] != Fin:
-        raise ValueError(f"W has {W.shape[1]} input features, seq has {Fin}")
+    W = pad_last(params["W"])[None]                                      # (1,F,width)
+    if wide:
+        a1, a2 = pad_last(params["a1"])[None], pad_last(params["a2"])[None]
+        b1, b2 = params["b1"].reshape(1), params["b2"].reshape(1)
+    else:
+        fpk = next(w for w in (4, 8, 16, 32, 64) if out_sz <= w)
+        K = D // fpk
+        a1 = torch.cat([pad_last(params["a1"], fpk)[None], x.new_zeros(K - 1, fpk)])[None]   # (1,K,F'k)
+        a2 = torch.cat([pad_last(params["a2"], fpk)[None], x.new_zeros(K - 1, fpk)])[None]
+        b1 = pad_last(params["b1"].reshape(1), K)[None]
+        b2 = pad_last(params["b2"].reshape(1), K)[None]
+    c = pad_last(params["c"])[None]
     code, post = _act_code(activation)
     train = bool(training) or in_drop > 0 or coef_drop > 0 or W.requires_grad
-    cfg = {"train": train, "in_drop": in_drop, "coef_drop": coef_drop,
-           "seeds": (rng.next_seed() if seed is None else seed,), "act": code, "part": None,
-           "coef_sink": [] if return_coef else None}
+    run = LayerRun(train=train, in_drop=in_drop, coef_drop=coef_drop,
+                   seeds=(rng.next_seed() if seed is None else seed,), act=code,
+                   coef_sink=[] if return_coef else None, coef_mean=wide)
     Wr = br = None
     if residual and Fin != out_sz:
         # utils/layers.py:38-40: + conv1d(seq, out_sz, 1) of the DROPPED input, before the
         # activation; when the widths are equal the reference's branch is a no-op (:42)
-        Wr = pad_last(params["res_W"], D)[None]
-        br = pad_last(params["res_b"], D)[None]
-    M = NodeLevelAttention.apply(None, W, a1, b1, a2, b2, c, Wr, br, (x,), (graph,), cfg)
-    ret = M[:, 0, :out_sz]
-    if post is not None:
-        ret = post(ret)
-    if return_coef:       # slot 0 of the K head slots is this head
-        coefs = torch.sparse_csr_tensor(graph.rowptr, graph.colidx.long(),
-                                        cfg["coef_sink"][0][:, 0].contiguous(), (graph.n_rows, graph.n_cols))
-        return ret[None], coefs
-    return ret[None]     # (1,N,out_sz)
-
-
-def _single_wide_head(x, out_sz, graph, activation, in_drop, coef_drop, residual, params, training, seed,
-                      return_coef):
-    """One head wider than 64 columns: ceil(out_sz / 64) column slices that share the head's scores, coefficients
-    and per-head dropout draws (WideHeadAttention); columns beyond out_sz carry zero weights."""
-    S = -(-out_sz // D)
-    Fin = x.shape[1]
-
-    def pad_last(t):
-        out = t.new_zeros(t.shape[:-1] + (S * D,))
-        out[..., :t.shape[-1]] = t
-        return out
-
-    W = pad_last(params["W"])[None]
-    if W.shape[1] != Fin:
-        raise ValueError(f"W has {W.shape[1]} input features, seq has {Fin}")
-    a1, a2, c = (pad_last(params[k])[None] for k in ("a1", "a2", "c"))
-    b1, b2 = params["b1"].reshape(1), params["b2"].reshape(1)
-    code, post = _act_code(activation)
-    train = bool(training) or in_drop > 0 or coef_drop > 0 or W.requires_grad
-    cfg = {"train": train, "in_drop": in_drop, "coef_drop": coef_drop,
-           "seeds": (rng.next_seed() if seed is None else seed,), "act": code, "part": None,
-           "coef_sink": [] if return_coef else None, "coef_mean": True}
-    Wr = br = None
-    if residual and Fin != out_sz:
         Wr, br = pad_last(params["res_W"])[None], pad_last(params["res_b"])[None]
-    M = WideHeadAttention.apply(None, W, a1, b1, a2, b2, c, Wr, br, (x,), (graph,), cfg)
+    fn = WideHeadAttention if wide else NodeLevelAttention
+    M = fn.apply(None, W, a1, b1, a2, b2, c, Wr, br, (x,), (graph,), run)
     ret = M[:, 0, :out_sz]
     if post is not None:
         ret = post(ret)
-    if return_coef:
-        coefs = torch.sparse_csr_tensor(graph.rowptr, graph.colidx.long(), cfg["coef_sink"][0].contiguous(),
+    if return_coef:       # the head's mean over its one head (wide), or slot 0 of the K head slots
+        coef = run.coef_sink[0] if wide else run.coef_sink[0][:, 0]
+        coefs = torch.sparse_csr_tensor(graph.rowptr, graph.colidx.long(), coef.contiguous(),
                                         (graph.n_rows, graph.n_cols))
         return ret[None], coefs
-    return ret[None]
+    return ret[None]     # (1,N,out_sz)
 
 
 def attn_head(seq, out_sz, bias_mat, activation, in_drop=0.0, coef_drop=0.0, residual=False,

@@ -6,6 +6,7 @@ kernel sees the pointers (the kernels assume validated input).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import torch
@@ -51,6 +52,28 @@ _retired_workspaces: list = []      # superseded buffers stay alive: a captured 
 K2_TIMING: list | None = None
 
 
+def _ptr(t):
+    """Device pointer of an optional tensor (NULL for None)."""
+    return t.data_ptr() if t is not None else None
+
+
+class _k2_timed:
+    """Bracket a K2 launch with the timing events of K2_TIMING (nothing when it is None)."""
+
+    def __init__(self, tag, n_rows, nnz):
+        self.sink, self.rec = K2_TIMING, (tag, n_rows, nnz)
+
+    def __enter__(self):
+        if self.sink is not None:
+            self.ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.ev[0].record()
+
+    def __exit__(self, *exc):
+        if self.sink is not None:
+            self.ev[1].record()
+            self.sink.append((self.rec[0],) + self.ev + self.rec[1:])
+
+
 def _dev_word(t):
     """Device pointer of a 1-element int64 tensor (seed_dev / step_dev of the C ABI), or None."""
     if t is None:
@@ -72,8 +95,22 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-WS_SUFFIX = ""             # set by layers._on_path: kernels of different meta-paths that run concurrently (one side stream per
-                           # meta-path inside a captured epoch) must not share a scratch buffer
+WS_SUFFIX = ""             # set by branch(): kernels that run concurrently (one stream per meta-path inside a captured epoch,
+                           # the side stream, the eval branch) must not share a scratch buffer
+
+
+@contextlib.contextmanager
+def branch(stream, suffix=""):
+    """Run the enclosed launches on `stream` (None: in place) with scratch buffers of their own: `suffix` is appended
+    to every workspace tag (_ws).  Scopes nest, suffixes in nesting order.  The caller orders the streams (fork before,
+    join after); the suffix is the caller's too, since an in-place branch may still need its own buffers."""
+    global WS_SUFFIX
+    prev, WS_SUFFIX = WS_SUFFIX, WS_SUFFIX + suffix
+    try:
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            yield
+    finally:
+        WS_SUFFIX = prev
 
 
 def _ws(nbytes: int, device, tag: str = "") -> torch.Tensor:
@@ -147,7 +184,6 @@ def _row_split_arg(graph: CSRGraph, tag: str, bins: bool = True, split: bool = T
     if sp is None and rb is None:
         return None, None
     lib = _lib.load()
-    ptr = lambda t: t.data_ptr() if t is not None else None
     if sp is not None:
         ws = _ws(lib.han_row_split_workspace(sp["n_chunks"]), graph.device, "split" + tag)
         st = _lib.HanRowSplit(sp["split_deg"], sp["n_long"], sp["n_chunks"], sp["long_rows"].data_ptr(),
@@ -159,7 +195,7 @@ def _row_split_arg(graph: CSRGraph, tag: str, bins: bool = True, split: bool = T
         st = _lib.HanRowSplit(SPLIT_DEG, 0, 0, None, None, None, None, None, None, 0, 0, 0, None, None)
     if rb is not None:
         st.n_short, st.n_mid = rb["n_short"], rb["n_mid"]
-        st.short_rows, st.mid_rows = ptr(rb["short_rows"]), ptr(rb["mid_rows"])
+        st.short_rows, st.mid_rows = _ptr(rb["short_rows"]), _ptr(rb["mid_rows"])
     return st, (sp, rb, ws)
 
 
@@ -224,44 +260,52 @@ def project_fwd(X, W, a1, a2, b1, b2, in_drop=0.0, fts_drop=0.0, seed=0, row_off
     lib = _lib.load()
     if X.dim() != 2:
         raise ValueError(f"X: expected (N,F), got {tuple(X.shape)}")
+    xcode, ldx, N, F, K, FP, in_drop, fts_drop, H, f1, f2, ws, keep = _project_fwd_setup(
+        X, W, a1, a2, b1, b2, (), in_drop, fts_drop, table_dtype, flags, want_keep, lib.han_project_fwd_workspace)
+    _lib.check(lib.han_project_fwd(
+        X.data_ptr(), xcode, ldx, W.data_ptr(), a1.data_ptr(),
+        a2.data_ptr(), b1.data_ptr(), b2.data_ptr(), H.data_ptr(), DTYPE_CODE[table_dtype],
+        f1.data_ptr(), f2.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0, N, F, K, FP,
+        in_drop, fts_drop, int(seed), _dev_word(seed_dev), int(row_offset),
+        _ptr(keep), int(flags), _stream()), "han_project_fwd")
+    if want_keep:
+        return H, f1, f2, keep
+    return H, f1, f2
+
+
+def _project_fwd_setup(X, W, a1, a2, b1, b2, lead, in_drop, fts_drop, table_dtype, flags, want_keep, ws_bytes):
+    """What project_fwd (lead = ()) and project_fwd_multi (lead = (P,)) share: the argument checks, the outputs
+    H lead + (N,D), f1 / f2 lead + (N,K), the workspace of ws_bytes(N, F, K, FP, *lead) bytes (> 0 only for short
+    inputs: split-F) and the keep table lead + (han_project_keep_bytes(),), or None when this call has none."""
     _chk(X, "X", contiguous=False, dtype=X.dtype)
     xcode = _dtype_code(X, "X")
     if X.stride(1) != 1:
         raise ValueError("X: rows must be contiguous")
     N, F = X.shape
     dev = X.device
-    K, FP = a1.shape
+    K, FP = a1.shape[len(lead):]
     if table_dtype not in DTYPE_CODE:
         raise ValueError(f"table_dtype {table_dtype}: expected float32 or bfloat16")
     _check_heads(K, FP)
-    _chk(W, "W", (F, D), device=dev)
-    _chk(a1, "a1", (K, FP), device=dev)
-    _chk(a2, "a2", (K, FP), device=dev)
-    _chk(b1, "b1", (K,), device=dev)
-    _chk(b2, "b2", (K,), device=dev)
+    _chk(W, "W", lead + (F, D), device=dev)
+    _chk(a1, "a1", lead + (K, FP), device=dev)
+    _chk(a2, "a2", lead + (K, FP), device=dev)
+    _chk(b1, "b1", lead + (K,), device=dev)
+    _chk(b2, "b2", lead + (K,), device=dev)
     in_drop = _check_drop(in_drop, "in_drop")
     fts_drop = _check_drop(fts_drop, "fts_drop")
-    H = torch.empty((N, D), dtype=table_dtype, device=dev)
-    f1 = torch.empty((N, K), dtype=torch.float32, device=dev)
-    f2 = torch.empty((N, K), dtype=torch.float32, device=dev)
-    nbytes = lib.han_project_fwd_workspace(N, F, K, FP)      # > 0 only for short inputs (split-F)
+    H = torch.empty(lead + (N, D), dtype=table_dtype, device=dev)
+    f1 = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
+    f2 = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
+    nbytes = ws_bytes(N, F, K, FP, *lead)
     ws = _ws(nbytes, dev, "projf") if nbytes else None
     ldx = X.stride(0) if N > 1 else max(F, X.stride(0))
     keep = None
     if want_keep and in_drop > 0 and not (flags & FLAG_K1_EXACT_PIPE) and X.data_ptr() % 16 == 0:
-        kb = lib.han_project_keep_bytes(N, F, ldx, K, FP)
+        kb = _lib.load().han_project_keep_bytes(N, F, ldx, K, FP)
         if kb:
-            keep = torch.empty(kb, dtype=torch.uint8, device=dev)
-    _lib.check(lib.han_project_fwd(
-        X.data_ptr(), xcode, ldx, W.data_ptr(), a1.data_ptr(),
-        a2.data_ptr(), b1.data_ptr(), b2.data_ptr(), H.data_ptr(), DTYPE_CODE[table_dtype],
-        f1.data_ptr(), f2.data_ptr(), ws.data_ptr() if ws is not None else None,
-        ws.numel() if ws is not None else 0, N, F, K, FP,
-        in_drop, fts_drop, int(seed), _dev_word(seed_dev), int(row_offset),
-        keep.data_ptr() if keep is not None else None, int(flags), _stream()), "han_project_fwd")
-    if want_keep:
-        return H, f1, f2, keep
-    return H, f1, f2
+            keep = torch.empty(lead + (kb,), dtype=torch.uint8, device=dev)
+    return xcode, ldx, N, F, K, FP, in_drop, fts_drop, H, f1, f2, ws, keep
 
 
 def keep_bytes(N, F, ldx, K=8, FP=8) -> int:
@@ -279,43 +323,19 @@ def project_fwd_multi(X, W, a1, a2, b1, b2, in_drop=0.0, fts_drop=0.0, seeds=Non
     lib = _lib.load()
     if X.dim() != 2 or W.dim() != 3:
         raise ValueError(f"X: expected (N,F) and W (P,F,D), got {tuple(X.shape)}, {tuple(W.shape)}")
-    _chk(X, "X", contiguous=False, dtype=X.dtype)
-    xcode = _dtype_code(X, "X")
-    if X.stride(1) != 1:
-        raise ValueError("X: rows must be contiguous")
-    N, F = X.shape
-    dev = X.device
-    P, K, FP = a1.shape
-    if table_dtype not in DTYPE_CODE:
-        raise ValueError(f"table_dtype {table_dtype}: expected float32 or bfloat16")
-    _check_heads(K, FP)
-    _chk(W, "W", (P, F, D), device=dev)
-    _chk(a1, "a1", (P, K, FP), device=dev)
-    _chk(a2, "a2", (P, K, FP), device=dev)
-    _chk(b1, "b1", (P, K), device=dev)
-    _chk(b2, "b2", (P, K), device=dev)
-    in_drop = _check_drop(in_drop, "in_drop")
-    fts_drop = _check_drop(fts_drop, "fts_drop")
+    P = a1.shape[0]
+    xcode, ldx, N, F, K, FP, in_drop, fts_drop, H, f1, f2, ws, keep = _project_fwd_setup(
+        X, W, a1, a2, b1, b2, (P,), in_drop, fts_drop, table_dtype, flags, want_keep,
+        lib.han_project_fwd_multi_workspace)
     if (in_drop > 0 or fts_drop > 0) and (seeds is None or len(seeds) != P):
         raise ValueError("dropout needs one seed per meta-path")
-    H = torch.empty((P, N, D), dtype=table_dtype, device=dev)
-    f1 = torch.empty((P, N, K), dtype=torch.float32, device=dev)
-    f2 = torch.empty((P, N, K), dtype=torch.float32, device=dev)
-    nbytes = lib.han_project_fwd_multi_workspace(N, F, K, FP, P)
-    ws = _ws(nbytes, dev, "projf") if nbytes else None
-    ldx = X.stride(0) if N > 1 else max(F, X.stride(0))
-    keep, kb = None, 0
-    if want_keep and in_drop > 0 and not (flags & FLAG_K1_EXACT_PIPE) and X.data_ptr() % 16 == 0:
-        kb = lib.han_project_keep_bytes(N, F, ldx, K, FP)
-        if kb:
-            keep = torch.empty((P, kb), dtype=torch.uint8, device=dev)
     seed_arr = (ctypes.c_uint64 * P)(*[int(x) & ((1 << 64) - 1) for x in (seeds if seeds is not None else [0] * P)])
     _lib.check(lib.han_project_fwd_multi(
         X.data_ptr(), xcode, ldx, W.data_ptr(), a1.data_ptr(), a2.data_ptr(), b1.data_ptr(), b2.data_ptr(),
         H.data_ptr(), DTYPE_CODE[table_dtype], f1.data_ptr(), f2.data_ptr(),
-        ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, N, F, K, FP, P,
+        _ptr(ws), ws.numel() if ws is not None else 0, N, F, K, FP, P,
         in_drop, fts_drop, seed_arr, _dev_word(seed_dev), int(row_offset),
-        keep.data_ptr() if keep is not None else None, int(flags), _stream()), "han_project_fwd_multi")
+        _ptr(keep), int(flags), _stream()), "han_project_fwd_multi")
     if want_keep:
         return H, f1, f2, [keep[p] if keep is not None else None for p in range(P)]
     return H, f1, f2
@@ -339,7 +359,7 @@ def project_bwd(X, dH, K, FP, in_drop=0.0, seed=0, row_offset=0, seed_dev=None, 
     _lib.check(lib.han_project_bwd(
         X.data_ptr(), xcode, ldx, dH.data_ptr(), dW.data_ptr(),
         ws.data_ptr(), ws.numel(), N, F, K, FP, _check_drop(in_drop, "in_drop"), int(seed), _dev_word(seed_dev),
-        int(row_offset), keep.data_ptr() if keep is not None else None, _stream()), "han_project_bwd")
+        int(row_offset), _ptr(keep), _stream()), "han_project_bwd")
     return dW
 
 
@@ -430,26 +450,19 @@ def node_attn_fwd(graph: CSRGraph, H_tab, f1, a2, b2, c, out=None, train=False, 
         ptrs = [None, lse.data_ptr(), aggp.data_ptr(), tsum.data_ptr()]
     split, _keep = _row_split_arg(graph, "f", bins=not lean, split=not lean)
     dense, _keep_d = _dense_arg(graph, train, "f") if (lean and f2_src is None and _use_dense(graph, H_tab, K, FP)) else (None, None)
-    timing = K2_TIMING
-    if timing is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _lib.check(lib.han_node_attn_fwd(
-        graph.rowptr.data_ptr(), graph.colidx.data_ptr(),
-        graph.values.data_ptr() if graph.values is not None else None, H_tab.data_ptr(), tcode,
-        table_gid.data_ptr() if table_gid is not None else None, f1.data_ptr(),
-        f2.data_ptr() if (lean or f2_src is not None) else None,
-        a2.data_ptr(), b2.data_ptr(), c.data_ptr(), res.data_ptr() if res is not None else None,
-        out.data_ptr(), out.stride(0) if N > 1 else D,
-        ptrs[0], ptrs[1], ptrs[2], ptrs[3], N, graph.nnz, K, FP, LEAKY_SLOPE, coef_drop, fts_drop,
-        int(seed), _dev_word(seed_dev), int(row_offset), int(activation),
-        (FLAG_XCD_ORDER if graph.has_locality() else 0) | (FLAG_LEAN if lean else 0) | (FLAG_K2_DEEP if K2_DEEP else 0)
-        | (FLAG_K2_SHARED_HASH if K2_SHARED_HASH else 0),
-        ctypes.byref(split) if split is not None else None,
-        ctypes.byref(dense) if dense is not None else None, _stream()), "han_node_attn_fwd")
-    if timing is not None:
-        ev1.record()
-        timing.append(("train" if train else "eval", ev0, ev1, N, graph.nnz))
+    with _k2_timed("train" if train else "eval", N, graph.nnz):
+        _lib.check(lib.han_node_attn_fwd(
+            graph.rowptr.data_ptr(), graph.colidx.data_ptr(),
+            _ptr(graph.values), H_tab.data_ptr(), tcode, _ptr(table_gid), f1.data_ptr(),
+            f2.data_ptr() if (lean or f2_src is not None) else None,
+            a2.data_ptr(), b2.data_ptr(), c.data_ptr(), _ptr(res),
+            out.data_ptr(), out.stride(0) if N > 1 else D,
+            ptrs[0], ptrs[1], ptrs[2], ptrs[3], N, graph.nnz, K, FP, LEAKY_SLOPE, coef_drop, fts_drop,
+            int(seed), _dev_word(seed_dev), int(row_offset), int(activation),
+            (FLAG_XCD_ORDER if graph.has_locality() else 0) | (FLAG_LEAN if lean else 0) | (FLAG_K2_DEEP if K2_DEEP else 0)
+            | (FLAG_K2_SHARED_HASH if K2_SHARED_HASH else 0),
+            ctypes.byref(split) if split is not None else None,
+            ctypes.byref(dense) if dense is not None else None, _stream()), "han_node_attn_fwd")
     return out, saved
 
 
@@ -473,8 +486,7 @@ def node_attn_coefs(graph: CSRGraph, f1, f2, coef_drop=0.0, seed=0, row_offset=0
     coef = torch.empty((graph.nnz,) if mean_heads else (graph.nnz, K), dtype=torch.float32, device=dev)
     _lib.check(lib.han_node_attn_coefs(
         graph.rowptr.data_ptr(), graph.colidx.data_ptr(),
-        graph.values.data_ptr() if graph.values is not None else None,
-        table_gid.data_ptr() if table_gid is not None else None, f1.data_ptr(), f2.data_ptr(),
+        _ptr(graph.values), _ptr(table_gid), f1.data_ptr(), f2.data_ptr(),
         coef.data_ptr(), int(bool(mean_heads)), graph.n_rows, graph.nnz, K, FP, LEAKY_SLOPE,
         _check_drop(coef_drop, "coef_drop"), int(seed), _dev_word(seed_dev), int(row_offset), _stream()), "han_node_attn_coefs")
     return coef
@@ -526,7 +538,7 @@ def node_attn_bwd_rows(dOut, out, aggp, tsum, f1, lse, c, activation=ACT_ELU, K=
     _lib.check(lib.han_node_attn_bwd_rows(
         dOut.data_ptr(), dOut.stride(0) if N > 1 else D, out.data_ptr(), out.stride(0) if N > 1 else D, aggp.data_ptr(),
         tsum.data_ptr(), f1.data_ptr(), lse.data_ptr(), c.data_ptr(),
-        res.data_ptr() if res is not None else None, gs.data_ptr(),
+        _ptr(res), gs.data_ptr(),
         DTYPE_CODE[table_dtype], df1.data_ptr(), dc.data_ptr(), ws.data_ptr(), ws.numel(), N, K, FP,
         int(activation), _stream()), "han_node_attn_bwd_rows")
     return gs, df1, dc
@@ -558,24 +570,17 @@ def node_attn_bwd_cols(graph_t: CSRGraph, gs_tab, H, f2, df1, a1, a2, coef_drop=
     lean_b = not graph_t.masked and _use_lean(graph_t, H)
     split, _keep = _row_split_arg(graph_t, "b", bins=not lean_b, split=not lean_b)
     dense, _keep_d = _dense_arg(graph_t, False, "b") if (lean_b and table_gid is None and _use_dense(graph_t, H, K, FP)) else (None, None)
-    timing = K2_TIMING
-    if timing is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    _lib.check(lib.han_node_attn_bwd_cols(
-        graph_t.rowptr.data_ptr(), graph_t.colidx.data_ptr(),
-        graph_t.values.data_ptr() if graph_t.values is not None else None, gs_tab.data_ptr(),
-        table_gid.data_ptr() if table_gid is not None else None, H.data_ptr(),
-        tcode, f2.data_ptr(), df1.data_ptr(), a1.data_ptr(), a2.data_ptr(), dH.data_ptr(), df2.data_ptr(),
-        NS, graph_t.nnz, K, FP, LEAKY_SLOPE, _check_drop(coef_drop, "coef_drop"), fts_drop,
-        int(seed), _dev_word(seed_dev), int(src_offset), int(dst_offset),
-        (FLAG_XCD_ORDER if graph_t.has_locality() else 0) | (FLAG_MASKED_EDGES if graph_t.masked else 0)
-        | (FLAG_LEAN if lean_b else 0),
-        ctypes.byref(split) if split is not None else None,
-        ctypes.byref(dense) if dense is not None else None, _stream()), "han_node_attn_bwd_cols")
-    if timing is not None:
-        ev1.record()
-        timing.append(("bwd_cols", ev0, ev1, NS, graph_t.nnz))
+    with _k2_timed("bwd_cols", NS, graph_t.nnz):
+        _lib.check(lib.han_node_attn_bwd_cols(
+            graph_t.rowptr.data_ptr(), graph_t.colidx.data_ptr(),
+            _ptr(graph_t.values), gs_tab.data_ptr(), _ptr(table_gid), H.data_ptr(),
+            tcode, f2.data_ptr(), df1.data_ptr(), a1.data_ptr(), a2.data_ptr(), dH.data_ptr(), df2.data_ptr(),
+            NS, graph_t.nnz, K, FP, LEAKY_SLOPE, _check_drop(coef_drop, "coef_drop"), fts_drop,
+            int(seed), _dev_word(seed_dev), int(src_offset), int(dst_offset),
+            (FLAG_XCD_ORDER if graph_t.has_locality() else 0) | (FLAG_MASKED_EDGES if graph_t.masked else 0)
+            | (FLAG_LEAN if lean_b else 0),
+            ctypes.byref(split) if split is not None else None,
+            ctypes.byref(dense) if dense is not None else None, _stream()), "han_node_attn_bwd_cols")
     return dH, df2
 
 
@@ -646,21 +651,26 @@ def sem_attn_bwd(M, w_omega, b_omega, u_omega, beta, dZ, out=None, flags=0):
 
 
 # ------------------------------------------------------------- classifier + loss
-def classifier_loss(Z, Wc, bc, labels, mask, row_weight, backward=False, grad_out=None):
-    """models/gat.py:65-72 + models/base_gattn.py:41-48,61-69.
-    Z (N,D); Wc (HC,D,C); bc (HC,C); labels int32 (N,); mask uint8 (N,).
-    Returns logits (N,C), loss_acc (2,) [masked CE, masked accuracy] and, if
-    backward, (dZ, dWc, dbc) [dWc, dbc written to the tensors of grad_out when given]."""
-    lib = _lib.load()
+def _classifier_args(Z, Wc, bc):
+    """The checks classifier_loss and classifier_bwd share; returns (N, device, HC, D, C)."""
     _chk(Z, "Z")
-    N = Z.shape[0]
-    dev = Z.device
+    N, dev = Z.shape[0], Z.device
     HC, Dm, C = Wc.shape
     if Dm % 64 != 0 or Dm == 0:
         raise ValueError(f"Wc: the embedding width must be a multiple of 64 (zero-pad it), got {Dm}")
     _chk(Z, "Z", (N, Dm))
     _chk(Wc, "Wc", (HC, Dm, C), device=dev)
     _chk(bc, "bc", (HC, C), device=dev)
+    return N, dev, HC, Dm, C
+
+
+def classifier_loss(Z, Wc, bc, labels, mask, row_weight, backward=False, grad_out=None):
+    """models/gat.py:65-72 + models/base_gattn.py:41-48,61-69.
+    Z (N,D); Wc (HC,D,C); bc (HC,C); labels int32 (N,); mask uint8 (N,).
+    Returns logits (N,C), loss_acc (2,) [masked CE, masked accuracy] and, if
+    backward, (dZ, dWc, dbc) [dWc, dbc written to the tensors of grad_out when given]."""
+    lib = _lib.load()
+    N, dev, HC, Dm, C = _classifier_args(Z, Wc, bc)
     _chk(labels, "labels", (N,), dtype=torch.int32, device=dev)
     _chk(mask, "mask", (N,), dtype=torch.uint8, device=dev)
     logits = torch.empty((N, C), dtype=torch.float32, device=dev)
@@ -686,14 +696,7 @@ def classifier_bwd(Z, Wc, bc, dlogits):
     """Backward of logits = (1/HC) sum_h (Z Wc[h] + bc[h]) (models/gat.py:65-72) for a given dlogits (N,C):
     returns (dZ, dWc, dbc)."""
     lib = _lib.load()
-    _chk(Z, "Z")
-    N, dev = Z.shape[0], Z.device
-    HC, Dm, C = Wc.shape
-    if Dm % 64 != 0 or Dm == 0:
-        raise ValueError(f"Wc: the embedding width must be a multiple of 64 (zero-pad it), got {Dm}")
-    _chk(Z, "Z", (N, Dm))
-    _chk(Wc, "Wc", (HC, Dm, C), device=dev)
-    _chk(bc, "bc", (HC, C), device=dev)
+    N, dev, HC, Dm, C = _classifier_args(Z, Wc, bc)
     _chk(dlogits, "dlogits", (N, C), device=dev)
     dZ = torch.empty((N, Dm), dtype=torch.float32, device=dev)
     dWc, dbc = torch.empty_like(Wc), torch.empty_like(bc)

@@ -27,7 +27,7 @@ class _EvalBranch:
     that fit the training step's fork / join sections: node_level() (K1 + K2 of every meta-path -> M) runs beside
     the training forward's per-meta-path chains, head() (K3, classifier, loss; the copy of the parameters) beside
     the backward's.  Each piece forks `stream` from the current stream, runs as one chain with scratch buffers of
-    its own (ops.WS_SUFFIX) and is joined by the section's own join (`join()`); with stream None the pieces run in
+    its own (ops.branch) and is joined by the section's own join (`join()`); with stream None the pieces run in
     place."""
 
     def __init__(self, trainer, stream):
@@ -38,17 +38,13 @@ class _EvalBranch:
         m = self.tr.model
         streams, m.path_streams = m.path_streams, None        # one chain: K1 of every meta-path in one launch
         branch, m.overlap_branch = getattr(m, "overlap_branch", None), None
-        prev, ops.WS_SUFFIX = ops.WS_SUFFIX, ops.WS_SUFFIX + "@eval"
         try:
-            with torch.no_grad():
-                if self.stream is None:
-                    fn()
-                else:
-                    self.stream.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(self.stream):
-                        fn()
+            if self.stream is not None:
+                self.stream.wait_stream(torch.cuda.current_stream())
+            with torch.no_grad(), ops.branch(self.stream, "@eval"):
+                fn()
         finally:
-            m.path_streams, m.overlap_branch, ops.WS_SUFFIX = streams, branch, prev
+            m.path_streams, m.overlap_branch = streams, branch
 
     def join(self):
         if self.stream is not None:
@@ -86,7 +82,7 @@ class HANTrainer:
         built with an all-to-all-v of the edges (NodePartition.shard_local_graph);
         labels int32 (N_local,) class ids; masks uint8/bool (N_local,).
         side_stream: False | True | "auto" -- the eager training step of a single process runs the backward's dW of
-        meta-path p on a second stream beside the transposed-graph gather of meta-path p + 1 (layers._on_side): +1.3-2.5 %
+        meta-path p on a second stream beside the transposed-graph gather of meta-path p + 1 (layers.NodeLevelAttention.backward): +1.3-2.5 %
         epochs/s at SYN-1M, bit-equal results.  Off by default: the gather's launch time then includes that company and
         no longer measures the gather.  "auto" = on from 262 144 table rows, where a gather is long enough to hide a dW.
         use_graph: capture one whole epoch (train step + eval forward, ~60 launches) into a
@@ -209,7 +205,7 @@ class HANTrainer:
             self.opt.step_dev = self.step_state[1:2]
             # one stream per meta-path: inside the captured epoch the per-meta-path chains (K1 -> K2, and the four
             # backward kernels) become parallel branches of the graph -- at these sizes every kernel is a few
-            # microseconds on a few CUs (layers._on_path); HAN_PATH_STREAMS=0 keeps the single chain
+            # microseconds on a few CUs (layers._each_path); HAN_PATH_STREAMS=0 keeps the single chain
             if dev.type == "cuda" and os.environ.get("HAN_PATH_STREAMS", "1") != "0" and len(self.graphs) > 1:
                 model.path_streams = [torch.cuda.Stream(device=dev) for _ in self.graphs]
             if self.overlap_eval:

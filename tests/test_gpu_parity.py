@@ -911,8 +911,7 @@ def test_sp_attn_head_weighted_adjacency_values(dev, drop, monkeypatch):
         leaf = {k: bp[k][0].clone().to(torch.float32).to(dev).requires_grad_(True)
                 for k in ("W", "a1", "b1", "a2", "b2", "c")}
         seed = 0xABCDEF12345
-        cfg = {"train": True, "in_drop": drop, "coef_drop": drop, "seeds": (seed,), "act": ops.ACT_ELU,
-               "part": None}
+        cfg = layers.LayerRun(train=True, in_drop=drop, coef_drop=drop, seeds=(seed,), act=ops.ACT_ELU, part=None)
         x = _t(prob["x"][0], dev)
         M = layers.NodeLevelAttention.apply(None, *(leaf[k][None] for k in ("W", "a1", "b1", "a2", "b2", "c")),
                                             None, None, (x,), (g,), cfg)
@@ -1557,7 +1556,7 @@ def test_path_streams_do_not_change_the_numbers(dev, monkeypatch):
 @pytest.mark.parametrize("residual", [False, True])
 def test_side_stream_does_not_change_the_numbers(dev, residual):
     """HANTrainer(side_stream=True): the backward's dW of meta-path p runs on a second stream beside the gather of
-    meta-path p + 1 (layers._on_side).  Same epochs on one stream: bit-equal losses and parameters -- the stream only
+    meta-path p + 1 (layers.NodeLevelAttention.backward).  Same epochs on one stream: bit-equal losses and parameters -- the stream only
     moves independent launches; dH is handed to it with record_stream, its scratch buffers are its own."""
     from han_amd import rng as hrng
     from han_amd.trainer import HANTrainer

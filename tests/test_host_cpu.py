@@ -209,7 +209,7 @@ def test_weighted_adjacency_values_on_cpu_backend(cpu_ops):
     bp = ht.to_batched(prob["params"])
     names = ("W", "a1", "b1", "a2", "b2", "c")
     leaf = {k: bp[k][0].clone().to(torch.float32).requires_grad_(True) for k in names}
-    cfg = {"train": True, "in_drop": 0.0, "coef_drop": 0.0, "seeds": (1,), "act": 1, "part": None}
+    cfg = layers.LayerRun(train=True, in_drop=0.0, coef_drop=0.0, seeds=(1,), act=1, part=None)
     x = torch.tensor(prob["x"][0], dtype=torch.float32)
     M = layers.NodeLevelAttention.apply(None, *(leaf[k][None] for k in names), None, None, (x,), (g,), cfg)
     wgt = torch.tensor(rng.standard_normal((n, 64)))
