@@ -85,9 +85,13 @@ SIGNATURES = {
     "han_spgemm_row_bounds": (c_int, [P, P, P, I64, I64, c_int, P, P]),
     "han_spgemm_count": (c_int, [P, P, P, P, I64, I64, I64, P, P, I64, I64, c_int, P, P]),
     "han_spgemm_fill": (c_int, [P, P, P, P, I64, I64, I64, P, P, I64, I64, c_int, P, P, P]),
+    "han_spgemm_values": (c_int, [P, P, P, P, P, P, I64, I64, I64, P, P, I64, I64, c_int, P, P, I64, P, P]),
+    "han_csr_pathsim": (c_int, [P, P, P, I64, P, P, P]),
+    "han_csr_row_topk_count": (c_int, [P, P, I64, I64, c_int, P, P]),
+    "han_csr_row_topk_fill": (c_int, [P, P, P, I64, I64, c_int, P, P, P, P]),
 }
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 _lib = None
 
 

@@ -15,6 +15,8 @@
 //       candidate reads.
 // Both forms write sorted, unique columns, so the output does not depend on scheduling (bitwise deterministic).
 // Offsets (row pointers, bounds, output positions) are int64 throughout.
+// Weighted graphs (further down): the int64 instance counts of C in one more pass over the same bins, PathSim of a
+// counted graph, and the per-row top-k cut of a graph with values.
 #include "han_common.h"
 
 namespace {
@@ -62,14 +64,14 @@ __global__ __launch_bounds__(kBoundsBlock) void spgemm_row_bounds(const int64_t 
     }
 }
 
-// Calls f(p, c) for every candidate column c of `row` (one call per product, repeats included; p = the candidate's
-// position in A-row order) spread over the G threads of the block -- G consecutive A entries at a time: an
+// Calls f(p, ea, eb) for every product of `row` (repeats included; p = the product's position in A-row order, ea / eb
+// the entries of A and B it joins) spread over the G threads of the block -- G consecutive A entries at a time: an
 // inclusive scan of their B-row lengths in LDS, then thread t takes positions t, t + G, ... of the chunk and finds
-// its A entry by a binary search over the scan (balanced whatever the B-row lengths).  Returns the candidate count.
+// its A entry by a binary search over the scan (balanced whatever the B-row lengths).  Returns the product count.
 // Every thread of the block must call it (it synchronises).
 template <int G, typename F>
-__device__ __forceinline__ int64_t for_each_candidate(const SpgemmArgs &a, int64_t row, int64_t *s_off,
-                                                      int64_t *s_beg, F &&f) {
+__device__ __forceinline__ int64_t for_each_product(const SpgemmArgs &a, int64_t row, int64_t *s_off,
+                                                    int64_t *s_beg, F &&f) {
     const int t = threadIdx.x;
     const int64_t a0 = a.a_rowptr[row], a1 = a.a_rowptr[row + 1];
     int64_t base = 0;
@@ -101,12 +103,19 @@ __device__ __forceinline__ int64_t for_each_candidate(const SpgemmArgs &a, int64
                 if (s_off[mid] <= p) lo = mid;
                 else hi = mid;
             }
-            f(base + p, a.b_colidx[s_beg[lo] + (p - s_off[lo])]);
+            f(base + p, c0 + lo, s_beg[lo] + (p - s_off[lo]));
         }
         base += total;
         __syncthreads();         // s_off / s_beg are rewritten by the next chunk
     }
     return base;
+}
+
+// f(p, c) for every candidate column c of `row`: the column of every product
+template <int G, typename F>
+__device__ __forceinline__ int64_t for_each_candidate(const SpgemmArgs &a, int64_t row, int64_t *s_off,
+                                                      int64_t *s_beg, F &&f) {
+    return for_each_product<G>(a, row, s_off, s_beg, [&](int64_t p, int64_t, int64_t eb) { f(p, a.b_colidx[eb]); });
 }
 
 template <bool FILL>
@@ -166,8 +175,9 @@ __device__ __forceinline__ void spgemm_short_rows(const SpgemmArgs &a) {
     }
 }
 
-// exclusive scan of v over the 256 threads of the block (every thread also gets the total)
-__device__ __forceinline__ int block_excl_scan256(int v, int *s_wave, int &total) {
+// exclusive scan of v over the G threads of the block (every thread also gets the total)
+template <int G>
+__device__ __forceinline__ int block_excl_scan(int v, int *s_wave, int &total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int x = v;
 #pragma unroll
@@ -180,7 +190,7 @@ __device__ __forceinline__ int block_excl_scan256(int v, int *s_wave, int &total
     int pre = 0;
     total = 0;
 #pragma unroll
-    for (int k = 0; k < kLongBlock / 64; ++k) {
+    for (int k = 0; k < G / 64; ++k) {
         pre += k < w ? s_wave[k] : 0;
         total += s_wave[k];
     }
@@ -218,7 +228,7 @@ __device__ __forceinline__ void spgemm_long_rows(const SpgemmArgs &a) {
             int mine = 0;
             for (int w = w0; w < w1; ++w) mine += __popc(bits[w]);
             int tile_total;
-            const int excl = block_excl_scan256(mine, s_wave, tile_total);
+            const int excl = block_excl_scan<kLongBlock>(mine, s_wave, tile_total);
             if (FILL) {
                 int64_t pos = base + total + excl;
                 for (int w = w0; w < w1; ++w) {
@@ -243,18 +253,15 @@ __global__ __launch_bounds__(64) void spgemm_short_fill(SpgemmArgs a) { spgemm_s
 __global__ __launch_bounds__(kLongBlock) void spgemm_long_count(SpgemmArgs a) { spgemm_long_rows<false>(a); }
 __global__ __launch_bounds__(kLongBlock) void spgemm_long_fill(SpgemmArgs a) { spgemm_long_rows<true>(a); }
 
-int spgemm_launch(bool fill, const int64_t *a_rowptr, const int32_t *a_colidx, const int64_t *b_rowptr,
-                  const int32_t *b_colidx, int64_t n_rows, int64_t n_mid, int64_t n_cols, const int32_t *rows,
-                  const int64_t *n_long, int64_t short_max, int64_t tile_cols, int flags, int64_t *counts,
-                  const int64_t *c_rowptr, int32_t *c_colidx, void *stream) {
+// checks the arguments that count, fill and values share and sets them in `a` (0, or HAN_E_BADARG)
+int spgemm_args(SpgemmArgs &a, const int64_t *a_rowptr, const int32_t *a_colidx, const int64_t *b_rowptr,
+                const int32_t *b_colidx, int64_t n_rows, int64_t n_mid, int64_t n_cols, const int32_t *rows,
+                const int64_t *n_long, int64_t short_max, int64_t tile_cols, int flags) {
     if (!a_rowptr || !b_rowptr || !rows || !n_long || n_rows < 0 || n_mid < 0 || n_cols < 0) return HAN_E_BADARG;
-    if (fill ? !c_rowptr : !counts) return HAN_E_BADARG;
     if (short_max < 0 || short_max > HAN_SPGEMM_MAX_SHORT || tile_cols < 32 || tile_cols % 32 != 0 ||
         tile_cols > HAN_SPGEMM_MAX_TILE)
         return HAN_E_BADARG;
     if ((flags & HAN_SPGEMM_DIAG) && n_rows != n_cols) return HAN_E_BADARG;
-    if (n_rows == 0) return 0;
-    SpgemmArgs a;
     a.a_rowptr = a_rowptr; a.a_colidx = a_colidx; a.b_rowptr = b_rowptr; a.b_colidx = b_colidx;
     a.n_rows = n_rows; a.n_mid = n_mid; a.n_cols = n_cols;
     a.rows = rows; a.n_long = n_long;
@@ -263,19 +270,309 @@ int spgemm_launch(bool fill, const int64_t *a_rowptr, const int32_t *a_colidx, c
     a.stage_cap = cap;
     a.tile_cols = tile_cols;
     a.diag = (flags & HAN_SPGEMM_DIAG) ? 1 : 0;
+    return 0;
+}
+
+size_t spgemm_bitmap_bytes(int64_t n_cols, int64_t tile_cols) {
+    const int64_t bm_cols = n_cols < tile_cols ? (n_cols + 31) / 32 * 32 : tile_cols;
+    return (size_t)(bm_cols > 0 ? bm_cols : 32) / 8;
+}
+
+unsigned spgemm_grid(int64_t n_rows, int cap) { return (unsigned)(n_rows < cap ? n_rows : cap); }
+
+int spgemm_launch(bool fill, const int64_t *a_rowptr, const int32_t *a_colidx, const int64_t *b_rowptr,
+                  const int32_t *b_colidx, int64_t n_rows, int64_t n_mid, int64_t n_cols, const int32_t *rows,
+                  const int64_t *n_long, int64_t short_max, int64_t tile_cols, int flags, int64_t *counts,
+                  const int64_t *c_rowptr, int32_t *c_colidx, void *stream) {
+    SpgemmArgs a;
+    const int rc = spgemm_args(a, a_rowptr, a_colidx, b_rowptr, b_colidx, n_rows, n_mid, n_cols, rows, n_long,
+                               short_max, tile_cols, flags);
+    if (rc != 0) return rc;
+    if (fill ? !c_rowptr : !counts) return HAN_E_BADARG;
+    if (n_rows == 0) return 0;
     a.counts = counts; a.c_rowptr = c_rowptr; a.c_colidx = c_colidx;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t bm_cols = n_cols < tile_cols ? (n_cols + 31) / 32 * 32 : tile_cols;
-    const size_t bm_bytes = (size_t)(bm_cols > 0 ? bm_cols : 32) / 8;
-    const unsigned g_long = (unsigned)(n_rows < kLongCap ? n_rows : kLongCap);
-    const unsigned g_short = (unsigned)(n_rows < kShortCap ? n_rows : kShortCap);
-    hipError_t e = han_launch_lds(fill ? spgemm_long_fill : spgemm_long_count, dim3(g_long), dim3(kLongBlock),
-                                  bm_bytes, st, a);
+    hipError_t e = han_launch_lds(fill ? spgemm_long_fill : spgemm_long_count, dim3(spgemm_grid(n_rows, kLongCap)),
+                                  dim3(kLongBlock), spgemm_bitmap_bytes(n_cols, tile_cols), st, a);
     if (e != hipSuccess) return (int)e;
-    e = han_launch_lds(fill ? spgemm_short_fill : spgemm_short_count, dim3(g_short), dim3(64),
-                       (size_t)cap * sizeof(int32_t), st, a);
+    e = han_launch_lds(fill ? spgemm_short_fill : spgemm_short_count, dim3(spgemm_grid(n_rows, kShortCap)), dim3(64),
+                       (size_t)a.stage_cap * sizeof(int32_t), st, a);
     if (e != hipSuccess) return (int)e;
     return 0;
+}
+
+// ---- the counted product: one values pass over the finished structure of C ------------------------------------------
+// c_ij = sum over the products of row i that land on column j of a_val x b_val (1 where an operand has no values),
+// int64, integer adds only: the sum does not depend on the order of the adds, so the result is bitwise reproducible.
+// The columns of C are known (han_spgemm_fill), so no candidate is sorted again:
+//   short rows: the wave copies the row of C into LDS beside one int64 accumulator per entry; every product finds its
+//       entry by a binary search over those columns and is added with an LDS atomic; the accumulators are then stored.
+//   long rows: the bit map of the tile is set from the row of C (not from the candidates), per-word prefix popcounts are
+//       computed once per tile, and a product on column c goes to the global slot c_rowptr[row] + (entries of the
+//       earlier tiles) + (set bits below c) with a 64-bit atomic add -- only this workgroup touches the row.
+// c_vals is cleared by the entry point (a memset on the stream): an entry without a product (the added diagonal) is 0.
+struct SpgemmValArgs {
+    SpgemmArgs g;                    // (g.c_colidx is only read here)
+    const int64_t *a_vals, *b_vals;  // NULL: every stored entry is 1
+    int64_t *c_vals;
+};
+
+__device__ __forceinline__ int64_t product_value(const SpgemmValArgs &v, int64_t ea, int64_t eb) {
+    return (v.a_vals ? v.a_vals[ea] : 1) * (v.b_vals ? v.b_vals[eb] : 1);
+}
+
+__global__ __launch_bounds__(64) void spgemm_short_values(SpgemmValArgs v) {
+    extern __shared__ int64_t acc[];           // stage_cap accumulators, then stage_cap columns
+    __shared__ int64_t s_off[65], s_beg[64];
+    const SpgemmArgs &a = v.g;
+    const int t = threadIdx.x;
+    const int cap = a.stage_cap;
+    int32_t *cols = reinterpret_cast<int32_t *>(acc + cap);
+    for (int64_t r = *a.n_long + blockIdx.x; r < a.n_rows; r += gridDim.x) {
+        const int64_t row = a.rows[r];
+        const int64_t base = a.c_rowptr[row], len = a.c_rowptr[row + 1] - base;
+        if (len <= 0 || len > cap) continue;   // (len <= ub <= cap when C was filled under the same bins)
+        const int n = (int)len;
+        for (int p = t; p < n; p += 64) {
+            cols[p] = a.c_colidx[base + p];
+            acc[p] = 0;
+        }
+        __syncthreads();
+        for_each_product<64>(a, row, s_off, s_beg, [&](int64_t, int64_t ea, int64_t eb) {
+            const int32_t c = a.b_colidx[eb];
+            int lo = 0, hi = n;                // first position with cols[pos] >= c
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (cols[mid] < c) lo = mid + 1;
+                else hi = mid;
+            }
+            if (lo < n && cols[lo] == c)
+                atomicAdd(reinterpret_cast<unsigned long long *>(&acc[lo]), (unsigned long long)product_value(v, ea, eb));
+        });
+        for (int p = t; p < n; p += 64) v.c_vals[base + p] = acc[p];     // (for_each_product ends on a barrier)
+        __syncthreads();                       // cols / acc are rewritten by the next row
+    }
+}
+
+__global__ __launch_bounds__(kLongBlock) void spgemm_long_values(SpgemmValArgs v) {
+    extern __shared__ uint32_t bits[];         // W words of the tile's bit map, then W prefix popcounts
+    __shared__ int64_t s_off[kLongBlock + 1], s_beg[kLongBlock];
+    __shared__ int s_wave[kLongBlock / 64];
+    const SpgemmArgs &a = v.g;
+    const int t = threadIdx.x;
+    const int64_t n_long = *a.n_long;
+    const int64_t tile_w = ((a.n_cols < a.tile_cols ? a.n_cols : a.tile_cols) + 31) >> 5;
+    uint32_t *pre = bits + (tile_w > 0 ? tile_w : 1);
+    for (int64_t r = blockIdx.x; r < n_long; r += gridDim.x) {
+        const int64_t row = a.rows[r];
+        const int64_t base = a.c_rowptr[row], end = a.c_rowptr[row + 1];
+        int64_t total = 0;                     // entries of the row in the tiles before this one
+        for (int64_t lo = 0; lo < a.n_cols && base + total < end; lo += a.tile_cols) {
+            const int64_t width = a.n_cols - lo < a.tile_cols ? a.n_cols - lo : a.tile_cols;
+            const int W = (int)((width + 31) >> 5);
+            for (int w = t; w < W; w += kLongBlock) bits[w] = 0u;
+            __syncthreads();
+            for (int64_t e = base + total + t; e < end; e += kLongBlock) {     // ascending: the tile's entries come first
+                const int64_t off = (int64_t)a.c_colidx[e] - lo;
+                if (off >= width) break;
+                if (off >= 0) atomicOr(&bits[off >> 5], 1u << (off & 31));
+            }
+            __syncthreads();
+            const int wpt = (W + kLongBlock - 1) / kLongBlock;         // thread t owns words [w0, w1)
+            const int w0 = t * wpt < W ? t * wpt : W, w1 = w0 + wpt < W ? w0 + wpt : W;
+            int mine = 0;
+            for (int w = w0; w < w1; ++w) mine += __popc(bits[w]);
+            int tile_total;
+            int below = block_excl_scan<kLongBlock>(mine, s_wave, tile_total);
+            for (int w = w0; w < w1; ++w) {
+                pre[w] = (uint32_t)below;
+                below += __popc(bits[w]);
+            }
+            __syncthreads();
+            if (tile_total > 0) {
+                const int64_t tile_base = base + total;
+                for_each_product<kLongBlock>(a, row, s_off, s_beg, [&](int64_t, int64_t ea, int64_t eb) {
+                    const int64_t off = (int64_t)a.b_colidx[eb] - lo;
+                    if (off < 0 || off >= width) return;
+                    const uint32_t word = bits[off >> 5], bit = 1u << (off & 31);
+                    if (!(word & bit)) return;                         // (not a column of C: a foreign structure)
+                    const int64_t pos = tile_base + pre[off >> 5] + __popc(word & (bit - 1u));
+                    if (pos < end)
+                        atomicAdd(reinterpret_cast<unsigned long long *>(&v.c_vals[pos]),
+                                  (unsigned long long)product_value(v, ea, eb));
+                });
+            }
+            total += tile_total;
+            __syncthreads();             // the bit map is cleared for the next tile / row
+        }
+    }
+}
+
+// ---- PathSim ---------------------------------------------------------------------------------------------------------
+constexpr int kRowBlock = 256;       // a wave per row, four rows per block
+constexpr int kRowCap = 8192;
+
+// diag[i] = the count of (i, i), 0 when row i does not hold it: a binary search over the row's ascending columns,
+// a thread per row
+__global__ __launch_bounds__(kRowBlock) void pathsim_diag(const int64_t *__restrict__ rowptr,
+                                                          const int32_t *__restrict__ colidx,
+                                                          const int64_t *__restrict__ counts, int64_t n,
+                                                          int64_t *__restrict__ diag) {
+    for (int64_t i = (int64_t)blockIdx.x * kRowBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRowBlock) {
+        int64_t lo = rowptr[i], hi = rowptr[i + 1];
+        const int64_t end = hi;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if ((int64_t)colidx[mid] < i) lo = mid + 1;
+            else hi = mid;
+        }
+        diag[i] = (lo < end && (int64_t)colidx[lo] == i) ? counts[lo] : 0;
+    }
+}
+
+// w_ij = 2 c_ij / (c_ii + c_jj) in double, stored as fp32; w_ii = 1
+__global__ __launch_bounds__(kRowBlock) void pathsim_values(const int64_t *__restrict__ rowptr,
+                                                            const int32_t *__restrict__ colidx,
+                                                            const int64_t *__restrict__ counts, int64_t n,
+                                                            const int64_t *__restrict__ diag, float *__restrict__ w) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t i = ((int64_t)blockIdx.x * kRowBlock + threadIdx.x) >> 6; i < n;
+         i += (int64_t)gridDim.x * (kRowBlock / 64)) {
+        const int64_t e1 = rowptr[i + 1], dii = diag[i];
+        for (int64_t e = rowptr[i] + lane; e < e1; e += 64) {
+            const int64_t j = colidx[e];
+            float x = 1.0f;
+            if (j != i) {
+                const int64_t djj = (uint64_t)j < (uint64_t)n ? diag[j] : 0;
+                x = (float)(2.0 * (double)counts[e] / (double)(dii + djj));
+            }
+            w[e] = x;
+        }
+    }
+}
+
+// ---- per-row top-k ---------------------------------------------------------------------------------------------------
+// The usual monotone map of fp32 bits to unsigned: a < b (as finite floats) iff ord(a) < ord(b); -0 sorts below +0.
+__device__ __forceinline__ uint32_t float_ord(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// 16 lanes per row: counts[i] = min(k, entries off the diagonal) + (keep_diag ? entries on it : 0)
+__global__ __launch_bounds__(kBoundsBlock) void topk_count(const int64_t *__restrict__ rowptr,
+                                                           const int32_t *__restrict__ colidx, int64_t n, int64_t k,
+                                                           int keep_diag, int64_t *__restrict__ counts) {
+    const int q = threadIdx.x & 15;
+    for (int64_t i = ((int64_t)blockIdx.x * kBoundsBlock + threadIdx.x) >> 4; i < n;
+         i += (int64_t)gridDim.x * (kBoundsBlock / 16)) {
+        const int64_t e0 = rowptr[i], e1 = rowptr[i + 1];
+        int64_t nd = 0;
+        for (int64_t e = e0 + q; e < e1; e += 16) nd += (int64_t)colidx[e] == i;
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) nd += __shfl_xor(nd, o, 16);
+        const int64_t off = e1 - e0 - nd;
+        if (q == 0) counts[i] = (off < k ? off : k) + (keep_diag ? nd : 0);
+    }
+}
+
+constexpr int kTopkWaveMax = 2048;   // rows up to this many entries: a wave each; longer rows: a 256-thread workgroup
+
+// One row per block of G threads (G = 64 takes the rows of at most kTopkWaveMax entries, G = 256 the others; each launch
+// strides over every row and skips those of the other).  A row with more than k entries off the diagonal is decided by
+// the k-th largest ord among them: an MSB-first radix select, 8 bits per round, over a 256-bin LDS histogram finds that
+// value `thr` and how many of the entries equal to it are still needed; one pass in column order then keeps the
+// entries above thr and the first `need` entries equal to thr -- with ascending columns, the ties of smaller column.
+template <int G>
+__device__ __forceinline__ void topk_fill_rows(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ colidx,
+                                               const float *__restrict__ vals, int64_t n, int64_t k, int keep_diag,
+                                               const int64_t *__restrict__ o_rowptr, int32_t *__restrict__ o_colidx,
+                                               float *__restrict__ o_vals) {
+    __shared__ int hist[256];
+    __shared__ int s_wave[G / 64];
+    __shared__ int s_sel[2];
+    const int t = threadIdx.x;
+    constexpr int B = 256 / G;                 // histogram bins per thread, taken from the top
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const int64_t e0 = rowptr[i], e1 = rowptr[i + 1];
+        if (e1 <= e0 || ((e1 - e0 > kTopkWaveMax) != (G > 64))) continue;
+        int nd = 0;
+        for (int64_t e = e0 + t; e < e1; e += G) nd += (int64_t)colidx[e] == i;
+        int nd_total;
+        block_excl_scan<G>(nd, s_wave, nd_total);
+        uint32_t thr = 0u;
+        int64_t need = 0;
+        const bool cut = e1 - e0 - nd_total > k;
+        if (cut) {
+            uint32_t mask = 0u;
+            need = k;
+            for (int shift = 24; shift >= 0; shift -= 8) {
+                for (int b = t; b < 256; b += G) hist[b] = 0;
+                __syncthreads();
+                for (int64_t e = e0 + t; e < e1; e += G) {
+                    const uint32_t o = float_ord(vals[e]);
+                    if ((int64_t)colidx[e] != i && (o & mask) == thr) atomicAdd(&hist[(o >> shift) & 255u], 1);
+                }
+                __syncthreads();
+                int mine = 0;                  // thread t owns the digits 255 - t B, ..., 255 - t B - (B - 1)
+#pragma unroll
+                for (int q = 0; q < B; ++q) mine += hist[255 - (t * B + q)];
+                int all;
+                const int above = block_excl_scan<G>(mine, s_wave, all);
+                if (above < need && need <= (int64_t)above + mine) {          // exactly one thread
+                    int64_t left = need - above;
+                    int d = 255 - t * B;
+                    while (hist[d] < left) left -= hist[d--];
+                    s_sel[0] = d;
+                    s_sel[1] = (int)left;
+                }
+                __syncthreads();
+                thr |= (uint32_t)s_sel[0] << shift;
+                mask |= 255u << shift;
+                need = s_sel[1];
+                __syncthreads();             // hist / s_sel are rewritten by the next round
+            }
+        }
+        const int64_t o_end = o_rowptr[i + 1];
+        int64_t pos = o_rowptr[i], ties = 0;
+        for (int64_t c0 = e0; c0 < e1; c0 += G) {
+            const int64_t e = c0 + t;
+            bool keep = false, tie = false;
+            int32_t c = 0;
+            float x = 0.f;
+            if (e < e1) {
+                c = colidx[e];
+                x = vals[e];
+                if ((int64_t)c == i) keep = keep_diag != 0;
+                else if (!cut) keep = true;
+                else {
+                    const uint32_t o = float_ord(x);
+                    tie = o == thr;
+                    keep = o > thr;
+                }
+            }
+            int n_tie, n_keep;
+            const int tie_before = block_excl_scan<G>(tie ? 1 : 0, s_wave, n_tie);
+            keep = keep || (tie && ties + tie_before < need);
+            const int keep_before = block_excl_scan<G>(keep ? 1 : 0, s_wave, n_keep);
+            if (keep && pos + keep_before < o_end) {
+                o_colidx[pos + keep_before] = c;
+                o_vals[pos + keep_before] = x;
+            }
+            ties += n_tie;
+            pos += n_keep;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void topk_fill_wave(const int64_t *rowptr, const int32_t *colidx, const float *vals,
+                                                     int64_t n, int64_t k, int keep_diag, const int64_t *o_rowptr,
+                                                     int32_t *o_colidx, float *o_vals) {
+    topk_fill_rows<64>(rowptr, colidx, vals, n, k, keep_diag, o_rowptr, o_colidx, o_vals);
+}
+__global__ __launch_bounds__(256) void topk_fill_block(const int64_t *rowptr, const int32_t *colidx, const float *vals,
+                                                       int64_t n, int64_t k, int keep_diag, const int64_t *o_rowptr,
+                                                       int32_t *o_colidx, float *o_vals) {
+    topk_fill_rows<256>(rowptr, colidx, vals, n, k, keep_diag, o_rowptr, o_colidx, o_vals);
 }
 
 }  // namespace
@@ -304,4 +601,70 @@ extern "C" int han_spgemm_fill(const int64_t *a_rowptr, const int32_t *a_colidx,
                                int flags, const int64_t *c_rowptr, int32_t *c_colidx, void *stream) {
     return spgemm_launch(true, a_rowptr, a_colidx, b_rowptr, b_colidx, n_rows, n_mid, n_cols, rows, n_long,
                          short_max, tile_cols, flags, nullptr, c_rowptr, c_colidx, stream);
+}
+
+extern "C" int han_spgemm_values(const int64_t *a_rowptr, const int32_t *a_colidx, const int64_t *a_vals,
+                                 const int64_t *b_rowptr, const int32_t *b_colidx, const int64_t *b_vals,
+                                 int64_t n_rows, int64_t n_mid, int64_t n_cols, const int32_t *rows,
+                                 const int64_t *n_long, int64_t short_max, int64_t tile_cols, int flags,
+                                 const int64_t *c_rowptr, const int32_t *c_colidx, int64_t nnz_c, int64_t *c_vals,
+                                 void *stream) {
+    SpgemmValArgs v;
+    const int rc = spgemm_args(v.g, a_rowptr, a_colidx, b_rowptr, b_colidx, n_rows, n_mid, n_cols, rows, n_long,
+                               short_max, tile_cols, flags);
+    if (rc != 0) return rc;
+    if (!c_rowptr || nnz_c < 0 || (nnz_c > 0 && (!c_colidx || !c_vals))) return HAN_E_BADARG;
+    if (n_rows == 0 || nnz_c == 0) return 0;
+    v.g.counts = nullptr; v.g.c_rowptr = c_rowptr; v.g.c_colidx = const_cast<int32_t *>(c_colidx);
+    v.a_vals = a_vals; v.b_vals = b_vals; v.c_vals = c_vals;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(c_vals, 0, (size_t)nnz_c * sizeof(int64_t), st);
+    if (e != hipSuccess) return (int)e;
+    e = han_launch_lds(spgemm_long_values, dim3(spgemm_grid(n_rows, kLongCap)), dim3(kLongBlock),
+                       2 * spgemm_bitmap_bytes(n_cols, tile_cols), st, v);
+    if (e != hipSuccess) return (int)e;
+    e = han_launch_lds(spgemm_short_values, dim3(spgemm_grid(n_rows, kShortCap)), dim3(64),
+                       (size_t)v.g.stage_cap * (sizeof(int64_t) + sizeof(int32_t)), st, v);
+    if (e != hipSuccess) return (int)e;
+    return 0;
+}
+
+extern "C" int han_csr_pathsim(const int64_t *rowptr, const int32_t *colidx, const int64_t *counts, int64_t n,
+                               int64_t *diag, float *values, void *stream) {
+    if (!rowptr || !diag || n < 0) return HAN_E_BADARG;
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    pathsim_diag<<<han_grid_for(n, kRowBlock, kRowCap), kRowBlock, 0, st>>>(rowptr, colidx, counts, n, diag);
+    HAN_CHECK_LAUNCH();
+    pathsim_values<<<han_grid_for(n, kRowBlock / 64, kRowCap), kRowBlock, 0, st>>>(rowptr, colidx, counts, n, diag,
+                                                                                    values);
+    HAN_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int han_csr_row_topk_count(const int64_t *rowptr, const int32_t *colidx, int64_t n_rows, int64_t k,
+                                      int keep_diag, int64_t *counts, void *stream) {
+    if (!rowptr || !counts || n_rows < 0 || k < 1) return HAN_E_BADARG;
+    if (n_rows == 0) return 0;
+    topk_count<<<han_grid_for(n_rows, kBoundsBlock / 16, kBoundsCap), kBoundsBlock, 0, (hipStream_t)stream>>>(
+        rowptr, colidx, n_rows, k, keep_diag ? 1 : 0, counts);
+    HAN_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int han_csr_row_topk_fill(const int64_t *rowptr, const int32_t *colidx, const float *values,
+                                     int64_t n_rows, int64_t k, int keep_diag, const int64_t *out_rowptr,
+                                     int32_t *out_colidx, float *out_values, void *stream) {
+    if (!rowptr || !out_rowptr || n_rows < 0 || k < 1) return HAN_E_BADARG;
+    if (n_rows == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    topk_fill_block<<<han_grid_for(n_rows, 1, kLongCap), 256, 0, st>>>(rowptr, colidx, values, n_rows, k,
+                                                                       keep_diag ? 1 : 0, out_rowptr, out_colidx,
+                                                                       out_values);
+    HAN_CHECK_LAUNCH();
+    topk_fill_wave<<<han_grid_for(n_rows, 1, 4 * kShortCap), 64, 0, st>>>(rowptr, colidx, values, n_rows, k,
+                                                                          keep_diag ? 1 : 0, out_rowptr, out_colidx,
+                                                                          out_values);
+    HAN_CHECK_LAUNCH();
+    return 0;
 }

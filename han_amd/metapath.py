@@ -3,8 +3,10 @@
 The reference reads its meta-path graphs preprocessed (``ex_acm3025.py:57-87``: PAP, PLP, ... as dense matrices of a
 ``.mat`` file) and leaves building them to the user.  Here a meta-path such as APCPA is the boolean product of the
 typed relations along it -- paper-author, paper-conference, ... edge lists --, computed on the GPU by
-``ops.csr_bool_matmul`` (``han_spgemm_*``, ``csrc/metapath.hip``).  The results are ``CSRGraph``s that go straight
-into ``bias_mat_list``::
+``ops.csr_bool_matmul`` (``han_spgemm_*``, ``csrc/metapath.hip``).  With ``weights="count"`` / ``"pathsim"`` the
+product is taken over the integers (``ops.csr_count_matmul``) and the graph carries the instance counts or their
+PathSim as ``values``; ``top_k`` keeps the strongest neighbours of every node.  The results are ``CSRGraph``s that go
+straight into ``bias_mat_list``::
 
     rel = {"AP": relation(author_ids, paper_ids, n_authors, n_papers, device=dev),
            "PC": relation(paper_ids2, conf_ids, n_papers, n_confs, device=dev)}
@@ -61,11 +63,27 @@ def relation(src, dst, n_src: int, n_dst: int, device=None) -> CSRGraph:
     return _from_keys(torch.unique(s * n_dst + d), n_src, n_dst, s.device)
 
 
-def compose(graphs, self_loops: bool = False) -> CSRGraph:
-    """The boolean product of a chain of graphs, left to right: entry (i, j) iff a path i -> ... -> j exists
-    (graphs[k].n_cols == graphs[k+1].n_rows).  self_loops=True needs a square result and adds (i, i).  The result
-    has strictly increasing columns per row and values None.  GPU graphs only (han_amd has no CPU path)."""
-    graphs = list(graphs)
+WEIGHTS = (None, "count", "pathsim")
+
+
+def _check_weights(weights, top_k=None):
+    if weights not in WEIGHTS:
+        raise ValueError(f"weights = {weights!r}: expected None, 'count' or 'pathsim'")
+    if top_k is not None:
+        if weights is None:
+            raise ValueError("top_k needs weights ('count' or 'pathsim'): a boolean graph has nothing to rank")
+        if isinstance(top_k, bool) or int(top_k) != top_k or top_k < 1:
+            raise ValueError(f"top_k = {top_k!r}: expected an integer >= 1")
+
+
+def _weighted(g: CSRGraph, counts, weights, top_k=None) -> CSRGraph:
+    """`g` with the values that `weights` asks for from its instance counts, cut to top_k entries per row."""
+    values = counts.to(torch.float32) if weights == "count" else ops.csr_pathsim(g, counts)
+    g = CSRGraph(g.rowptr, g.colidx, g.n_cols, validate=False, values=values)
+    return g if top_k is None else ops.csr_row_topk(g, int(top_k), keep_diag=True)
+
+
+def _check_chain(graphs, self_loops):
     if not graphs:
         raise ValueError("compose: no graphs")
     for k, g in enumerate(graphs):
@@ -77,19 +95,50 @@ def compose(graphs, self_loops: bool = False) -> CSRGraph:
                              f"{graphs[k + 1].n_rows} rows")
     if self_loops and graphs[0].n_rows != graphs[-1].n_cols:
         raise ValueError(f"compose: self_loops needs a square result, got {graphs[0].n_rows} x {graphs[-1].n_cols}")
-    for k, g in enumerate(graphs):
-        ops.require_gpu(g.rowptr, f"compose: graphs[{k}]")
+
+
+def _compose(graphs, self_loops, counted):
+    """(graph, counts) of the chain left to right; counts None unless `counted` (then int64 per entry: the instances,
+    every product fed the counts of the one before as operand values)."""
     if len(graphs) == 1:       # no product: the graph itself, sorted and unique (+ I)
         g = graphs[0]
         rows = torch.repeat_interleave(torch.arange(g.n_rows, device=g.device), g.degrees())
         key = rows * g.n_cols + g.colidx.long()
+        n_stored = key.numel()
         if self_loops:
             key = torch.cat([key, torch.arange(g.n_rows, device=g.device) * (g.n_cols + 1)])
-        return _from_keys(torch.unique(key), g.n_rows, g.n_cols, g.device)
-    c = graphs[0]
+        if not counted:
+            return _from_keys(torch.unique(key), g.n_rows, g.n_cols, g.device), None
+        key, inv = torch.unique(key, return_inverse=True)
+        counts = torch.bincount(inv[:n_stored], minlength=key.numel())      # an added (i, i) counts 0
+        return _from_keys(key, g.n_rows, g.n_cols, g.device), counts
+    c, counts = graphs[0], None
     for k, g in enumerate(graphs[1:]):
-        c = ops.csr_bool_matmul(c, g, diag=self_loops and k == len(graphs) - 2)
-    return c
+        diag = self_loops and k == len(graphs) - 2
+        if counted:
+            c, counts = ops.csr_count_matmul(c, g, a_counts=counts, diag=diag)
+        else:
+            c = ops.csr_bool_matmul(c, g, diag=diag)
+    return c, counts
+
+
+def compose(graphs, self_loops: bool = False, weights=None) -> CSRGraph:
+    """The product of a chain of graphs, left to right: entry (i, j) iff a path i -> ... -> j exists
+    (graphs[k].n_cols == graphs[k+1].n_rows).  self_loops=True needs a square result and adds (i, i).  The result
+    has strictly increasing columns per row.  weights=None: the boolean product, values None.  weights="count": values
+    = the number of paths i -> ... -> j as fp32 (a repeated stored entry of a graph is as many parallel edges), 0 for an
+    (i, i) that only self_loops added.  weights="pathsim" (square results): values = 2 c_ij / (c_ii + c_jj), 1 on the
+    diagonal.  GPU graphs only (han_amd has no CPU path)."""
+    graphs = list(graphs)
+    _check_weights(weights)
+    _check_chain(graphs, self_loops)
+    if weights == "pathsim" and graphs[0].n_rows != graphs[-1].n_cols:
+        raise ValueError(f"compose: weights='pathsim' needs a square result, got {graphs[0].n_rows} x "
+                         f"{graphs[-1].n_cols}")
+    for k, g in enumerate(graphs):
+        ops.require_gpu(g.rowptr, f"compose: graphs[{k}]")
+    c, counts = _compose(graphs, self_loops, weights is not None)
+    return c if weights is None else _weighted(c, counts, weights)
 
 
 def plan(relations: dict, metapath: str) -> dict:
@@ -126,20 +175,43 @@ def plan(relations: dict, metapath: str) -> dict:
     return dict(hops=hops, split=split, sizes=sizes)
 
 
-def metapath_graph(relations: dict, metapath: str, self_loops: bool = True) -> CSRGraph:
+def _transposed(g: CSRGraph, counts):
+    """(gᵀ, its counts): CSRGraph.transpose carries fp32 values only, the int64 counts take the same stable order."""
+    order = torch.sort(g.colidx.long(), stable=True).indices
+    return g.transpose(), counts[order]
+
+
+def metapath_graph(relations: dict, metapath: str, self_loops: bool = True, weights=None, top_k=None) -> CSRGraph:
     """The meta-path graph of `metapath` (e.g. "APCPA") over typed `relations` ({"AP": CSRGraph, "PC": ...}):
     entry (i, j) iff an instance of the path leads from i to j; with self_loops (the default, as adj_to_bias /
     adj_to_graph add I) also (i, i).  A palindromic path whose second half runs on derived transposes is evaluated as
     H Hᵀ, H = the product over its first half (AP PC for APCPA, AP for APA) -- the same graph as the chain left to
-    right, without the chain's wide intermediates; any other path left to right (compose)."""
+    right, without the chain's wide intermediates; any other path left to right (compose).
+
+    weights: None -- a boolean graph (values None); "count" -- values = the number of path instances between i and j,
+    as fp32 (exact below 2^24); "pathsim" -- values = 2 c_ij / (c_ii + c_jj) in (0, 1], the form meant for training
+    (metapath must read the same backwards).  An (i, i) that only self_loops added has count 0 and PathSim 1.  The
+    values scale the attention logits (CSRGraph.values), so raw counts saturate the softmax.  top_k (needs weights):
+    keep per row the top_k strongest neighbours besides (i, i), ties to the smaller column (ops.csr_row_topk).  H is
+    built with counts and enters H Hᵀ as operand values, so both plans count the same instances."""
+    _check_weights(weights, top_k)
     p = plan(relations, metapath)
     if self_loops and metapath[0] != metapath[-1]:
         raise ValueError(f"meta-path {metapath!r}: self_loops needs a path that ends on the type it starts from")
+    if weights == "pathsim" and metapath != metapath[::-1]:
+        raise ValueError(f"meta-path {metapath!r}: weights='pathsim' needs a path that reads the same backwards")
     for key, _ in p["hops"]:
         ops.require_gpu(relations[key].rowptr, f"relations[{key!r}]")
     graphs = [relations[k].transpose() if t else relations[k] for k, t in p["hops"]]
+    counted = weights is not None
     if p["split"] is None:
-        return compose(graphs, self_loops=self_loops)
-    k = p["split"]
-    h = compose(graphs[:k]) if k > 1 else graphs[0]
-    return ops.csr_bool_matmul(h, h.transpose(), diag=self_loops)
+        _check_chain(graphs, self_loops)
+        g, counts = _compose(graphs, self_loops, counted)
+    else:
+        k = p["split"]
+        h, hc = _compose(graphs[:k], False, counted) if k > 1 else (graphs[0], None)
+        if not counted:
+            return ops.csr_bool_matmul(h, h.transpose(), diag=self_loops)
+        ht, htc = _transposed(h, hc) if hc is not None else (h.transpose(), None)
+        g, counts = ops.csr_count_matmul(h, ht, a_counts=hc, b_counts=htc, diag=self_loops)
+    return g if not counted else _weighted(g, counts, weights, top_k)

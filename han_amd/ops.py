@@ -741,12 +741,7 @@ SPGEMM_TILE = 1 << 17
 SPGEMM_STATS: list | None = None   # tools/metapath_bench.py: csr_bool_matmul appends one dict of counts per product
 
 
-def csr_bool_matmul(A: CSRGraph, B: CSRGraph, diag: bool = False) -> CSRGraph:
-    """Boolean product C = A B (han_spgemm_*): entry (i, j) iff some l has (i, l) in A and (l, j) in B, and with
-    diag=True also (i, i) (square products).  A and B may hold unsorted or repeated columns; their values are
-    ignored.  C has strictly increasing columns in every row and values None.  Row bounds, count and fill launches,
-    the rows binned by their bound on the device; the one host sync reads nnz(C)."""
-    lib = _lib.load()
+def _spgemm_check(A: CSRGraph, B: CSRGraph, diag: bool):
     for g, name in ((A, "A"), (B, "B")):
         if not isinstance(g, CSRGraph):
             raise ValueError(f"{name}: expected a CSRGraph, got {type(g)}")
@@ -757,10 +752,17 @@ def csr_bool_matmul(A: CSRGraph, B: CSRGraph, diag: bool = False) -> CSRGraph:
         raise ValueError(f"A has {A.n_cols} columns, B has {B.n_rows} rows")
     if diag and A.n_rows != B.n_cols:
         raise ValueError(f"diag needs a square product, got {A.n_rows} x {B.n_cols}")
+
+
+def _spgemm_structure(A: CSRGraph, B: CSRGraph, diag: bool):
+    """The launches of csr_bool_matmul: (C, the arguments count / fill / values share), the latter None for a product
+    without rows."""
+    _spgemm_check(A, B, diag)
+    lib = _lib.load()
     n, dev = A.n_rows, A.device
     if n == 0:
         return CSRGraph(torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
-                        B.n_cols, validate=False)
+                        B.n_cols, validate=False), None
     flags = SPGEMM_DIAG if diag else 0
     st = _stream()
     ptr = lambda t: t.data_ptr() if t.numel() else None
@@ -782,4 +784,92 @@ def csr_bool_matmul(A: CSRGraph, B: CSRGraph, diag: bool = False) -> CSRGraph:
     _lib.check(lib.han_spgemm_fill(*args, rowptr.data_ptr(), ptr(colidx), st), "han_spgemm_fill")
     if SPGEMM_STATS is not None:
         SPGEMM_STATS.append(dict(rows=n, cols=B.n_cols, nnz_a=A.nnz, nnz=nnz, candidates=ub.sum(), n_long=n_long))
-    return CSRGraph(rowptr, colidx, B.n_cols, validate=False)
+    return CSRGraph(rowptr, colidx, B.n_cols, validate=False), (rows, n_long, SPGEMM_SHORT, SPGEMM_TILE, flags)
+
+
+def csr_bool_matmul(A: CSRGraph, B: CSRGraph, diag: bool = False) -> CSRGraph:
+    """Boolean product C = A B (han_spgemm_*): entry (i, j) iff some l has (i, l) in A and (l, j) in B, and with
+    diag=True also (i, i) (square products).  A and B may hold unsorted or repeated columns; their values are
+    ignored.  C has strictly increasing columns in every row and values None.  Row bounds, count and fill launches,
+    the rows binned by their bound on the device; the one host sync reads nnz(C)."""
+    return _spgemm_structure(A, B, diag)[0]
+
+
+def _entry_counts(t, name, graph: CSRGraph):
+    if t is None:
+        return None
+    _chk(t, name, (graph.nnz,), dtype=torch.int64, device=graph.device)
+    return t
+
+
+def csr_count_matmul(A: CSRGraph, B: CSRGraph, a_counts=None, b_counts=None, diag: bool = False):
+    """Counted product C = A B over the integers (han_spgemm_values after the launches of csr_bool_matmul):
+    (graph, counts) with the graph bitwise that of csr_bool_matmul(A, B, diag) and counts (nnz,) int64 on the device,
+    counts[e] = sum over l of a_il b_lj for the entry e = (i, j).  a_counts / b_counts: (nnz,) int64 per stored entry
+    of A / B, None = every stored entry is 1; a repeated stored entry counts once per repetition.  An (i, i) that only
+    diag=True added has count 0.  Sums are int64 (no check for wrap-around beyond 2^63) and integer adds only, so the
+    result is bitwise reproducible."""
+    _spgemm_check(A, B, diag)
+    a_counts, b_counts = _entry_counts(a_counts, "a_counts", A), _entry_counts(b_counts, "b_counts", B)
+    C, bins = _spgemm_structure(A, B, diag)
+    counts = torch.empty(C.nnz, dtype=torch.int64, device=C.device)
+    if C.nnz:
+        rows, n_long, short_max, tile_cols, flags = bins
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        _lib.check(_lib.load().han_spgemm_values(
+            A.rowptr.data_ptr(), ptr(A.colidx), ptr(a_counts), B.rowptr.data_ptr(), ptr(B.colidx), ptr(b_counts),
+            A.n_rows, A.n_cols, B.n_cols, rows.data_ptr(), n_long.data_ptr(), short_max, tile_cols, flags,
+            C.rowptr.data_ptr(), C.colidx.data_ptr(), C.nnz, counts.data_ptr(), _stream()), "han_spgemm_values")
+    return C, counts
+
+
+def csr_pathsim(graph: CSRGraph, counts: torch.Tensor) -> torch.Tensor:
+    """PathSim values (nnz,) fp32 of a square counted graph with strictly increasing columns per row (a K0 product):
+    w_ij = 2 c_ij / (c_ii + c_jj), evaluated in double and rounded once; w_ii = 1 exactly, also when c_ii = 0; a row
+    that does not store its diagonal has c_ii = 0 (han_csr_pathsim)."""
+    if not isinstance(graph, CSRGraph):
+        raise ValueError(f"graph: expected a CSRGraph, got {type(graph)}")
+    if graph.n_rows != graph.n_cols:
+        raise ValueError(f"PathSim needs a square graph, got {graph.n_rows} x {graph.n_cols}")
+    require_gpu(graph.rowptr, "graph")
+    _chk(counts, "counts", (graph.nnz,), dtype=torch.int64, device=graph.device)
+    w = torch.empty(graph.nnz, dtype=torch.float32, device=graph.device)
+    if graph.nnz:
+        diag = torch.empty(graph.n_rows, dtype=torch.int64, device=graph.device)
+        _lib.check(_lib.load().han_csr_pathsim(graph.rowptr.data_ptr(), graph.colidx.data_ptr(), counts.data_ptr(),
+                                               graph.n_rows, diag.data_ptr(), w.data_ptr(), _stream()),
+                   "han_csr_pathsim")
+    return w
+
+
+def csr_row_topk(graph: CSRGraph, k: int, keep_diag: bool = True) -> CSRGraph:
+    """Per row of a graph with values, the k entries of largest value that are not (i, i) -- ties go to the smaller
+    column --, and with keep_diag also (i, i) if present; a row with at most k such entries is kept whole.  Columns
+    stay ascending and values travel with them.  Rows must hold strictly increasing columns (every K0 product does).
+    Values are ordered as finite floats (-0 below +0); where a NaN sorts is unspecified.  Count and fill launches
+    (han_csr_row_topk_*), one host sync for the new nnz."""
+    if not isinstance(graph, CSRGraph):
+        raise ValueError(f"graph: expected a CSRGraph, got {type(graph)}")
+    if isinstance(k, bool) or int(k) != k or k < 1:
+        raise ValueError(f"k = {k!r}: expected an integer >= 1")
+    if graph.values is None:
+        raise ValueError("csr_row_topk: the graph has no values to rank")
+    if graph.row_base:
+        raise ValueError("csr_row_topk: the diagonal of a row shard (row_base != 0) is not supported")
+    require_gpu(graph.rowptr, "graph")
+    lib, k, n, dev, st = _lib.load(), int(k), graph.n_rows, graph.device, _stream()
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        counts = torch.empty(n, dtype=torch.int64, device=dev)
+        _lib.check(lib.han_csr_row_topk_count(graph.rowptr.data_ptr(), ptr(graph.colidx), n, k, int(keep_diag),
+                                              counts.data_ptr(), st), "han_csr_row_topk_count")
+        torch.cumsum(counts, 0, out=rowptr[1:])
+    nnz = int(rowptr[-1])
+    colidx = torch.empty(nnz, dtype=torch.int32, device=dev)
+    values = torch.empty(nnz, dtype=torch.float32, device=dev)
+    if nnz:
+        _lib.check(lib.han_csr_row_topk_fill(graph.rowptr.data_ptr(), graph.colidx.data_ptr(), graph.values.data_ptr(),
+                                             n, k, int(keep_diag), rowptr.data_ptr(), colidx.data_ptr(),
+                                             values.data_ptr(), st), "han_csr_row_topk_fill")
+    return CSRGraph(rowptr, colidx, graph.n_cols, validate=False, values=values)

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HAN_ABI_VERSION 7
+#define HAN_ABI_VERSION 8
 
 #define HAN_E_BADARG   (-1)   /* null pointer, negative size, inconsistent shape.  The forward
                               * entry points return 0 at once for N == 0 (empty tensors may
@@ -417,6 +417,43 @@ int han_spgemm_fill(const int64_t *a_rowptr, const int32_t *a_colidx, const int6
                     const int32_t *b_colidx, int64_t n_rows, int64_t n_mid, int64_t n_cols, const int32_t *rows,
                     const int64_t *n_long, int64_t short_max, int64_t tile_cols, int flags,
                     const int64_t *c_rowptr, int32_t *c_colidx, void *stream);
+
+/* ---- K0: weighted meta-path graphs (ABI 8) ----------------------------------
+ * han_spgemm_values: the counted product over the structure han_spgemm_fill wrote.  c_vals (nnz_c) int64,
+ *   c_ij = sum over l of a_il b_lj: one term per pair of stored entries (i, l) of A and (l, j) of B, so a repeated
+ *   stored entry counts once per repetition.  a_vals / b_vals: int64, one per stored entry of A / B, or NULL = every
+ *   stored entry is 1.  Sums are int64 and integer adds only (wrap-around beyond 2^63 is not detected), so the result
+ *   does not depend on scheduling.  An entry of C that no product reaches -- the (i, i) HAN_SPGEMM_DIAG added -- is 0.
+ *   Takes the rows, n_long, short_max, tile_cols and flags of the count and fill calls that made c_rowptr / c_colidx
+ *   (nnz_c = c_rowptr[n_rows]); c_vals needs no initialisation (it is cleared on the stream).  Not checked: that C is
+ *   that structure.  With another one nothing is written out of bounds, but a product whose column is not in its row
+ *   of C is dropped and a short-bin row of C longer than short_max (rounded up to a power of two) keeps 0.
+ *   a_colidx / b_colidx / c_colidx / c_vals may be NULL when their graph has no entries.
+ * han_csr_pathsim: values (nnz) fp32 of a square counted graph (n x n, strictly increasing columns in every row --
+ *   not checked), w_ij = 2 c_ij / (c_ii + c_jj) evaluated in double and rounded once to fp32; w_ii = 1 exactly
+ *   (also when c_ii = 0); c_jj = 0 when row j does not store (j, j).  diag: n int64 of caller scratch (the c_ii, found
+ *   by a binary search per row).  An off-diagonal entry with c_ii + c_jj = 0 gives what IEEE division gives.
+ * han_csr_row_topk_count / _fill: per row the k (>= 1) entries of largest value that are not (i, i), and with
+ *   keep_diag != 0 also (i, i); ties go to the smaller column; the output keeps the row's column order, values travel
+ *   with their columns; a row with at most k entries off the diagonal is kept whole.  Rows must hold strictly
+ *   increasing columns (not checked; otherwise which of several equal values stay is unspecified, nothing is written
+ *   out of bounds).  Values are ordered by the monotone map of fp32 bits to unsigned: a total order on the finite
+ *   values and the infinities (-0 below +0); where NaN sorts is unspecified.  count: counts (n_rows) int64; the
+ *   caller scans them into out_rowptr (n_rows+1) and allocates out_colidx / out_values; fill writes both.  count and
+ *   fill take the same k and keep_diag.
+ * All four run on `stream`, allocate nothing and never synchronise.                                                  */
+int han_spgemm_values(const int64_t *a_rowptr, const int32_t *a_colidx, const int64_t *a_vals,
+                      const int64_t *b_rowptr, const int32_t *b_colidx, const int64_t *b_vals, int64_t n_rows,
+                      int64_t n_mid, int64_t n_cols, const int32_t *rows, const int64_t *n_long, int64_t short_max,
+                      int64_t tile_cols, int flags, const int64_t *c_rowptr, const int32_t *c_colidx, int64_t nnz_c,
+                      int64_t *c_vals, void *stream);
+int han_csr_pathsim(const int64_t *rowptr, const int32_t *colidx, const int64_t *counts, int64_t n, int64_t *diag,
+                    float *values, void *stream);
+int han_csr_row_topk_count(const int64_t *rowptr, const int32_t *colidx, int64_t n_rows, int64_t k, int keep_diag,
+                           int64_t *counts, void *stream);
+int han_csr_row_topk_fill(const int64_t *rowptr, const int32_t *colidx, const float *values, int64_t n_rows,
+                          int64_t k, int keep_diag, const int64_t *out_rowptr, int32_t *out_colidx,
+                          float *out_values, void *stream);
 
 #ifdef __cplusplus
 }

@@ -14,10 +14,16 @@ One JSON line per (preset, meta-path):
                 plus 4 B per output entry;
   exact         GPU output == scipy output (row pointers and columns, bit for bit).
 --sweep: the GPU time alone over short-row bounds S x bit-map tiles (ops.SPGEMM_SHORT / SPGEMM_TILE).
+--weights: per (preset, meta-path) the boolean call beside the weighted ones, same process, same median: bool_ms,
+count_ms (weights="count"), pathsim_ms, pathsim_topk_ms (weights="pathsim", top_k=--top-k), count_over_bool, and
+scipy_count_s = scipy's int64 product of the same chain (+ the stored diagonal, indices sorted), count_exact = the GPU
+counts equal it, count_vs_scipy = scipy_count_s / count_ms.
 
     python tools/metapath_bench.py [--out FILE]
     python tools/metapath_bench.py --sweep [--out FILE]
     python tools/metapath_bench.py --no-scipy            # GPU only (the rocprofv3 run)
+    python tools/metapath_bench.py --weights [--out FILE]
+    python tools/metapath_bench.py --weights --no-scipy --presets pap-3m --reps 1     # (the rocprofv3 run)
 """
 import argparse
 import json
@@ -41,7 +47,7 @@ def fresh(rel):
     return {k: CSRGraph(g.rowptr, g.colidx, g.n_cols, validate=False) for k, g in rel.items()}
 
 
-def gpu_time(rel, mp, reps):
+def gpu_time(rel, mp, reps, **kw):
     ts, out = [], None
     for i in range(2 + reps):
         r = fresh(rel)
@@ -49,7 +55,7 @@ def gpu_time(rel, mp, reps):
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        out = metapath.metapath_graph(r, mp)
+        out = metapath.metapath_graph(r, mp, **kw)
         e1.record()
         torch.cuda.synchronize()
         if i >= 2:
@@ -94,11 +100,52 @@ def scipy_build(host, hops, n, sym):
     return m, time.perf_counter() - t0
 
 
+def scipy_count(host, hops, n):
+    """scipy's int64 product of the chain left to right with every (i, i) stored (0 without an instance), indices
+    sorted: (matrix, seconds)."""
+    ones = {k: sp.csr_matrix(m, dtype=np.int64) for k, m in host.items()}
+    t0 = time.perf_counter()
+    m = None
+    for key, t in hops:
+        r = ones[key].T.tocsr() if t else ones[key]
+        m = r if m is None else m @ r
+    m = sp.csr_matrix(m + sp.identity(n, dtype=np.int64, format="csr"))
+    m.sort_indices()
+    dt = time.perf_counter() - t0
+    m.data -= m.indices == np.repeat(np.arange(n), np.diff(m.indptr))
+    return m, dt
+
+
+def weights_line(rel, host, preset, mp, plan, reps, top_k):
+    d = dict(preset=preset, metapath=mp, form="H Ht" if plan["split"] is not None else "left to right", top_k=top_k)
+    for name, kw in (("bool", {}), ("count", dict(weights="count")), ("pathsim", dict(weights="pathsim")),
+                     ("pathsim_topk", dict(weights="pathsim", top_k=top_k))):
+        g, ts = gpu_time(rel, mp, reps, **kw)
+        d[name + "_ms"] = round(float(np.median(ts)), 4)
+        d[name + "_ms_all"] = [round(t, 4) for t in ts]
+        d["nnz_topk" if name == "pathsim_topk" else "nnz"] = g.nnz
+        if name == "count" and host is not None:
+            ref, dt = scipy_count(host, plan["hops"], g.n_rows)
+            d["count_exact"] = bool(np.array_equal(g.rowptr.cpu().numpy(), ref.indptr.astype(np.int64)) and
+                                    np.array_equal(g.colidx.cpu().numpy(), ref.indices.astype(np.int32)) and
+                                    np.array_equal(g.values.cpu().numpy(), ref.data.astype(np.float32)))
+            d["scipy_count_s"] = round(dt, 3)
+            del ref
+        del g
+        torch.cuda.empty_cache()
+    d["count_over_bool"] = round(d["count_ms"] / d["bool_ms"], 2)
+    if "scipy_count_s" in d:
+        d["count_vs_scipy"] = round(d["scipy_count_s"] * 1e3 / d["count_ms"], 1)
+    return d
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--presets", default="dblp-like,pap-3m")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--weights", action="store_true")
+    ap.add_argument("--top-k", type=int, default=32)
     ap.add_argument("--no-scipy", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -124,6 +171,9 @@ def main():
                         _, ts = gpu_time(rel, mp, args.reps)
                         emit(dict(preset=preset, metapath=mp, short_max=S, tile_cols=T,
                                   gpu_ms=round(float(np.median(ts)), 4), gpu_ms_all=[round(t, 4) for t in ts]))
+                continue
+            if args.weights:
+                emit(weights_line(rel, host, preset, mp, plan, args.reps, args.top_k))
                 continue
             g, ts = gpu_time(rel, mp, args.reps)
             med = float(np.median(ts))
