@@ -12,6 +12,7 @@ import torch
 from oracle import han_oracle as ho
 from oracle import han_oracle_torch as ht
 from tests import rng_ref
+from tests.k1_cases import forward_path, fwd_reference, dw_reference
 from tests.helpers import load_params, build_model, gpu_inputs, group_masks, make_problem, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -71,14 +72,16 @@ def test_project_dropout_matches_hash_masks(dev, n, f):
 
 
 @pytest.mark.parametrize("variant", ["1"])
-@pytest.mark.parametrize("n,f,xbf", [(16384 + 77, 64, False), (20000, 1870 - 2, False), (17000, 256, True),
-                                     (40000, 36, False), (16500, 200, True)])
+@pytest.mark.parametrize("n,f,xbf", [(16384 + 77, 64, False), (32641 + 59, 460, False), (32641 + 59, 256, True),
+                                     (40000, 36, False), (32641, 200, True)])
 def test_project_matrix_pipe_kernel_fp32_class_accuracy(dev, n, f, xbf, variant, monkeypatch):
     """Large inputs run K1 on the bf16 matrix pipe with an exact three-way bf16 split of both operands
     (six products; project_fwd_b6_kernel).  It must be as accurate as the exact-fp32 MFMA kernel: both
-    against the float64 product, at the ACM feature width (1868 ~ 1870, F % 4 == 0) too; F = 36 has a
-    partial last K-step; xbf: bf16 features (their split is one term)."""
+    against the float64 product; F = 460 has the partial last K-step of the ACM feature width (1868 % 32 == 12, at
+    which the matrix pipe starts at N = 32641 like for every F >= 128), F = 36 a partial only K-step; xbf: bf16
+    features (their split is one term)."""
     from han_amd import ops
+    assert forward_path(n, f) == "pipe"
     rng = np.random.default_rng(n + f)
     x = rng.standard_normal((n, f)) * np.exp(rng.standard_normal((n, 1)))       # rows of very different scale
     W = rng.standard_normal((f, 64)) * 0.2
@@ -107,7 +110,8 @@ def test_project_matrix_pipe_kernel_dropout_masks(dev, f, xbf, variant, monkeypa
     the A fragments) and the projected-row keep bits, against the NumPy-regenerated hash masks -- and
     bit-for-bit the same keep decisions as the fp32 kernel."""
     from han_amd import ops
-    n = 16384 + 130
+    n = (16384 if f < 128 else 32641) + 130      # F >= 128 is whole-F (and so on the matrix pipe) from N = 32641
+    assert forward_path(n, f) == "pipe"
     rng = np.random.default_rng(f)
     seed, drop, off = 0x0BADC0DE1234, 0.6, 977
     x = rng.standard_normal((n, f))
@@ -119,25 +123,23 @@ def test_project_matrix_pipe_kernel_dropout_masks(dev, f, xbf, variant, monkeypa
         x = xt.to(torch.float32).cpu().numpy().astype(np.float64)
     H, _, _ = ops.project_fwd(xt, _t(W, dev), _t(a[0], dev), _t(a[1], dev), _t(a[2], dev), _t(a[3], dev),
                               in_drop=drop, fts_drop=drop, seed=seed, row_offset=off)
-    keep = rng_ref.keep_prob32(drop)
-    sm = rng_ref.seq_mask(seed, n, f, 8, drop, row_offset=off)
+    # (the masked float64 products in row blocks: k1_cases.fwd_reference / dw_reference -- the full (8, N, F) mask of
+    # rng_ref.seq_mask takes gigabytes at these row counts)
     Wd = W.astype(np.float32).astype(np.float64)
-    Href = np.concatenate([(x / keep * sm[k]) @ Wd[:, 8 * k:8 * k + 8] for k in range(8)], 1)
+    Href = fwd_reference(x, Wd, 8, 8, drop, seed, off)[0]
     assert np.abs(H.cpu().numpy() - Href).max() < 1e-5 * max(1.0, np.abs(Href).max())
     fm = rng_ref.fts_mask(seed, n, 64, drop, row_offset=off)
     assert np.array_equal((H.cpu().numpy().view(np.uint32) & 1).astype(np.float64), fm)
     # the backward (exact-fp32 dW kernel) regenerates the very same draws
     dH = rng.standard_normal((n, 64))
     dW = ops.project_bwd(xt, _t(dH, dev), 8, 8, in_drop=drop, seed=seed, row_offset=off)
-    dWref = np.concatenate([(x / keep * sm[k]).T @ dH[:, 8 * k:8 * k + 8] for k in range(8)], 1)
+    dWref = dw_reference(x, dH, 8, 8, drop, seed, off)[0]
     assert rel_err(dW.cpu().numpy(), dWref) < 2e-6
     # other drop rates exercise the threshold arithmetic of the packed compare (odd / even thresholds)
     for dr in (0.25, 0.9):
         H2, _, _ = ops.project_fwd(xt, _t(W, dev), _t(a[0], dev), _t(a[1], dev), _t(a[2], dev), _t(a[3], dev),
                                    in_drop=dr, seed=seed, row_offset=off)
-        kp = rng_ref.keep_prob32(dr)
-        sm2 = rng_ref.seq_mask(seed, n, f, 8, dr, row_offset=off)
-        Href2 = np.concatenate([(x / kp * sm2[k]) @ Wd[:, 8 * k:8 * k + 8] for k in range(8)], 1)
+        Href2 = fwd_reference(x, Wd, 8, 8, dr, seed, off)[0]
         assert np.abs(H2.cpu().numpy() - Href2).max() < 1e-5 * max(1.0, np.abs(Href2).max()), dr
 
 
@@ -192,17 +194,20 @@ def test_project_keep_table_and_block_mfma_dw(dev, n, f, xbf):
                            in_drop=drop, seed=seed, want_keep=True)[3] is None
 
 
-@pytest.mark.parametrize("P,n,f,xbf,K,FP,tdt", [(4, 16384 + 200, 256, False, 8, 8, torch.float32),
+@pytest.mark.parametrize("P,n,f,xbf,K,FP,tdt", [(4, 32641 + 200, 256, False, 8, 8, torch.float32),
                                                 (3, 17000, 72, False, 8, 8, torch.float32),
-                                                (2, 20000, 132, True, 8, 8, torch.bfloat16),
+                                                (2, 32641 + 59, 132, True, 8, 8, torch.bfloat16),
                                                 (5, 16500, 64, False, 4, 16, torch.float32),
                                                 (2, 3000, 256, False, 8, 8, torch.float32)])
 @pytest.mark.parametrize("flags", [0, 32])
 def test_project_fwd_multi_matches_the_per_meta_path_kernel(dev, P, n, f, xbf, K, FP, tdt, flags):
     """Round 3: the eval forward of all P meta-paths of a shared X in one fused launch (X read, split and staged once
     for 4 or 2 meta-paths per block; odd P leaves one to the single kernel; short inputs and other cases loop):
-    H against the float64 product, and H / f1 / f2 against the per-meta-path kernel on the same matrix pipe."""
+    H against the float64 product, and H / f1 / f2 against the per-meta-path kernel on the same matrix pipe.
+    (2, 3000, 256) is the short input that loops over the per-meta-path split-F kernel."""
     from han_amd import ops
+    path = "split" if n < 16384 else "pipe"
+    assert forward_path(n, f, P) == path and forward_path(n, f) == path
     rng = np.random.default_rng(P * 100 + f)
     x = rng.standard_normal((n, f)) * np.exp(0.5 * rng.standard_normal((n, 1)))
     W = rng.standard_normal((P, f, 64)) * 0.2
