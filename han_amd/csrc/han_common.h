@@ -99,17 +99,20 @@ __device__ __forceinline__ uint32_t han_f32_to_bf16_bits(float f) {
     return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
 }
 
+// four bf16 elements (8 B) widened to fp32
+__device__ __forceinline__ float4_t han_widen_bf16x4(const uint2 w) {
+    float4_t v;
+    v[0] = __uint_as_float(w.x << 16);
+    v[1] = __uint_as_float(w.x & 0xFFFF0000u);
+    v[2] = __uint_as_float(w.y << 16);
+    v[3] = __uint_as_float(w.y & 0xFFFF0000u);
+    return v;
+}
+
 template <bool BF>
 __device__ __forceinline__ float4_t han_load_row4(const void *tab, int64_t row, int q) {
-    if (BF) {
-        const uint2 w = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(tab) + row * 64 + 4 * q);
-        float4_t v;
-        v[0] = __uint_as_float(w.x << 16);
-        v[1] = __uint_as_float(w.x & 0xFFFF0000u);
-        v[2] = __uint_as_float(w.y << 16);
-        v[3] = __uint_as_float(w.y & 0xFFFF0000u);
-        return v;
-    }
+    if (BF)
+        return han_widen_bf16x4(*reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(tab) + row * 64 + 4 * q));
     return *reinterpret_cast<const float4_t *>(reinterpret_cast<const float *>(tab) + row * 64 + 4 * q);
 }
 
@@ -269,6 +272,15 @@ static inline bool han_fp_supported(int K, int FP) {
     do {                                                                              \
         if (BFV) { constexpr bool BF = true; HAN_DISPATCH_FP(FPV, __VA_ARGS__) }      \
         else { constexpr bool BF = false; HAN_DISPATCH_FP(FPV, __VA_ARGS__) }         \
+    } while (0)
+
+// runs the statement(s) twice over, with `constexpr bool NAME` = true where VALUE holds and false where it does not.
+// Both copies are instantiated: where a combination of bools must not exist as a kernel, fold it in the template
+// argument (`TRAIN && FAST`) or keep an `if constexpr` in front of the launch.
+#define HAN_DISPATCH_BOOL(NAME, VALUE, ...)                       \
+    do {                                                          \
+        if (VALUE) { constexpr bool NAME = true; __VA_ARGS__; }   \
+        else { constexpr bool NAME = false; __VA_ARGS__; }        \
     } while (0)
 
 // meta-path counts of the K3 kernels that keep a node's P rows inside 16-lane groups

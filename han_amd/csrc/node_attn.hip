@@ -114,15 +114,7 @@ struct GsRow {
 template <int FP, bool BF>
 __device__ __forceinline__ float4_t gs_load_g4(const void *gs, int64_t row, int q) {
     const char *base = reinterpret_cast<const char *>(gs) + row * GsRow<FP, BF>::bytes;
-    if (BF) {
-        const uint2 w = *reinterpret_cast<const uint2 *>(base + 8 * q);
-        float4_t v;
-        v[0] = __uint_as_float(w.x << 16);
-        v[1] = __uint_as_float(w.x & 0xFFFF0000u);
-        v[2] = __uint_as_float(w.y << 16);
-        v[3] = __uint_as_float(w.y & 0xFFFF0000u);
-        return v;
-    }
+    if (BF) return han_widen_bf16x4(*reinterpret_cast<const uint2 *>(base + 8 * q));
     return *reinterpret_cast<const float4_t *>(base + 16 * q);
 }
 
@@ -169,6 +161,20 @@ __device__ __forceinline__ int han_bit_mask(int x) {
     int r;
     asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(r) : "v"(x), "n"(BIT));
     return r;
+}
+
+// projected-row dropout, layers.py:31-32: AND an element with its sign-extended keep bit, bit BIT of the element
+// (one v_bfe_i32 + one v_and per element)
+template <int BIT>
+__device__ __forceinline__ float keep_bit_and(const float v) {
+    const int bits = __float_as_int(v);
+    return __int_as_float(bits & han_bit_mask<BIT>(bits));
+}
+template <int BIT>
+__device__ __forceinline__ float4_t keep_bit_and(float4_t v) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v[t] = keep_bit_and<BIT>(v[t]);
+    return v;
 }
 
 // the value lane `u` of this lane's DPP quad (4 consecutive lanes) holds: quad_perm [u, u, u, u], a full-rate move
@@ -257,14 +263,10 @@ __device__ __forceinline__ void consume_edges(const FwdArgs &a, const int (&j)[U
                                                 gj * (uint32_t)KQ + (uint32_t)(head >> 2));
                 pd = rn.field(head & 3) < a.thr_coef ? p : 0.f;
             }
-            // projected-row dropout, layers.py:31-32 (after the score was taken): AND the
-            // element with the sign-extended keep bit (one v_bfe_i32 + one v_and per element)
+            // projected-row dropout, layers.py:31-32 (after the score was taken)
             if (FAST || a.lsb_mask) {
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int bits = __float_as_int(hv[u][t]);
-                    hv[u][t] = __int_as_float(bits & han_bit_mask<BF ? 16 : 0>(bits));
-                }
+                for (int t = 0; t < 4; ++t) hv[u][t] = keep_bit_and<BF ? 16 : 0>(hv[u][t]);
             }
         }
 #pragma unroll
@@ -521,13 +523,7 @@ __device__ __forceinline__ void lean_fwd_step(const FwdArgs &a, const float *til
     for (int u = 0; u < 4; ++u) {
         float x = __builtin_fmaf(f2v[u], kLog2e, f1s);      // (f1_i + f2_j) * log2 e
         if (VAL) x *= wv4[u];
-        if (TRAIN && a.lsb_mask) {                          // layers.py:31-32, after the score was taken (it comes from the table)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int bits = __float_as_int(hv[u][t]);
-                hv[u][t] = __int_as_float(bits & han_bit_mask<0>(bits));
-            }
-        }
+        if (TRAIN && a.lsb_mask) hv[u] = keep_bit_and<0>(hv[u]);    // layers.py:31-32, after the score was taken (it comes from the table)
         if (TRAIN) {
             sg[u] = x > 0.f ? 1.f : a.slope;
             if (VAL) sg[u] *= wv4[u];
@@ -724,10 +720,7 @@ __global__ __launch_bounds__(256) void node_attn_fwd_h8_kernel(const FwdArgs a_i
                     }
                     if (drop_f) {                           // layers.py:31-32, after the score was taken (it comes from the table)
 #pragma unroll
-                        for (int t = 0; t < 8; ++t) {
-                            const int bits = __float_as_int(hv[u][t]);
-                            hv[u][t] = __int_as_float(bits & han_bit_mask<0>(bits));
-                        }
+                        for (int t = 0; t < 8; ++t) hv[u][t] = keep_bit_and<0>(hv[u][t]);
                     }
                     ev[u] = valid[u] ? fmaxf(x, a.slope * x) : HAN_NEG_BIG;
                     mc = fmaxf(mc, ev[u]);
@@ -1208,20 +1201,6 @@ __global__ __launch_bounds__(256) void node_attn_bwd_cols_kernel(const BwdColsAr
                         ew[u] = VAL ? __shfl(myval, idx, 64) : 1.f;
                     }
                     bwd_consume<FP, U, BF, VAL, FAST, !MASKED, MASKED, DEDUP && U == 4>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
-                }
-                if (U > 4 && (st + 4) * 4 <= cnt) {             // long unrolls: one half step before the singles
-                    int i[4];
-                    float ew[4];
-                    bool valid[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int idx = (st + u) * 4 + g;
-                        i[u] = __shfl(myrow, idx, 64);
-                        valid[u] = MASKED ? i[u] >= 0 : true;
-                        ew[u] = VAL ? __shfl(myval, idx, 64) : 1.f;
-                    }
-                    bwd_consume<FP, 4, BF, VAL, FAST, !MASKED, MASKED, DEDUP>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
-                    st += 4;
                 }
                 for (; st * 4 < cnt; ++st) {                    // tail: single steps of 4 edges
                     const int idx = st * 4 + g;
@@ -1720,9 +1699,8 @@ static void launch_fwd_rows(const FwdArgs &a, bool train, bool short_rows, hipSt
     const bool fast = train && a.thr_coef < HAN_KEEP_ALL && a.lsb_mask && !a.gid && !a.f2g;
     if (short_rows) {
         const int grid = attn_grid((a.n_work + 3) / 4);
-        if (train && fast) node_attn_fwd_kernel<FPC, true, 4, 4, BF, VAL, true, false><<<grid, 256, 0, st>>>(a);
-        else if (train) node_attn_fwd_kernel<FPC, true, 4, 4, BF, VAL, false, false><<<grid, 256, 0, st>>>(a);
-        else node_attn_fwd_kernel<FPC, false, 4, 4, BF, VAL, false, false><<<grid, 256, 0, st>>>(a);
+        HAN_DISPATCH_BOOL(TRAIN, train, HAN_DISPATCH_BOOL(FAST, fast,
+            node_attn_fwd_kernel<FPC, TRAIN, 4, 4, BF, VAL, TRAIN && FAST, false><<<grid, 256, 0, st>>>(a)));
     } else {
         const int grid = attn_grid(a.n_work);
         // steps of 4 x 4 rows for both table types.  (Rounds 2-3 ran the bf16 eval forward with 8 steps in flight, 114-125
@@ -1744,8 +1722,7 @@ static void launch_fwd_rows(const FwdArgs &a, bool train, bool short_rows, hipSt
         constexpr bool DD_OK = FPC == 8 && !VAL;
         if (DD_OK && train && fast && a.shared_hash) {
             if constexpr (DD_OK) node_attn_fwd_kernel<FPC, true, 1, 4, BF, VAL, true, true, true><<<grid, 256, 0, st>>>(a);
-        } else if (train && fast) node_attn_fwd_kernel<FPC, true, 1, 4, BF, VAL, true, true><<<grid, 256, 0, st>>>(a);
-        else if (train) node_attn_fwd_kernel<FPC, true, 1, 4, BF, VAL, false, true><<<grid, 256, 0, st>>>(a);
+        } else if (train) HAN_DISPATCH_BOOL(FAST, fast, node_attn_fwd_kernel<FPC, true, 1, 4, BF, VAL, FAST, true><<<grid, 256, 0, st>>>(a));
         else if (BF && a.deep) {      // HAN_FLAG_K2_DEEP: bf16 tables only
             if constexpr (BF) node_attn_fwd_kernel<FPC, false, 1, 8, BF, VAL, false, BF><<<grid, 256, 0, st>>>(a);
         } else node_attn_fwd_kernel<FPC, false, 1, UE, BF, VAL, false, BF><<<grid, 256, 0, st>>>(a);
@@ -1769,53 +1746,56 @@ static RowBins bins_of(const han_row_split_t *sp) {
     return b;
 }
 
-template <int FPC, bool BF, bool VAL>
-static void launch_fwd_v(const FwdArgs &a_in, bool train, bool low, bool has_split, const RowBins &bins, hipStream_t st) {
-    FwdArgs a = a_in;
+// The bin walk of a launch, forward or backward: one row launch per listed bin (rows below 16 entries four to a wave,
+// the others a wave each), or one launch over all `n_rows` rows with `low`.  Rows beyond split_deg are skipped by the
+// row kernels; their chunk and finish launches follow at the caller.
+template <typename Args, typename RowLaunch>
+static void for_each_bin(Args &a, int64_t n_rows, bool low, const RowBins &bins, RowLaunch launch_rows) {
     if (bins.binned) {
-        // degree-binned: rows below 16 entries four to a wave, the others a wave each (rows beyond split_deg: chunks)
         if (bins.n_short > 0) {
             a.rows = bins.short_rows; a.n_work = bins.n_short;
-            launch_fwd_rows<FPC, BF, VAL>(a, train, true, st);
+            launch_rows(a, true);
         }
         if (bins.n_mid > 0) {
             a.rows = bins.mid_rows; a.n_work = bins.n_mid;
-            launch_fwd_rows<FPC, BF, VAL>(a, train, false, st);
+            launch_rows(a, false);
         }
     } else {
-        a.rows = nullptr; a.n_work = a.N;
-        launch_fwd_rows<FPC, BF, VAL>(a, train, low, st);
+        a.rows = nullptr; a.n_work = n_rows;
+        launch_rows(a, low);
     }
+}
+
+// VAL: the binary-adjacency instantiation (every shipped config) carries no edge-value registers
+template <int FPC, bool BF, bool VAL>
+static void launch_fwd_v(const FwdArgs &a_in, bool train, bool low, bool has_split, const RowBins &bins, hipStream_t st) {
+    FwdArgs a = a_in;
+    for_each_bin(a, a.N, low, bins, [&](const FwdArgs &b, bool short_rows) { launch_fwd_rows<FPC, BF, VAL>(b, train, short_rows, st); });
     if (has_split) {
         const int cgrid = attn_grid(a.n_chunks);
         const int fgrid = (int)a.n_long;      // one block per long row
-        if (train) {
-            node_attn_fwd_chunk_kernel<FPC, true, 4, BF, VAL><<<cgrid, 256, 0, st>>>(a);
-            node_attn_fwd_finish_kernel<FPC, true><<<fgrid, 256, 0, st>>>(a);
-        } else {
-            node_attn_fwd_chunk_kernel<FPC, false, 4, BF, VAL><<<cgrid, 256, 0, st>>>(a);
-            node_attn_fwd_finish_kernel<FPC, false><<<fgrid, 256, 0, st>>>(a);
-        }
+        HAN_DISPATCH_BOOL(TRAIN, train, {
+            node_attn_fwd_chunk_kernel<FPC, TRAIN, 4, BF, VAL><<<cgrid, 256, 0, st>>>(a);
+            node_attn_fwd_finish_kernel<FPC, TRAIN><<<fgrid, 256, 0, st>>>(a);
+        });
     }
 }
 
 template <int FPC, bool BF, bool VAL>
 static void launch_bwd_rows(const BwdColsArgs &a, bool short_rows, hipStream_t st) {
     const bool fast = a.thr_coef < HAN_KEEP_ALL && !a.gid;
-    if (a.masked) {      // opt-in masked backward: the general instantiations, dead entries skipped in place
-        if (short_rows) node_attn_bwd_cols_kernel<FPC, 4, 4, BF, VAL, false, true><<<attn_grid((a.n_work + 3) / 4), 256, 0, st>>>(a);
-        else node_attn_bwd_cols_kernel<FPC, 1, 4, BF, VAL, false, true><<<attn_grid(a.n_work), 256, 0, st>>>(a);
-    } else if (short_rows) {
-        if (fast) node_attn_bwd_cols_kernel<FPC, 4, 4, BF, VAL, true><<<attn_grid((a.n_work + 3) / 4), 256, 0, st>>>(a);
-        else node_attn_bwd_cols_kernel<FPC, 4, 4, BF, VAL, false><<<attn_grid((a.n_work + 3) / 4), 256, 0, st>>>(a);
-    } else if (fast) node_attn_bwd_cols_kernel<FPC, 1, 4, BF, VAL, true><<<attn_grid(a.n_work), 256, 0, st>>>(a);
-    else node_attn_bwd_cols_kernel<FPC, 1, 4, BF, VAL, false><<<attn_grid(a.n_work), 256, 0, st>>>(a);
+    const int grid = attn_grid(short_rows ? (a.n_work + 3) / 4 : a.n_work);
+    HAN_DISPATCH_BOOL(SHORT, short_rows, {
+        constexpr int RPW = SHORT ? 4 : 1;
+        if (a.masked)      // opt-in masked backward: the general instantiations, dead entries skipped in place
+            node_attn_bwd_cols_kernel<FPC, RPW, 4, BF, VAL, false, true><<<grid, 256, 0, st>>>(a);
+        else HAN_DISPATCH_BOOL(FAST, fast, node_attn_bwd_cols_kernel<FPC, RPW, 4, BF, VAL, FAST><<<grid, 256, 0, st>>>(a));
+    });
 }
 
 template <int FPC, bool BF, bool VAL>
 static void launch_bwd_cols_v(const BwdColsArgs &a_in, bool low, bool has_split, const RowBins &bins, hipStream_t st) {
     BwdColsArgs a = a_in;
-    a.rows = nullptr; a.n_work = a.NS;
     if (a.lean && !a.masked && !low && !BF && FPC == 8 && !a.gid) {      // small graphs, 8 x 8: one lane per head
         node_attn_bwd_cols_h8_kernel<VAL><<<attn_grid(a.NS), 256, 0, st>>>(a);
         return;      // whole rows of any length: no chunk / finish launches behind it
@@ -1823,18 +1803,8 @@ static void launch_bwd_cols_v(const BwdColsArgs &a_in, bool low, bool has_split,
         a.split_deg = INT64_MAX;
         node_attn_bwd_cols_kernel<FPC, 1, 4, false, VAL, false, false, true><<<attn_grid(a.NS), 256, 0, st>>>(a);
         return;
-    } else if (bins.binned) {
-        if (bins.n_short > 0) {
-            a.rows = bins.short_rows; a.n_work = bins.n_short;
-            launch_bwd_rows<FPC, BF, VAL>(a, true, st);
-        }
-        if (bins.n_mid > 0) {
-            a.rows = bins.mid_rows; a.n_work = bins.n_mid;
-            launch_bwd_rows<FPC, BF, VAL>(a, false, st);
-        }
-    } else {
-        launch_bwd_rows<FPC, BF, VAL>(a, low, st);
     }
+    for_each_bin(a, a.NS, low, bins, [&](const BwdColsArgs &b, bool short_rows) { launch_bwd_rows<FPC, BF, VAL>(b, short_rows, st); });
     if (has_split) {
         node_attn_bwd_chunk_kernel<FPC, 4, BF, VAL><<<attn_grid(a.n_chunks), 256, 0, st>>>(a);
         node_attn_bwd_finish_kernel<FPC, BF><<<(int)a.n_long, 256, 0, st>>>(a);
@@ -1844,23 +1814,26 @@ static void launch_bwd_cols_v(const BwdColsArgs &a_in, bool low, bool has_split,
 template <int FPC, bool VAL>
 static void launch_fwd_lean_v(const FwdArgs &a, bool train, hipStream_t st) {
     const int grid = attn_grid(a.N);
-    if (FPC == 8) {       // the reference shape: one lane per head
-        if (train) node_attn_fwd_h8_kernel<true, VAL><<<grid, 256, 0, st>>>(a);
-        else node_attn_fwd_h8_kernel<false, VAL><<<grid, 256, 0, st>>>(a);
-    } else if (train) node_attn_fwd_lean_kernel<FPC, true, VAL><<<grid, 256, 0, st>>>(a);
-    else node_attn_fwd_lean_kernel<FPC, false, VAL><<<grid, 256, 0, st>>>(a);
+    HAN_DISPATCH_BOOL(TRAIN, train, {
+        if (FPC == 8) node_attn_fwd_h8_kernel<TRAIN, VAL><<<grid, 256, 0, st>>>(a);       // the reference shape: one lane per head
+        else node_attn_fwd_lean_kernel<FPC, TRAIN, VAL><<<grid, 256, 0, st>>>(a);
+    });
 }
 
-// the binary-adjacency instantiation (every shipped config) carries no edge-value registers
-template <int FPC, bool BF>
-static void launch_fwd(const FwdArgs &a, bool train, bool low, bool has_split, const RowBins &bins, hipStream_t st) {
-    if (a.edge_val) launch_fwd_v<FPC, BF, true>(a, train, low, has_split, bins, st);
-    else launch_fwd_v<FPC, BF, false>(a, train, low, has_split, bins, st);
-}
-template <int FPC, bool BF>
-static void launch_bwd_cols(const BwdColsArgs &a, bool low, bool has_split, const RowBins &bins, hipStream_t st) {
-    if (a.edge_val) launch_bwd_cols_v<FPC, BF, true>(a, low, has_split, bins, st);
-    else launch_bwd_cols_v<FPC, BF, false>(a, low, has_split, bins, st);
+// Small dense graph on the matrix pipe (node_attn_dense.h), in front of the lean CSR kernel of either direction:
+// geometry, the scores' range, and the caller's two dense launches `launch(d, grid, finish_grid)`.  The lean kernel
+// behind it runs only when the range is too wide for the fixed-shift form; `only_if` is that device-side flag (no host
+// round trip).  Returns 0 or an error code.
+template <typename Launch>
+static int dense_front(const han_dense_t *dense, int64_t rows, bool train, const float *f2, int64_t n_f2, hipStream_t st,
+                       const int *&only_if, Launch launch) {
+    DenseArgs d;
+    if (!dense_geometry(rows, dense->n_table, train, dense, &d)) return HAN_E_WORKSPACE;
+    dense_f2_range_kernel<<<kDenseRangeBlocks, 256, 0, st>>>(f2, n_f2, d.hdr);
+    launch(d, dim3((unsigned)((rows + kDenseRowsPerBlock - 1) / kDenseRowsPerBlock), (unsigned)d.S), (int)((rows + 15) / 16));
+    HAN_CHECK_LAUNCH();
+    only_if = reinterpret_cast<const int *>(d.hdr) + 16;
+    return 0;
 }
 
 // bf16 tables: every head shape (the configs[4] shape 8 x 8 is the tuned one)
@@ -1913,34 +1886,25 @@ extern "C" int han_node_attn_fwd(const int64_t *rowptr, const int32_t *colidx, c
     hipStream_t st = (hipStream_t)stream;
     const bool low = (double)E < kLowDegree * (double)N;
     if (dense && dense->bits) {
-        // small dense graph on the matrix pipe (node_attn_dense.h); the lean CSR kernel behind it runs only when the
-        // scores' range is too wide for the fixed-shift form (a device-side flag: no host round trip)
         if (!(flags & HAN_FLAG_LEAN) || table_dtype != HAN_DTYPE_F32 || table_gid || !f2_src || edge_val || K != 8 || FP != 8)
             return HAN_E_BADARG;
-        DenseArgs d;
-        if (!dense_geometry(N, dense->n_table, train, dense, &d)) return HAN_E_WORKSPACE;
-        dense_f2_range_kernel<<<kDenseRangeBlocks, 256, 0, st>>>(f2_src, d.NT, d.hdr);
-        const dim3 dg((unsigned)((N + kDenseRowsPerBlock - 1) / kDenseRowsPerBlock), (unsigned)d.S);
-        const int fg = (int)((N + 15) / 16);
-        if (train) {
-            node_attn_fwd_dense_kernel<true><<<dg, 256, 0, st>>>(a, d);
-            node_attn_fwd_dense_finish_kernel<true><<<fg, 256, 0, st>>>(a, d);
-        } else {
-            node_attn_fwd_dense_kernel<false><<<dg, 256, 0, st>>>(a, d);
-            node_attn_fwd_dense_finish_kernel<false><<<fg, 256, 0, st>>>(a, d);
-        }
-        HAN_CHECK_LAUNCH();
-        a.only_if = reinterpret_cast<const int *>(d.hdr) + 16;
+        const int err = dense_front(dense, N, train, f2_src, dense->n_table, st, a.only_if, [&](const DenseArgs &d, dim3 dg, int fg) {
+            HAN_DISPATCH_BOOL(TRAIN, train, {
+                node_attn_fwd_dense_kernel<TRAIN><<<dg, 256, 0, st>>>(a, d);
+                node_attn_fwd_dense_finish_kernel<TRAIN><<<fg, 256, 0, st>>>(a, d);
+            });
+        });
+        if (err) return err;
     }
     if ((flags & HAN_FLAG_LEAN) && table_dtype == HAN_DTYPE_F32 && !table_gid && f2_src) {
         // small graph, table in the L2s: scores gathered, one hash per (edge, four heads); whole rows (no row split)
-        if (edge_val) { HAN_DISPATCH_FP(FP, { launch_fwd_lean_v<FPC, true>(a, train, st); }) }
-        else { HAN_DISPATCH_FP(FP, { launch_fwd_lean_v<FPC, false>(a, train, st); }) }
+        HAN_DISPATCH_BOOL(VAL, edge_val != nullptr, HAN_DISPATCH_FP(FP, { launch_fwd_lean_v<FPC, VAL>(a, train, st); }));
         HAN_CHECK_LAUNCH();
         return 0;
     }
     const RowBins bins = bins_of(split);
-    HAN_DISPATCH_FP_BF(FP, table_dtype == HAN_DTYPE_BF16, launch_fwd<FPC, BF>(a, train, low, has_split, bins, st));
+    HAN_DISPATCH_BOOL(VAL, edge_val != nullptr,
+                      HAN_DISPATCH_FP_BF(FP, table_dtype == HAN_DTYPE_BF16, launch_fwd_v<FPC, BF, VAL>(a, train, low, has_split, bins, st)));
     HAN_CHECK_LAUNCH();
     return 0;
 }
@@ -2011,21 +1975,18 @@ extern "C" int han_node_attn_bwd_cols(const int64_t *colptr, const int32_t *rowi
     hipStream_t st = (hipStream_t)stream;
     const bool low = (double)E < kLowDegree * (double)NS;
     if (dense && dense->bits) {
-        // small dense graph: the transposed bit mask on the matrix pipe (node_attn_dense.h), the lean CSR kernel behind it
-        // predicated on the range flag
+        // the transposed bit mask
         if (!a.lean || a.masked || low || table_dtype != HAN_DTYPE_F32 || table_gid || edge_val || K != 8 || FP != 8)
             return HAN_E_BADARG;
-        DenseArgs d;
-        if (!dense_geometry(NS, dense->n_table, false, dense, &d)) return HAN_E_WORKSPACE;
-        dense_f2_range_kernel<<<kDenseRangeBlocks, 256, 0, st>>>(f2, NS, d.hdr);
-        const dim3 dg((unsigned)((NS + kDenseRowsPerBlock - 1) / kDenseRowsPerBlock), (unsigned)d.S);
-        node_attn_bwd_dense_kernel<<<dg, 256, 0, st>>>(a, d);
-        node_attn_bwd_dense_finish_kernel<<<(int)((NS + 15) / 16), 256, 0, st>>>(a, d);
-        HAN_CHECK_LAUNCH();
-        a.only_if = reinterpret_cast<const int *>(d.hdr) + 16;
+        const int err = dense_front(dense, NS, false, f2, NS, st, a.only_if, [&](const DenseArgs &d, dim3 dg, int fg) {
+            node_attn_bwd_dense_kernel<<<dg, 256, 0, st>>>(a, d);
+            node_attn_bwd_dense_finish_kernel<<<fg, 256, 0, st>>>(a, d);
+        });
+        if (err) return err;
     }
     const RowBins bins = bins_of(split);
-    HAN_DISPATCH_FP_BF(FP, table_dtype == HAN_DTYPE_BF16, launch_bwd_cols<FPC, BF>(a, low, has_split, bins, st));
+    HAN_DISPATCH_BOOL(VAL, edge_val != nullptr,
+                      HAN_DISPATCH_FP_BF(FP, table_dtype == HAN_DTYPE_BF16, launch_bwd_cols_v<FPC, BF, VAL>(a, low, has_split, bins, st)));
     HAN_CHECK_LAUNCH();
     return 0;
 }

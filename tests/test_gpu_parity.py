@@ -1918,16 +1918,22 @@ def test_syn1m_size_independent_properties(dev):
 
 
 # ------------------------------------------------------------------------ bf16 tables
-def test_node_attn_bf16_table_exact_against_rounded_inputs(dev):
+@pytest.mark.parametrize("deep", [False, True])
+def test_node_attn_bf16_table_exact_against_rounded_inputs(dev, monkeypatch, deep):
     """bf16 storage, fp32 accumulate: fed the bf16-rounded rows, the oracle must be
-    matched to fp32 accuracy (the only error is the storage rounding of H itself)."""
+    matched to fp32 accuracy (the only error is the storage rounding of H itself).
+    The eval forward with ops.K2_DEEP is the 8-steps-in-flight instantiation: at mean degree 40 every row is in the
+    mid bin, and a 64-entry piece has full 8-steps, the half step (16 or more entries left) and single steps."""
     from han_amd import ops
+    monkeypatch.setattr(ops, "K2_DEEP", deep)
     rng = np.random.default_rng(12)
     n = 400
     bias, rp, ci, H, f1, a2, b2, c, g = _k2_inputs(rng, n, 0.1, dev)
     Hb = _t(H, dev).to(torch.bfloat16)
     Hr = Hb.to(torch.float32).cpu().numpy().astype(np.float64)          # what the kernel reads
     ref, pre_ref, lse_ref = _k2_oracle(bias, Hr, f1, _f2(Hr, a2, b2), c)
+    out_eval, _ = ops.node_attn_fwd(g, Hb, _t(f1, dev), _t(a2, dev), _t(b2, dev), _t(c, dev), train=False)
+    assert np.abs(out_eval.cpu().numpy() - ref).max() < TOL
     out, saved = ops.node_attn_fwd(g, Hb, _t(f1, dev), _t(a2, dev), _t(b2, dev), _t(c, dev), train=True)
     assert np.abs(out.cpu().numpy() - ref).max() < TOL
     assert saved[0].data_ptr() == out.data_ptr()           # the output itself (the pre-activation is not stored)
