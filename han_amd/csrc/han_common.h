@@ -296,6 +296,16 @@ static inline bool han_pow2_p(int P) { return P == 1 || P == 2 || P == 4 || P ==
         default: { constexpr int PC = 16; __VA_ARGS__; } break; \
     }
 
+// runs the statement(s) with `constexpr int CA` = AV / 64, the attention width in 64-column units (1, 2, 3; anything
+// else: 4)
+#define HAN_DISPATCH_CA(AV, ...)                                \
+    switch ((AV) / 64) {                                        \
+        case 1: { constexpr int CA = 1; __VA_ARGS__; } break;   \
+        case 2: { constexpr int CA = 2; __VA_ARGS__; } break;   \
+        case 3: { constexpr int CA = 3; __VA_ARGS__; } break;   \
+        default: { constexpr int CA = 4; __VA_ARGS__; } break;  \
+    }
+
 // a launch with `lds` bytes of dynamic LDS: beyond 64 KiB the kernel is first allowed that size; returns the HIP error
 template <typename... KArgs, typename... Args>
 static inline hipError_t han_launch_lds(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st,

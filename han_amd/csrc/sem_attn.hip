@@ -137,17 +137,44 @@ __device__ __forceinline__ void wave_node_softmax(const float (&sc)[4], const fl
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Dynamic LDS of each kernel, written once: the kernel carves its pointers with the offsets, its launcher passes
+// `bytes`.  Every gradient kernel ends by reducing its block's [dW | db | du] in `red` floats from the start of the
+// LDS, over the operands it no longer needs.
+// ---------------------------------------------------------------------------------------------
+// fp32 forward: Womega [D][WLD] | scores [2][ROWS] (the wave-local kernel has no score exchange: `wave_bytes`)
+template <int D, int A>
+struct FwdLds {
+    static constexpr int WLD = A + 16;   // (WLD mod 32) == 16: rows k and k+1 hit disjoint bank halves
+    static constexpr int sc = D * WLD;
+    static constexpr size_t wave_bytes = sc * sizeof(float);
+    static constexpr size_t bytes = (sc + 2 * ROWS) * sizeof(float);
+};
+// fp32 backward: Womega twice, [D][WLD1] for G1 | [D][WLD2] for G2 | dpre [4 waves][16][WLD2] | d s [2][ROWS] |
+// beta [2][ROWS] (the wave-local kernel forms d s in registers and leaves the last two unused)
+template <int D, int A>
+struct BwdLds {
+    static constexpr int WLD1 = A + 16;   // G1 B-operand reads: lanes step a, lane groups step f
+    static constexpr int WLD2 = A + 2;    // G2 reads: lanes step f / r, lane groups step a
+    static constexpr int w2 = D * WLD1, dp = w2 + D * WLD2, dsb = dp + 4 * 16 * WLD2, btb = dsb + 2 * ROWS;
+    static constexpr int red = D * A + 2 * A;
+    static constexpr size_t bytes = (btb + 2 * ROWS) * sizeof(float);
+    static_assert(red <= dp, "the gradient reduction reuses the two copies of Womega");
+};
 
+// The block-level forward at D = 64, A <= 128 for the meta-path counts the wave-local kernels below do not take (P = 3
+// of DBLP): a chunk of NB = 64/P whole nodes per block iteration, scores exchanged through LDS.
 template <int CA>
 __global__ __launch_bounds__(256) void sem_attn_fwd_kernel(const float *__restrict__ M, const float *Wg,
                                                            const float *bw, const float *uw, float *Z,
                                                            float *beta, int64_t N, int P) {
     constexpr int A = 64 * CA;
     constexpr int TA = A / 16;
-    constexpr int WLD = A + 16;   // (WLD mod 32) == 16: rows k and k+1 hit disjoint bank halves
+    using L = FwdLds<64, A>;
+    constexpr int WLD = L::WLD;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *Wl = smem;                 // [64][WLD]
-    float *sc = smem + 64 * WLD;      // [2][ROWS]
+    float *sc = smem + L::sc;         // [2][ROWS]
     for (int i = threadIdx.x; i < 64 * A; i += 256) Wl[(i / A) * WLD + (i % A)] = Wg[i];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
@@ -207,8 +234,8 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_kernel(const float *__restri
     }
 }
 
-// Forward for P in {1,2,4} (P divides 4; P = 8, 16 span 2 / 4 groups, see node_xsum): the P rows of a node sit in ONE 16-lane
-// group of the accumulator layout (rows 4*l4 .. 4*l4+3), so the per-node softmax
+// Forward for P in {1,2,4,8,16}: the P rows of a node sit in ONE 16-lane group of the accumulator layout (rows
+// 4*l4 .. 4*l4+3; P = 8 / 16 span 2 / 4 groups, see node_xsum), so the per-node softmax
 // and the weighted sum finish inside the group -- no LDS exchange, no barrier; each
 // wave streams its own 16-row tiles.
 template <int CA, int P>
@@ -220,7 +247,7 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_wave_kernel(const float *__r
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     // Womega in LDS for the whole kernel: B fragment of k-step ks, column tile t is W[4ks + l4][16t + l15]
-    constexpr int WLD = A + 16;
+    constexpr int WLD = FwdLds<64, A>::WLD;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     for (int i = threadIdx.x; i < 64 * A; i += 256) smem[(i / A) * WLD + (i % A)] = Wg[i];
     __syncthreads();
@@ -321,6 +348,13 @@ __device__ __forceinline__ void split_arow(const float4_t (&araw)[4], i32x4 (&af
     for (int s2 = 0; s2 < 2; ++s2) han_b6_split8(araw[2 * s2], araw[2 * s2 + 1], af[s2]);
 }
 
+// its LDS: the split, transposed Womega [3][A][LDB bytes]
+template <int A>
+struct B6FwdLds {
+    static constexpr int LDB = 128;
+    static constexpr size_t bytes = (size_t)3 * A * LDB;
+};
+
 template <int CA, int P>
 __global__ __launch_bounds__(256) void sem_attn_fwd_wave_b6_kernel(const float *__restrict__ M, const float *Wg,
                                                                    const float *bw, const float *uw, float *Z,
@@ -331,7 +365,7 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_wave_b6_kernel(const float *
     // [3][A][128 B], XOR-swizzled: the 16-byte chunk g of row a sits at chunk g ^ ((a >> 1) & 7).  Two 128-B rows span
     // the 64 banks, so the 16 lanes that read chunk g of 16 consecutive rows (8 of each parity) hit 64 different banks
     // WITHOUT padding the rows to 144 B -- 48 KB instead of 54 KB at A = 128: three blocks per CU instead of two (round 3)
-    constexpr int FWLDB = 128;
+    constexpr int FWLDB = B6FwdLds<A>::LDB;
     unsigned char *Wt = reinterpret_cast<unsigned char *>(smem);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
@@ -377,6 +411,10 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_wave_b6_kernel(const float *
     }
 }
 
+// The block-level backward at D = 64, A <= 128 for the meta-path counts the wave-local kernels do not take (P = 3 of
+// DBLP): a chunk of NB = 64/P whole nodes per block iteration.  It is sem_attn_bwd_gen_kernel<4> with the whole
+// attention width as one compile-time slice, and stays a kernel of its own: the compiler contracts the
+// multiply-adds of the two differently, so their results differ in the last bits (profiles/r09_k3_refactor_bitwise.txt).
 // slab row per block: [64*A] dW | [A] db | [A] du
 template <int CA>
 __global__ __launch_bounds__(256) void sem_attn_bwd_kernel(const float *__restrict__ M, const float *Wg,
@@ -385,14 +423,14 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_kernel(const float *__restri
                                                            float *slab, int64_t N, int P) {
     constexpr int A = 64 * CA;
     constexpr int TA = A / 16;
-    constexpr int WLD1 = A + 16;   // G1 B-operand reads: lanes step a, lane groups step f
-    constexpr int WLD2 = A + 2;    // G2 reads: lanes step f / r, lane groups step a
+    using L = BwdLds<64, A>;
+    constexpr int WLD1 = L::WLD1, WLD2 = L::WLD2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *W1 = smem;                         // [64][WLD1]
-    float *W2 = W1 + 64 * WLD1;               // [64][WLD2]
-    float *dp = W2 + 64 * WLD2;               // [4 waves][16][WLD2]
-    float *dsb = dp + 4 * 16 * WLD2;          // [2][ROWS]  d s_r
-    float *btb = dsb + 2 * ROWS;              // [2][ROWS]  beta_r
+    float *W2 = smem + L::w2;                 // [64][WLD2]
+    float *dp = smem + L::dp;                 // [4 waves][16][WLD2]
+    float *dsb = smem + L::dsb;               // [2][ROWS]  d s_r
+    float *btb = smem + L::btb;               // [2][ROWS]  beta_r
     for (int i = threadIdx.x; i < 64 * A; i += 256) {
         const float v = Wg[i];
         W1[(i / A) * WLD1 + (i % A)] = v;
@@ -561,12 +599,12 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_kernel(const float *__r
                                                                 float *slab, int64_t N) {
     constexpr int A = 64 * CA;
     constexpr int TA = A / 16;
-    constexpr int WLD1 = A + 16;
-    constexpr int WLD2 = A + 2;
+    using L = BwdLds<64, A>;
+    constexpr int WLD1 = L::WLD1, WLD2 = L::WLD2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *W1 = smem;                         // [64][WLD1]
-    float *W2 = W1 + 64 * WLD1;               // [64][WLD2]
-    float *dp = W2 + 64 * WLD2;               // [4 waves][16][WLD2]
+    float *W2 = smem + L::w2;                 // [64][WLD2]
+    float *dp = smem + L::dp;                 // [4 waves][16][WLD2]
     for (int i = threadIdx.x; i < 64 * A; i += 256) {
         const float v = Wg[i];
         W1[(i / A) * WLD1 + (i % A)] = v;
@@ -766,6 +804,18 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_kernel(const float *__r
     for (int i = threadIdx.x; i < 64 * A + 2 * A; i += 256) out[i] = red[i];
 }
 
+// LDS of the bf16-pipe backward kernels, in bytes: the split Womega twice, [3][A][SA_WLDB] transposed for G1 |
+// [3][64 f][W2LDB] as stored for G2 | dpre [4 waves or pairs][16][WLD2] fp32 | b_omega, u_omega [2][A] fp32
+template <int A>
+struct B6BwdLds {
+    static constexpr int WLD2 = A + 4;          // dpre tile rows: 16-B aligned for the 8-float fragment reads
+    static constexpr int W2LDB = A * 2 + 32;    // bytes per row of the split Womega [f][a] (G2's B operand)
+    static constexpr int w2s = 3 * A * SA_WLDB, dp = w2s + 3 * 64 * W2LDB;
+    static constexpr int bus = dp + 4 * 16 * WLD2 * (int)sizeof(float);
+    static constexpr size_t bytes = bus + 2 * A * sizeof(float);
+    static_assert((64 * A + 2 * A) * (int)sizeof(float) <= dp, "the gradient reduction reuses the split Womega");
+};
+
 // First attention column of the eight a lane group l4 contributes to step s of G2's reduction (see the kernel's header).
 template <int CA>
 __device__ __forceinline__ int g2_col(int s, int l4) {
@@ -777,7 +827,7 @@ __device__ __forceinline__ int g2_col(int s, int l4) {
 // row 16 ft + i holds feature 4 i + ft, its 16-byte piece g the columns of step g / 4, lane group g % 4 (g2_col).
 template <int CA, int NT>
 __device__ __forceinline__ void stage_w_fa(const float *Wg, unsigned char *W2s) {
-    constexpr int A = 64 * CA, W2LDB = A * 2 + 32;
+    constexpr int A = 64 * CA, W2LDB = B6BwdLds<A>::W2LDB;
     for (int it = threadIdx.x; it < 64 * (A / 8); it += NT) {
         const int lr = it / (A / 8), g = it % (A / 8);
         const int f = 4 * (lr & 15) + (lr >> 4);
@@ -823,16 +873,16 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_b6_kernel(const float *
                                                                 float *slab, int64_t N) {
     constexpr int A = 64 * CA;
     constexpr int TA = A / 16;
-    constexpr int WLD2 = A + 4;                 // dpre tile rows: 16-B aligned for the 8-float fragment reads
-    constexpr int W2LDB = A * 2 + 32;           // bytes per row of the split Womega [f][a] (G2's B operand)
+    using L = B6BwdLds<A>;
+    constexpr int WLD2 = L::WLD2, W2LDB = L::W2LDB;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    unsigned char *Wt = reinterpret_cast<unsigned char *>(smem);        // G1 B operand: [3][A][144 B]   (transposed [a][k])
-    unsigned char *W2s = Wt + 3 * A * SA_WLDB;                          // G2 B operand: [3][64 f][W2LDB] (as stored [f][a])
-    float *dp = reinterpret_cast<float *>(W2s + 3 * 64 * W2LDB);        // [4 waves][16][WLD2] fp32
+    unsigned char *Wt = reinterpret_cast<unsigned char *>(smem);        // G1 B operand: [3][A][SA_WLDB] (transposed [a][k])
+    unsigned char *W2s = Wt + L::w2s;                                   // G2 B operand: [3][64 f][W2LDB] (as stored [f][a])
+    float *dp = reinterpret_cast<float *>(Wt + L::dp);                  // [4 waves][16][WLD2] fp32
     // b_omega | u_omega: held in registers up to P = 4; the P = 8 / 16 variants (node sums across lane groups) would
     // spill five registers, and read the two values of a column tile from LDS instead (3 % slower at P = 4: measured)
     constexpr bool BU_LDS = G3B && P >= 8;
-    float *bus = dp + 4 * 16 * WLD2;
+    float *bus = reinterpret_cast<float *>(Wt + L::bus);
     if (BU_LDS)
         for (int it = threadIdx.x; it < 2 * A; it += 256) bus[it] = it < A ? bw[it] : uw[it - A];
     stage_w_t<A, 256, SA_WLDB, false>(Wg, Wt);
@@ -1094,12 +1144,12 @@ __global__ __launch_bounds__(512) void sem_attn_bwd_pair_b6_kernel(const float *
     constexpr int CA = 2;
     constexpr int A = 128;
     constexpr int TH = 4;                       // column tiles per wave
-    constexpr int WLD2 = A + 4;
-    constexpr int W2LDB = A * 2 + 32;
+    using L = B6BwdLds<A>;
+    constexpr int WLD2 = L::WLD2, W2LDB = L::W2LDB;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned char *Wt = reinterpret_cast<unsigned char *>(smem);        // G1 B operand: [3][A][SA_WLDB]
-    unsigned char *W2s = Wt + 3 * A * SA_WLDB;                          // G2 B operand: [3][64][W2LDB]
-    float *dp = reinterpret_cast<float *>(W2s + 3 * 64 * W2LDB);        // [4 pairs][16][WLD2] fp32
+    unsigned char *W2s = Wt + L::w2s;                                   // G2 B operand: [3][64][W2LDB]
+    float *dp = reinterpret_cast<float *>(Wt + L::dp);                  // [4 pairs][16][WLD2] fp32
     // stage_w_t / stage_w_fa written out: called from here they change this kernel's register allocation (one more
     // spilled register at P = 2, 4) and how the compiler pairs the LDS accesses of the gradient reduction
     for (int it = threadIdx.x; it < A * 8; it += 512) {
@@ -1313,11 +1363,11 @@ __global__ __launch_bounds__(512) void sem_attn_bwd_pair_b6_kernel(const float *
 }
 
 // ---------------------------------------------------------------------------------------------
-// Wider embeddings: D = 128 (e.g. hid_units = [16] with 8 heads, models/gat.py:42-57 leaves both
-// free).  The block-level kernels above with the feature width as a template parameter
-// (D = 16*DT); the D = 64 kernels stay as they are.  The backward keeps D*AS/64 dW accumulators
-// per lane, so at D = 128 it runs over the attention space in slices of AS = 64 columns
-// (one launch per slice; slices after the first ADD their dM contribution).
+// The block-level kernels with the feature width as a template parameter (D = 16*DT), for the tuned shapes beyond
+// D = 64, A <= 128: D = 128 (e.g. hid_units = [16] with 8 heads, models/gat.py:42-57 leaves both free) and D = 64 with
+// attention spaces of 192 / 256 columns; the D = 64, A <= 128 kernels (sem_attn_fwd_kernel, sem_attn_bwd_kernel) stay
+// as they are.  The backward keeps D*AS/64 dW accumulators per lane, so it runs over the attention space in slices of
+// AS = 64 columns (one launch per slice; slices after the first ADD their dM contribution).
 // ---------------------------------------------------------------------------------------------
 template <int CA, int DT>
 __global__ __launch_bounds__(256) void sem_attn_fwd_gen_kernel(const float *__restrict__ M, const float *Wg,
@@ -1327,10 +1377,11 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_gen_kernel(const float *__re
     constexpr int NF = D / 64;       // features per lane in the lane = feature phases
     constexpr int A = 64 * CA;
     constexpr int TA = A / 16;
-    constexpr int WLD = A + 16;
+    using L = FwdLds<D, A>;
+    constexpr int WLD = L::WLD;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *Wl = smem;                 // [D][WLD]
-    float *sc = smem + D * WLD;       // [2][ROWS]
+    float *sc = smem + L::sc;         // [2][ROWS]
     for (int i = threadIdx.x; i < D * A; i += 256) Wl[(i / A) * WLD + (i % A)] = Wg[i];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
@@ -1400,14 +1451,14 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_gen_kernel(const float *__re
     constexpr int NF = D / 64;
     constexpr int AS = 64;           // columns of the attention space per launch
     constexpr int TA = AS / 16;
-    constexpr int WLD1 = AS + 16;
-    constexpr int WLD2 = AS + 2;
+    using L = BwdLds<D, AS>;
+    constexpr int WLD1 = L::WLD1, WLD2 = L::WLD2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *W1 = smem;                         // [D][WLD1]
-    float *W2 = W1 + D * WLD1;                // [D][WLD2]
-    float *dp = W2 + D * WLD2;                // [4 waves][16][WLD2]
-    float *dsb = dp + 4 * 16 * WLD2;          // [2][ROWS]
-    float *btb = dsb + 2 * ROWS;              // [2][ROWS]
+    float *W2 = smem + L::w2;                 // [D][WLD2]
+    float *dp = smem + L::dp;                 // [4 waves][16][WLD2]
+    float *dsb = smem + L::dsb;               // [2][ROWS]  d s_r
+    float *btb = smem + L::btb;               // [2][ROWS]  beta_r
     for (int i = threadIdx.x; i < D * AS; i += 256) {
         const float v = Wg[(int64_t)(i / AS) * A + a_off + (i % AS)];
         W1[(i / AS) * WLD1 + (i % AS)] = v;
@@ -1436,6 +1487,7 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_gen_kernel(const float *__re
         const int rows = nodes * P;
         const int64_t row0 = node0 * P;
         float *dsr = dsb + buf * ROWS, *btr = btb + buf * ROWS;
+        // ---- P0: d beta, d s per node (lane = feature); padding rows of the chunk get d s = beta = 0
         if (threadIdx.x < ROWS && threadIdx.x >= rows) {
             dsr[threadIdx.x] = 0.f;
             btr[threadIdx.x] = 0.f;
@@ -1460,7 +1512,10 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_gen_kernel(const float *__re
                 btr[nd * P + lane] = breg;
             }
         }
+        // no second barrier at the end of the pass: the next one writes the other d s / beta buffer, and the
+        // barrier inside it orders this pass's reads before the reuse after
         __syncthreads();
+        // ---- G1: pre = M_tile . Womega
         f32x4 acc[TA];
 #pragma unroll
         for (int t = 0; t < TA; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1476,6 +1531,7 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_gen_kernel(const float *__re
                     acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, wr[16 * t], acc[t], 0, 0, 0);
             }
         }
+        // ---- dpre in the accumulator layout (row r = 4*l4 + reg, col a = 16t + l15)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const float ds = dsr[16 * w + 4 * l4 + reg];
@@ -1489,6 +1545,7 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_gen_kernel(const float *__re
                 mydp[(4 * l4 + reg) * WLD2 + 16 * t + l15] = d;
             }
         }
+        // ---- G3: dW += M_tile^T . dpre   (k-step `reg` holds rows 4g + reg, g = lane group)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
             const int lr = 16 * w + 4 * l4 + reg;
@@ -1501,6 +1558,7 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_gen_kernel(const float *__re
                     dW[ft][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, acc[t][reg], dW[ft][t], 0, 0, 0);
             }
         }
+        // ---- G2: dMx = dpre . Womega^T   (A operand from the wave's LDS tile)
         f32x4 acc2[DT];
 #pragma unroll
         for (int ft = 0; ft < DT; ++ft) acc2[ft] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1529,6 +1587,7 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_gen_kernel(const float *__re
             }
         }
     }
+    // ---- parameter gradients: lane groups -> waves (LDS) -> slab row
 #pragma unroll
     for (int t = 0; t < TA; ++t) {
 #pragma unroll
@@ -1648,6 +1707,15 @@ __global__ __launch_bounds__(256) void sem_attn_fwd_wide_kernel(const float *__r
 
 constexpr int kWideDChunk = 128;     // embedding columns of dWomega per backward launch (DTC = 8 tiles)
 
+// its LDS: dpre [4 waves][16][WLD2] | d s [2][ROWS] | beta [2][ROWS]; the gradient reduction of a chunk needs more
+struct WideBwdLds {
+    static constexpr int AS = 64, WLD2 = AS + 2;
+    static constexpr int dsb = 4 * 16 * WLD2, btb = dsb + 2 * ROWS;
+    static constexpr int red = kWideDChunk * AS + 2 * AS;
+    static constexpr size_t bytes = red * sizeof(float);
+    static_assert(btb + 2 * ROWS <= red, "the tiles fit inside the reduction's region");
+};
+
 // slab row per block: [D*A] dW | [A] db | [A] du; this launch owns the attention columns [a_off, a_off + 64) and the
 // dW rows [d_off, d_off + 128); the launch with d_off == 0 also owns db / du of its slice and adds the slice's dM term
 __global__ __launch_bounds__(256) void sem_attn_bwd_wide_kernel(const float *__restrict__ M, const float *__restrict__ Wg,
@@ -1655,14 +1723,15 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wide_kernel(const float *__r
                                                                 const float *beta, const float *dZ, float *dM,
                                                                 float *slab, int64_t N, int P, int D, int A,
                                                                 int a_off, int d_off) {
-    constexpr int AS = 64;
+    using L = WideBwdLds;
+    constexpr int AS = L::AS;
     constexpr int TA = AS / 16;
     constexpr int DTC = kWideDChunk / 16;
-    constexpr int WLD2 = AS + 2;
+    constexpr int WLD2 = L::WLD2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *dp = smem;                         // [4 waves][16][WLD2]
-    float *dsb = dp + 4 * 16 * WLD2;          // [2][ROWS]
-    float *btb = dsb + 2 * ROWS;              // [2][ROWS]
+    float *dsb = smem + L::dsb;               // [2][ROWS]
+    float *btb = smem + L::btb;               // [2][ROWS]
     const bool first = d_off == 0;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
@@ -1828,114 +1897,115 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wide_kernel(const float *__r
 
 constexpr int kSemBwdBlocks = 256;   // one 4-wave block per CU (104 KB of LDS at A = 128)
 
-template <int CA>
-size_t fwd_lds() { return (size_t)(64 * (64 * CA + 16) + 2 * ROWS) * sizeof(float); }
-template <int CA>
-size_t bwd_lds() {
-    constexpr int A = 64 * CA;
-    return (size_t)(64 * (A + 16) + 64 * (A + 2) + 4 * 16 * (A + 2) + 4 * ROWS) * sizeof(float);
-}
-
-template <int CA>
-int launch_fwd(const float *M, const float *w, const float *b, const float *u, float *Z, float *beta,
-               int64_t N, int P, int flags, hipStream_t st) {
-    hipError_t e;
-    if (han_pow2_p(P) && N * P >= 64 * 1024 && !(flags & HAN_FLAG_K3_EXACT_PIPE)) {
-        // large inputs: the contraction on the bf16 matrix pipe (exact 3-way split, fp32-class accuracy)
-        const size_t blds = (size_t)3 * 64 * CA * 128;       // swizzled 128-B rows (sem_attn_fwd_wave_b6_kernel)
-        const int grid = han_grid_for(N * P, 64, 256 * 3);
-        HAN_DISPATCH_P(P, e = han_launch_lds(sem_attn_fwd_wave_b6_kernel<CA, PC>, grid, 256, blds, st, M, w, b, u, Z, beta, N))
-    } else if (han_pow2_p(P)) {
-        const size_t wlds = (size_t)64 * (64 * CA + 16) * sizeof(float);
-        const int grid = han_grid_for(N * P, 64, 256 * 4);
-        HAN_DISPATCH_P(P, e = han_launch_lds(sem_attn_fwd_wave_kernel<CA, PC>, grid, 256, wlds, st, M, w, b, u, Z, beta, N))
-    } else {
-        const int grid = han_grid_for(N, ROWS / P, 256 * 3);
-        e = han_launch_lds(sem_attn_fwd_kernel<CA>, grid, 256, fwd_lds<CA>(), st, M, w, b, u, Z, beta, N, P);
+// The arguments of a forward / backward call, filled once by the entry point.  `launch` appends what a kernel takes
+// after N (the block-level kernels P, the run-time-width ones P, D, A, the sliced ones their offsets).
+struct K3Fwd {
+    const float *M, *w, *b, *u;
+    float *Z, *beta;
+    int64_t N;
+    int P, D, A, flags;
+    hipStream_t st;
+    template <typename... KArgs, typename... Tail>
+    hipError_t launch(void (*kernel)(KArgs...), int grid, int block, size_t lds, Tail... tail) const {
+        return han_launch_lds(kernel, grid, block, lds, st, M, w, b, u, Z, beta, N, tail...);
     }
-    return (int)e;
-}
-
-template <int CA>
-int launch_bwd(const float *M, const float *w, const float *b, const float *u, const float *beta,
-               const float *dZ, float *dM, float *slab, int64_t N, int P, int *grid_out, int flags, hipStream_t st) {
-    const size_t lds = bwd_lds<CA>();
-    hipError_t e;
-    if (han_pow2_p(P) && N * P >= 64 * 1024 && !(flags & HAN_FLAG_K3_EXACT_PIPE)) {
-        const int grid = han_grid_for(N * P, 64, kSemBwdBlocks);
-        *grid_out = grid;
-        constexpr int A6 = 64 * CA;
-        const size_t blds = (size_t)3 * A6 * SA_WLDB + (size_t)3 * 64 * (A6 * 2 + 32) + (size_t)(4 * 16 * (A6 + 4) + 2 * A6) * sizeof(float);
-        HAN_DISPATCH_P(P, {
-            if (CA == 2 && (flags & HAN_FLAG_K3_PAIRS))
-                e = han_launch_lds(sem_attn_bwd_pair_b6_kernel<PC>, grid, 512, blds, st, M, w, b, u, beta, dZ, dM, slab, N);
-            else if (flags & HAN_FLAG_K3_G3_F32)
-                e = han_launch_lds(sem_attn_bwd_wave_b6_kernel<CA, PC, false>, grid, 256, blds, st, M, w, b, u, beta, dZ, dM, slab, N);
-            else
-                e = han_launch_lds(sem_attn_bwd_wave_b6_kernel<CA, PC, true>, grid, 256, blds, st, M, w, b, u, beta, dZ, dM, slab, N);
-        })
-    } else if (han_pow2_p(P)) {
-        const int grid = han_grid_for(N > 0 ? N * P : 1, 64, kSemBwdBlocks);
-        *grid_out = grid;
-        HAN_DISPATCH_P(P, e = han_launch_lds(sem_attn_bwd_wave_kernel<CA, PC>, grid, 256, lds, st, M, w, b, u, beta, dZ, dM, slab, N))
-    } else {
-        const int grid = han_grid_for(N > 0 ? N : 1, ROWS / P, kSemBwdBlocks);
-        *grid_out = grid;
-        e = han_launch_lds(sem_attn_bwd_kernel<CA>, grid, 256, lds, st, M, w, b, u, beta, dZ, dM, slab, N, P);
+};
+struct K3Bwd {
+    const float *M, *w, *b, *u, *beta, *dZ;
+    float *dM, *slab;
+    int64_t N;
+    int P, D, A, flags;
+    hipStream_t st;
+    int grid;      // blocks = slab rows of the launches (the same for every slice of a call)
+    template <typename... KArgs, typename... Tail>
+    hipError_t launch(void (*kernel)(KArgs...), int block, size_t lds, Tail... tail) const {
+        return han_launch_lds(kernel, grid, block, lds, st, M, w, b, u, beta, dZ, dM, slab, N, tail...);
     }
-    return (int)e;
-}
-
-template <int CA, int DT>
-int launch_fwd_gen(const float *M, const float *w, const float *b, const float *u, float *Z, float *beta,
-                   int64_t N, int P, hipStream_t st) {
-    const size_t lds = (size_t)(16 * DT * (64 * CA + 16) + 2 * ROWS) * sizeof(float);
-    const int grid = han_grid_for(N, ROWS / P, 256 * 2);
-    return (int)han_launch_lds(sem_attn_fwd_gen_kernel<CA, DT>, grid, 256, lds, st, M, w, b, u, Z, beta, N, P);
-}
-
-template <int DT>
-int launch_bwd_gen(const float *M, const float *w, const float *b, const float *u, const float *beta,
-                   const float *dZ, float *dM, float *slab, int64_t N, int P, int A, int *grid_out,
-                   hipStream_t st) {
-    constexpr int D = 16 * DT;
-    const size_t lds = (size_t)(D * (64 + 16) + D * (64 + 2) + 4 * 16 * (64 + 2) + 4 * ROWS) * sizeof(float);
-    const int grid = han_grid_for(N > 0 ? N : 1, ROWS / P, kSemBwdBlocks);
-    *grid_out = grid;
-    for (int a_off = 0; a_off < A; a_off += 64) {      // same grid every pass: a block's slab row fills up slice by slice
-        const hipError_t e = han_launch_lds(sem_attn_bwd_gen_kernel<DT>, grid, 256, lds, st, M, w, b, u, beta, dZ, dM,
-                                            slab, N, P, A, a_off);
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
-template <int CA>
-int launch_fwd_wide(const float *M, const float *w, const float *b, const float *u, float *Z, float *beta,
-                    int64_t N, int P, int D, int A, hipStream_t st) {
-    const int grid = han_grid_for(N, ROWS / P, 256 * 4);
-    sem_attn_fwd_wide_kernel<CA><<<grid, 256, 0, st>>>(M, w, b, u, Z, beta, N, P, D, A);
-    HAN_CHECK_LAUNCH();
-    return 0;
-}
-
-int launch_bwd_wide(const float *M, const float *w, const float *b, const float *u, const float *beta,
-                    const float *dZ, float *dM, float *slab, int64_t N, int P, int D, int A, int *grid_out,
-                    hipStream_t st) {
-    const size_t lds = (size_t)(kWideDChunk * 64 + 2 * 64) * sizeof(float);
-    const int grid = han_grid_for(N > 0 ? N : 1, ROWS / P, kSemBwdBlocks);
-    *grid_out = grid;
-    for (int a_off = 0; a_off < A; a_off += 64)          // same grid every pass: a block's slab row fills up piece by piece
-        for (int d_off = 0; d_off < D; d_off += kWideDChunk) {
-            sem_attn_bwd_wide_kernel<<<grid, 256, lds, st>>>(M, w, b, u, beta, dZ, dM, slab, N, P, D, A, a_off, d_off);
-            HAN_CHECK_LAUNCH();
-        }
-    return 0;
-}
+};
 
 // shapes of the tuned kernels; everything else (multiples of 64) goes to the run-time-width kernels
 bool k3_tuned(int D, int A) { return (D == 64 || D == 128) && A >= 64 && A <= 256; }
 bool k3_shape_ok(int P, int D, int A) { return P >= 1 && P <= 64 && D >= 64 && D % 64 == 0 && A >= 64 && A % 64 == 0; }
+// ... of the wave-local kernels (the others of the tuned shapes go to the block-level kernels)
+bool k3_wave_local(int P, int D, int A) { return D == 64 && A <= 128 && han_pow2_p(P); }
+// large inputs: the contractions on the bf16 matrix pipe (exact 3-way split, fp32-class accuracy)
+bool k3_b6(int64_t N, int P, int flags) { return N * P >= 64 * 1024 && !(flags & HAN_FLAG_K3_EXACT_PIPE); }
+
+template <int CA>
+hipError_t launch_fwd_wave(const K3Fwd &a) {
+    constexpr int A = 64 * CA;
+    hipError_t e = hipSuccess;
+    if (k3_b6(a.N, a.P, a.flags)) {
+        const int grid = han_grid_for(a.N * a.P, 64, 256 * 3);
+        HAN_DISPATCH_P(a.P, e = a.launch(sem_attn_fwd_wave_b6_kernel<CA, PC>, grid, 256, B6FwdLds<A>::bytes))
+    } else {
+        const int grid = han_grid_for(a.N * a.P, 64, 256 * 4);
+        HAN_DISPATCH_P(a.P, e = a.launch(sem_attn_fwd_wave_kernel<CA, PC>, grid, 256, FwdLds<64, A>::wave_bytes))
+    }
+    return e;
+}
+
+template <int CA>
+hipError_t launch_fwd_block(const K3Fwd &a) {      // D = 64, A <= 128: three blocks per CU
+    return a.launch(sem_attn_fwd_kernel<CA>, han_grid_for(a.N, ROWS / a.P, 256 * 3), 256, FwdLds<64, 64 * CA>::bytes, a.P);
+}
+
+template <int CA, int DT>
+hipError_t launch_fwd_gen(const K3Fwd &a) {
+    return a.launch(sem_attn_fwd_gen_kernel<CA, DT>, han_grid_for(a.N, ROWS / a.P, 256 * 2), 256,
+                    FwdLds<16 * DT, 64 * CA>::bytes, a.P);
+}
+
+template <int CA>
+hipError_t launch_fwd_wide(const K3Fwd &a) {
+    return a.launch(sem_attn_fwd_wide_kernel<CA>, han_grid_for(a.N, ROWS / a.P, 256 * 4), 256, 0, a.P, a.D, a.A);
+}
+
+template <int CA>
+hipError_t launch_bwd_wave(K3Bwd &a) {
+    constexpr int A = 64 * CA;
+    hipError_t e = hipSuccess;
+    a.grid = han_grid_for(a.N * a.P, 64, kSemBwdBlocks);
+    if (k3_b6(a.N, a.P, a.flags)) {
+        const size_t lds = B6BwdLds<A>::bytes;
+        HAN_DISPATCH_P(a.P, {
+            if (CA == 2 && (a.flags & HAN_FLAG_K3_PAIRS))
+                e = a.launch(sem_attn_bwd_pair_b6_kernel<PC>, 512, lds);
+            else
+                HAN_DISPATCH_BOOL(G3B, !(a.flags & HAN_FLAG_K3_G3_F32),
+                                  e = a.launch(sem_attn_bwd_wave_b6_kernel<CA, PC, G3B>, 256, lds));
+        })
+    } else {
+        HAN_DISPATCH_P(a.P, e = a.launch(sem_attn_bwd_wave_kernel<CA, PC>, 256, BwdLds<64, A>::bytes))
+    }
+    return e;
+}
+
+template <int CA>
+hipError_t launch_bwd_block(K3Bwd &a) {      // D = 64, A <= 128
+    a.grid = han_grid_for(a.N, ROWS / a.P, kSemBwdBlocks);
+    return a.launch(sem_attn_bwd_kernel<CA>, 256, BwdLds<64, 64 * CA>::bytes, a.P);
+}
+
+template <int DT>
+hipError_t launch_bwd_gen(K3Bwd &a) {
+    a.grid = han_grid_for(a.N, ROWS / a.P, kSemBwdBlocks);
+    for (int a_off = 0; a_off < a.A; a_off += 64) {      // a block's slab row fills up slice by slice
+        const hipError_t e = a.launch(sem_attn_bwd_gen_kernel<DT>, 256, BwdLds<16 * DT, 64>::bytes, a.P, a.A, a_off);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_bwd_wide(K3Bwd &a) {
+    a.grid = han_grid_for(a.N, ROWS / a.P, kSemBwdBlocks);
+    for (int a_off = 0; a_off < a.A; a_off += WideBwdLds::AS)          // a block's slab row fills up piece by piece
+        for (int d_off = 0; d_off < a.D; d_off += kWideDChunk) {
+            const hipError_t e = a.launch(sem_attn_bwd_wide_kernel, 256, WideBwdLds::bytes, a.P, a.D, a.A, a_off, d_off);
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
+}
 
 }  // namespace
 
@@ -1945,28 +2015,21 @@ extern "C" int han_sem_attn_fwd(const float *M, const float *w_omega, const floa
     if (N == 0) return 0;   // nothing to do; row pointers of empty tensors may be null
     if (!M || !w_omega || !b_omega || !u_omega || !Z || !beta || N < 0 || P <= 0) return HAN_E_BADARG;
     if (!k3_shape_ok(P, D, A)) return HAN_E_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (!k3_tuned(D, A)) {      // any wider embedding / attention space
-        if (A % 256 == 0) return launch_fwd_wide<4>(M, w_omega, b_omega, u_omega, Z, beta, N, P, D, A, st);
-        if (A % 192 == 0) return launch_fwd_wide<3>(M, w_omega, b_omega, u_omega, Z, beta, N, P, D, A, st);
-        if (A % 128 == 0) return launch_fwd_wide<2>(M, w_omega, b_omega, u_omega, Z, beta, N, P, D, A, st);
-        return launch_fwd_wide<1>(M, w_omega, b_omega, u_omega, Z, beta, N, P, D, A, st);
+    const K3Fwd a = {M, w_omega, b_omega, u_omega, Z, beta, N, P, D, A, flags, (hipStream_t)stream};
+    hipError_t e = hipSuccess;
+    if (!k3_tuned(D, A)) {      // any wider embedding / attention space, in slices of the widest of 256 .. 64 columns
+        const int slice = A % 256 == 0 ? 256 : A % 192 == 0 ? 192 : A % 128 == 0 ? 128 : 64;
+        HAN_DISPATCH_CA(slice, e = launch_fwd_wide<CA>(a));
+    } else if (k3_wave_local(P, D, A)) {
+        HAN_DISPATCH_CA(A, if constexpr (CA <= 2) e = launch_fwd_wave<CA>(a));
+    } else if (D == 64 && A <= 128) {
+        HAN_DISPATCH_CA(A, if constexpr (CA <= 2) e = launch_fwd_block<CA>(a));
+    } else if (D == 64) {
+        HAN_DISPATCH_CA(A, if constexpr (CA >= 3) e = launch_fwd_gen<CA, 4>(a));
+    } else {
+        HAN_DISPATCH_CA(A, e = launch_fwd_gen<CA, 8>(a));
     }
-    // attention spaces of 192 / 256 columns (round 3) and 128-wide embeddings: the width-templated block-level kernels
-    if (D == 128 || A > 128) {
-        if (D == 128) {
-            switch (A / 64) {
-                case 1: return launch_fwd_gen<1, 8>(M, w_omega, b_omega, u_omega, Z, beta, N, P, st);
-                case 2: return launch_fwd_gen<2, 8>(M, w_omega, b_omega, u_omega, Z, beta, N, P, st);
-                case 3: return launch_fwd_gen<3, 8>(M, w_omega, b_omega, u_omega, Z, beta, N, P, st);
-                default: return launch_fwd_gen<4, 8>(M, w_omega, b_omega, u_omega, Z, beta, N, P, st);
-            }
-        }
-        if (A == 192) return launch_fwd_gen<3, 4>(M, w_omega, b_omega, u_omega, Z, beta, N, P, st);
-        return launch_fwd_gen<4, 4>(M, w_omega, b_omega, u_omega, Z, beta, N, P, st);
-    }
-    if (A == 64) return launch_fwd<1>(M, w_omega, b_omega, u_omega, Z, beta, N, P, flags, st);
-    return launch_fwd<2>(M, w_omega, b_omega, u_omega, Z, beta, N, P, flags, st);
+    return (int)e;
 }
 
 extern "C" size_t han_sem_attn_bwd_workspace(int64_t N, int P, int D, int A) {
@@ -1983,23 +2046,22 @@ extern "C" int han_sem_attn_bwd(const float *M, const float *w_omega, const floa
         return HAN_E_BADARG;
     if (!k3_shape_ok(P, D, A)) return HAN_E_UNSUPPORTED;
     if (workspace_bytes < han_sem_attn_bwd_workspace(N, P, D, A)) return HAN_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    float *slab = (float *)workspace;
-    int grid = 0;
-    int rc;
-    if (!k3_tuned(D, A)) rc = launch_bwd_wide(M, w_omega, b_omega, u_omega, beta, dZ, dM, slab, N, P, D, A, &grid, st);
-    else if (D == 128) rc = launch_bwd_gen<8>(M, w_omega, b_omega, u_omega, beta, dZ, dM, slab, N, P, A, &grid, st);
-    else if (A > 128) rc = launch_bwd_gen<4>(M, w_omega, b_omega, u_omega, beta, dZ, dM, slab, N, P, A, &grid, st);
-    else rc = (A == 64)
-                 ? launch_bwd<1>(M, w_omega, b_omega, u_omega, beta, dZ, dM, slab, N, P, &grid, flags, st)
-                 : launch_bwd<2>(M, w_omega, b_omega, u_omega, beta, dZ, dM, slab, N, P, &grid, flags, st);
-    if (rc != 0) return rc;
+    K3Bwd a = {M, w_omega, b_omega, u_omega, beta, dZ, dM, (float *)workspace, N, P, D, A, flags, (hipStream_t)stream, 0};
+    hipError_t e = hipSuccess;
+    if (!k3_tuned(D, A)) {
+        e = launch_bwd_wide(a);
+    } else if (k3_wave_local(P, D, A)) {
+        HAN_DISPATCH_CA(A, if constexpr (CA <= 2) e = launch_bwd_wave<CA>(a));
+    } else if (D == 64 && A <= 128) {
+        HAN_DISPATCH_CA(A, if constexpr (CA <= 2) e = launch_bwd_block<CA>(a));
+    } else {
+        HAN_DISPATCH_BOOL(D128, D == 128, e = launch_bwd_gen<D128 ? 8 : 4>(a));
+    }
+    if (e != hipSuccess) return (int)e;
     const int width = D * A + 2 * A;
     HanReduceOut o = han_reduce_to(dw_omega, width);
     o.ptr[1] = db_omega; o.ptr[2] = du_omega;
     o.seg_end[0] = D * A; o.seg_end[1] = D * A + A; o.seg_end[2] = width;
     o.nseg = 3;
-    hipError_t e = han_reduce_slabs(slab, grid, width, width, o, st);
-    if (e != hipSuccess) return (int)e;
-    return 0;
+    return (int)han_reduce_slabs(a.slab, a.grid, width, width, o, (hipStream_t)stream);
 }

@@ -645,7 +645,11 @@ def test_other_head_shapes_match_oracle(dev, K, FP, A, drop, monkeypatch):
                                      # run-time-width kernels: 8 x 32 last layers (D = 256), hid_units = [128] x 8 heads
                                      # (D = 1024), mp_att_size = 320 / 512; dW chunks of 128 columns incl. a short one
                                      (300, 3, 128, 256), (257, 4, 320, 192), (100, 2, 512, 1024), (70, 5, 64, 320),
-                                     (1, 1, 128, 256), (3000, 4, 256, 256), (129, 64, 64, 192), (50, 2, 320, 64)])
+                                     (1, 1, 128, 256), (3000, 4, 256, 256), (129, 64, 64, 192), (50, 2, 320, 64),
+                                     # the block-level kernels at D = 64 with more chunks (21 nodes at P = 3, 12 at
+                                     # P = 5) than blocks (768 forward, 256 backward): the blocks loop and use both of
+                                     # their score / d s buffers; 63 rows: padding rows zeroed, a partial wave tile
+                                     (16200, 3, 128, 64), (9300, 5, 64, 64), (10, 7, 128, 64)])
 def test_semantic_attention_fwd_bwd(dev, n, p, a, d):
     from han_amd import ops
     rng = np.random.default_rng(n + p)

@@ -103,3 +103,23 @@ def test_verdicts():
     assert kd.verdict(base, (renamed, n[k], 7)) == "changed"
     assert kd.verdict(base, (renamed + [renamed[2]], n[k], o[k])) == "changed"          # one global store more
     assert kd.verdict(base, (renamed + ["v_mov_b32_e32 v2, 0 // 7E040280"], n[k], o[k])) == "equivalent"
+
+
+def test_rename_pairs_a_renamed_kernel_and_leaves_the_rest_alone():
+    parent = {"_Z3genILi4EEvPf": 1, "_Z3genILi8EEvPf": 2, "_Z3oldILi1EEvPf": 3, "_Z4keepPf": 4, "_Z4gonePf": 5}
+    cand = {"_Z3genILi1ELi4EEvPf": 1, "_Z3genILi1ELi8EEvPf": 2, "_Z4keepPf": 4, "_Z3newPf": 6}
+    pairs, only_p, only_c = kd.pair_symbols(parent, cand)
+    assert pairs == [("_Z4keepPf", "_Z4keepPf")] and len(only_p) == 4 and len(only_c) == 3
+    # a substring of the mangled name, every occurrence in every parent symbol; renames apply in the order given
+    pairs, only_p, only_c = kd.pair_symbols(parent, cand, [("genILi", "genILi1ELi"), ("3oldILi1E", "3genILi1ELi4E")])
+    assert pairs == [("_Z3genILi4EEvPf", "_Z3genILi1ELi4EEvPf"), ("_Z3genILi8EEvPf", "_Z3genILi1ELi8EEvPf"),
+                     ("_Z3oldILi1EEvPf", "_Z3genILi1ELi4EEvPf"), ("_Z4keepPf", "_Z4keepPf")]   # two parents, one candidate
+    assert only_p == ["_Z4gonePf"] and only_c == ["_Z3newPf"]
+    # a rename that produces no candidate symbol leaves the parent symbol unpaired under its own name
+    # the renamed kernel's own name after a branch, and the padding behind it, are no difference
+    old = DIS.replace("\ts_barrier ", "\ts_cbranch_scc0 2                 // 000000001104: BF840002 <_Z4betaPf+0x10>\n\ts_barrier ")
+    new = old.replace("_Z4betaPf", "_Z4betaILi1EEPf").replace("00000000110C: BF810000", "00000000110C: BF810000\n\t...")
+    so, sn = kd.parse_disassembly(old), kd.parse_disassembly(new)
+    assert so["_Z4betaPf"] == sn["_Z4betaILi1EEPf"] and len(so["_Z4betaPf"]) == 4
+    assert so["_Z4betaPf"][1] == "s_cbranch_scc0 2 // BF840002"
+    assert kd.pair_symbols({"_Z1aPf": 1}, {"_Z1bPf": 1}, [("1a", "1c")]) == ([], ["_Z1aPf"], ["_Z1bPf"])

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 kernels of two source trees, without a GPU (and without torch).
 
-    python tools/kernel_diff.py <parent tree> <candidate tree> [--jobs N] [--keep DIR]
+    python tools/kernel_diff.py <parent tree> <candidate tree> [--jobs N] [--keep DIR] [--rename OLD=NEW ...]
 
 Every HIP source of `han_amd/_lib.py:SOURCES` is compiled device-only in both trees with the flags
 `_lib.build` uses, and every kernel symbol gets one line with a verdict:
@@ -16,6 +16,11 @@ Every HIP source of `han_amd/_lib.py:SOURCES` is compiled device-only in both tr
 Exit status 1 when the symbol sets differ, a tree yields no kernels, or any kernel is `changed`.  A refactor of
 the kernel sources is gated on this: renamed registers or commuted operands pass, a changed resource or a
 memory / matrix instruction more or less does not.
+
+A kernel that the candidate renames (another template argument list, another name) is paired with `--rename OLD=NEW`
+(repeatable): every OLD in a parent symbol (the mangled name, as printed) is replaced by NEW before the symbols are
+paired, so the kernel gets a verdict instead of two "only in" lines.  Two parent kernels may end up paired with the
+same candidate kernel, when one kernel has taken the place of both.
 """
 import argparse
 import importlib.util
@@ -34,11 +39,14 @@ COUNTED = re.compile(r"^(v_mfma|v_smfmac|global_|buffer_|flat_|scratch_|ds_|s_ba
 
 _SYM = re.compile(r"^[0-9a-fA-F]+ <(.+)>:\s*$")
 _ADDR = re.compile(r"//\s*[0-9A-Fa-f]+:\s*")
+_TARGET = re.compile(r"\s*<[^<>\s]+\+0x[0-9A-Fa-f]+>\s*$")
 
 
 def parse_disassembly(text):
     """`llvm-objdump -d` text -> {symbol: [instruction line without its address, ...]}.
-    An instruction line reads `<tab>mnemonic operands   // ADDRESS: ENCODING ...`; the encoding stays."""
+    An instruction line reads `<tab>mnemonic operands   // ADDRESS: ENCODING ...`; the encoding stays.  What only
+    restates where the code lies goes as well: the `<symbol+0xOFFSET>` that follows a branch (its encoding holds the
+    relative target; the symbol differs for a renamed kernel) and the `...` lines of zero padding between symbols."""
     out, cur = {}, None
     for line in text.splitlines():
         m = _SYM.match(line)
@@ -46,9 +54,9 @@ def parse_disassembly(text):
             cur = out.setdefault(m.group(1), [])
             continue
         s = line.strip()
-        if cur is None or not s or s.startswith("Disassembly of section") or "file format" in s:
+        if cur is None or not s or s == "..." or s.startswith("Disassembly of section") or "file format" in s:
             continue
-        cur.append(" ".join(_ADDR.sub("// ", s).split()))
+        cur.append(" ".join(_TARGET.sub("", _ADDR.sub("// ", s)).split()))
     return out
 
 
@@ -113,6 +121,22 @@ def verdict(a, b):
     return "changed"
 
 
+def pair_symbols(parent, candidate, renames=()):
+    """-> (pairs, only_parent, only_candidate): pairs = sorted (parent symbol, candidate symbol) after the `renames`
+    [(old, new), ...] have been applied, in order, to the parent's names; the rest of either side, sorted."""
+    pairs, only_parent = [], []
+    for k in sorted(parent):
+        r = k
+        for old, new in renames:
+            r = r.replace(old, new)
+        if r in candidate:
+            pairs.append((k, r))
+        else:
+            only_parent.append(k)
+    taken = {r for _, r in pairs}
+    return pairs, only_parent, sorted(k for k in candidate if k not in taken)
+
+
 def _tool(name):
     for cand in (shutil.which(name), os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", name)):
         if cand and os.path.exists(cand):
@@ -155,7 +179,12 @@ def main(argv=None):
     ap.add_argument("candidate")
     ap.add_argument("--jobs", type=int, default=8, help="parallel compiles (at most 16)")
     ap.add_argument("--keep", metavar="DIR", default=None, help="keep the code objects here")
+    ap.add_argument("--rename", metavar="OLD=NEW", action="append", default=[],
+                    help="replace OLD by NEW in the parent's symbol names before pairing (repeatable)")
     args = ap.parse_args(argv)
+    if any("=" not in r for r in args.rename):
+        ap.error("--rename takes OLD=NEW")
+    renames = [tuple(r.split("=", 1)) for r in args.rename]
     work = args.keep or tempfile.mkdtemp(prefix="kernel_diff_")
     try:
         pa = build_tree(os.path.abspath(args.parent), os.path.join(work, "parent"), args.jobs)
@@ -169,25 +198,28 @@ def main(argv=None):
         if not p or not c:
             print(f"{src}: no kernels in the {'parent' if not p else 'candidate'} tree")
             bad += 1
-        for k in sorted(set(p) ^ set(c)):
-            print(f"{src} {k}: only in the {'parent' if k in p else 'candidate'} tree")
-            bad += 1
+        pairs, only_p, only_c = pair_symbols(p, c, renames)
+        for k in only_p:
+            print(f"{src} {k}: only in the parent tree")
+        for k in only_c:
+            print(f"{src} {k}: only in the candidate tree")
+        bad += len(only_p) + len(only_c)
         tally = Counter()
-        for k in sorted(set(p) & set(c)):
-            v = verdict(p[k], c[k])
+        for k, kc in pairs:
+            v = verdict(p[k], c[kc])
             tally[v] += 1
             bad += v == "changed"
-            extra = "" if v == "identical" else f"  instructions {len(p[k][0])} -> {len(c[k][0])}"
+            extra = "" if v == "identical" else f"  instructions {len(p[k][0])} -> {len(c[kc][0])}"
             if v == "changed":
-                diff = {key: (p[k][1].get(key), c[k][1].get(key)) for key in RESOURCE_KEYS
-                        if p[k][1].get(key) != c[k][1].get(key)}
-                if p[k][2] != c[k][2]:
-                    diff["occupancy"] = (p[k][2], c[k][2])
-                ops = {op: (opcode_counts(p[k][0])[op], opcode_counts(c[k][0])[op])
-                       for op in set(opcode_counts(p[k][0])) | set(opcode_counts(c[k][0]))
-                       if opcode_counts(p[k][0])[op] != opcode_counts(c[k][0])[op]}
+                diff = {key: (p[k][1].get(key), c[kc][1].get(key)) for key in RESOURCE_KEYS
+                        if p[k][1].get(key) != c[kc][1].get(key)}
+                if p[k][2] != c[kc][2]:
+                    diff["occupancy"] = (p[k][2], c[kc][2])
+                ops = {op: (opcode_counts(p[k][0])[op], opcode_counts(c[kc][0])[op])
+                       for op in set(opcode_counts(p[k][0])) | set(opcode_counts(c[kc][0]))
+                       if opcode_counts(p[k][0])[op] != opcode_counts(c[kc][0])[op]}
                 extra += f"  {diff} {ops}"
-            print(f"{src} {k}: {v}{extra}")
+            print(f"{src} {k}{'' if kc == k else ' -> ' + kc}: {v}{extra}")
         print(f"== {src}: {len(p)} kernels in the parent, {len(c)} in the candidate; "
               + ", ".join(f"{tally[v]} {v}" for v in ("identical", "equivalent", "changed")))
     return 1 if bad else 0
