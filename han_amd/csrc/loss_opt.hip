@@ -320,18 +320,17 @@ __global__ __launch_bounds__(256) void classifier_wide_kernel(const ClsArgs a) {
     }
 }
 
+// the tuned kernels: up to MAXC classes 16 rows per block iteration (CM = 4, 8 or 16), beyond that class-per-lane
 template <int NV>
 static void launch_classifier(const ClsArgs &a, bool bwd, int grid, hipStream_t st) {
-    if (a.C <= 4) {
-        if (bwd) classifier_kernel<true, 4, NV><<<grid, 256, 0, st>>>(a);
-        else classifier_kernel<false, 4, NV><<<grid, 256, 0, st>>>(a);
-    } else if (a.C <= 8) {
-        if (bwd) classifier_kernel<true, 8, NV><<<grid, 256, 0, st>>>(a);
-        else classifier_kernel<false, 8, NV><<<grid, 256, 0, st>>>(a);
-    } else {
-        if (bwd) classifier_kernel<true, 16, NV><<<grid, 256, 0, st>>>(a);
-        else classifier_kernel<false, 16, NV><<<grid, 256, 0, st>>>(a);
-    }
+    HAN_DISPATCH_BOOL(BWD, bwd, {
+        switch (a.C <= 4 ? 4 : a.C <= 8 ? 8 : a.C <= MAXC ? 16 : 0) {
+            case 4: classifier_kernel<BWD, 4, NV><<<grid, 256, 0, st>>>(a); break;
+            case 8: classifier_kernel<BWD, 8, NV><<<grid, 256, 0, st>>>(a); break;
+            case 16: classifier_kernel<BWD, 16, NV><<<grid, 256, 0, st>>>(a); break;
+            default: classifier_wide_kernel<BWD, NV><<<grid, 256, 0, st>>>(a); break;
+        }
+    });
 }
 
 __global__ void adam_kernel(float *p, const float *g, float *m, float *v, int64_t n, float lr_t, float b1,
@@ -587,19 +586,57 @@ static int cls_dw_splits(int D, int C) {
     return s < 1 ? 1 : (s > 256 ? 256 : s);
 }
 
-// workspace of the general path, in floats: WmT | bm | loss/acc slabs | dL | dW slabs
-static size_t cls_gen_workspace_floats(int64_t N, int D, int C) {
-    return (size_t)D * C + (size_t)C + (size_t)kClsGenBlocks * 2 + (size_t)N * C +
-           (size_t)cls_dw_splits(D, C) * ((size_t)D * C + C);
+// workspace of the three-kernel paths, offsets in floats: WmT (at 0) | bm | loss/acc slabs | dL | dW slabs; the
+// backward of given dlogits (han_classifier_bwd) has neither slabs of loss / accuracy nor a dL table of its own
+struct ClsGenWs { size_t bm, la, dL, dws, floats; };
+
+static ClsGenWs cls_gen_ws(int64_t N, int D, int C, bool loss) {
+    ClsGenWs w;
+    w.bm = (size_t)D * C;
+    w.la = w.bm + (size_t)C;
+    w.dL = w.la + (loss ? (size_t)kClsGenBlocks * 2 : 0);
+    w.dws = w.dL + (loss ? (size_t)N * C : 0);
+    w.floats = w.dws + (size_t)cls_dw_splits(D, C) * ((size_t)D * C + C);
+    return w;
 }
 
+static bool cls_shape(int D, int C) { return D >= 64 && D % 64 == 0 && C >= 1; }
 static bool cls_tuned(int D, int C) { return (D == 64 || D == 128) && C >= 1 && C <= 64; }
+
+// the head gradients dWc | dbc of a slab row [D*C] | [C]: every head receives the same (1/HC)-scaled gradient
+// (models/gat.py:72 averages them); loss_acc, when given, takes the two slab columns behind them as a third segment
+static HanReduceOut cls_head_grads(float *dWc, float *dbc, float *loss_acc, int D, int C, int HC) {
+    const int dc = D * C;
+    HanReduceOut o = han_reduce_to(dWc, dc + C + (loss_acc ? 2 : 0));
+    o.nseg = loss_acc ? 3 : 2;
+    o.ptr[1] = dbc; o.ptr[2] = loss_acc;
+    o.seg_end[0] = dc; o.seg_end[1] = dc + C;
+    o.scale[0] = o.scale[1] = 1.f / (float)HC;
+    o.rep[0] = o.rep[1] = HC;
+    o.rep_stride[0] = (int64_t)dc; o.rep_stride[1] = C;
+    return o;
+}
+
+static int launch_cls_mean(const float *Wc, const float *bc, float *ws, const ClsGenWs &w, int D, int C, int HC, hipStream_t st) {
+    cls_mean_kernel<<<han_grid_for((int64_t)D * C, 256, 256), 256, 0, st>>>(Wc, bc, ws, ws + w.bm, D, C, HC);
+    HAN_CHECK_LAUNCH();
+    return 0;
+}
+
+// dWm = Z^T dL per row split, then the head gradients from the slabs
+static int launch_cls_dw(const float *Z, const float *dL, const uint8_t *mask, float *dws, float *dWc, float *dbc,
+                         int64_t N, int D, int C, int HC, hipStream_t st) {
+    const int S = cls_dw_splits(D, C), width = D * C + C;
+    cls_dw_kernel<<<dim3(S, D / 64, (C + 15) / 16), 256, 0, st>>>(Z, dL, mask, dws, N, D, C);
+    HAN_CHECK_LAUNCH();
+    const hipError_t e = han_reduce_slabs(dws, S, width, width, cls_head_grads(dWc, dbc, nullptr, D, C, HC), st);
+    return e != hipSuccess ? (int)e : 0;
+}
 
 }  // namespace
 
-extern "C" size_t han_classifier_workspace(int64_t N, int D, int C, int HC) {
-    (void)HC;
-    if (D >= 64 && D % 64 == 0 && C >= 1 && !cls_tuned(D, C)) return cls_gen_workspace_floats(N, D, C) * sizeof(float);
+extern "C" size_t han_classifier_workspace(int64_t N, int D, int C, int) {
+    if (cls_shape(D, C) && !cls_tuned(D, C)) return cls_gen_ws(N, D, C, true).floats * sizeof(float);
     return (size_t)kClsBlocks * (size_t)(D * C + C + 2) * sizeof(float);
 }
 
@@ -609,115 +646,65 @@ extern "C" int han_classifier_loss(const float *Z, const float *Wc, const float 
                                    int64_t N, int D, int C, int HC, void *stream) {
     if (!Z || !Wc || !bc || !labels || !mask || !logits || !loss_acc || !workspace || N < 0 || HC <= 0)
         return HAN_E_BADARG;
-    if (D < 64 || D % 64 != 0 || C < 1) return HAN_E_UNSUPPORTED;
+    if (!cls_shape(D, C)) return HAN_E_UNSUPPORTED;
     const bool bwd = dZ != nullptr;
     if (bwd && (!dWc || !dbc)) return HAN_E_BADARG;
     if (workspace_bytes < han_classifier_workspace(N, D, C, HC)) return HAN_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
+    float *ws = (float *)workspace;
     if (!cls_tuned(D, C)) {       // any embedding width / class count: the three-kernel path
-        float *ws = (float *)workspace;
+        const ClsGenWs w = cls_gen_ws(N, D, C, true);
         ClsGenArgs g;
-        float *WmT = ws, *bm = WmT + (size_t)D * C, *la = bm + C, *dL = la + (size_t)kClsGenBlocks * 2,
-              *dws = dL + (size_t)N * C;
-        g.Z = Z; g.WmT = WmT; g.bm = bm; g.labels = labels; g.mask = mask; g.row_weight = row_weight;
-        g.logits = logits; g.dZ = dZ; g.dL = dL; g.slab = la; g.N = N; g.D = D; g.C = C;
-        cls_mean_kernel<<<han_grid_for((int64_t)D * C, 256, 256), 256, 0, st>>>(Wc, bc, WmT, bm, D, C, HC);
-        HAN_CHECK_LAUNCH();
+        g.Z = Z; g.WmT = ws; g.bm = ws + w.bm; g.labels = labels; g.mask = mask; g.row_weight = row_weight;
+        g.logits = logits; g.dZ = dZ; g.dL = ws + w.dL; g.slab = ws + w.la; g.N = N; g.D = D; g.C = C;
+        const int rc = launch_cls_mean(Wc, bc, ws, w, D, C, HC, st);
+        if (rc != 0) return rc;
         const int grid = han_grid_for(N > 0 ? N : 1, 4, kClsGenBlocks);
-#define HAN_CLS_GEN(NVV)                                                   \
-    if (bwd) cls_gen_kernel<true, NVV><<<grid, 256, 0, st>>>(g);           \
-    else cls_gen_kernel<false, NVV><<<grid, 256, 0, st>>>(g);
-        if (D <= 256) { HAN_CLS_GEN(4) } else if (D <= 512) { HAN_CLS_GEN(8) } else if (D <= 1024) { HAN_CLS_GEN(16) } else { HAN_CLS_GEN(0) }
-#undef HAN_CLS_GEN
+        HAN_DISPATCH_BOOL(BWD, bwd, {      // NV: registers holding the row, 0 beyond 1024 columns
+            switch (D <= 256 ? 4 : D <= 512 ? 8 : D <= 1024 ? 16 : 0) {
+                case 4: cls_gen_kernel<BWD, 4><<<grid, 256, 0, st>>>(g); break;
+                case 8: cls_gen_kernel<BWD, 8><<<grid, 256, 0, st>>>(g); break;
+                case 16: cls_gen_kernel<BWD, 16><<<grid, 256, 0, st>>>(g); break;
+                default: cls_gen_kernel<BWD, 0><<<grid, 256, 0, st>>>(g); break;
+            }
+        });
         HAN_CHECK_LAUNCH();
-        hipError_t e = han_reduce_slabs(la, grid, 2, 2, han_reduce_to(loss_acc, 2), st);
+        const hipError_t e = han_reduce_slabs(g.slab, grid, 2, 2, han_reduce_to(loss_acc, 2), st);
         if (e != hipSuccess) return (int)e;
-        if (bwd) {
-            const int S = cls_dw_splits(D, C);
-            cls_dw_kernel<<<dim3(S, D / 64, (C + 15) / 16), 256, 0, st>>>(Z, dL, mask, dws, N, D, C);
-            HAN_CHECK_LAUNCH();
-            const int width = D * C + C;
-            HanReduceOut o = han_reduce_to(dWc, width);
-            o.nseg = 2;
-            o.ptr[1] = dbc;
-            o.seg_end[0] = D * C; o.seg_end[1] = width;
-            o.scale[0] = o.scale[1] = 1.f / (float)HC;
-            o.rep[0] = o.rep[1] = HC;
-            o.rep_stride[0] = (int64_t)D * C; o.rep_stride[1] = C;
-            e = han_reduce_slabs(dws, S, width, width, o, st);
-            if (e != hipSuccess) return (int)e;
-        }
-        return 0;
+        return bwd ? launch_cls_dw(Z, g.dL, mask, ws + w.dws, dWc, dbc, N, D, C, HC, st) : 0;
     }
     ClsArgs a;
     a.Z = Z; a.Wc = Wc; a.bc = bc; a.labels = labels; a.mask = mask; a.row_weight = row_weight;
-    a.logits = logits; a.dZ = dZ; a.slab = (float *)workspace; a.N = N; a.C = C; a.HC = HC;
-    int grid = han_grid_for(N > 0 ? N : 1, 16, kClsBlocks);
-    if (C > MAXC) {        // class-per-lane kernel, one wave per row
-        grid = han_grid_for(N > 0 ? N : 1, 4, kClsBlocks);
-        if (D == 128) {
-            if (bwd) classifier_wide_kernel<true, 2><<<grid, 256, 0, st>>>(a);
-            else classifier_wide_kernel<false, 2><<<grid, 256, 0, st>>>(a);
-        } else {
-            if (bwd) classifier_wide_kernel<true, 1><<<grid, 256, 0, st>>>(a);
-            else classifier_wide_kernel<false, 1><<<grid, 256, 0, st>>>(a);
-        }
-    } else if (D == 128) launch_classifier<2>(a, bwd, grid, st);
+    a.logits = logits; a.dZ = dZ; a.slab = ws; a.N = N; a.C = C; a.HC = HC;
+    const int grid = han_grid_for(N > 0 ? N : 1, C > MAXC ? 4 : 16, kClsBlocks);      // class-per-lane: one wave per row
+    if (D == 128) launch_classifier<2>(a, bwd, grid, st);
     else launch_classifier<1>(a, bwd, grid, st);
     HAN_CHECK_LAUNCH();
+    // one second-stage launch: the head gradients and loss / accuracy (the last two slab columns)
     const int width = D * C + C + 2;
-    // one second-stage launch: the head gradients (every head receives the same (1/HC)-scaled gradient,
-    // models/gat.py:72 averages them) and loss / accuracy (the last two slab columns)
-    const float *slab = (const float *)workspace;
-    if (bwd) {
-        HanReduceOut o = han_reduce_to(dWc, width);
-        o.nseg = 3;
-        o.ptr[1] = dbc; o.ptr[2] = loss_acc;
-        o.seg_end[0] = D * C; o.seg_end[1] = D * C + C; o.seg_end[2] = width;
-        o.scale[0] = o.scale[1] = 1.f / (float)HC;
-        o.rep[0] = o.rep[1] = HC;
-        o.rep_stride[0] = (int64_t)D * C; o.rep_stride[1] = C;
-        hipError_t e = han_reduce_slabs(slab, grid, width, width, o, st);
-        if (e != hipSuccess) return (int)e;
-    } else {
-        hipError_t e = han_reduce_slabs(slab + D * C + C, grid, width, 2, han_reduce_to(loss_acc, 2), st);
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
+    const hipError_t e = bwd ? han_reduce_slabs(ws, grid, width, width, cls_head_grads(dWc, dbc, loss_acc, D, C, HC), st)
+                             : han_reduce_slabs(ws + D * C + C, grid, width, 2, han_reduce_to(loss_acc, 2), st);
+    return e != hipSuccess ? (int)e : 0;
 }
 
-extern "C" size_t han_classifier_bwd_workspace(int64_t N, int D, int C, int HC) {
-    (void)N; (void)HC;
-    if (D < 64 || D % 64 != 0 || C < 1) return 0;
-    return ((size_t)D * C + (size_t)C + (size_t)cls_dw_splits(D, C) * ((size_t)D * C + C)) * sizeof(float);
+extern "C" size_t han_classifier_bwd_workspace(int64_t N, int D, int C, int) {
+    return cls_shape(D, C) ? cls_gen_ws(N, D, C, false).floats * sizeof(float) : 0;
 }
 
 extern "C" int han_classifier_bwd(const float *Z, const float *Wc, const float *bc, const float *dlogits, float *dZ,
                                   float *dWc, float *dbc, void *workspace, size_t workspace_bytes, int64_t N, int D,
                                   int C, int HC, void *stream) {
     if (!Z || !Wc || !bc || !dlogits || !dZ || !dWc || !dbc || !workspace || N < 0 || HC <= 0) return HAN_E_BADARG;
-    if (D < 64 || D % 64 != 0 || C < 1) return HAN_E_UNSUPPORTED;
-    if (workspace_bytes < han_classifier_bwd_workspace(N, D, C, HC)) return HAN_E_WORKSPACE;
+    if (!cls_shape(D, C)) return HAN_E_UNSUPPORTED;
+    const ClsGenWs w = cls_gen_ws(N, D, C, false);
+    if (workspace_bytes < w.floats * sizeof(float)) return HAN_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    float *WmT = (float *)workspace, *bm = WmT + (size_t)D * C, *dws = bm + C;
-    cls_mean_kernel<<<han_grid_for((int64_t)D * C, 256, 256), 256, 0, st>>>(Wc, bc, WmT, bm, D, C, HC);
+    float *ws = (float *)workspace;
+    const int rc = launch_cls_mean(Wc, bc, ws, w, D, C, HC, st);
+    if (rc != 0) return rc;
+    cls_dz_kernel<<<han_grid_for(N > 0 ? N : 1, 4, kClsGenBlocks), 256, 0, st>>>(dlogits, ws, dZ, N, D, C);
     HAN_CHECK_LAUNCH();
-    cls_dz_kernel<<<han_grid_for(N > 0 ? N : 1, 4, kClsGenBlocks), 256, 0, st>>>(dlogits, WmT, dZ, N, D, C);
-    HAN_CHECK_LAUNCH();
-    const int S = cls_dw_splits(D, C);
-    cls_dw_kernel<<<dim3(S, D / 64, (C + 15) / 16), 256, 0, st>>>(Z, dlogits, nullptr, dws, N, D, C);
-    HAN_CHECK_LAUNCH();
-    const int width = D * C + C;
-    HanReduceOut o = han_reduce_to(dWc, width);
-    o.nseg = 2;
-    o.ptr[1] = dbc;
-    o.seg_end[0] = D * C; o.seg_end[1] = width;
-    o.scale[0] = o.scale[1] = 1.f / (float)HC;
-    o.rep[0] = o.rep[1] = HC;
-    o.rep_stride[0] = (int64_t)D * C; o.rep_stride[1] = C;
-    hipError_t e = han_reduce_slabs(dws, S, width, width, o, st);
-    if (e != hipSuccess) return (int)e;
-    return 0;
+    return launch_cls_dw(Z, dlogits, nullptr, ws + w.dws, dWc, dbc, N, D, C, HC, st);
 }
 
 extern "C" int han_adam_step(float *param, const float *grad, float *m, float *v, int64_t n, float lr_t,

@@ -1237,17 +1237,6 @@ __global__ __launch_bounds__(256, 4) void project_bwd_blk_kernel(const ProjBwdBl
 
 constexpr int kBwdMT = 2;   // project_bwd: 128 f rows per block
 
-void bwd_geometry(int64_t N, int F, int *ftiles, int64_t *rows_per_chunk, int64_t *nchunks) {
-    *ftiles = (F + 64 * kBwdMT - 1) / (64 * kBwdMT);
-    int64_t target = 1024 / *ftiles;
-    if (target < 1) target = 1;
-    int64_t rpc = (N + target - 1) / target;
-    rpc = ((rpc + BN - 1) / BN) * BN;
-    if (rpc < BN) rpc = BN;
-    *rows_per_chunk = rpc;
-    *nchunks = N > 0 ? (N + rpc - 1) / rpc : 1;
-}
-
 }  // namespace
 
 // Forward geometry.  Long inputs: 128-row blocks, one block per row tile.  Short inputs
@@ -1256,7 +1245,7 @@ void bwd_geometry(int64_t N, int F, int *ftiles, int64_t *rows_per_chunk, int64_
 static void fwd_geometry(int64_t N, int F, int *mt, int *nsplit, int *f_chunk) {
     *mt = 2; *nsplit = 1; *f_chunk = ((F + BK - 1) / BK) * BK;
     const int64_t tiles128 = (N + 127) / 128;
-    if (tiles128 >= 256 || F < 4 * BK) return;
+    if (tiles128 >= 256 || F < 4 * BK || N <= 0) return;      // (no rows: nothing to split, and no tile count to divide by)
     *mt = 1;
     const int64_t tiles64 = (N + 63) / 64;
     int64_t want = (512 + tiles64 - 1) / tiles64;
@@ -1268,46 +1257,115 @@ static void fwd_geometry(int64_t N, int F, int *mt, int *nsplit, int *f_chunk) {
     *nsplit = (F + chunk - 1) / chunk;
 }
 
+// dW geometry: blocks of 64 * kBwdMT features, the rows cut into chunks so that ~1024 blocks are in flight
+static void bwd_geometry(int64_t N, int F, int *ftiles, int64_t *rows_per_chunk, int64_t *nchunks) {
+    *ftiles = (F + 64 * kBwdMT - 1) / (64 * kBwdMT);
+    int64_t target = 1024 / *ftiles;
+    if (target < 1) target = 1;
+    int64_t rpc = (N + target - 1) / target;
+    rpc = ((rpc + BN - 1) / BN) * BN;
+    if (rpc < BN) rpc = BN;
+    *rows_per_chunk = rpc;
+    *nchunks = N > 0 ? (N + rpc - 1) / rpc : 1;
+}
+
 // bytes of the pre-split W image of P meta-paths (project_wimage_kernel)
 static size_t wimage_bytes(int F, int P) { return (size_t)((F + 31) / 32) * (size_t)P * B6_WTILE; }
-// shapes the bf16 x 6 matrix-pipe kernels may run on (whole-F blocks of 128 rows)
-static bool b6_shape(int64_t N, int nsplit) { return nsplit == 1 && N >= 64 * 256; }
 
-// the bf16 x 6 forward of one meta-path: blocks of 8 waves, of 4 under HAN_FLAG_K1_4WAVE
-template <bool DROP, bool KEEP>
-static void launch_fwd_b6(const ProjFwdArgs &a, int flags, hipStream_t st) {
-    const dim3 g6((unsigned)((a.N + B6_ROWS - 1) / B6_ROWS));
-    if (a.x_bf16) {
-        if (flags & HAN_FLAG_K1_4WAVE) project_fwd_b6_kernel<DROP, true, KEEP, 4><<<g6, 256, 0, st>>>(a);
-        else project_fwd_b6_kernel<DROP, true, KEEP, 8><<<g6, 512, 0, st>>>(a);
-    } else if (flags & HAN_FLAG_K1_4WAVE) {
-        project_fwd_b6_kernel<DROP, false, KEEP, 4><<<g6, 256, 0, st>>>(a);
-    } else {
-        project_fwd_b6_kernel<DROP, false, KEEP, 8><<<g6, 512, 0, st>>>(a);
-    }
+// what the shape alone decides, for every entry point
+struct K1Plan {
+    int mt, nsplit, f_chunk;    // fwd_geometry
+    bool pipe_shape;            // whole-F blocks of 128 rows: the shapes the bf16 x 6 matrix-pipe kernels may run on
+    bool keep_table;            // the training forward writes, and dW reads, the keep table
+    size_t fwd_bytes;           // forward workspace: the split-F partial tiles (one meta-path at a time), or the W images of P meta-paths
+};
+
+static K1Plan k1_plan(int64_t N, int F, int64_t ldx, int K, int FP, int P) {
+    K1Plan p;
+    fwd_geometry(N, F, &p.mt, &p.nsplit, &p.f_chunk);
+    p.pipe_shape = p.nsplit == 1 && N >= 64 * 256;
+    // The reference head shape on the matrix-pipe forward.  The row bound is not pipe_shape's: below 256 row tiles of
+    // 128 fwd_geometry splits every F >= 4 BK, so pipe_shape holds from 64 * 256 rows for narrow inputs only and for
+    // EVERY F from 128 * 256.  The table takes the second bound, so that han_project_keep_bytes() (han_hip.h: N >= 32768)
+    // needs no geometry and keep_table implies pipe_shape; narrow inputs in between run without a table (dW redraws).
+    p.keep_table = F > 0 && K == 8 && FP == 8 && F % 8 == 0 && ldx % 4 == 0 && N >= 128 * 256;
+    p.fwd_bytes = p.nsplit > 1 ? (size_t)p.nsplit * (size_t)N * HAN_D * sizeof(float)
+                               : p.pipe_shape ? wimage_bytes(F, P > 0 ? P : 1) : 0;
+    return p;
+}
+
+// 16-byte fp32 / 8-byte bf16 X loads (the scalar path costs 1.7x in dW at SYN-10M: 14.3 vs 8.4 ms per launch)
+static bool x_vec(const void *X, int64_t ldx, int F, bool x_bf16) {
+    return (F % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)X & (x_bf16 ? 7 : 15)) == 0);
+}
+
+static bool k1_dtype(int code) { return code == HAN_DTYPE_F32 || code == HAN_DTYPE_BF16; }
+
+// bf16 x 6 matrix-pipe kernel (fp32-class accuracy, see project_fwd_b6_kernel) for one meta-path: whole-F blocks
+// of 128 rows with 16-byte X loads; with dropout it is built for the reference head shape (8 x 8).
+// Used for the training forward (measured at SYN-1M in one process: 0.77 ms against 0.96 ms for the
+// exact-fp32 kernel); without dropout both take the same time (0.48 / 0.50 ms: staging-latency bound), so
+// the eval forward stays on the exact-fp32 pipe unless HAN_FLAG_K1_MATRIX_PIPE asks for this kernel.  (A
+// wave-local variant -- no LDS staging of X, no barrier per K-step, W chunks of 128 k in LDS -- measured the
+// same: 0.49 / 0.80 ms against 0.46 / 0.78 ms for this one, eval / training, kernel_bench.py k1.)
+// bf16 features are their own high term (no split, three products instead of six): there the matrix-pipe
+// kernel is also the faster eval forward
+static bool use_b6(const K1Plan &p, bool vec, bool x_bf16, float in_drop, int K, int FP, int flags) {
+    const bool want = (in_drop > 0.f || x_bf16) ? !(flags & HAN_FLAG_K1_EXACT_PIPE) : (flags & HAN_FLAG_K1_MATRIX_PIPE) != 0;
+    return vec && p.pipe_shape && (in_drop == 0.f || (K == 8 && FP == 8)) && want;
+}
+
+// the fused eval forward of han_project_fwd_multi: no dropout, at least one pair of meta-paths, the matrix-pipe
+// shape; HAN_FLAG_K1_MATRIX_PIPE is not needed (and not looked at), HAN_FLAG_K1_EXACT_PIPE keeps it off
+static bool use_fused(const K1Plan &p, bool vec, int P, float in_drop, float fts_drop, int flags) {
+    return in_drop == 0.f && fts_drop == 0.f && P >= 2 && vec && p.pipe_shape && !(flags & HAN_FLAG_K1_EXACT_PIPE);
+}
+
+// the parameter, output and keep-table pointers of one meta-path
+struct K1Path { const float *W, *a1, *a2, *b1, *b2; void *H; float *f1, *f2; uint8_t *keep; };
+
+// meta-path p of the contiguous (P, ...) tensors `all`; hb / kb: bytes of one H table / keep table (0: none)
+static K1Path path_of(const K1Path &all, size_t p, int64_t N, int F, int K, size_t hb, size_t kb) {
+    return {all.W + p * F * HAN_D, all.a1 + p * HAN_D, all.a2 + p * HAN_D, all.b1 + p * K, all.b2 + p * K,
+            (char *)all.H + p * hb, all.f1 + p * N * K, all.f2 + p * N * K, (all.keep && kb) ? all.keep + p * kb : nullptr};
+}
+
+// W of P meta-paths is split into its three bf16 terms ONCE, into the LDS-ready image every block copies per K-step
+static int launch_wimage(const float *W, void *workspace, size_t workspace_bytes, int F, int P, hipStream_t st) {
+    if (!workspace || workspace_bytes < wimage_bytes(F, P)) return HAN_E_WORKSPACE;
+    const int ktiles = (F + 31) / 32;
+    project_wimage_kernel<<<(int)(((int64_t)ktiles * 512 * P + 255) / 256), 256, 0, st>>>(W, (unsigned char *)workspace, F, ktiles, P);
+    HAN_CHECK_LAUNCH();
+    return 0;
+}
+
+// f1 / f2 from the stored rows.  The lane map of the scores follows the head width for both storage types (a bf16
+// table with F' != 8 through the 8 x 8 instantiation wrote f1 / f2 out of bounds for K < 8 and a wrong layout for K = 16)
+static int launch_scores(const K1Path &q, int64_t N, int FP, bool h_bf16, hipStream_t st) {
+    const ScoreArgs s = {q.H, q.a1, q.a2, q.b1, q.b2, q.f1, q.f2, N};
+    const int sgrid = han_grid_for(N, 16, 256 * 8);
+    HAN_DISPATCH_FP_BF(FP, h_bf16, project_scores_kernel<FPC, BF><<<sgrid, 256, 0, st>>>(s));
+    HAN_CHECK_LAUNCH();
+    return 0;
+}
+
+// the second stage of both dW kernels: the nch slabs of the workspace summed into dW in a fixed order
+static int reduce_dw(const void *workspace, int64_t nch, int F, float *dW, hipStream_t st) {
+    const int width = F * HAN_D;
+    const hipError_t e = han_reduce_slabs((const float *)workspace, (int)nch, width, width, han_reduce_to(dW, width), st);
+    return e != hipSuccess ? (int)e : 0;
 }
 
 extern "C" size_t han_project_fwd_multi_workspace(int64_t N, int F, int K, int FP, int P) {
-    (void)K; (void)FP;
-    int mt, nsplit, f_chunk;
-    fwd_geometry(N > 0 ? N : 0, F, &mt, &nsplit, &f_chunk);
-    if (nsplit > 1) return (size_t)nsplit * (size_t)N * HAN_D * sizeof(float);      // split-F partial tiles (one meta-path at a time)
-    return b6_shape(N, nsplit) ? wimage_bytes(F, P > 0 ? P : 1) : 0;
+    return k1_plan(N, F, F, K, FP, P).fwd_bytes;
 }
 
 extern "C" size_t han_project_fwd_workspace(int64_t N, int F, int K, int FP) {
-    return han_project_fwd_multi_workspace(N, F, K, FP, 1);
-}
-
-// the shapes for which the training forward writes (and dW reads) the keep table: the reference head shape on the
-// matrix-pipe forward (whole-F blocks of 128 rows, no split-F: at least 256 row tiles)
-static bool keep_table_shape(int64_t N, int F, int64_t ldx, int K, int FP) {
-    return K == 8 && FP == 8 && F % 8 == 0 && ldx % 4 == 0 && N >= 128 * 256;
+    return k1_plan(N, F, F, K, FP, 1).fwd_bytes;
 }
 
 extern "C" size_t han_project_keep_bytes(int64_t N, int F, int64_t ldx, int K, int FP) {
-    if (N <= 0 || F <= 0 || !keep_table_shape(N, F, ldx, K, FP)) return 0;
-    return (size_t)N * (size_t)F + 128;
+    return k1_plan(N, F, ldx, K, FP, 1).keep_table ? (size_t)N * (size_t)F + 128 : 0;
 }
 
 extern "C" int han_project_fwd(const void *X, int x_dtype, int64_t ldx, const float *W, const float *a1,
@@ -1317,87 +1375,52 @@ extern "C" int han_project_fwd(const void *X, int x_dtype, int64_t ldx, const fl
                                const uint64_t *seed_dev, int64_t row_offset, uint8_t *keep, int flags,
                                void *stream) {
     if (N == 0) return 0;   // nothing to do; row pointers of empty tensors may be null
-    if (!X || !W || !a1 || !a2 || !b1 || !b2 || !H || !f1 || !f2 || N < 0 || F <= 0 || ldx < F)
-        return HAN_E_BADARG;
+    if (!X || !W || !a1 || !a2 || !b1 || !b2 || !H || !f1 || !f2 || N < 0 || F <= 0 || ldx < F) return HAN_E_BADARG;
     if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
-    if ((x_dtype != HAN_DTYPE_F32 && x_dtype != HAN_DTYPE_BF16) ||
-        (table_dtype != HAN_DTYPE_F32 && table_dtype != HAN_DTYPE_BF16))
-        return HAN_E_UNSUPPORTED;
+    if (!k1_dtype(x_dtype) || !k1_dtype(table_dtype)) return HAN_E_UNSUPPORTED;
     if (in_drop < 0.f || in_drop >= 1.f || fts_drop < 0.f || fts_drop >= 1.f) return HAN_E_BADARG;
     if ((flags & HAN_FLAG_K1_EXACT_PIPE) && (flags & HAN_FLAG_K1_MATRIX_PIPE)) return HAN_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
+    const K1Plan plan = k1_plan(N, F, ldx, K, FP, 1);
+    const bool split = plan.nsplit > 1, drop = in_drop > 0.f;
+    const K1Path q = {W, a1, a2, b1, b2, H, f1, f2, drop ? keep : nullptr};   // a keep pointer without dropout is ignored
     ProjFwdArgs a;
     a.X = X; a.ldx = ldx; a.W = W; a.H = H; a.N = N; a.F = F;
     a.x_bf16 = x_dtype == HAN_DTYPE_BF16; a.h_bf16 = table_dtype == HAN_DTYPE_BF16;
     han_set_dropout(a, seed, seed_dev, in_drop, a.thr_in, a.inv_keep_in);
     a.thr_fts = han_drop_threshold(fts_drop);
     a.fts_stream = HAN_STREAM_FTS + 4u * (uint32_t)HAN_FLAG_FTS_SLICE_OF(flags);
-    a.row_offset = row_offset;
-    a.keep = in_drop > 0.f ? keep : nullptr;
-    const bool vec = (F % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)X & (a.x_bf16 ? 7 : 15)) == 0);
-    int mt, nsplit;
-    fwd_geometry(N, F, &mt, &nsplit, &a.f_chunk);
-    a.partial = nullptr;
-    a.a1 = a1; a.a2 = a2; a.b1 = b1; a.b2 = b2; a.f1 = f1; a.f2 = f2;      // scores fused into the epilogue ...
-    if (nsplit > 1) {
-        a.f1 = nullptr; a.f2 = nullptr;                                     // ... except on the split-F path
-        if (!workspace || workspace_bytes < han_project_fwd_workspace(N, F, K, FP)) return HAN_E_WORKSPACE;
-        a.partial = (float *)workspace;
-    }
-    // bf16 x 6 matrix-pipe kernel (fp32-class accuracy, see project_fwd_b6_kernel): whole-F blocks of 128
-    // rows with 16-byte X loads; with dropout it is built for the reference head shape (8 x 8).
-    // Used for the training forward (measured at SYN-1M in one process: 0.77 ms against 0.96 ms for the
-    // exact-fp32 kernel); without dropout both take the same time (0.48 / 0.50 ms: staging-latency bound), so
-    // the eval forward stays on the exact-fp32 pipe unless HAN_FLAG_K1_MATRIX_PIPE asks for this kernel.  (A
-    // wave-local variant -- no LDS staging of X, no barrier per K-step, W chunks of 128 k in LDS -- measured the
-    // same: 0.49 / 0.80 ms against 0.46 / 0.78 ms for this one, eval / training, kernel_bench.py k1.)
-    // bf16 features are their own high term (no split, three products instead of six): there the matrix-pipe
-    // kernel is also the faster eval forward
-    const bool b6_want = (in_drop > 0.f || a.x_bf16) ? !(flags & HAN_FLAG_K1_EXACT_PIPE) : (flags & HAN_FLAG_K1_MATRIX_PIPE) != 0;
-    const bool b6 = vec && b6_shape(N, nsplit) && (in_drop == 0.f || (K == 8 && FP == 8)) && b6_want;
-    if (a.keep && !(b6 && keep_table_shape(N, F, ldx, K, FP))) return HAN_E_BADARG;   // no kernel writes a table here
-    a.wimg = nullptr;
+    a.row_offset = row_offset; a.keep = q.keep; a.f_chunk = plan.f_chunk;
+    a.a1 = a1; a.a2 = a2; a.b1 = b1; a.b2 = b2;
+    a.f1 = split ? nullptr : f1; a.f2 = split ? nullptr : f2;      // scores fused into the epilogue, except on the split-F path
+    if (split && (!workspace || workspace_bytes < plan.fwd_bytes)) return HAN_E_WORKSPACE;
+    a.partial = split ? (float *)workspace : nullptr;
+    const bool b6 = use_b6(plan, x_vec(X, ldx, F, a.x_bf16), a.x_bf16, in_drop, K, FP, flags);
+    if (a.keep && !(b6 && plan.keep_table)) return HAN_E_BADARG;   // no kernel writes a table here
+    a.wimg = b6 ? (const unsigned char *)workspace : nullptr;
     if (b6) {
-        // W is split into its three bf16 terms ONCE, into the LDS-ready image every block copies per K-step
-        if (!workspace || workspace_bytes < wimage_bytes(F, 1)) return HAN_E_WORKSPACE;
-        const int ktiles = (F + 31) / 32;
-        project_wimage_kernel<<<(ktiles * 512 + 255) / 256, 256, 0, st>>>(W, (unsigned char *)workspace, F, ktiles, 1);
-        HAN_CHECK_LAUNCH();
-        a.wimg = (const unsigned char *)workspace;
-        if (in_drop > 0.f) {
-            if (a.keep) launch_fwd_b6<true, true>(a, flags, st);
-            else launch_fwd_b6<true, false>(a, flags, st);
-        } else {
-            launch_fwd_b6<false, false>(a, flags, st);
-        }
+        const int rc = launch_wimage(W, workspace, workspace_bytes, F, 1, st);
+        if (rc != 0) return rc;
+        // blocks of 8 waves, of 4 under HAN_FLAG_K1_4WAVE; a table is written only with dropout (KEEP without DROP does not exist)
+        const dim3 g6((unsigned)((N + B6_ROWS - 1) / B6_ROWS));
+        HAN_DISPATCH_BOOL(DROP, drop, HAN_DISPATCH_BOOL(KEEP, a.keep != nullptr, HAN_DISPATCH_BOOL(XBF, a.x_bf16,
+            HAN_DISPATCH_BOOL(W4, (flags & HAN_FLAG_K1_4WAVE) != 0,
+                project_fwd_b6_kernel<DROP, XBF, DROP && KEEP, W4 ? 4 : 8><<<g6, W4 ? 256 : 512, 0, st>>>(a)))));
         HAN_CHECK_LAUNCH();
     } else {
-        const dim3 grid((unsigned)((N + 64 * mt - 1) / (64 * mt)), (unsigned)nsplit);
-        HAN_DISPATCH_FP(FP, {
-            if (mt == 2 && in_drop > 0.f) project_fwd_kernel<FPC, true, 2><<<grid, 256, 0, st>>>(a);
-            else if (mt == 2) project_fwd_kernel<FPC, false, 2><<<grid, 256, 0, st>>>(a);
-            else if (in_drop > 0.f) project_fwd_kernel<FPC, true, 1><<<grid, 256, 0, st>>>(a);
-            else project_fwd_kernel<FPC, false, 1><<<grid, 256, 0, st>>>(a);
-        })
+        const dim3 grid((unsigned)((N + 64 * plan.mt - 1) / (64 * plan.mt)), (unsigned)plan.nsplit);
+        HAN_DISPATCH_FP(FP, HAN_DISPATCH_BOOL(DROP, drop, HAN_DISPATCH_BOOL(MT2, plan.mt == 2,
+            project_fwd_kernel<FPC, DROP, MT2 ? 2 : 1><<<grid, 256, 0, st>>>(a))))
         HAN_CHECK_LAUNCH();
     }
-    if (nsplit > 1) {      // sums the partial tiles, stamps / rounds, and takes the scores from the stored row
+    if (split) {      // sums the partial tiles, stamps / rounds, and takes the scores from the stored row
         const int fgrid = han_grid_for(N, 16, 256 * 8);
-        a.a1 = a1; a.a2 = a2; a.b1 = b1; a.b2 = b2;
-        HAN_DISPATCH_FP_BF(FP, a.h_bf16, project_finish_kernel<FPC, BF><<<fgrid, 256, 0, st>>>(a, nsplit, f1, f2));
+        HAN_DISPATCH_FP_BF(FP, a.h_bf16, project_finish_kernel<FPC, BF><<<fgrid, 256, 0, st>>>(a, plan.nsplit, f1, f2));
         HAN_CHECK_LAUNCH();
         return 0;
     }
-    if (a.f1 && !(b6 && in_drop == 0.f)) return 0;      // f1 / f2 were written by the epilogue
-    ScoreArgs s;
-    s.H = H; s.a1 = a1; s.a2 = a2; s.b1 = b1; s.b2 = b2; s.f1 = f1; s.f2 = f2;
-    s.N = N;
-    const int sgrid = han_grid_for(N, 16, 256 * 8);
-    // the lane map of the scores follows the head width for both storage types (a bf16 table with F' != 8 through the
-    // 8 x 8 instantiation wrote f1 / f2 out of bounds for K < 8 and a wrong layout for K = 16)
-    HAN_DISPATCH_FP_BF(FP, a.h_bf16, project_scores_kernel<FPC, BF><<<sgrid, 256, 0, st>>>(s));
-    HAN_CHECK_LAUNCH();
-    return 0;
+    if (!(b6 && !drop)) return 0;      // f1 / f2 were written by the epilogue; the eval matrix-pipe kernel leaves them to the scores launch
+    return launch_scores(q, N, FP, a.h_bf16, st);
 }
 
 // multi-meta-path eval forward on the fused kernel: groups of 4, then 2 meta-paths per block
@@ -1413,8 +1436,9 @@ static int launch_multi(ProjMultiArgs m, int P, int np_max, hipStream_t st, int 
         const int groups = (P - p) / np;
         const size_t lds = xb + (size_t)3 * np * B6_WBYTES;
         m.p_first = p;
-        const hipError_t e = np == 4 ? han_launch_lds(project_fwd_b6_multi_kernel<XBF, 4, MT>, dim3(tiles, groups), 512, lds, st, m)
-                                     : han_launch_lds(project_fwd_b6_multi_kernel<XBF, 2, MT>, dim3(tiles, groups), 512, lds, st, m);
+        hipError_t e;
+        HAN_DISPATCH_BOOL(NP4, np == 4,
+            e = han_launch_lds(project_fwd_b6_multi_kernel<XBF, NP4 ? 4 : 2, MT>, dim3(tiles, groups), 512, lds, st, m));
         if (e != hipSuccess) return (int)e;
         p += groups * np;
         *done = p;      // meta-paths done; a last odd one is left to the caller
@@ -1432,53 +1456,39 @@ extern "C" int han_project_fwd_multi(const void *X, int x_dtype, int64_t ldx, co
     if (N == 0) return 0;
     if (!X || !W || !a1 || !a2 || !b1 || !b2 || !H || !f1 || !f2 || N < 0 || F <= 0 || ldx < F) return HAN_E_BADARG;
     if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
+    if (!k1_dtype(x_dtype) || !k1_dtype(table_dtype)) return HAN_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
     const bool x_bf16 = x_dtype == HAN_DTYPE_BF16, h_bf16 = table_dtype == HAN_DTYPE_BF16;
-    const size_t hb = (size_t)N * HAN_D * (h_bf16 ? 2 : 4), kb = han_project_keep_bytes(N, F, ldx, K, FP);
-    int mt, nsplit, fch;
-    fwd_geometry(N, F, &mt, &nsplit, &fch);
-    const bool vec = (F % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)X & (x_bf16 ? 7 : 15)) == 0);
+    const K1Plan plan = k1_plan(N, F, ldx, K, FP, P);
+    const size_t hb = (size_t)N * HAN_D * (h_bf16 ? 2 : 4), kb = plan.keep_table ? (size_t)N * (size_t)F + 128 : 0;
+    const K1Path all = {W, a1, a2, b1, b2, H, f1, f2, keep};
     int done = 0;
-    if (in_drop == 0.f && fts_drop == 0.f && P >= 2 && vec && nsplit == 1 && N >= 64 * 256 &&
-        !(flags & HAN_FLAG_K1_EXACT_PIPE) && (x_dtype == HAN_DTYPE_F32 || x_dtype == HAN_DTYPE_BF16) &&
-        (table_dtype == HAN_DTYPE_F32 || h_bf16)) {
-        hipStream_t st = (hipStream_t)stream;
-        if (!workspace || workspace_bytes < wimage_bytes(F, P)) return HAN_E_WORKSPACE;
-        const int ktiles = (F + 31) / 32;
-        project_wimage_kernel<<<(int)(((int64_t)ktiles * 512 * P + 255) / 256), 256, 0, st>>>(W, (unsigned char *)workspace, F, ktiles, P);
-        HAN_CHECK_LAUNCH();
+    if (use_fused(plan, x_vec(X, ldx, F, x_bf16), P, in_drop, fts_drop, flags)) {
+        int rc = launch_wimage(W, workspace, workspace_bytes, F, P, st);
+        if (rc != 0) return rc;
         ProjMultiArgs m;
         m.wimg = (const unsigned char *)workspace; m.P = P;
         m.X = X; m.ldx = ldx; m.W = W; m.H = H; m.h_bf16 = h_bf16; m.N = N; m.F = F; m.p_first = 0;
         m.a1 = a1; m.a2 = a2; m.b1 = b1; m.b2 = b2; m.f1 = f1; m.f2 = f2; m.K = K; m.fuse_scores = FP == 8;
         const int np_max = (flags & HAN_FLAG_K1_PAIRS) ? 2 : 4;
-        const int rc = x_bf16 ? launch_multi<true>(m, P, np_max, st, &done) : launch_multi<false>(m, P, np_max, st, &done);
+        HAN_DISPATCH_BOOL(XBF, x_bf16, rc = launch_multi<XBF>(m, P, np_max, st, &done));
         if (rc != 0) return rc;
-        if (FP != 8) {                               // other head widths: scores from the stored rows
-            for (int p = 0; p < done; ++p) {
-                ScoreArgs s;
-                s.H = (const char *)H + (size_t)p * hb; s.a1 = a1 + (size_t)p * HAN_D; s.a2 = a2 + (size_t)p * HAN_D;
-                s.b1 = b1 + (size_t)p * K; s.b2 = b2 + (size_t)p * K;
-                s.f1 = f1 + (size_t)p * N * K; s.f2 = f2 + (size_t)p * N * K; s.N = N;
-                const int sgrid = han_grid_for(N, 16, 256 * 8);
-                HAN_DISPATCH_FP_BF(FP, h_bf16, project_scores_kernel<FPC, BF><<<sgrid, 256, 0, st>>>(s));
-                HAN_CHECK_LAUNCH();
-            }
+        for (int p = 0; p < done && !m.fuse_scores; ++p) {      // other head widths: scores from the stored rows
+            rc = launch_scores(path_of(all, p, N, F, K, hb, kb), N, FP, h_bf16, st);
+            if (rc != 0) return rc;
         }
     }
     for (int p = done; p < P; ++p) {                 // everything else: one meta-path at a time
-        const int rc = han_project_fwd(X, x_dtype, ldx, W + (size_t)p * F * HAN_D, a1 + (size_t)p * HAN_D,
-                                       a2 + (size_t)p * HAN_D, b1 + (size_t)p * K, b2 + (size_t)p * K,
-                                       (char *)H + (size_t)p * hb, table_dtype, f1 + (size_t)p * N * K,
-                                       f2 + (size_t)p * N * K, workspace, workspace_bytes, N, F, K, FP, in_drop,
-                                       fts_drop, seeds ? seeds[p] : 0, seed_dev, row_offset,
-                                       (keep && kb) ? keep + (size_t)p * kb : nullptr, flags, stream);
+        const K1Path q = path_of(all, p, N, F, K, hb, kb);
+        const int rc = han_project_fwd(X, x_dtype, ldx, q.W, q.a1, q.a2, q.b1, q.b2, q.H, table_dtype, q.f1, q.f2,
+                                       workspace, workspace_bytes, N, F, K, FP, in_drop, fts_drop,
+                                       seeds ? seeds[p] : 0, seed_dev, row_offset, q.keep, flags, stream);
         if (rc != 0) return rc;
     }
     return 0;
 }
 
-extern "C" size_t han_project_bwd_workspace(int64_t N, int F, int K, int FP) {
-    (void)K; (void)FP;
+extern "C" size_t han_project_bwd_workspace(int64_t N, int F, int, int) {
     int ftiles; int64_t rpc, nch;
     bwd_geometry(N, F, &ftiles, &rpc, &nch);
     return (size_t)nch * (size_t)F * HAN_D * sizeof(float);
@@ -1490,47 +1500,37 @@ extern "C" int han_project_bwd(const void *X, int x_dtype, int64_t ldx, const fl
                                void *stream) {
     if (!X || !dH || !dW || !workspace || N < 0 || F <= 0 || ldx < F) return HAN_E_BADARG;
     if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
-    if (x_dtype != HAN_DTYPE_F32 && x_dtype != HAN_DTYPE_BF16) return HAN_E_UNSUPPORTED;
+    if (!k1_dtype(x_dtype)) return HAN_E_UNSUPPORTED;
     if (in_drop < 0.f || in_drop >= 1.f) return HAN_E_BADARG;
     if (workspace_bytes < han_project_bwd_workspace(N, F, K, FP)) return HAN_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     int ftiles; int64_t rpc, nch;
     bwd_geometry(N, F, &ftiles, &rpc, &nch);
-    const bool x_bf16 = x_dtype == HAN_DTYPE_BF16;
-    // 16-byte fp32 / 8-byte bf16 X loads (the scalar path costs 1.7x at SYN-10M: 14.3 vs 8.4 ms per launch)
-    const bool vec = (F % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)X & (x_bf16 ? 7 : 15)) == 0);
-    if (keep && in_drop > 0.f && !(vec && keep_table_shape(N, F, ldx, K, FP) && ((uintptr_t)keep & 7) == 0))
+    const bool x_bf16 = x_dtype == HAN_DTYPE_BF16, drop = in_drop > 0.f;
+    if (!drop) keep = nullptr;      // a keep pointer without dropout is ignored
+    if (keep && !(x_vec(X, ldx, F, x_bf16) && k1_plan(N, F, ldx, K, FP, 1).keep_table && ((uintptr_t)keep & 7) == 0))
         return HAN_E_BADARG;      // a table exists only for the shapes han_project_keep_bytes() names
-    const int width = F * HAN_D;
-    if (keep && in_drop > 0.f && N > 0) {
+    if (keep) {
         // the 16-block 4x4x1 kernel: the forward's keep words are the A operand's lane masks (no draw is regenerated)
         ProjBwdBlkArgs b;
         b.X = X; b.ldx = ldx; b.dH = dH; b.keep = keep; b.slab = (float *)workspace; b.N = N; b.F = F;
         b.rows_per_chunk = rpc; b.inv_keep_in = 1.f / (1.f - in_drop);
         const dim3 gb((unsigned)((F + DW_FB - 1) / DW_FB), (unsigned)nch);
-        if (x_bf16) project_bwd_blk_kernel<true, true><<<gb, 256, 0, st>>>(b);
-        else project_bwd_blk_kernel<true, false><<<gb, 256, 0, st>>>(b);
-        HAN_CHECK_LAUNCH();
-        hipError_t e = han_reduce_slabs((const float *)workspace, (int)nch, width, width, han_reduce_to(dW, width), st);
-        return e != hipSuccess ? (int)e : 0;
+        HAN_DISPATCH_BOOL(XBF, x_bf16, project_bwd_blk_kernel<true, XBF><<<gb, 256, 0, st>>>(b));
+    } else {
+        ProjBwdArgs a;
+        a.X = X; a.x_bf16 = x_bf16; a.ldx = ldx; a.dH = dH; a.slab = (float *)workspace; a.N = N; a.F = F;
+        a.rows_per_chunk = rpc;
+        han_set_dropout(a, seed, seed_dev, in_drop, a.thr_in, a.inv_keep_in);
+        a.row_offset = row_offset;
+        const dim3 grid(ftiles, (unsigned)nch);
+        // (dW on the bf16 x 6 matrix pipe was built and measured in round 2 -- coalesced loads + on-chip transpose:
+        // 0.55 ms without / 0.83 ms with dropout against 0.41 / 0.84 ms for this exact-fp32 kernel at SYN-1M --
+        // and not kept: the transposition of both operands through LDS costs what the shorter matrix time saves.)
+        HAN_DISPATCH_FP(FP, HAN_DISPATCH_BOOL(DROP, drop, project_bwd_kernel<FPC, DROP, kBwdMT><<<grid, 256, 0, st>>>(a)))
     }
-    ProjBwdArgs a;
-    a.X = X; a.x_bf16 = x_bf16; a.ldx = ldx; a.dH = dH; a.slab = (float *)workspace; a.N = N; a.F = F;
-    a.rows_per_chunk = rpc;
-    han_set_dropout(a, seed, seed_dev, in_drop, a.thr_in, a.inv_keep_in);
-    a.row_offset = row_offset;
-    dim3 grid(ftiles, (unsigned)nch);
-    // (dW on the bf16 x 6 matrix pipe was built and measured in round 2 -- coalesced loads + on-chip transpose:
-    // 0.55 ms without / 0.83 ms with dropout against 0.41 / 0.84 ms for this exact-fp32 kernel at SYN-1M --
-    // and not kept: the transposition of both operands through LDS costs what the shorter matrix time saves.)
-    HAN_DISPATCH_FP(FP, {
-        if (in_drop > 0.f) project_bwd_kernel<FPC, true, kBwdMT><<<grid, 256, 0, st>>>(a);
-        else project_bwd_kernel<FPC, false, kBwdMT><<<grid, 256, 0, st>>>(a);
-    })
     HAN_CHECK_LAUNCH();
-    hipError_t e = han_reduce_slabs((const float *)workspace, (int)nch, width, width, han_reduce_to(dW, width), st);
-    if (e != hipSuccess) return (int)e;
-    return 0;
+    return reduce_dw(workspace, nch, F, dW, st);
 }
 
 extern "C" int han_project_bwd_input(const float *dH, const float *W, float *dX, int64_t ldo, int64_t N,
@@ -1546,10 +1546,7 @@ extern "C" int han_project_bwd_input(const float *dH, const float *W, float *dX,
     a.row_offset = row_offset;
     hipStream_t st = (hipStream_t)stream;
     const int grid = han_grid_for((N + 15) / 16, 4, 256 * 8);
-    HAN_DISPATCH_FP(FP, {
-        if (in_drop > 0.f) project_bwd_input_kernel<FPC, true><<<grid, 256, 0, st>>>(a);
-        else project_bwd_input_kernel<FPC, false><<<grid, 256, 0, st>>>(a);
-    })
+    HAN_DISPATCH_FP(FP, HAN_DISPATCH_BOOL(DROP, in_drop > 0.f, project_bwd_input_kernel<FPC, DROP><<<grid, 256, 0, st>>>(a)))
     HAN_CHECK_LAUNCH();
     return 0;
 }

@@ -232,6 +232,13 @@ def _dense_arg(graph: CSRGraph, train: bool, tag: str):
     return _lib.HanDense(bits.data_ptr(), bits.shape[1], graph.n_cols, ws.data_ptr(), ws.numel()), (bits, ws)
 
 
+def _ld(t: torch.Tensor, width: int) -> int:
+    """Leading dimension of the (N, width) view t, in elements.  The stride of a dimension of size <= 1 means nothing
+    (torch leaves it arbitrary, and no second row is addressed): such a view passes at least `width`, which is all
+    the library asks of a leading dimension."""
+    return t.stride(0) if t.shape[0] > 1 else max(width, t.stride(0))
+
+
 def _check_heads(K: int, FP: int):
     if K * FP != D or FP not in (4, 8, 16, 32, 64):
         raise NotImplementedError(
@@ -299,7 +306,7 @@ def _project_fwd_setup(X, W, a1, a2, b1, b2, lead, in_drop, fts_drop, table_dtyp
     f2 = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
     nbytes = ws_bytes(N, F, K, FP, *lead)
     ws = _ws(nbytes, dev, "projf") if nbytes else None
-    ldx = X.stride(0) if N > 1 else max(F, X.stride(0))
+    ldx = _ld(X, F)
     keep = None
     if want_keep and in_drop > 0 and not (flags & FLAG_K1_EXACT_PIPE) and X.data_ptr() % 16 == 0:
         kb = _lib.load().han_project_keep_bytes(N, F, ldx, K, FP)
@@ -353,7 +360,7 @@ def project_bwd(X, dH, K, FP, in_drop=0.0, seed=0, row_offset=0, seed_dev=None, 
     dW = _out(out, "out", (F, D), X.device)
     nbytes = lib.han_project_bwd_workspace(N, F, K, FP)
     ws = _ws(nbytes, X.device, "proj")
-    ldx = X.stride(0) if N > 1 else max(F, X.stride(0))
+    ldx = _ld(X, F)
     if keep is not None:
         _chk(keep, "keep", (lib.han_project_keep_bytes(N, F, ldx, K, FP),), dtype=torch.uint8, device=X.device)
     _lib.check(lib.han_project_bwd(
@@ -381,7 +388,7 @@ def project_bwd_input(dH, W, K, FP, out=None, in_drop=0.0, seed=0, row_offset=0,
         if out.stride(1) != 1:
             raise ValueError("out: rows must be contiguous")
     _lib.check(lib.han_project_bwd_input(
-        dH.data_ptr(), W.data_ptr(), out.data_ptr(), out.stride(0) if N > 1 else max(F, out.stride(0)),
+        dH.data_ptr(), W.data_ptr(), out.data_ptr(), _ld(out, F),
         N, F, K, FP, _check_drop(in_drop, "in_drop"), int(seed), _dev_word(seed_dev), int(row_offset), _stream()),
         "han_project_bwd_input")
     return out
@@ -456,7 +463,7 @@ def node_attn_fwd(graph: CSRGraph, H_tab, f1, a2, b2, c, out=None, train=False, 
             _ptr(graph.values), H_tab.data_ptr(), tcode, _ptr(table_gid), f1.data_ptr(),
             f2.data_ptr() if (lean or f2_src is not None) else None,
             a2.data_ptr(), b2.data_ptr(), c.data_ptr(), _ptr(res),
-            out.data_ptr(), out.stride(0) if N > 1 else D,
+            out.data_ptr(), _ld(out, D),
             ptrs[0], ptrs[1], ptrs[2], ptrs[3], N, graph.nnz, K, FP, LEAKY_SLOPE, coef_drop, fts_drop,
             int(seed), _dev_word(seed_dev), int(row_offset), int(activation),
             (FLAG_XCD_ORDER if graph.has_locality() else 0) | (FLAG_LEAN if lean else 0) | (FLAG_K2_DEEP if K2_DEEP else 0)
@@ -536,7 +543,7 @@ def node_attn_bwd_rows(dOut, out, aggp, tsum, f1, lse, c, activation=ACT_ELU, K=
     dc = _out(dc_out, "dc_out", (D,), dev)
     ws = _ws(lib.han_node_attn_bwd_workspace(N, K, FP), dev, "rows")
     _lib.check(lib.han_node_attn_bwd_rows(
-        dOut.data_ptr(), dOut.stride(0) if N > 1 else D, out.data_ptr(), out.stride(0) if N > 1 else D, aggp.data_ptr(),
+        dOut.data_ptr(), _ld(dOut, D), out.data_ptr(), _ld(out, D), aggp.data_ptr(),
         tsum.data_ptr(), f1.data_ptr(), lse.data_ptr(), c.data_ptr(),
         _ptr(res), gs.data_ptr(),
         DTYPE_CODE[table_dtype], df1.data_ptr(), dc.data_ptr(), ws.data_ptr(), ws.numel(), N, K, FP,

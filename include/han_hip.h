@@ -139,9 +139,10 @@ int han_project_fwd(const void *X, int x_dtype, int64_t ldx, const float *W, con
 /* All P meta-paths of ONE shared feature matrix in one call (the reference feeds the same matrix to every
  * meta-path: ex_acm3025.py:86, models/gat.py:39).  W (P,F,D), a1/a2 (P,K,FP), b1/b2 (P,K), H (P,N,D),
  * f1/f2 (P,N,K), all contiguous over p; seeds: HOST array of P seeds (may be NULL when in_drop == fts_drop == 0);
- * keep: NULL or P tables, han_project_keep_bytes() apart.  The eval forward of long inputs (no dropout,
- * N >= 16384, 16-byte aligned rows) runs fused: X is read, split and staged once for 4 (or 2) meta-paths per
- * block; every other case is a loop over han_project_fwd, with the same results.                      */
+ * keep: NULL or P tables, han_project_keep_bytes() apart.  The eval forward of long inputs (no dropout, P >= 2,
+ * N >= 16384 -- N >= 32641 from F = 128, where shorter inputs split F --, 16-byte aligned rows) runs fused: X is
+ * read, split and staged once for 4 (or 2) meta-paths per block; an odd last meta-path and every other case is a
+ * loop over han_project_fwd, with the same results.                                                    */
 int han_project_fwd_multi(const void *X, int x_dtype, int64_t ldx, const float *W, const float *a1,
                           const float *a2, const float *b1, const float *b2, void *H, int table_dtype,
                           float *f1, float *f2, void *workspace, size_t workspace_bytes, int64_t N,

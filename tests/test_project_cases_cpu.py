@@ -104,6 +104,14 @@ def test_forward_path_boundaries(lib):
     assert lib.han_project_keep_bytes(32767, 8, 8, 8, 8) == 0 and lib.han_project_keep_bytes(32768, 8, 8, 8, 8) > 0
 
 
+def test_size_queries_of_an_empty_input(lib):
+    """no rows: no workspace and no table at any width (the split-F geometry divides by the row-tile count, so F >= 128
+    must not reach it); ops.project_fwd asks these before it sees that N == 0"""
+    for f in (5, 127, 128, 1870):
+        assert lib.han_project_fwd_workspace(0, f, 8, 8) == 0 and lib.han_project_fwd_multi_workspace(0, f, 8, 8, 3) == 0
+        assert lib.han_project_keep_bytes(0, f, f, 8, 8) == 0 and lib.han_project_bwd_workspace(0, f, 8, 8) == f * 64 * 4
+
+
 @pytest.mark.parametrize("n,f", [(20000, 1868), (17000, 256), (16500, 200), (16514, 256), (16514, 328),
                                  (16584, 256), (20000, 132)])
 def test_shapes_the_matrix_pipe_tests_used_to_run_are_split(lib, n, f):
