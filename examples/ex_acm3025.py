@@ -4,7 +4,7 @@
 full-graph with early stopping, restore the best weights, report the test metrics and the
 KNN / KMeans scores of ``final_embed``.
 
-    python examples/ex_acm3025.py [--mat ACM3025.mat] [--epochs 200] [--graph]
+    python examples/ex_acm3025.py [--mat ACM3025.mat] [--epochs 200] [--graph] [--eval-device gpu]
 
 Hyper-parameters are the reference's (ex_acm3025.py:16-31): lr 0.005, l2 0.001,
 hid_units [8], n_heads [8, 1], dropout 0.6/0.6, patience 100, mp_att_size 128.
@@ -35,6 +35,9 @@ def main():
                     help="without --mat: a synthetic task WITH structure (communities) instead of the ACM-shaped "
                          "random-label workload, to watch the model learn")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--eval-device", choices=("cpu", "gpu"), default="cpu",
+                    help="where final_embed is scored: cpu = scikit-learn on the host, as the reference; gpu = the "
+                         "evaluation kernels (the embeddings are not copied to the host)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(args.seed)
@@ -89,10 +92,14 @@ def main():
     with torch.no_grad():
         _, final_embed, att = model.inference(xs, nb_classes, n, False, 0.0, 0.0, graphs, [8], [8, 1])
     print("mean meta-path attention:", att.mean(0).tolist())
-    sel = masks[2].bool().cpu().numpy()
-    emb, lab = final_embed.cpu().numpy()[sel], labels.cpu().numpy()[sel]
-    evaluate.my_KNN(emb, lab, seed=args.seed)                     # ex_acm3025.py:288
-    evaluate.my_Kmeans(emb, lab, k=nb_classes, seed=args.seed)    # :289
+    if args.eval_device == "gpu":
+        sel = masks[2].bool()
+        emb, lab, eval_dev = final_embed[sel], labels[sel], dev
+    else:
+        sel = masks[2].bool().cpu().numpy()
+        emb, lab, eval_dev = final_embed.cpu().numpy()[sel], labels.cpu().numpy()[sel], None
+    evaluate.my_KNN(emb, lab, seed=args.seed, device=eval_dev)                     # ex_acm3025.py:288
+    evaluate.my_Kmeans(emb, lab, k=nb_classes, seed=args.seed, device=eval_dev)    # :289
 
 
 if __name__ == "__main__":

@@ -14,7 +14,7 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_uint64, c_void
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhan_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("node_attn.hip", "project.hip", "sem_attn.hip", "loss_opt.hip", "metapath.hip")
+SOURCES = ("node_attn.hip", "project.hip", "sem_attn.hip", "loss_opt.hip", "metapath.hip", "evaluate.hip")
 # node_attn.hip: the dense K2 kernels (node_attn_dense.h) keep 8-16 fp32 MFMA accumulators in a rolled loop; with the
 # default AGPR form hipcc shuffles them through v_accvgpr_read / _mov / _write every iteration (each a wait for the
 # matrix pipe); the VGPR form of the MFMA destination has no such traffic
@@ -89,9 +89,15 @@ SIGNATURES = {
     "han_csr_pathsim": (c_int, [P, P, P, I64, P, P, P]),
     "han_csr_row_topk_count": (c_int, [P, P, I64, I64, c_int, P, P]),
     "han_csr_row_topk_fill": (c_int, [P, P, P, I64, I64, c_int, P, P, P, P]),
+    "han_knn_topk_workspace": (c_size_t, [I64, I64, c_int, c_int]),
+    "han_knn_topk": (c_int, [P, I64, P, I64, P, P, P, c_size_t, I64, I64, c_int, c_int, P]),
+    "han_knn_vote": (c_int, [P, P, P, I64, c_int, I64, P]),
+    "han_contingency": (c_int, [P, P, I64, c_int, c_int, P, P]),
+    "han_kmeans_step_workspace": (c_size_t, [I64, c_int, c_int]),
+    "han_kmeans_step": (c_int, [P, I64, P, P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, P]),
 }
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 _lib = None
 
 

@@ -4,6 +4,11 @@
 the reference (``ex_acm3025.py:279-291``); it returns the scores instead of only
 printing them.
 
+With ``device=`` given, ``my_KNN`` / ``my_Kmeans`` run on the GPU instead (the ``han_knn_topk`` / ``han_knn_vote``
+/ ``han_contingency`` / ``han_kmeans_step`` kernels behind ``knn_classify``, ``f1_scores``, ``nmi_ari`` and
+``kmeans``): the embeddings stay on the device and only the small count tables come back.  The scores are formed
+on the host in float64 from those tables (``f1_from_table``, ``nmi_ari_from_table``: scikit-learn's conventions).
+
 Random streams: the reference draws its shuffles from NumPy's GLOBAL legacy generator
 (``np.random.permutation``, jhyexp.py:33) and lets scikit-learn's KMeans fall back on the
 same global generator (``random_state=None``, jhyexp.py:62).  Here both use ONE
@@ -15,9 +20,13 @@ from __future__ import annotations
 import numpy as np
 
 
-def my_KNN(x, y, k=5, split_list=(0.2, 0.4, 0.6, 0.8), time=10, shuffle=True, seed=None, verbose=True):
+def my_KNN(x, y, k=5, split_list=(0.2, 0.4, 0.6, 0.8), time=10, shuffle=True, seed=None, verbose=True, device=None):
     """jhyexp.py:20-51.  x (n,d) embeddings, y (n,) labels or one-hot (n,c).
-    Returns {split: (macro_f1, micro_f1)} averaged over `time` repetitions."""
+    Returns {split: (macro_f1, micro_f1)} averaged over `time` repetitions.
+    device=None: scikit-learn on the host, as the reference.  With a device: the same permutations from the same
+    RandomState -- hence the same splits --, scored by knn_classify / f1_scores on the GPU."""
+    if device is not None:
+        return _my_knn_device(x, y, k, split_list, time, shuffle, seed, verbose, device)
     from sklearn.metrics import f1_score
     from sklearn.neighbors import KNeighborsClassifier
     rng = np.random.RandomState(seed) if not isinstance(seed, np.random.RandomState) else seed
@@ -44,8 +53,13 @@ def my_KNN(x, y, k=5, split_list=(0.2, 0.4, 0.6, 0.8), time=10, shuffle=True, se
     return out
 
 
-def my_Kmeans(x, y, k=4, time=10, seed=None, verbose=True):
-    """jhyexp.py:54-86.  Returns (NMI, ARI) averaged over `time` fits."""
+def my_Kmeans(x, y, k=4, time=10, seed=None, verbose=True, device=None):
+    """jhyexp.py:54-86.  Returns (NMI, ARI) averaged over `time` fits.
+    device=None: scikit-learn on the host, as the reference.  With a device: `time` fits of kmeans() (k-means++
+    seeding, Lloyd on the GPU) drawing from ONE RandomState, scored by nmi_ari; the random stream is not
+    scikit-learn's, so the clusterings are equally good, not identical."""
+    if device is not None:
+        return _my_kmeans_device(x, y, k, time, seed, verbose, device)
     from sklearn.cluster import KMeans
     from sklearn.metrics import adjusted_rand_score, normalized_mutual_info_score
     x = np.squeeze(np.array(x))
@@ -59,6 +73,288 @@ def my_Kmeans(x, y, k=4, time=10, seed=None, verbose=True):
         pred = est.fit(x, y).predict(x)                  # re-fitted `time` times (jhyexp.py:67-68)
         nmi.append(normalized_mutual_info_score(y, pred))
         ari.append(adjusted_rand_score(y, pred))
+    res = float(np.mean(nmi)), float(np.mean(ari))
+    if verbose:
+        print("NMI (10 avg): {:.4f} , ARI (10avg): {:.4f}".format(*res))
+    return res
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# The GPU path
+# ----------------------------------------------------------------------------------------------------------------
+KNN_MAX_K = 16          # han_knn_topk
+KMEANS_MAX_K = 64       # han_kmeans_step
+
+
+def _is_tensor(a):
+    return type(a).__module__.startswith("torch") and hasattr(a, "device")
+
+
+def _pick_device(device, *arrays):
+    import torch
+    if device is not None:
+        return torch.device(device)
+    for a in arrays:
+        if _is_tensor(a) and a.is_cuda:
+            return a.device
+    return torch.device("cuda")
+
+
+def _embed(a, device):
+    """An (n, d) fp32 matrix on the device: a GPU tensor is used as it is, anything else is copied once."""
+    import torch
+    t = a if _is_tensor(a) else torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float32)))
+    t = t.to(device=device, dtype=torch.float32)
+    return t if t.stride(-1) == 1 else t.contiguous()
+
+
+def _labels(a, device):
+    """(n,) int32 class ids on the device (one-hot rows are reduced by argmax)."""
+    import torch
+    if not _is_tensor(a):
+        a = np.asarray(a)
+        if a.ndim > 1:
+            a = np.argmax(a, axis=1)
+        a = torch.as_tensor(np.ascontiguousarray(a.astype(np.int32)))
+    elif a.dim() > 1:
+        a = a.argmax(dim=1)
+    return a.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _shape2(a, name):
+    shp = tuple(a.shape)
+    if len(shp) != 2:
+        raise ValueError(f"{name}: expected an (n, d) matrix, got shape {shp}")
+    return shp
+
+
+def knn_classify(x_train, y_train, x_test, k=5, device=None):
+    """KNeighborsClassifier(n_neighbors=k).fit(x_train, y_train).predict(x_test) on the GPU: brute-force neighbours
+    under the total order (distance, train index) and a majority vote with ties to the smallest class id.
+    Returns the (n_test,) int32 predictions as a tensor on the device."""
+    n_train, d = _shape2(x_train, "x_train")
+    n_test, d_test = _shape2(x_test, "x_test")
+    if isinstance(k, bool) or int(k) != k or k < 1 or k > KNN_MAX_K:
+        raise ValueError(f"k = {k!r}: expected an integer in [1, {KNN_MAX_K}]")
+    if k > n_train:
+        raise ValueError(f"k = {k} neighbours of {n_train} train rows")
+    if d != d_test:
+        raise ValueError(f"x_train has width {d}, x_test {d_test}")
+    if tuple(y_train.shape)[0] != n_train:
+        raise ValueError(f"y_train: {tuple(y_train.shape)[0]} labels for {n_train} rows")
+    from . import ops
+    dev = _pick_device(device, x_train, x_test)
+    idx, _ = ops.knn_topk(_embed(x_test, dev), _embed(x_train, dev), int(k))
+    return ops.knn_vote(idx, _labels(y_train, dev))
+
+
+def _table(y_true, y_pred, ca=None, cb=None):
+    from . import ops
+    dev = _pick_device(None, y_true, y_pred)
+    a, b = _labels(y_true, dev), _labels(y_pred, dev)
+    if a.shape != b.shape:
+        raise ValueError(f"{tuple(a.shape)} true labels, {tuple(b.shape)} predictions")
+    if ca is None or cb is None:
+        import torch
+        if a.numel() == 0:
+            raise ValueError("no labels")
+        top = torch.stack([a.max(), b.max()]).tolist()          # one small read
+        ca = top[0] + 1 if ca is None else ca
+        cb = top[1] + 1 if cb is None else cb
+    return ops.contingency(a, b, int(ca), int(cb)).numpy()
+
+
+def f1_from_table(table):
+    """(macro, micro) F1 from a square count table[true, predicted], as sklearn.metrics.f1_score: macro over the
+    labels present in either array, a class without true positives scores 0; micro is the accuracy."""
+    t = np.asarray(table, dtype=np.int64)
+    if t.ndim != 2 or t.shape[0] != t.shape[1]:
+        raise ValueError(f"table: expected a square matrix, got {t.shape}")
+    tp = np.diag(t).astype(np.float64)
+    true_n, pred_n = t.sum(axis=1).astype(np.float64), t.sum(axis=0).astype(np.float64)
+    present = (true_n + pred_n) > 0
+    f1 = 2.0 * tp[present] / (true_n[present] + pred_n[present])
+    total = float(t.sum())
+    return (float(f1.mean()) if f1.size else 0.0), (float(tp.sum() / total) if total else 0.0)
+
+
+def nmi_ari_from_table(table):
+    """(NMI, ARI) from a count table[true, predicted], as sklearn.metrics: NMI with natural logarithms and the
+    arithmetic mean of the entropies (1.0 when both labellings are a single cluster), ARI in its pair-count form."""
+    t = np.asarray(table, dtype=np.int64)
+    t = t[t.sum(axis=1) > 0][:, t.sum(axis=0) > 0]
+    a, b = t.sum(axis=1), t.sum(axis=0)
+    n = int(t.sum())
+    # NMI
+    if a.size <= 1 and b.size <= 1:
+        nmi = 1.0
+    elif a.size == 1 or b.size == 1:
+        nmi = 0.0
+    else:
+        i, j = np.nonzero(t)
+        nij = t[i, j].astype(np.float64)
+        outer = a[i].astype(np.int64) * b[j].astype(np.int64)
+        log_outer = -np.log(outer) + np.log(a.sum()) + np.log(b.sum())
+        terms = (nij / n) * (np.log(nij) - np.log(n)) + (nij / n) * log_outer
+        terms = np.where(np.abs(terms) < np.finfo(np.float64).eps, 0.0, terms)
+        mi = max(float(terms.sum()), 0.0)
+        if abs(mi) < np.finfo(np.float64).eps:
+            nmi = 0.0
+        else:
+            def entropy(c):
+                c = c[c > 0].astype(np.float64)
+                return -float(np.sum((c / c.sum()) * (np.log(c) - np.log(c.sum()))))
+            nmi = float(mi / max(0.5 * (entropy(a) + entropy(b)), np.finfo(np.float64).eps))
+    # ARI: exact integer pair counts
+    cells = [[int(v) for v in row] for row in t]            # Python integers: no overflow at any n
+    ai, bj = [int(v) for v in a], [int(v) for v in b]
+    sum_sq = sum(v * v for row in cells for v in row)
+    fp = sum(v * bj[j] for row in cells for j, v in enumerate(row)) - sum_sq
+    fn = sum(v * ai[i] for i, row in enumerate(cells) for v in row) - sum_sq
+    tp = sum_sq - n
+    tn = n * n - fp - fn - sum_sq
+    if fn == 0 and fp == 0:
+        ari = 1.0
+    else:
+        ari = 2.0 * (tp * tn - fn * fp) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
+    return nmi, float(ari)
+
+
+def f1_scores(y_true, y_pred, n_classes=None):
+    """(macro, micro) F1 of two label vectors (NumPy or GPU tensors): a contingency table on the GPU, the scores
+    from it on the host."""
+    return f1_from_table(_table(y_true, y_pred, n_classes, n_classes) if n_classes is not None else
+                         _square(_table(y_true, y_pred)))
+
+
+def _square(t):
+    c = max(t.shape)
+    out = np.zeros((c, c), dtype=np.int64)
+    out[:t.shape[0], :t.shape[1]] = t
+    return out
+
+
+def nmi_ari(y_true, y_pred):
+    """(NMI, ARI) of two labellings (NumPy or GPU tensors)."""
+    return nmi_ari_from_table(_table(y_true, y_pred))
+
+
+def _kmeanspp(x, k, rs):
+    """k-means++ seeding: k rows of x, the first uniform, each next one drawn with probability proportional to its
+    squared distance to the chosen ones.  The k uniform draws come from the host RandomState; the distances, their
+    running sum and the search for the drawn row are torch ops on the device (no read-back)."""
+    import torch
+    n = x.shape[0]
+    u = torch.as_tensor(rs.random_sample(k), dtype=torch.float64, device=x.device)
+    first = torch.clamp((u[0] * n).long(), max=n - 1)
+    centres = [x[first]]
+    d2 = ((x - centres[0]) ** 2).sum(dim=1, dtype=torch.float64)
+    for j in range(1, k):
+        cum = torch.cumsum(d2, 0)
+        pick = torch.clamp(torch.searchsorted(cum, (u[j] * cum[-1]).reshape(1), right=True)[0], max=n - 1)
+        centres.append(x[pick])
+        d2 = torch.minimum(d2, ((x - centres[-1]) ** 2).sum(dim=1, dtype=torch.float64))
+    return torch.stack(centres).contiguous()
+
+
+def _lloyd(x, init, max_iter, tol_abs):
+    import torch
+    from . import ops
+    centres, prev, history = init, None, []
+    n_iter, converged = 0, False
+    for it in range(1, max_iter + 1):
+        step = ops.kmeans_step(x, centres, prev, want_d2=False)
+        history.append(step["inertia"])
+        shift = ((step["centres"] - centres).double() ** 2).sum().reshape(1)
+        changed, shift = torch.cat([step["changed"].double(), shift]).tolist()      # the one small read of the iteration
+        n_iter, labels = it, step["labels"]
+        if changed == 0:                    # the labels are the assignment to `centres`, which are their means
+            converged = True
+            break
+        prev, centres = labels, step["centres"]
+        if tol_abs > 0 and shift <= tol_abs:
+            break
+    if not converged:                       # the labels of the centres that are returned
+        step = ops.kmeans_step(x, centres, None, want_d2=False)
+        labels = step["labels"]
+        history.append(step["inertia"])
+    hist = torch.cat(history).cpu().numpy()
+    return dict(labels=labels, centers=centres, inertia=float(hist[-1]), n_iter=n_iter, init_centers=init,
+                inertia_history=hist)
+
+
+def kmeans(x, k, init=None, seed=None, n_init=1, max_iter=300, tol=1e-4, device=None):
+    """Lloyd's k-means on the GPU (han_kmeans_step per iteration).  init: an explicit (k, d) array, or None for
+    k-means++ seeding with the uniform draws of np.random.RandomState(seed) (a RandomState may be passed as seed).
+    Stops when no label changed, when the centres moved by sum |dc|^2 <= tol * mean per-column variance of x (not
+    with tol=0), or after max_iter iterations.  Returns dict(labels (n,) int32, centers (k, d), inertia, n_iter,
+    init_centers, inertia_history): tensors on the device, the labels being the assignment to the returned centres;
+    inertia_history[i] is the inertia of the centres that iteration i + 1 started from.  A cluster that loses all its
+    rows keeps its centre (scikit-learn relocates it).  With n_init > 1 the fit of lowest inertia is returned."""
+    n, d = _shape2(x, "x")
+    if isinstance(k, bool) or int(k) != k or k < 1 or k > KMEANS_MAX_K:
+        raise ValueError(f"k = {k!r}: expected an integer in [1, {KMEANS_MAX_K}]")
+    if k > n:
+        raise ValueError(f"k = {k} clusters of {n} rows")
+    if init is not None and tuple(init.shape) != (k, d):
+        raise ValueError(f"init: shape {tuple(init.shape)}, expected {(k, d)}")
+    if n_init < 1 or max_iter < 1 or tol < 0:
+        raise ValueError("n_init >= 1, max_iter >= 1 and tol >= 0 are required")
+    dev = _pick_device(device, x)
+    x = _embed(x, dev)
+    rs = seed if isinstance(seed, np.random.RandomState) else np.random.RandomState(seed)
+    tol_abs = float(tol) * float(x.var(dim=0, unbiased=False).mean()) if tol > 0 else 0.0
+    best = None
+    for _ in range(1 if init is not None else int(n_init)):
+        start = _embed(init, dev).contiguous() if init is not None else _kmeanspp(x, int(k), rs)
+        fit = _lloyd(x, start, int(max_iter), tol_abs)
+        if best is None or fit["inertia"] < best["inertia"]:
+            best = fit
+    return best
+
+
+def _my_knn_device(x, y, k, split_list, time, shuffle, seed, verbose, device):
+    import torch
+    rng = np.random.RandomState(seed) if not isinstance(seed, np.random.RandomState) else seed
+    dev = torch.device(device)
+    x = _embed(x, dev)
+    if x.dim() > 2:
+        x = x.squeeze()
+    y = _labels(y, dev)
+    n_classes = int(y.max()) + 1
+    out = {}
+    for ss in split_list:
+        split = int(x.shape[0] * ss)
+        macro, micro = [], []
+        for _ in range(time):
+            if shuffle:
+                perm = torch.as_tensor(rng.permutation(x.shape[0]), device=dev)
+                x, y = x[perm], y[perm]
+            pred = knn_classify(x[:split], y[:split], x[split:], k, device=dev)
+            f = f1_scores(y[split:], pred, n_classes)
+            macro.append(f[0])
+            micro.append(f[1])
+        out[ss] = (float(np.mean(macro)), float(np.mean(micro)))
+        if verbose:
+            print("KNN({}avg, split:{}, k={}) f1_macro: {:.4f}, f1_micro: {:.4f}".format(
+                time, ss, k, out[ss][0], out[ss][1]))
+    return out
+
+
+def _my_kmeans_device(x, y, k, time, seed, verbose, device):
+    import torch
+    dev = torch.device(device)
+    x = _embed(x, dev)
+    if x.dim() > 2:
+        x = x.squeeze()
+    y = _labels(y, dev)
+    rs = np.random.RandomState(seed) if not isinstance(seed, np.random.RandomState) else seed
+    nmi, ari = [], []
+    for _ in range(time):
+        fit = kmeans(x, k, seed=rs, device=dev)
+        s = nmi_ari(y, fit["labels"])
+        nmi.append(s[0])
+        ari.append(s[1])
     res = float(np.mean(nmi)), float(np.mean(ari))
     if verbose:
         print("NMI (10 avg): {:.4f} , ARI (10avg): {:.4f}".format(*res))

@@ -880,3 +880,109 @@ def csr_row_topk(graph: CSRGraph, k: int, keep_diag: bool = True) -> CSRGraph:
                                              n, k, int(keep_diag), rowptr.data_ptr(), colidx.data_ptr(),
                                              values.data_ptr(), st), "han_csr_row_topk_fill")
     return CSRGraph(rowptr, colidx, graph.n_cols, validate=False, values=values)
+
+
+# ------------------------------------------------- evaluation of the embeddings
+KNN_MAX_K = 16             # neighbours per query of han_knn_topk
+EVAL_MAX_D = 512           # embedding width of han_knn_topk / han_kmeans_step
+KMEANS_MAX_K = 64          # centres of han_kmeans_step
+CONTINGENCY_MAX_CELLS = 4096
+
+
+def _chk_int(v, name, lo, hi=None):
+    if isinstance(v, bool) or not isinstance(v, int) and int(v) != v or v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{name} = {v!r}: expected an integer in [{lo}, {hi if hi is not None else 'inf'}]")
+    return int(v)
+
+
+def _chk_rows(t, name, device=None):
+    """A 2-D fp32 GPU matrix whose rows are contiguous (a row slice or column slice of a larger one is fine);
+    returns its leading dimension in elements."""
+    _chk(t, name, (None, None), device=device, contiguous=False)
+    if t.shape[1] < 1 or t.shape[1] > EVAL_MAX_D:
+        raise ValueError(f"{name}: width {t.shape[1]}, expected 1 .. {EVAL_MAX_D}")
+    if t.shape[0] > 1 and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+        raise ValueError(f"{name}: rows must be contiguous, got strides {t.stride()}")
+    if t.shape[0] <= 1 and t.shape[1] > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name}: rows must be contiguous, got strides {t.stride()}")
+    return int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def knn_topk(queries, train, k: int):
+    """(idx (Nq, k) int32, d2 (Nq, k) fp32): per query row the k nearest train rows by squared Euclidean distance,
+    ascending under the total order (d2, train index) -- equal distances go to the smaller index (han_knn_topk:
+    brute force on the fp32 matrix pipe, the distance matrix is never stored)."""
+    k = _chk_int(k, "k", 1, KNN_MAX_K)
+    ldt = _chk_rows(train, "train")
+    ldq = _chk_rows(queries, "queries", device=train.device)
+    nq, nt, d = queries.shape[0], train.shape[0], train.shape[1]
+    if queries.shape[1] != d:
+        raise ValueError(f"queries have width {queries.shape[1]}, train rows {d}")
+    if k > nt:
+        raise ValueError(f"k = {k} neighbours of {nt} train rows")
+    if nt >= 2 ** 31:
+        raise ValueError("train: at most 2^31 - 1 rows")
+    lib, dev = _lib.load(), train.device
+    idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    d2 = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    if nq:
+        ws = _ws(lib.han_knn_topk_workspace(nq, nt, d, k), dev, "knn")
+        _lib.check(lib.han_knn_topk(queries.data_ptr(), ldq, train.data_ptr(), ldt, idx.data_ptr(), d2.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), nq, nt, d, k, _stream()), "han_knn_topk")
+    return idx, d2
+
+
+def knn_vote(idx, labels_train):
+    """pred (Nq,) int32: the most frequent of labels_train[idx[q, :]], ties to the smallest class id
+    (han_knn_vote; KNeighborsClassifier(weights="uniform").predict)."""
+    _chk(idx, "idx", (None, None), dtype=torch.int32)
+    k = _chk_int(idx.shape[1], "k", 1, KNN_MAX_K)
+    _chk(labels_train, "labels_train", (None,), dtype=torch.int32, device=idx.device)
+    pred = torch.empty(idx.shape[0], dtype=torch.int32, device=idx.device)
+    if idx.shape[0]:
+        _lib.check(_lib.load().han_knn_vote(idx.data_ptr(), labels_train.data_ptr(), pred.data_ptr(), idx.shape[0], k,
+                                            labels_train.shape[0], _stream()), "han_knn_vote")
+    return pred
+
+
+def contingency(a, b, ca: int, cb: int):
+    """The (ca, cb) int64 count table of two int32 label vectors, table[x, y] = #{i: a[i] == x and b[i] == y}, as a
+    HOST tensor (han_contingency; the one copy to the host also carries the kernel's flag word: a label outside
+    [0, ca) / [0, cb) raises ValueError)."""
+    ca, cb = _chk_int(ca, "ca", 1), _chk_int(cb, "cb", 1)
+    if ca * cb > CONTINGENCY_MAX_CELLS:
+        raise ValueError(f"contingency: {ca} x {cb} cells, at most {CONTINGENCY_MAX_CELLS}")
+    _chk(a, "a", (None,), dtype=torch.int32)
+    _chk(b, "b", (a.shape[0],), dtype=torch.int32, device=a.device)
+    table = torch.empty(ca * cb + 1, dtype=torch.int64, device=a.device)
+    _lib.check(_lib.load().han_contingency(_ptr(a) if a.numel() else None, _ptr(b) if b.numel() else None, a.shape[0],
+                                           ca, cb, table.data_ptr(), _stream()), "han_contingency")
+    host = table.cpu()
+    if int(host[-1]) != 0:
+        raise ValueError(f"contingency: a label outside [0, {ca}) x [0, {cb})")
+    return host[:-1].reshape(ca, cb)
+
+
+def kmeans_step(x, centres, prev=None, want_d2=True):
+    """One Lloyd iteration (han_kmeans_step): dict(labels (N,) int32 -- the nearest centre, ties to the smaller
+    index --, d2 (N,) fp32 or None, counts (k,) int64, centres (k, D) fp32 -- the mean of each cluster's rows, a
+    cluster without rows keeps its centre --, inertia (1,) float64, changed (1,) int64 -- rows whose label differs
+    from prev, N when prev is None).  Everything stays on the device."""
+    ldx = _chk_rows(x, "x")
+    n, d = x.shape
+    _chk(centres, "centres", (None, d), device=x.device)
+    k = _chk_int(centres.shape[0], "k", 1, KMEANS_MAX_K)
+    if prev is not None:
+        _chk(prev, "prev", (n,), dtype=torch.int32, device=x.device)
+    lib, dev = _lib.load(), x.device
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    d2 = torch.empty(n, dtype=torch.float32, device=dev) if want_d2 else None
+    counts = torch.empty(k, dtype=torch.int64, device=dev)
+    new = torch.empty((k, d), dtype=torch.float32, device=dev)
+    inertia = torch.empty(1, dtype=torch.float64, device=dev)
+    changed = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = _ws(lib.han_kmeans_step_workspace(n, d, k), dev, "kmeans")
+    _lib.check(lib.han_kmeans_step(x.data_ptr() if n else None, ldx, centres.data_ptr(), _ptr(prev), labels.data_ptr() if n else None,
+                                   _ptr(d2), counts.data_ptr(), new.data_ptr(), inertia.data_ptr(), changed.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), n, d, k, _stream()), "han_kmeans_step")
+    return dict(labels=labels, d2=d2, counts=counts, centres=new, inertia=inertia, changed=changed)

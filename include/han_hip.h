@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HAN_ABI_VERSION 8
+#define HAN_ABI_VERSION 9
 
 #define HAN_E_BADARG   (-1)   /* null pointer, negative size, inconsistent shape.  The forward
                               * entry points return 0 at once for N == 0 (empty tensors may
@@ -455,6 +455,46 @@ int han_csr_row_topk_count(const int64_t *rowptr, const int32_t *colidx, int64_t
 int han_csr_row_topk_fill(const int64_t *rowptr, const int32_t *colidx, const float *values, int64_t n_rows,
                           int64_t k, int keep_diag, const int64_t *out_rowptr, int32_t *out_colidx,
                           float *out_values, void *stream);
+
+/* ---- evaluation of the embeddings (ABI 9) -----------------------------------
+ * The reference scores final_embed on the host with scikit-learn: my_KNN (jhyexp.py:20-51) and my_Kmeans
+ * (jhyexp.py:54-86), called at ex_acm3025.py:288-289.  These entry points are the device side of both.
+ * Embeddings are fp32, row-major, with a leading dimension in elements (>= D); 1 <= D <= 512.  Squared distances
+ * have the form d2 = |q|^2 + |t|^2 - 2 q.t with the q.t term on the exact-fp32 matrix pipe; no pair matrix is ever
+ * stored.  Every result is bitwise the same from run to run (no floating-point atomics; cross-block sums are
+ * slabs added in a fixed order).
+ *
+ * han_knn_topk: KNeighborsClassifier(n_neighbors=k).fit(x[:split]).kneighbors(x[split:]), jhyexp.py:38-41.
+ *   Q (Nq, D) queries, T (Nt, D) train rows, 1 <= k <= 16.  idx (Nq, k) int32 / d2 (Nq, k) fp32: per query the k
+ *   smallest pairs under the total order (d2, train index), ascending -- equal distances go to the smaller index.
+ *   k > Nt: HAN_E_BADARG; k > 16, D > 512 or Nt >= 2^31: HAN_E_UNSUPPORTED; Nq == 0 returns 0.  workspace:
+ *   han_knn_topk_workspace() bytes (the row norms; with few queries the train set is split over workgroups and the
+ *   partial lists are merged from it).
+ * han_knn_vote: KNeighborsClassifier(weights="uniform").predict, jhyexp.py:41: pred[q] = the most frequent of
+ *   labels_train[idx[q, :]], ties to the smallest class id (k^2 compares in registers, no table sized by the class
+ *   count).  An idx entry outside [0, Nt) is skipped.
+ * han_contingency: the count table behind f1_score (jhyexp.py:43-44) and normalized_mutual_info_score /
+ *   adjusted_rand_score (jhyexp.py:70-71): table[x * Cb + y] = number of i with a[i] == x and b[i] == y, int64,
+ *   Ca * Cb <= 4096.  `table` holds Ca * Cb + 1 words and is cleared on the stream; the LAST word is a flag: non-zero
+ *   when some label was outside [0, Ca) / [0, Cb) (such elements are not counted) -- the caller reads it with the
+ *   table and treats it as HAN_E_BADARG.
+ * han_kmeans_step: one Lloyd iteration of KMeans(n_clusters=k).fit, jhyexp.py:62-68.  X (N, D), C (k, D) contiguous,
+ *   1 <= k <= 64; prev (N) int32 or NULL.  labels (N) int32: the nearest centre, ties to the smaller centre index;
+ *   d2 (N) fp32 or NULL: that distance; counts (k) int64; new_centres (k, D) fp32: the mean of each cluster's rows
+ *   (summed in double in a fixed order) -- a cluster without rows keeps its centre and has count 0 (scikit-learn
+ *   relocates such a centre); *inertia (double): the sum of the fp32 d2, added in double in a fixed order;
+ *   *changed (int64): rows whose label differs from prev (N when prev is NULL).  counts / changed are cleared on
+ *   the stream.  workspace: han_kmeans_step_workspace() bytes.                                              */
+size_t han_knn_topk_workspace(int64_t Nq, int64_t Nt, int D, int k);
+int han_knn_topk(const float *Q, int64_t ldq, const float *T, int64_t ldt, int32_t *idx, float *d2,
+                 void *workspace, size_t workspace_bytes, int64_t Nq, int64_t Nt, int D, int k, void *stream);
+int han_knn_vote(const int32_t *idx, const int32_t *labels_train, int32_t *pred, int64_t Nq, int k, int64_t Nt,
+                 void *stream);
+int han_contingency(const int32_t *a, const int32_t *b, int64_t n, int Ca, int Cb, int64_t *table, void *stream);
+size_t han_kmeans_step_workspace(int64_t N, int D, int k);
+int han_kmeans_step(const float *X, int64_t ldx, const float *C, const int32_t *prev, int32_t *labels, float *d2,
+                    int64_t *counts, float *new_centres, double *inertia, int64_t *changed, void *workspace,
+                    size_t workspace_bytes, int64_t N, int D, int k, void *stream);
 
 #ifdef __cplusplus
 }
