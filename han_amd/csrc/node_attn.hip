@@ -48,6 +48,23 @@ __device__ __forceinline__ float dot4(const float4_t &x, const float4_t &y) {
     return x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3];
 }
 
+// The predicated backward gather (bwd_consume_pred) writes out the roundings behind its gathered values, because how
+// its loads are arranged must not decide how its sums are rounded: left to itself the compiler fuses multiply-adds
+// differently from one arrangement to the next.  The forms below follow what it had made of the FAST kernels of the
+// 8 x 8 fp32 shape -- in the 4-edge tail step dot4 as four products added left to right; in a full step dot4 as one
+// product and three fused multiply-adds (last-bit differences from bwd_consume remain: DESIGN.md section 3).
+__device__ __forceinline__ float dot4_unfused(const float4_t &x, const float4_t &y) {
+#pragma clang fp contract(off)
+    return ((x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]) + x[3] * y[3];
+}
+__device__ __forceinline__ float dot4_fused(const float4_t &x, const float4_t &y) {
+    return __builtin_fmaf(x[3], y[3], __builtin_fmaf(x[2], y[2], __builtin_fmaf(x[1], y[1], x[0] * y[0])));
+}
+__device__ __forceinline__ float mul_add_unfused(const float a, const float b, const float c) {
+#pragma clang fp contract(off)
+    return a * b + c;
+}
+
 // XCD-aware work order.  Blocks are dealt round-robin over the 8 XCDs (blocks b and b + 8 share one, each XCD
 // has its own 4 MB L2), and a grid-stride sweep keeps ~gridDim.x * 4 consecutive rows in flight.  With the
 // identity order every XCD touches rows spread over that whole stripe, so on a graph with locality all eight
@@ -116,6 +133,19 @@ __device__ __forceinline__ float4_t gs_load_g4(const void *gs, int64_t row, int 
     const char *base = reinterpret_cast<const char *>(gs) + row * GsRow<FP, BF>::bytes;
     if (BF) return han_widen_bf16x4(*reinterpret_cast<const uint2 *>(base + 8 * q));
     return *reinterpret_cast<const float4_t *>(base + 16 * q);
+}
+
+// The lane's four g values where it wants them, zeros where it does not -- without control flow, which would split the
+// loads of a step into blocks that wait for one another: a lane that does not want its part reads its own statistics
+// record instead, in the line that gs_load_stats of the same step has just requested, and drops what it read.
+template <int FP>
+__device__ __forceinline__ float4_t gs_load_g4_if(const void *gs, int64_t row, int q, int head, bool want) {
+    const char *p = reinterpret_cast<const char *>(gs) + row * GsRow<FP, false>::bytes +
+                    (want ? 16 * q : GsRow<FP, false>::g_bytes + 16 * head);
+    float4_t v = *reinterpret_cast<const float4_t *>(p);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v[t] = want ? v[t] : 0.f;
+    return v;
 }
 
 template <int FP, bool BF>
@@ -1029,6 +1059,7 @@ struct BwdColsArgs {
     int xcd_order;
     int masked;          // HAN_FLAG_MASKED_EDGES
     int lean;            // HAN_FLAG_LEAN
+    int full_gather;     // HAN_FLAG_K2_FULL_GATHER (measurements)
     const int *only_if;  // lean kernel behind the dense path: run only when this device word is non-zero (null: always)
     int64_t split_deg;
     int64_t n_long, n_chunks;
@@ -1131,6 +1162,78 @@ __device__ __forceinline__ void bwd_consume(const BwdColsArgs &a, const int (&i)
     }
 }
 
+// The predicated backward gather (MODE 1; fp32 tables) and its measurement twin (MODE 2, HAN_FLAG_K2_FULL_GATHER: whole g
+// rows, same roundings).  An (edge, head) whose attention-dropout draw fell has am == 0, and its g values enter only
+// w * g  with  w = alpha * am = +0  and  am * dot:  exact zeros for any finite g (acc and dfacc are never -0, so adding
+// either zero leaves them as they are).  So the statistics of the U edges -- always needed: alpha, and the  - s  term --
+// are requested first, the U fields are drawn, and a lane loads its four g values only where its own head was kept and
+// its slot holds an edge; the others hold zeros.  A 128-byte line of g none of whose lanes asks for it is not requested
+// at all: with 8 x 8 heads that is the four heads of one hash word pair, 0.6^4 = 13 % of the g lines at the reference's
+// attention dropout 0.6 (two heads a line at 4 x 16: 36 %; one head a row at 1 x 64: 60 %).  MODE 1 and MODE 2 agree to
+// the bit for finite g: the roundings from the gathered values on are written out (dot4_unfused), because left to
+// itself the compiler fuses them differently from one arrangement of the loads to the next (what leads up to alpha is
+// the same expression in both and compiles alike today).  bwd_consume, the form of every other launch, is untouched.
+template <int FP, int U, bool VAL, bool FAST, bool ALLV, bool MASKED, int MODE>
+__device__ __forceinline__ void bwd_consume_pred(const BwdColsArgs &a, const int (&i)[U], const float (&ew)[U],
+                                                 const bool (&valid)[U], const SrcRow &sr, const int q, const int head, const bool drop_c,
+                                                 float (&acc)[4], float &dfacc) {
+    constexpr int KQ = (HAN_D / FP + 3) / 4;
+    static_assert(MODE == 1 || MODE == 2, "MODE 0 is bwd_consume");
+    float4_t gv[U], st[U];
+    float am[U];
+    // MASKED: a dead entry reads the statistics record of row 0 (one line that every wave shares) and drops it.
+    // A slot past the end of its row (!ALLV) has alpha == 0: it needs no g either.
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        st[u] = gs_load_stats<FP, false>(a.gs, (MASKED && !valid[u]) ? (int64_t)0 : (int64_t)i[u], head);
+        if (MASKED) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) st[u][t] = valid[u] ? st[u][t] : 0.f;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        am[u] = 1.f;
+        if (FAST || drop_c) {
+            const HanRand64 rn = han_rand64(a.seed_lo, a.seed_hi, HAN_STREAM_COEF,
+                                            (uint32_t)(((!FAST && a.gid) ? (int64_t)a.gid[(MASKED && !valid[u]) ? 0 : i[u]] : (int64_t)i[u]) + a.dst_offset),
+                                            sr.gj * (uint32_t)KQ + (uint32_t)(head >> 2));
+            am[u] = rn.field(head & 3) < a.thr_coef ? a.inv_keep_coef : 0.f;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        gv[u] = gs_load_g4_if<FP>(a.gs, (MASKED && !valid[u]) ? (int64_t)0 : (int64_t)i[u], q, head,
+                                  (MODE == 2 || am[u] != 0.f) && (ALLV || valid[u]));
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        float x = st[u][0] + sr.f2h;
+        if (VAL) x *= ew[u];
+        float sg = x > 0.f ? 1.f : a.slope;
+        if (VAL) sg *= ew[u];
+        float alpha = __expf(han_lrelu(x, a.slope) - st[u][1]);
+        alpha = (ALLV || valid[u]) ? alpha : 0.f;
+        const float w = alpha * am[u];
+        if (U > 1) {      // full steps
+            const float dot = head_sum<FP>(dot4_fused(gv[u], sr.hd));
+            dfacc = mul_add_unfused(alpha * sg, __builtin_fmaf(am[u], dot, -st[u][2]), dfacc);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] = t < 2 ? __builtin_fmaf(w, gv[u][t], acc[t]) : mul_add_unfused(w, gv[u][t], acc[t]);
+        } else {          // tail steps
+            const float dot = head_sum<FP>(dot4_unfused(gv[u], sr.hd));
+            dfacc = __builtin_fmaf(alpha * sg, __builtin_fmaf(am[u], dot, -st[u][2]), dfacc);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) acc[t] = __builtin_fmaf(w, gv[u][t], acc[t]);
+        }
+    }
+    // The fourth word of a statistics record is padding that nothing reads.  Left dead, its register goes to the hash,
+    // which then waits for the statistics to land before it may overwrite it -- and the g loads behind the hash wait
+    // with it, one memory latency after the other (read from the ISA; the form without this line was not timed).  This
+    // keeps the register taken until the step is done.
+#pragma unroll
+    for (int u = 0; u < U; ++u) asm volatile("" ::"v"(st[u][3]));
+}
+
 template <int FP>
 __device__ __forceinline__ void write_src(const BwdColsArgs &a, const int64_t src, const SrcRow &sr,
                                           const float (&acc)[4], const float dfacc, const int q, const int head,
@@ -1144,7 +1247,8 @@ __device__ __forceinline__ void write_src(const BwdColsArgs &a, const int64_t sr
     if ((4 * q) % FP == 0) a.df2[src * K + head] = dfacc;
 }
 
-template <int FP, int RPW, int U, bool BF, bool VAL, bool FAST, bool MASKED = false, bool DEDUP = false>
+// MODE: 0 = bwd_consume, 1 / 2 = bwd_consume_pred (the FAST fp32 launches: bwd_gather_mode)
+template <int FP, int RPW, int U, bool BF, bool VAL, bool FAST, bool MASKED = false, bool DEDUP = false, int MODE = 0>
 __global__ __launch_bounds__(256) void node_attn_bwd_cols_kernel(const BwdColsArgs a_in) {
     BwdColsArgs a = a_in;
     han_resolve_seed(a.seed_lo, a.seed_hi, a.seed_dev);
@@ -1200,14 +1304,16 @@ __global__ __launch_bounds__(256) void node_attn_bwd_cols_kernel(const BwdColsAr
                         valid[u] = MASKED ? i[u] >= 0 : true;
                         ew[u] = VAL ? __shfl(myval, idx, 64) : 1.f;
                     }
-                    bwd_consume<FP, U, BF, VAL, FAST, !MASKED, MASKED, DEDUP && U == 4>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
+                    if constexpr (MODE == 0) bwd_consume<FP, U, BF, VAL, FAST, !MASKED, MASKED, DEDUP && U == 4>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
+                    else bwd_consume_pred<FP, U, VAL, FAST, !MASKED, MASKED, MODE>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
                 }
                 for (; st * 4 < cnt; ++st) {                    // tail: single steps of 4 edges
                     const int idx = st * 4 + g;
                     const int i[1] = {__shfl(myrow, idx & 63, 64)};
                     const bool valid[1] = {idx < cnt && (!MASKED || i[0] >= 0)};
                     const float ew[1] = {VAL ? __shfl(myval, idx & 63, 64) : 1.f};
-                    bwd_consume<FP, 1, BF, VAL, FAST, false, MASKED>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
+                    if constexpr (MODE == 0) bwd_consume<FP, 1, BF, VAL, FAST, false, MASKED, false>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
+                    else bwd_consume_pred<FP, 1, VAL, FAST, false, MASKED, MODE>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
                 }
             }
         }
@@ -1231,7 +1337,8 @@ __global__ __launch_bounds__(256) void node_attn_bwd_cols_kernel(const BwdColsAr
                         if (MASKED) valid[u] = valid[u] && i[u] >= 0;
                         ew[u] = VAL ? __shfl(myval, (lane & 48) + ((st + u) & 15), 64) : 1.f;
                     }
-                    bwd_consume<FP, U, BF, VAL, FAST, false, MASKED>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
+                    if constexpr (MODE == 0) bwd_consume<FP, U, BF, VAL, FAST, false, MASKED, false>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
+                    else bwd_consume_pred<FP, U, VAL, FAST, false, MASKED, MODE>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
                 }
             }
         }
@@ -1384,7 +1491,7 @@ __global__ __launch_bounds__(256) void node_attn_bwd_cols_h8_kernel(const BwdCol
 }
 
 // Split source rows: one wave per chunk -> partial sums; one 16-lane group per long row adds them.
-template <int FP, int U, bool BF, bool VAL>
+template <int FP, int U, bool BF, bool VAL, int MODE = 0>
 __global__ __launch_bounds__(256) void node_attn_bwd_chunk_kernel(const BwdColsArgs a_in) {
     BwdColsArgs a = a_in;
     han_resolve_seed(a.seed_lo, a.seed_hi, a.seed_dev);
@@ -1413,7 +1520,8 @@ __global__ __launch_bounds__(256) void node_attn_bwd_chunk_kernel(const BwdColsA
                 valid[u] = valid[u] && i[u] >= 0;          // masked edges (HAN_FLAG_MASKED_EDGES) are skipped
                 ew[u] = VAL ? a.edge_val[valid[u] ? s + k : s] : 1.f;
             }
-            bwd_consume<FP, U, BF, VAL, false, false, true>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
+            if constexpr (MODE == 0) bwd_consume<FP, U, BF, VAL, false, false, true, false>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
+            else bwd_consume_pred<FP, U, VAL, false, false, true, MODE>(a, i, ew, valid, sr, q, head, drop_c, acc, dfacc);
         }
 #pragma unroll
         for (int off = 16; off <= 32; off <<= 1) {
@@ -1781,15 +1889,30 @@ static void launch_fwd_v(const FwdArgs &a_in, bool train, bool low, bool has_spl
     }
 }
 
+// The form of the backward gather a launch runs (bwd_consume's MODE).  0, the parent form, wherever predication has nothing
+// to leave out or measured slower: no attention dropout; bf16 tables (eight heads share a 128-byte line: 1.85 -> 1.94 ms
+// at N = 1M); a table of ids (the draw waits for the id lookup and the g loads wait for the draw, two latencies in a row:
+// 3.38 -> 3.72 ms); the masked backward, which already loads nothing for nine entries in ten (bench.py --masked-backward
+// 33.3 -> 31.2 epochs/s).  Otherwise 1, or 2 under HAN_FLAG_K2_FULL_GATHER.
+static int bwd_gather_mode(const BwdColsArgs &a, bool bf) {
+    if (bf || a.thr_coef >= HAN_KEEP_ALL || a.gid != nullptr || a.masked != 0) return 0;
+    return a.full_gather ? 2 : 1;
+}
+
 template <int FPC, bool BF, bool VAL>
 static void launch_bwd_rows(const BwdColsArgs &a, bool short_rows, hipStream_t st) {
     const bool fast = a.thr_coef < HAN_KEEP_ALL && !a.gid;
     const int grid = attn_grid(short_rows ? (a.n_work + 3) / 4 : a.n_work);
     HAN_DISPATCH_BOOL(SHORT, short_rows, {
         constexpr int RPW = SHORT ? 4 : 1;
+        const int mode = bwd_gather_mode(a, BF);      // 1 / 2: attention dropout on and no id table, i.e. `fast`
         if (a.masked)      // opt-in masked backward: the general instantiations, dead entries skipped in place
             node_attn_bwd_cols_kernel<FPC, RPW, 4, BF, VAL, false, true><<<grid, 256, 0, st>>>(a);
-        else HAN_DISPATCH_BOOL(FAST, fast, node_attn_bwd_cols_kernel<FPC, RPW, 4, BF, VAL, FAST><<<grid, 256, 0, st>>>(a));
+        else if (mode == 0) HAN_DISPATCH_BOOL(FAST, fast, node_attn_bwd_cols_kernel<FPC, RPW, 4, BF, VAL, FAST><<<grid, 256, 0, st>>>(a));
+        else if constexpr (!BF) {
+            if (mode == 1) node_attn_bwd_cols_kernel<FPC, RPW, 4, false, VAL, true, false, false, 1><<<grid, 256, 0, st>>>(a);
+            else node_attn_bwd_cols_kernel<FPC, RPW, 4, false, VAL, true, false, false, 2><<<grid, 256, 0, st>>>(a);
+        }
     });
 }
 
@@ -1806,7 +1929,12 @@ static void launch_bwd_cols_v(const BwdColsArgs &a_in, bool low, bool has_split,
     }
     for_each_bin(a, a.NS, low, bins, [&](const BwdColsArgs &b, bool short_rows) { launch_bwd_rows<FPC, BF, VAL>(b, short_rows, st); });
     if (has_split) {
-        node_attn_bwd_chunk_kernel<FPC, 4, BF, VAL><<<attn_grid(a.n_chunks), 256, 0, st>>>(a);
+        const int mode = bwd_gather_mode(a, BF);
+        if (mode == 0) node_attn_bwd_chunk_kernel<FPC, 4, BF, VAL><<<attn_grid(a.n_chunks), 256, 0, st>>>(a);
+        else if constexpr (!BF) {
+            if (mode == 1) node_attn_bwd_chunk_kernel<FPC, 4, false, VAL, 1><<<attn_grid(a.n_chunks), 256, 0, st>>>(a);
+            else node_attn_bwd_chunk_kernel<FPC, 4, false, VAL, 2><<<attn_grid(a.n_chunks), 256, 0, st>>>(a);
+        }
         node_attn_bwd_finish_kernel<FPC, BF><<<(int)a.n_long, 256, 0, st>>>(a);
     }
 }
@@ -1970,6 +2098,7 @@ extern "C" int han_node_attn_bwd_cols(const int64_t *colptr, const int32_t *rowi
     a.src_offset = src_offset; a.dst_offset = dst_offset; a.xcd_order = (flags & HAN_FLAG_XCD_ORDER) ? 1 : 0;
     a.masked = (flags & HAN_FLAG_MASKED_EDGES) ? 1 : 0;
     a.lean = (flags & HAN_FLAG_LEAN) ? 1 : 0;
+    a.full_gather = (flags & HAN_FLAG_K2_FULL_GATHER) ? 1 : 0;
     a.only_if = nullptr;
     const bool has_split = fill_split(a, split);
     hipStream_t st = (hipStream_t)stream;

@@ -21,6 +21,8 @@ FLAG_LEAN = 256            # HAN_FLAG_LEAN: the lean K2 kernels of small graphs 
 FLAG_K2_DEEP = 512         # HAN_FLAG_K2_DEEP (measurements: bf16 eval forward with 8 steps in flight)
 K2_DEEP = False            # set by tools/k2_regimes.py --deep
 K2_SHARED_HASH = False     # tests / measurements: FLAG_K2_SHARED_HASH on every node_attn_fwd call
+K2_FULL_GATHER = False     # tests / measurements: FLAG_K2_FULL_GATHER on every node_attn_bwd_cols call
+FLAG_K2_FULL_GATHER = 2048 # HAN_FLAG_K2_FULL_GATHER: measurements only (the backward gather requests g rows whole, dropped heads included)
 FLAG_MASKED_EDGES = 64     # HAN_FLAG_MASKED_EDGES: negative entries of the transposed graph are skipped in place
 FLAG_K1_EXACT_PIPE = 2     # HAN_FLAG_K1_EXACT_PIPE / _MATRIX_PIPE: force one of the two K1 forward kernels (tests, measurements)
 FLAG_K1_MATRIX_PIPE = 4
@@ -585,7 +587,7 @@ def node_attn_bwd_cols(graph_t: CSRGraph, gs_tab, H, f2, df1, a1, a2, coef_drop=
             NS, graph_t.nnz, K, FP, LEAKY_SLOPE, _check_drop(coef_drop, "coef_drop"), fts_drop,
             int(seed), _dev_word(seed_dev), int(src_offset), int(dst_offset),
             (FLAG_XCD_ORDER if graph_t.has_locality() else 0) | (FLAG_MASKED_EDGES if graph_t.masked else 0)
-            | (FLAG_LEAN if lean_b else 0),
+            | (FLAG_LEAN if lean_b else 0) | (FLAG_K2_FULL_GATHER if K2_FULL_GATHER else 0),
             ctypes.byref(split) if split is not None else None,
             ctypes.byref(dense) if dense is not None else None, _stream()), "han_node_attn_bwd_cols")
     return dH, df2

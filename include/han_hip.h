@@ -55,6 +55,15 @@ extern "C" {
 #define HAN_FLAG_K2_SHARED_HASH 1024 /* measurements only: han_node_attn_fwd, training forward of the 8 x 8 shape with both dropouts
                                   on, with ONE attention-dropout hash per lane and 4-edge step, the other three edges' words taken
                                   from the lane's DPP quad -- bitwise the same draws; no faster          */
+#define HAN_FLAG_K2_FULL_GATHER 2048 /* measurements only: han_node_attn_bwd_cols requests the whole g row of every edge, as it did
+                                  before the row and chunk kernels learned to leave out what attention dropout makes unused.  By
+                                  default a lane loads its part of g_i only where the draw of its own (edge, head) kept the
+                                  coefficient; a dropped head contributes exact zeros, so dH and df2 are bitwise those of this
+                                  form for finite g.  The one difference: a non-finite g under a DROPPED head no longer turns
+                                  the sums into NaN (the full gather multiplies it by zero), a non-finite g under a kept head
+                                  still does.  Predicated are fp32 tables with attention dropout, table_gid NULL and no
+                                  HAN_FLAG_MASKED_EDGES; every other launch gathers whole rows with or without this flag
+                                  (bf16 tables, table_gid, masked edges, the lean, one-lane-per-head and dense kernels).     */
 #define HAN_FLAG_MASKED_EDGES 64 /* han_node_attn_bwd_cols: entries of rowidx below 0 are skipped IN PLACE (their destination's
                                   g row is identically zero -- a destination outside the loss mask of a one-layer model);
                                   the remaining terms are summed in the positions and order of the full pass, so the

@@ -10,7 +10,7 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNELS = {"k2_fwd_eval": "node_attn_fwd_kernel<8, false, 1,", "k2_fwd_train": "node_attn_fwd_kernel<8, true, 1,",
-           "k2_bwd_cols": "node_attn_bwd_cols_kernel<8, 1,", "k1_fwd_eval_calibration": "project_fwd_kernel<8, false,"}
+           "k2_bwd_cols": "node_attn_bwd_cols_kernel<8, 1,", "k1_fwd_eval_calibration": "project_fwd_b6_multi_kernel<false,"}
 
 
 def main():
@@ -37,8 +37,8 @@ def main():
            "kernel": "node_attn_fwd_kernel<8,false,1,4> (K2 forward, eval)",
            "hbm_bytes_per_launch": detail["k2_fwd_eval"]["hbm_bytes_per_launch"],
            "formula": "(2*FETCH_SIZE + WRITE_SIZE)*1024 B; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 tallies "
-                      "128-B requests at 64 B); calibration in the same run: project_fwd_kernel<8,false> reads "
-                      "X = 1.024 GB (+W from L2)",
+                      "128-B requests at 64 B); calibration in the same run: the fused K1 eval forward "
+                      "(project_fwd_b6_multi_kernel<false,...>) reads X = 1.024 GB once (+W from L2)",
            "note": "fabric-side counter: Infinity-Cache hits are included, so this is L2-miss traffic, an upper bound "
                    "on HBM bytes; at SYN-1M the 256 MB H table sits in the 256 MiB Infinity Cache",
            "detail": detail,
