@@ -4,7 +4,7 @@
 full-graph with early stopping, restore the best weights, report the test metrics and the
 KNN / KMeans scores of ``final_embed``.
 
-    python examples/ex_acm3025.py [--mat ACM3025.mat] [--epochs 200] [--graph] [--eval-device gpu]
+    python examples/ex_acm3025.py [--mat ACM3025.mat] [--epochs 200] [--graph] [--eval-device gpu] [--sparse-features]
 
 Hyper-parameters are the reference's (ex_acm3025.py:16-31): lr 0.005, l2 0.001,
 hid_units [8], n_heads [8, 1], dropout 0.6/0.6, patience 100, mp_att_size 128.
@@ -17,7 +17,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from han_amd import evaluate, process, synth  # noqa: E402
+from han_amd import SparseFeatures, evaluate, process, synth  # noqa: E402
 from han_amd.gat import HeteGAT_multi  # noqa: E402
 from han_amd.trainer import HANTrainer  # noqa: E402
 
@@ -34,6 +34,9 @@ def main():
     ap.add_argument("--planted", action="store_true",
                     help="without --mat: a synthetic task WITH structure (communities) instead of the ACM-shaped "
                          "random-label workload, to watch the model learn")
+    ap.add_argument("--sparse-features", action="store_true",
+                    help="feed the features as a CSR matrix (han_amd.SparseFeatures): the first-layer projection then "
+                         "visits the stored entries only; without --mat, a generated bag-of-words of the ACM shape")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eval-device", choices=("cpu", "gpu"), default="cpu",
                     help="where final_embed is scored: cpu = scikit-learn on the host, as the reference; gpu = the "
@@ -45,7 +48,13 @@ def main():
     if args.mat:
         adj_list, fea_list, y_train, y_val, y_test, train_mask, val_mask, test_mask = process.load_data_mat(args.mat)
         graphs = [process.adj_to_graph(a, nhood=1, device=dev) for a in adj_list]      # == adj_to_bias's edge set
-        xs = [torch.tensor(f, dtype=torch.float32, device=dev) for f in fea_list[:len(graphs)]]
+        if args.sparse_features:
+            import scipy.sparse as sp
+            conv = {}      # the meta-paths usually share one matrix: convert it once
+            xs = [conv.setdefault(id(f), SparseFeatures.from_scipy(sp.csr_matrix(f), device=dev))
+                  for f in fea_list[:len(graphs)]]
+        else:
+            xs = [torch.tensor(f, dtype=torch.float32, device=dev) for f in fea_list[:len(graphs)]]
         y = y_train + y_val + y_test
         labels = torch.tensor(y.argmax(1), dtype=torch.int32, device=dev)
         masks = [torch.tensor(m, device=dev) for m in (train_mask, val_mask, test_mask)]
@@ -61,6 +70,8 @@ def main():
         labels, nb_classes = wl["labels"], wl["c"]
         test = ~(wl["train_mask"].bool() | wl["val_mask"].bool())
         masks = [wl["train_mask"], wl["val_mask"], test]
+        if args.sparse_features:      # ~1 % of the 1870 columns per row, a few words in most documents
+            xs = [synth.bag_of_words(wl["n"], wl["f"], 20, seed=args.seed, device=dev)] * wl["p"]
     n, ft = xs[0].shape
     print(f"nodes {n}, features {ft}, classes {nb_classes}, meta-paths {len(graphs)}, "
           f"edges {[g.nnz for g in graphs]}")

@@ -14,7 +14,7 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_uint64, c_void
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhan_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("node_attn.hip", "project.hip", "sem_attn.hip", "loss_opt.hip", "metapath.hip", "evaluate.hip")
+SOURCES = ("node_attn.hip", "project.hip", "project_sparse.hip", "sem_attn.hip", "loss_opt.hip", "metapath.hip", "evaluate.hip")
 # node_attn.hip: the dense K2 kernels (node_attn_dense.h) keep 8-16 fp32 MFMA accumulators in a rolled loop; with the
 # default AGPR form hipcc shuffles them through v_accvgpr_read / _mov / _write every iteration (each a wait for the
 # matrix pipe); the VGPR form of the MFMA destination has no such traffic
@@ -54,6 +54,11 @@ SIGNATURES = {
     "han_project_bwd": (c_int, [P, c_int, I64, P, P, P, c_size_t, I64, c_int, c_int, c_int, c_float,
                                 c_uint64, P, I64, P, P]),
     "han_project_bwd_input": (c_int, [P, P, P, I64, I64, c_int, c_int, c_int, c_float, c_uint64, P, I64, P]),
+    "han_project_sparse_fwd": (c_int, [P, P, P, P, P, P, P, P, P, c_int, P, P, I64, c_int, c_int, c_int, c_float, c_float,
+                                       c_uint64, P, I64, c_int, P]),
+    "han_project_sparse_bwd_workspace": (c_size_t, [I64]),
+    "han_project_sparse_bwd": (c_int, [P, P, P, I64, I64, I64, P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, c_int,
+                                       c_float, c_uint64, P, I64, P]),
     "han_row_split_workspace": (c_size_t, [I64]),
     "han_node_attn_fwd": (c_int, [P, P, P, P, c_int, P, P, P, P, P, P, P, P, I64, P, P, P, P, I64, I64, c_int,
                                   c_int, c_float, c_float, c_float, c_uint64, P, I64, c_int, c_int, P, P, P]),
@@ -97,7 +102,7 @@ SIGNATURES = {
     "han_kmeans_step": (c_int, [P, I64, P, P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, P]),
 }
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 _lib = None
 
 

@@ -259,6 +259,7 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         xs_full: under a node partition, the features of ALL rows (P tensors (N,F)): the first layer
         then projects the whole table on every rank instead of exchanging it (replicated projection)."""
         P = len(graphs)
+        layers._no_sparse_under_partition(self.partition is not None or xs_full is not None, xs, xs_full)
 
         def act(M, K, FP):
             if post is None:
@@ -361,7 +362,8 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
                    bias_mat_list, hid_units, n_heads, activation=F_torch.elu, residual=False,
                    mp_att_size=128, coef_sink=None):
         """Same positional arguments as models/gat.py:35-37.  `inputs_list[p]`:
-        (1,N,F) or (N,F) fp32 GPU tensor; `bias_mat_list[p]`: (1,N,N) additive
+        (1,N,F) or (N,F) fp32 GPU tensor, or sparse features (a SparseFeatures, or a torch sparse COO / CSR
+        tensor (N,F) / (1,N,F), converted once per tensor) -- dense and sparse may be mixed; `bias_mat_list[p]`: (1,N,N) additive
         mask, CSRGraph or (rowptr, colidx).  Lists are zipped, shorter wins
         (gat.py:39).  `training` and `nb_nodes` are accepted and ignored, as in
         the reference; dropout is driven by attn_drop / ffd_drop alone.

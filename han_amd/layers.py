@@ -26,6 +26,7 @@ import torch.nn.functional as F_torch
 
 from . import ops, rng
 from .dist import NodePartition
+from .features import SparseFeatures, as_features, is_sparse_input
 from .graph import as_graph
 
 D = ops.D
@@ -54,6 +55,8 @@ def _direct(p) -> bool:
 def _same_tensor(ts) -> bool:
     """True when every entry is the same view of the same storage (the meta-paths share their features)."""
     t0 = ts[0]
+    if any(isinstance(t, SparseFeatures) for t in ts):      # one sparse matrix for every meta-path, or no sharing
+        return all(t is t0 for t in ts[1:])
     return all(t.data_ptr() == t0.data_ptr() and t.shape == t0.shape and t.stride() == t0.stride()
                and t.dtype == t0.dtype for t in ts[1:])
 
@@ -64,6 +67,18 @@ def _used_on(stream, *tensors):
     for t in tensors:
         if t is not None:
             t.record_stream(stream)
+
+
+def _unit_stride(x) -> bool:
+    """Rows with contiguous elements (a SparseFeatures has no strides)."""
+    return isinstance(x, SparseFeatures) or x.stride(-1) == 1
+
+
+def _no_sparse_under_partition(partitioned: bool, *feature_lists):
+    """Sparse features are single-process for now: under a node partition they fail loudly, before any launch,
+    instead of falling into a dense path."""
+    if partitioned and any(is_sparse_input(x) for xs in feature_lists if xs is not None for x in xs):
+        raise NotImplementedError("sparse features under a node partition")
 
 
 def _fork(streams):
@@ -282,6 +297,7 @@ class NodeLevelAttention(torch.autograd.Function):
     def forward(ctx, Xin, W, a1, b1, a2, b2, c, Wr, br, xs, graphs, run):
         P = len(graphs)
         Xin, xs = _paths_in(Xin, xs, P)
+        _no_sparse_under_partition(run.part is not None, xs, run.xs_full)
         K, FP = a1.shape[1], a1.shape[2]
         part, multi, train = run.part, run.multi, run.train
         in_drop, coef_drop, row_offset, seed_dev, tdt = run.drop_in, run.drop_coef, run.row_offset, run.seed_dev, run.table_dtype
@@ -307,7 +323,7 @@ class NodeLevelAttention(torch.autograd.Function):
         overlap = run.overlap if (train and run.group == 0) else None
         if overlap is not None:
             overlap.node_level()
-        if streams is None and P > 1 and shared is not None and _same_tensor(shared) and W.is_contiguous() and shared[0].stride(-1) == 1:
+        if streams is None and P > 1 and shared is not None and _same_tensor(shared) and W.is_contiguous() and _unit_stride(shared[0]):
             full = all(replicated)
             Hs, f1s, f2s, keeps = ops.project_fwd_multi(shared[0], W, a1, a2, b1, b2, in_drop=in_drop, fts_drop=in_drop,
                                                         seeds=[int(v) for v in run.seeds],
@@ -497,6 +513,7 @@ class WideHeadAttention(torch.autograd.Function):
     def forward(ctx, Xin, W, a1, b1, a2, b2, c, Wr, br, xs, graphs, run):
         P = len(graphs)
         Xin, xs = _paths_in(Xin, xs, P)
+        _no_sparse_under_partition(run.part is not None, xs, run.xs_full)
         S = W.shape[2] // D
         train = run.train
         in_drop, coef_drop, row_offset, seed_dev = run.drop_in, run.drop_coef, run.row_offset, run.seed_dev
@@ -746,7 +763,12 @@ def classifier_loss_any(Z, Wc, bc, labels, mask, weight):
 # ---------------------------------------------------------------------------
 # reference-named functional API
 # ---------------------------------------------------------------------------
-def _squeeze_batch(seq: torch.Tensor, name="seq") -> torch.Tensor:
+def _squeeze_batch(seq, name="seq"):
+    """The (N,F) features of a `seq` argument: a dense (1,N,F) / (N,F) tensor, or sparse features -- a SparseFeatures
+    as it is, a torch sparse COO / CSR tensor (N,F) / (1,N,F) converted once (features.as_features)."""
+    seq = as_features(seq)
+    if isinstance(seq, SparseFeatures):
+        return seq
     if seq.dim() == 3:
         if seq.shape[0] != 1:
             raise ValueError(f"{name}: batch size must be 1 (ex_acm3025.py:21; "
@@ -784,8 +806,9 @@ def _single_head(seq, out_sz, graph, activation, in_drop, coef_drop, residual, p
     else:
         fpk = next(w for w in (4, 8, 16, 32, 64) if out_sz <= w)
         K = D // fpk
-        a1 = torch.cat([pad_last(params["a1"], fpk)[None], x.new_zeros(K - 1, fpk)])[None]   # (1,K,F'k)
-        a2 = torch.cat([pad_last(params["a2"], fpk)[None], x.new_zeros(K - 1, fpk)])[None]
+        zeros = (params["W"] if isinstance(x, SparseFeatures) else x).new_zeros(K - 1, fpk)
+        a1 = torch.cat([pad_last(params["a1"], fpk)[None], zeros])[None]   # (1,K,F'k)
+        a2 = torch.cat([pad_last(params["a2"], fpk)[None], zeros])[None]
         b1 = pad_last(params["b1"].reshape(1), K)[None]
         b2 = pad_last(params["b2"].reshape(1), K)[None]
     c = pad_last(params["c"])[None]

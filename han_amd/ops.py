@@ -12,6 +12,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .features import SparseFeatures
 from .graph import CSRGraph
 
 ACT_IDENTITY = 0
@@ -265,8 +266,14 @@ def project_fwd(X, W, a1, a2, b1, b2, in_drop=0.0, fts_drop=0.0, seed=0, row_off
     projected-row dropout rides in mantissa bit 0 of every H element.
     want_keep=True returns a 4th value: the keep table of the per-head input dropout for
     project_bwd (uint8, han_project_keep_bytes() long), or None when this shape has none
-    (small inputs, in_drop == 0, head shapes other than 8 x 8): dW then regenerates the draws."""
+    (small inputs, in_drop == 0, head shapes other than 8 x 8): dW then regenerates the draws.
+    X may be a SparseFeatures: the projection then visits the stored entries only (han_project_sparse_fwd), with the
+    same draws; there is no keep table."""
     lib = _lib.load()
+    if isinstance(X, SparseFeatures):
+        out = _project_sparse_fwd(X, W, a1, a2, b1, b2, (), in_drop, fts_drop, [seed], row_offset, table_dtype,
+                                  seed_dev, flags)
+        return out + (None,) if want_keep else out
     if X.dim() != 2:
         raise ValueError(f"X: expected (N,F), got {tuple(X.shape)}")
     xcode, ldx, N, F, K, FP, in_drop, fts_drop, H, f1, f2, ws, keep = _project_fwd_setup(
@@ -317,6 +324,67 @@ def _project_fwd_setup(X, W, a1, a2, b1, b2, lead, in_drop, fts_drop, table_dtyp
     return xcode, ldx, N, F, K, FP, in_drop, fts_drop, H, f1, f2, ws, keep
 
 
+def _project_sparse_fwd(X, W, a1, a2, b1, b2, lead, in_drop, fts_drop, seeds, row_offset, table_dtype, seed_dev, flags):
+    """project_fwd (lead = ()) / project_fwd_multi (lead = (P,): a loop over the meta-paths with their seeds -- fusing
+    them would save only the index stream) of a SparseFeatures: H lead + (N,D), f1 / f2 lead + (N,K)."""
+    lib = _lib.load()
+    if not X.is_cuda:
+        raise ValueError(f"X: must be on a GPU (han_amd has no CPU path); got {X.device}")
+    N, F = X.shape
+    dev = X.device
+    K, FP = a1.shape[len(lead):]
+    if table_dtype not in DTYPE_CODE:
+        raise ValueError(f"table_dtype {table_dtype}: expected float32 or bfloat16")
+    _check_heads(K, FP)
+    _chk(W, "W", lead + (F, D), device=dev)
+    _chk(a1, "a1", lead + (K, FP), device=dev)
+    _chk(a2, "a2", lead + (K, FP), device=dev)
+    _chk(b1, "b1", lead + (K,), device=dev)
+    _chk(b2, "b2", lead + (K,), device=dev)
+    in_drop = _check_drop(in_drop, "in_drop")
+    fts_drop = _check_drop(fts_drop, "fts_drop")
+    H = torch.empty(lead + (N, D), dtype=table_dtype, device=dev)
+    f1 = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
+    f2 = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
+    sel = (lambda t, p: t[p]) if lead else (lambda t, p: t)
+    for p in range(lead[0] if lead else 1):
+        _lib.check(lib.han_project_sparse_fwd(
+            X.rowptr.data_ptr(), X.colidx.data_ptr(), _ptr(X.values), sel(W, p).data_ptr(), sel(a1, p).data_ptr(),
+            sel(a2, p).data_ptr(), sel(b1, p).data_ptr(), sel(b2, p).data_ptr(), sel(H, p).data_ptr(),
+            DTYPE_CODE[table_dtype], sel(f1, p).data_ptr(), sel(f2, p).data_ptr(), N, F, K, FP, in_drop, fts_drop,
+            int(seeds[p]) & ((1 << 64) - 1), _dev_word(seed_dev), int(row_offset), int(flags), _stream()),
+            "han_project_sparse_fwd")
+    return H, f1, f2
+
+
+# columns of a SparseFeatures longer than this many entries are cut into chunks of it for dW, a wave per chunk
+# (SparseFeatures.transposed builds the table; han_project_sparse_bwd merges the chunks' partial rows in order): the
+# split rule of SPLIT_CHUNK -- a wave walking a column as long as N alone would be the tail of the launch.  A chunk is
+# 4 batches of 64 entries, about 20 dependent memory round trips: short enough that the longest wave does not set the
+# time of the 3025-row data sets' dW, long enough that a column of 262 144 rows merges 1024 partial rows, not 4096
+# (tools/k1_sparse_bench.py --chunks sweeps it: profiles/r12_k1_sparse_bench.jsonl, dw_sparse_by_chunk)
+SPARSE_COL_CHUNK = 256
+
+
+def _project_sparse_bwd(X, dH, K, FP, in_drop, seed, row_offset, seed_dev, out):
+    """project_bwd of a SparseFeatures: a gather of dH rows per feature through X.transposed()."""
+    lib = _lib.load()
+    N, F = X.shape
+    _chk(dH, "dH", (N, D), device=X.device)
+    _check_heads(K, FP)
+    dW = _out(out, "out", (F, D), X.device)
+    t = X.transposed()
+    nbytes = lib.han_project_sparse_bwd_workspace(t["n_chunks"])
+    ws = _ws(nbytes, X.device, "projs") if nbytes else None
+    _lib.check(lib.han_project_sparse_bwd(
+        t["colptr"].data_ptr(), t["rowidx"].data_ptr(), _ptr(t["values_t"]), t["col_chunk"], t["n_long"], t["n_chunks"],
+        _ptr(t["long_cols"]), _ptr(t["long_ptr"]), _ptr(t["chunk_col"]), _ptr(t["chunk_start"]), _ptr(t["chunk_end"]),
+        dH.data_ptr(), dW.data_ptr(), _ptr(ws), ws.numel() if ws is not None else 0, N, F, K, FP,
+        _check_drop(in_drop, "in_drop"), int(seed) & ((1 << 64) - 1), _dev_word(seed_dev), int(row_offset), _stream()),
+        "han_project_sparse_bwd")
+    return dW
+
+
 def keep_bytes(N, F, ldx, K=8, FP=8) -> int:
     """han_project_keep_bytes: size of the keep table of an (N, F) input, 0 when the shape has none."""
     return int(_lib.load().han_project_keep_bytes(int(N), int(F), int(ldx), int(K), int(FP)))
@@ -328,8 +396,16 @@ def project_fwd_multi(X, W, a1, a2, b1, b2, in_drop=0.0, fts_drop=0.0, seeds=Non
     every meta-path: ex_acm3025.py:86, models/gat.py:39).  W (P,F,D), a1/a2 (P,K,F'), b1/b2 (P,K) -- the
     model's own parameter tensors.  Returns H (P,N,D), f1, f2 (P,N,K) and, with want_keep, a list of P keep
     tables (or Nones).  The eval forward of long inputs runs as ONE fused launch (X read, split and staged
-    once for 4 meta-paths per block); every other case is the per-meta-path kernel, P times."""
+    once for 4 meta-paths per block); every other case is the per-meta-path kernel, P times.
+    X may be a SparseFeatures (a loop over the meta-paths; no keep tables)."""
     lib = _lib.load()
+    if isinstance(X, SparseFeatures):
+        P = a1.shape[0]
+        if (float(in_drop) > 0 or float(fts_drop) > 0) and (seeds is None or len(seeds) != P):
+            raise ValueError("dropout needs one seed per meta-path")
+        out = _project_sparse_fwd(X, W, a1, a2, b1, b2, (P,), in_drop, fts_drop, seeds if seeds is not None else [0] * P,
+                                  row_offset, table_dtype, seed_dev, flags)
+        return out + ([None] * P,) if want_keep else out
     if X.dim() != 2 or W.dim() != 3:
         raise ValueError(f"X: expected (N,F) and W (P,F,D), got {tuple(X.shape)}, {tuple(W.shape)}")
     P = a1.shape[0]
@@ -352,8 +428,13 @@ def project_fwd_multi(X, W, a1, a2, b1, b2, in_drop=0.0, fts_drop=0.0, seeds=Non
 
 def project_bwd(X, dH, K, FP, in_drop=0.0, seed=0, row_offset=0, seed_dev=None, out=None, keep=None):
     """dW (F,D) = dropout_k(X)^T dH (written to `out` when given).  keep: the table project_fwd(want_keep=True)
-    returned for the same X / seed (the draws are then read, not regenerated), or None."""
+    returned for the same X / seed (the draws are then read, not regenerated), or None.
+    X may be a SparseFeatures (han_project_sparse_bwd through X.transposed(); the draws are regenerated)."""
     lib = _lib.load()
+    if isinstance(X, SparseFeatures):
+        if keep is not None:
+            raise ValueError("keep: sparse features have no keep table")
+        return _project_sparse_bwd(X, dH, K, FP, in_drop, seed, row_offset, seed_dev, out)
     _chk(X, "X", contiguous=False, dtype=X.dtype)
     xcode = _dtype_code(X, "X")
     N, F = X.shape

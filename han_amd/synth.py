@@ -266,6 +266,28 @@ def _zipf_draw(cdf: torch.Tensor, shape, gen, device) -> torch.Tensor:
     return torch.searchsorted(cdf, u, right=True).clamp_(max=cdf.numel() - 1)
 
 
+def bag_of_words(n: int, f: int, nnz_per_row: int, seed: int, device="cpu", rows=None, binary=True, zipf: float = 1.0):
+    """Bag-of-words node features as a SparseFeatures (n, f): every row draws `nnz_per_row` words with popularity
+    ~ rank^-zipf (column 0 the most frequent: a few columns are long, most are short or empty).  A word drawn more
+    than once is stored once -- binary=True: every stored entry is 1 (values None); binary=False: its count.
+    Block-seeded like the other generators: rows = (r0, r1) returns exactly those rows of the full matrix."""
+    from .features import SparseFeatures
+    r0, r1 = _row_range(n, rows)
+    cdf = _zipf_cdf(f, zipf, device)
+    parts = []
+    for b, lo, hi in _blocks(r0, r1):
+        nb_rows = min(ROW_BLOCK, n - b * ROW_BLOCK)
+        parts.append(_zipf_draw(cdf, (nb_rows, nnz_per_row), _block_generator(seed, 51, b, device), device)[lo:hi])
+    cols = torch.cat(parts).reshape(-1) if parts else torch.empty(0, dtype=torch.int64, device=device)
+    row_ids = torch.arange(r1 - r0, device=device).repeat_interleave(nnz_per_row)
+    sf = SparseFeatures._from_coo(row_ids, cols, None, r1 - r0, f)      # repeated draws are summed: counts
+    if binary:
+        return SparseFeatures(sf.rowptr, sf.colidx, None, f)
+    if sf.values is None:
+        sf = SparseFeatures(sf.rowptr, sf.colidx, torch.ones(sf.nnz, dtype=torch.float32, device=sf.device), f)
+    return sf
+
+
 def hetero_relations(name: str, seed: int = 0, device="cpu"):
     """Typed relations of a synthetic heterogeneous graph, the input of han_amd.metapath: returns (relations,
     sizes) -- relations maps an ordered type pair to its CSRGraph (rows = nodes of the first type), sizes the node

@@ -18,6 +18,7 @@ import torch
 from . import layers, ops, rng
 from .base_gattn import TFAdam
 from .dist import NodePartition
+from .features import SparseFeatures, as_features
 from .gat import HeteGAT_multi
 from .graph import as_graph
 
@@ -74,7 +75,8 @@ class HANTrainer:
                  part: NodePartition | None = None, patience=100, max_halo_fraction=0.6,
                  use_graph=False, graphs_local=False, xs_full=None, replicate="auto", masked_backward=False,
                  side_stream=False, overlap_eval=False):
-        """xs: list of P (N_local,F) feature tensors (this rank's rows);
+        """xs: list of P (N_local,F) feature tensors (this rank's rows), or sparse features (SparseFeatures / torch
+        sparse COO or CSR tensors; single process only);
         graphs: list of P CSRGraph (or dense masks / CSR tuples).  Under a partition (`part`) either
         the GLOBAL graphs (graphs_local=False: each rank keeps its row block; small data sets) or --
         graphs_local=True, the scalable form -- THIS RANK'S destination rows [row_start, row_end) with
@@ -120,6 +122,7 @@ class HANTrainer:
         self.model = model
         model.direct_grads(True)      # gradients land in model.flat_grad without copy/accumulate launches
         self.part = part if (part is not None and part.active) else None
+        layers._no_sparse_under_partition(self.part is not None or xs_full is not None, xs, xs_full)
         model.partition = self.part
         dev = model.flat.device
         self.xs_full, self.replicate, self.replicate_info = None, frozenset(), None
@@ -142,7 +145,7 @@ class HANTrainer:
             self.xs_full = tuple(pad[id(x)] for x in xs_full)
             self.replicate = replication_policy(pt.world, replicate)
             self.replicate_info = {"policy": "static (han_amd.dist.replication_policy)"}
-        self.xs = [x.contiguous() for x in xs]
+        self.xs = [x if isinstance(x, SparseFeatures) else x.contiguous() for x in map(as_features, xs)]
         graphs = [as_graph(g, dev) for g in graphs]     # dense masks / (rowptr, colidx) accepted
         if self.part is not None:
             sharded = [self.part.shard_local_graph(g) if graphs_local else self.part.shard_graph(g)

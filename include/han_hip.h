@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HAN_ABI_VERSION 9
+#define HAN_ABI_VERSION 10
 
 #define HAN_E_BADARG   (-1)   /* null pointer, negative size, inconsistent shape.  The forward
                               * entry points return 0 at once for N == 0 (empty tensors may
@@ -174,6 +174,43 @@ int han_project_bwd(const void *X, int x_dtype, int64_t ldx, const float *dH, fl
 int han_project_bwd_input(const float *dH, const float *W, float *dX, int64_t ldo, int64_t N,
                           int F, int K, int FP, float in_drop, uint64_t seed, const uint64_t *seed_dev,
                           int64_t row_offset, void *stream);
+
+/* ---- K1 sparse: the first-layer projection of a CSR feature matrix (ABI 10) ----
+ * Bag-of-words features are almost all zero, and input dropout (layers.py:18-19) multiplies elements: a zero stays
+ * a zero whatever its draw.  These two entry points visit only the stored entries and regenerate exactly the draws
+ * the dense kernels use (counter (global row, f * ceil(K/4) + k/4), field k % 4), so they compute what
+ * han_project_fwd / han_project_bwd compute on the densified matrix, up to the order of the fp32 sums.
+ *
+ * han_project_sparse_fwd: the contract of han_project_fwd with the CSR triple in place of X, x_dtype, ldx:
+ *   rowptr (N+1) int64, colidx (nnz) int32 in [0, F), vals (nnz) fp32 or NULL (every stored entry is 1);
+ *   H[n, d] = 1/keep * sum_e vals[e] * keep_{d/FP}(n + row_offset, colidx[e]) * W[colidx[e], d];
+ * the epilogue (projected-row dropout bit, HAN_FLAG_FTS_SLICE, bf16 rounding, f1 / f2 from the row as stored) is
+ * han_project_fwd's.  A row without entries stores the (stamped) zero and gets f1 = b1, f2 = b2.  No workspace and no
+ * keep table: dW regenerates the draws.  N == 0 returns 0 at once; N >= 2^31: HAN_E_UNSUPPORTED.                */
+int han_project_sparse_fwd(const int64_t *rowptr, const int32_t *colidx, const float *vals, const float *W,
+                           const float *a1, const float *a2, const float *b1, const float *b2, void *H,
+                           int table_dtype, float *f1, float *f2, int64_t N, int F, int K, int FP,
+                           float in_drop, float fts_drop, uint64_t seed, const uint64_t *seed_dev,
+                           int64_t row_offset, int flags, void *stream);
+
+/* han_project_sparse_bwd: dW (F,D) from the TRANSPOSED (CSC) image of the matrix: colptr (F+1) int64, rowidx (nnz)
+ * int32 in [0, N), ascending within a column, vals_t (nnz) or NULL;
+ *   dW[f, d] = 1/keep * sum over the stored (n, f) of vals * keep_{d/FP}(n + row_offset, f) * dH[n, d].
+ * No float atomics: a wave sums a column in a fixed order, so the result is bitwise reproducible.  EVERY row of dW
+ * is written on every call (a feature without entries gets an exact zero row; N == 0 zeroes dW).
+ * A column can be as long as N, so the columns with more than col_chunk entries ("long": long_cols (n_long) int32,
+ * ascending) are cut into chunks of at most col_chunk entries: chunk c covers the entries [chunk_start[c],
+ * chunk_end[c]) of column chunk_col[c] (int64 / int64 / int32, n_chunks each), the chunks of long_cols[i] are
+ * [long_ptr[i], long_ptr[i+1]) (int64, n_long + 1), in entry order.  A wave per chunk writes a partial row to the
+ * workspace (han_project_sparse_bwd_workspace(n_chunks) bytes, any contents) and a second launch adds a column's
+ * partial rows in ascending chunk order.  n_long == 0: the chunk arguments and the workspace may be NULL.       */
+size_t han_project_sparse_bwd_workspace(int64_t n_chunks);
+int han_project_sparse_bwd(const int64_t *colptr, const int32_t *rowidx, const float *vals_t, int64_t col_chunk,
+                           int64_t n_long, int64_t n_chunks, const int32_t *long_cols, const int64_t *long_ptr,
+                           const int32_t *chunk_col, const int64_t *chunk_start, const int64_t *chunk_end,
+                           const float *dH, float *dW, void *workspace, size_t workspace_bytes, int64_t N, int F,
+                           int K, int FP, float in_drop, uint64_t seed, const uint64_t *seed_dev,
+                           int64_t row_offset, void *stream);
 
 /* Degree bins and row splitting for skewed graphs (optional; pass NULL for none: the library then picks ONE row
  * shape for the whole launch from E / N).
