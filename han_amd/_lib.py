@@ -94,6 +94,8 @@ SIGNATURES = {
     "han_csr_pathsim": (c_int, [P, P, P, I64, P, P, P]),
     "han_csr_row_topk_count": (c_int, [P, P, I64, I64, c_int, P, P]),
     "han_csr_row_topk_fill": (c_int, [P, P, P, I64, I64, c_int, P, P, P, P]),
+    "han_metapath_walk_count": (c_int, [P, P, P, c_int, I64, I64, I64, c_int, c_int, c_uint64, c_int, P, P]),
+    "han_metapath_walk_fill": (c_int, [P, P, P, c_int, I64, I64, I64, c_int, c_int, c_uint64, c_int, P, P, P, P]),
     "han_knn_topk_workspace": (c_size_t, [I64, I64, c_int, c_int]),
     "han_knn_topk": (c_int, [P, I64, P, I64, P, P, P, c_size_t, I64, I64, c_int, c_int, P]),
     "han_knn_vote": (c_int, [P, P, P, I64, c_int, I64, P]),
@@ -102,7 +104,7 @@ SIGNATURES = {
     "han_kmeans_step": (c_int, [P, I64, P, P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, P]),
 }
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 _lib = None
 
 

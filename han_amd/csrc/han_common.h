@@ -27,10 +27,14 @@ typedef float float4_t __attribute__((ext_vector_type(4)));
 //   stream 0  input-feature dropout (layers.py:19)   a = global row, b = f*ceil(K/4) + k/4,  field k%4
 //   stream 1  attention dropout     (layers.py:30)   a = global dst i, b = j*ceil(K/4) + k/4, field k%4
 //   stream 2  projected-row dropout (layers.py:32)   a = global row j, b = d/4,               field d%4
+//             (2 + 4 * slice: the column slices of a head wider than 64 columns)
+//   stream 3  meta-path random walks (metapath.hip)  a = global start node, b = walk * ceil(L/2) + hop/2,
+//             word x for an even hop, y for an odd one (one 32-bit draw per hop, not a 16-bit field)
 // ---------------------------------------------------------------------------
 #define HAN_STREAM_SEQ 0u
 #define HAN_STREAM_COEF 1u
 #define HAN_STREAM_FTS 2u
+#define HAN_STREAM_WALK 3u
 
 struct HanRand64 {
     uint32_t x, y;

@@ -17,6 +17,7 @@
 // Offsets (row pointers, bounds, output positions) are int64 throughout.
 // Weighted graphs (further down): the int64 instance counts of C in one more pass over the same bins, PathSim of a
 // counted graph, and the per-row top-k cut of a graph with values.
+// Sampled neighbours (the last section): meta-path-guided random walks instead of the product, a wave per start row.
 #include "han_common.h"
 
 namespace {
@@ -118,6 +119,26 @@ __device__ __forceinline__ int64_t for_each_candidate(const SpgemmArgs &a, int64
     return for_each_product<G>(a, row, s_off, s_beg, [&](int64_t p, int64_t, int64_t eb) { f(p, a.b_colidx[eb]); });
 }
 
+// ascending bitonic sort of the P (a power of two >= 64) LDS entries of `stage` by one wave (a 64-thread block); the
+// entries must be visible (a barrier after the last write) and are when it returns
+template <typename T>
+__device__ __forceinline__ void bitonic_sort_wave(T *stage, int P) {
+    const int t = threadIdx.x;
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int q = t; q < (P >> 1); q += 64) {
+                const int lo = 2 * q - (q & (j - 1)), hi = lo + j;
+                const T x = stage[lo], y = stage[hi];
+                if ((x > y) == ((lo & k) == 0)) {
+                    stage[lo] = y;
+                    stage[hi] = x;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 template <bool FILL>
 __device__ __forceinline__ void spgemm_short_rows(const SpgemmArgs &a) {
     extern __shared__ int32_t stage[];         // a.stage_cap entries
@@ -140,19 +161,7 @@ __device__ __forceinline__ void spgemm_short_rows(const SpgemmArgs &a) {
             while (P < n) P <<= 1;
             for (int p = n + t; p < P; p += 64) stage[p] = INT32_MAX;     // pads sort last
             __syncthreads();
-            for (int k = 2; k <= P; k <<= 1) {
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    for (int q = t; q < (P >> 1); q += 64) {
-                        const int lo = 2 * q - (q & (j - 1)), hi = lo + j;
-                        const int32_t x = stage[lo], y = stage[hi];
-                        if ((x > y) == ((lo & k) == 0)) {
-                            stage[lo] = y;
-                            stage[hi] = x;
-                        }
-                    }
-                    __syncthreads();
-                }
-            }
+            bitonic_sort_wave(stage, P);
             const int64_t base = FILL ? a.c_rowptr[row] : 0, end = FILL ? a.c_rowptr[row + 1] : 0;
             for (int p0 = 0; p0 < n; p0 += 64) {
                 const int p = p0 + t;
@@ -575,6 +584,236 @@ __global__ __launch_bounds__(256) void topk_fill_block(const int64_t *rowptr, co
     topk_fill_rows<256>(rowptr, colidx, vals, n, k, keep_diag, o_rowptr, o_colidx, o_vals);
 }
 
+
+// ---- sampled neighbours: meta-path-guided random walks -----------------------------------------------------------------
+// (the definition: include/han_hip.h.)  One wave per start row, a persistent grid striding over the rows.  A lane runs
+// kWalkUnroll walks at a time -- every hop is two dependent loads (row pointers, then the drawn entry), so the only
+// parallelism inside a walk is across walks: 4 x 64 walks of a wave are in flight together, and eight waves per SIMD
+// hide the rest.  The end points go to LDS (a dead walk as kWalkDead, above any int32 column), are sorted by the
+// short-row sorter, and the first of every run of equal columns is compacted in place beside its position: the run
+// lengths are the visit counts.  A row with more than `fanout` distinct end points (off the diagonal with diag) is cut
+// by count: a histogram of walks + 1 LDS bins gives the smallest count kept and how many of the columns with exactly
+// that count are still needed; one pass in column order then keeps those of smaller column (as topk_fill_rows).
+// count and fill walk again rather than stage rows x (fanout + 1) words: the K0 convention (no scratch of the size of
+// the output, one kernel body, bitwise the same walks by construction).
+constexpr int kWalkUnroll = 4;
+constexpr int kWalkCap = 4 * kShortCap;
+constexpr uint32_t kWalkDead = 0xFFFFFFFFu;
+
+struct WalkArgs {
+    const int64_t *rowptr[HAN_WALK_MAX_HOPS];
+    const int32_t *colidx[HAN_WALK_MAX_HOPS];
+    int64_t next_rows[HAN_WALK_MAX_HOPS];      // the nodes hop h leads to: rows of hop h + 1, n_cols after the last
+    int n_hops, walks, fanout, diag;
+    int stage_cap;                   // LDS entries of the sort: a power of two >= max(walks, 64)
+    uint32_t seed_lo, seed_hi;
+    int64_t row_base, n_rows;
+    int64_t *counts;                 // count pass
+    const int64_t *c_rowptr;         // fill pass
+    int32_t *c_colidx, *c_visits;
+};
+
+template <bool FILL>
+__device__ __forceinline__ void walk_rows(const WalkArgs &a) {
+    extern __shared__ uint32_t wstage[];       // stage_cap end points, stage_cap + 1 run starts, walks + 1 bins
+    const int t = threadIdx.x;
+    const int P = a.stage_cap, W = a.walks, L = a.n_hops;
+    uint32_t *ends = wstage;
+    int *start = reinterpret_cast<int *>(wstage + P);
+    int *hist = start + P + 1;
+    const uint32_t bq = (uint32_t)((L + 1) >> 1);
+    const uint64_t below = (1ull << t) - 1ull;
+    for (int64_t r = blockIdx.x; r < a.n_rows; r += gridDim.x) {
+        const int64_t i = a.row_base + r;
+        // the walks
+        for (int w0 = 0; w0 < P; w0 += 64 * kWalkUnroll) {
+            int64_t cur[kWalkUnroll];
+            bool alive[kWalkUnroll];
+#pragma unroll
+            for (int u = 0; u < kWalkUnroll; ++u) {
+                cur[u] = i;
+                alive[u] = w0 + 64 * u + t < W;
+            }
+            for (int h = 0; h < L; ++h) {
+                const int64_t *__restrict__ rp = a.rowptr[h];
+                const int32_t *__restrict__ ci = a.colidx[h];
+                const int64_t nxt = a.next_rows[h];
+                int64_t beg[kWalkUnroll], deg[kWalkUnroll];
+#pragma unroll
+                for (int u = 0; u < kWalkUnroll; ++u) {
+                    beg[u] = 0;
+                    deg[u] = 0;
+                    if (alive[u]) {
+                        beg[u] = rp[cur[u]];
+                        deg[u] = rp[cur[u] + 1] - beg[u];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < kWalkUnroll; ++u) {
+                    alive[u] = alive[u] && deg[u] > 0;
+                    if (alive[u]) {
+                        const uint32_t w = (uint32_t)(w0 + 64 * u + t);
+                        const HanRand64 d = han_rand64(a.seed_lo, a.seed_hi, HAN_STREAM_WALK, (uint32_t)i,
+                                                       w * bq + (uint32_t)(h >> 1));
+                        const uint32_t rnd = (h & 1) ? d.y : d.x;
+                        const uint64_t e = ((uint64_t)rnd * (uint64_t)(uint32_t)deg[u]) >> 32;
+                        cur[u] = ci[beg[u] + (int64_t)e];
+                        alive[u] = (uint64_t)cur[u] < (uint64_t)nxt;
+                    }
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kWalkUnroll; ++u) {
+                const int w = w0 + 64 * u + t;
+                if (w < P) ends[w] = alive[u] ? (uint32_t)cur[u] : kWalkDead;      // (the pads beyond W are dead too)
+            }
+        }
+        __syncthreads();
+        bitonic_sort_wave(ends, P);
+        // the first of every run of equal columns, compacted in place: ends[k] the k-th distinct column, start[k] the
+        // position of its run (a write lands at or below the position it was read from, and a chunk is read -- the
+        // barrier -- before it is written)
+        int nu = 0, n_live = 0, seen_diag = 0;
+        uint32_t prev_last = kWalkDead;
+        for (int p0 = 0; p0 < P; p0 += 64) {
+            const uint32_t v = ends[p0 + t];
+            uint32_t prev = __shfl_up(v, 1, 64);
+            if (t == 0) prev = prev_last;
+            const bool live = v != kWalkDead;
+            const bool head = live && (p0 + t == 0 || v != prev);
+            const uint64_t m = __ballot(head);
+            prev_last = __shfl(v, 63, 64);
+            __syncthreads();
+            if (head) {
+                const int k = nu + __popcll(m & below);
+                ends[k] = v;
+                start[k] = p0 + t;
+            }
+            seen_diag |= __ballot(head && a.diag && (int64_t)v == i) != 0ull;
+            nu += __popcll(m);
+            n_live += __popcll(__ballot(live));
+            __syncthreads();
+            if (n_live < p0 + 64) break;         // (uniform: only dead walks follow)
+        }
+        if (t == 0) start[nu] = n_live;
+        const int add_diag = (a.diag && !seen_diag) ? 1 : 0;     // (i, i) with count 0 joins the row
+        const int n_off = nu - seen_diag;                        // the columns that compete for fanout
+        const bool cut = n_off > a.fanout;
+        if (!FILL) {
+            if (t == 0) a.counts[r] = (int64_t)(cut ? a.fanout : n_off) + (a.diag ? 1 : 0);
+            __syncthreads();                 // the stage is rewritten by the next row
+            continue;
+        }
+        __syncthreads();
+        int thr = 0, need = 0;
+        if (cut) {
+            for (int b = t; b <= W; b += 64) hist[b] = 0;
+            __syncthreads();
+            for (int k = t; k < nu; k += 64)
+                if (!(a.diag && (int64_t)ends[k] == i)) atomicAdd(&hist[start[k + 1] - start[k]], 1);
+            __syncthreads();
+            const int B = (W + 63) >> 6;     // lane t owns the counts W - t B, ..., W - t B - (B - 1) (those >= 1)
+            int mine = 0;
+            for (int q = 0; q < B; ++q) {
+                const int c = W - t * B - q;
+                if (c >= 1) mine += hist[c];
+            }
+            int x = mine;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int y = __shfl_up(x, d, 64);
+                if (t >= d) x += y;
+            }
+            const int above = x - mine;
+            int c = 0, left = 0;
+            const bool sel = above < a.fanout && a.fanout <= above + mine;       // exactly one lane (cut)
+            if (sel) {
+                left = a.fanout - above;
+                c = W - t * B;
+                while (c > 1 && hist[c] < left) left -= hist[c--];
+            }
+            const int src = __ffsll((unsigned long long)__ballot(sel)) - 1;
+            thr = __shfl(c, src, 64);
+            need = __shfl(left, src, 64);
+        }
+        const int64_t base = a.c_rowptr[r], end = a.c_rowptr[r + 1];
+        int kept = 0, ties = 0, kept_below = 0;
+        for (int k0 = 0; k0 < nu; k0 += 64) {
+            const int k = k0 + t;
+            bool keep = false, tie = false, lower = false;
+            uint32_t col = 0u;
+            int cnt = 0;
+            if (k < nu) {
+                col = ends[k];
+                cnt = start[k + 1] - start[k];
+                lower = (int64_t)col < i;
+                if (a.diag && (int64_t)col == i) keep = true;
+                else if (!cut) keep = true;
+                else {
+                    tie = cnt == thr;
+                    keep = cnt > thr;
+                }
+            }
+            const int tie_before = __popcll(__ballot(tie) & below);
+            keep = keep || (tie && ties + tie_before < need);
+            const uint64_t mk = __ballot(keep);
+            if (keep) {
+                const int64_t pos = base + kept + __popcll(mk & below) + ((add_diag && !lower) ? 1 : 0);
+                if (pos < end) {
+                    a.c_colidx[pos] = (int32_t)col;
+                    a.c_visits[pos] = cnt;
+                }
+            }
+            ties += __popcll(__ballot(tie));
+            kept += __popcll(mk);
+            kept_below += __popcll(__ballot(keep && lower));
+        }
+        if (add_diag && t == 0 && base + kept_below < end) {
+            a.c_colidx[base + kept_below] = (int32_t)i;
+            a.c_visits[base + kept_below] = 0;
+        }
+        __syncthreads();                     // the stage is rewritten by the next row
+    }
+}
+
+// (eight waves per SIMD: the walks are latency-bound; without the bound the fill form takes 105 scalar registers = 7 waves)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void metapath_walk_count(WalkArgs a) { walk_rows<false>(a); }
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void metapath_walk_fill(WalkArgs a) { walk_rows<true>(a); }
+
+int walk_launch(bool fill, const int64_t *const *hop_rowptr, const int32_t *const *hop_colidx, const int64_t *hop_rows,
+                int n_hops, int64_t n_cols, int64_t row_base, int64_t n_rows, int walks, int fanout, uint64_t seed,
+                int diag, int64_t *counts, const int64_t *c_rowptr, int32_t *c_colidx, int32_t *c_visits,
+                void *stream) {
+    if (!hop_rowptr || !hop_colidx || !hop_rows || n_hops < 1 || n_hops > HAN_WALK_MAX_HOPS) return HAN_E_BADARG;
+    if (walks < 1 || walks > HAN_WALK_MAX_WALKS || fanout < 1 || fanout > walks) return HAN_E_BADARG;
+    if (n_cols < 0 || n_cols > INT32_MAX || row_base < 0 || n_rows < 0) return HAN_E_BADARG;
+    WalkArgs a;
+    for (int h = 0; h < HAN_WALK_MAX_HOPS; ++h) {
+        a.rowptr[h] = nullptr; a.colidx[h] = nullptr; a.next_rows[h] = 0;
+    }
+    for (int h = 0; h < n_hops; ++h) {
+        if (!hop_rowptr[h] || hop_rows[h] < 0) return HAN_E_BADARG;
+        a.rowptr[h] = hop_rowptr[h];
+        a.colidx[h] = hop_colidx[h];
+        a.next_rows[h] = h + 1 < n_hops ? hop_rows[h + 1] : n_cols;
+    }
+    if (row_base + n_rows > hop_rows[0]) return HAN_E_BADARG;
+    if (diag && n_cols != hop_rows[0]) return HAN_E_BADARG;
+    if (fill ? !c_rowptr : !counts) return HAN_E_BADARG;
+    if (n_rows == 0) return 0;
+    a.n_hops = n_hops; a.walks = walks; a.fanout = fanout; a.diag = diag ? 1 : 0;
+    int cap = 64;
+    while (cap < walks) cap <<= 1;
+    a.stage_cap = cap;
+    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32);
+    a.row_base = row_base; a.n_rows = n_rows;
+    a.counts = counts; a.c_rowptr = c_rowptr; a.c_colidx = c_colidx; a.c_visits = c_visits;
+    const size_t lds = ((size_t)2 * cap + 1 + (size_t)walks + 1) * sizeof(uint32_t);
+    const hipError_t e = han_launch_lds(fill ? metapath_walk_fill : metapath_walk_count,
+                                        dim3(han_grid_for(n_rows, 1, kWalkCap)), dim3(64), lds, (hipStream_t)stream, a);
+    return e == hipSuccess ? 0 : (int)e;
+}
+
 }  // namespace
 
 extern "C" int han_spgemm_row_bounds(const int64_t *a_rowptr, const int32_t *a_colidx, const int64_t *b_rowptr,
@@ -667,4 +906,20 @@ extern "C" int han_csr_row_topk_fill(const int64_t *rowptr, const int32_t *colid
                                                                           out_values);
     HAN_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int han_metapath_walk_count(const int64_t *const *hop_rowptr, const int32_t *const *hop_colidx,
+                                       const int64_t *hop_rows, int n_hops, int64_t n_cols, int64_t row_base,
+                                       int64_t n_rows, int walks, int fanout, uint64_t seed, int diag, int64_t *counts,
+                                       void *stream) {
+    return walk_launch(false, hop_rowptr, hop_colidx, hop_rows, n_hops, n_cols, row_base, n_rows, walks, fanout, seed,
+                       diag, counts, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int han_metapath_walk_fill(const int64_t *const *hop_rowptr, const int32_t *const *hop_colidx,
+                                      const int64_t *hop_rows, int n_hops, int64_t n_cols, int64_t row_base,
+                                      int64_t n_rows, int walks, int fanout, uint64_t seed, int diag,
+                                      const int64_t *c_rowptr, int32_t *c_colidx, int32_t *c_visits, void *stream) {
+    return walk_launch(true, hop_rowptr, hop_colidx, hop_rows, n_hops, n_cols, row_base, n_rows, walks, fanout, seed,
+                       diag, nullptr, c_rowptr, c_colidx, c_visits, stream);
 }

@@ -12,6 +12,12 @@ straight into ``bias_mat_list``::
            "PC": relation(paper_ids2, conf_ids, n_papers, n_confs, device=dev)}
     graphs = [metapath_graph(rel, mp) for mp in ("APA", "APCPA")]
 
+Where a hub type sits on the path (a conference, a term) the product is close to dense, and ``top_k`` prunes a graph
+that first has to exist.  ``metapath_sample`` draws the neighbours instead: meta-path-guided random walks from every
+node, the ``fanout`` most visited end points kept (``ops.metapath_walk``, ``han_metapath_walk_*``)::
+
+    graphs = [metapath_sample(rel, mp, walks=256, fanout=32, weights="prob") for mp in ("APCPA", "APTPA")]
+
 Node types are single letters; ``relations`` maps an ordered pair ``"XY"`` to the graph with rows = X nodes and
 columns = Y nodes, and a hop Y -> X without its own relation runs on the transpose of ``"XY"``.
 """
@@ -215,3 +221,43 @@ def metapath_graph(relations: dict, metapath: str, self_loops: bool = True, weig
         ht, htc = _transposed(h, hc) if hc is not None else (h.transpose(), None)
         g, counts = ops.csr_count_matmul(h, ht, a_counts=hc, b_counts=htc, diag=self_loops)
     return g if not counted else _weighted(g, counts, weights, top_k)
+
+
+SAMPLE_WEIGHTS = (None, "count", "prob")
+
+
+def metapath_sample(relations: dict, metapath: str, walks: int = 256, fanout=32, seed: int = 0,
+                    self_loops: bool = True, weights=None, rows=None) -> CSRGraph:
+    """Sampled neighbours of `metapath` over typed `relations`, without the product: from every start node `walks`
+    random walks along the path -- at every hop a uniformly drawn stored entry of the current node's row, a reverse hop
+    on the transpose as in metapath_graph; a node without entries ends the walk --, and per start node the `fanout`
+    (None = walks) most visited end points, ties to the smaller id.  Every entry is an entry of metapath_graph(...);
+    a row holds at most fanout + 1.  self_loops (the default; the path must end on the type it starts from): (i, i) is
+    always stored, with its own visit count, and does not compete for fanout.
+
+    weights: None -- a boolean graph; "count" -- values = the visits c_ij as fp32; "prob" -- c_ij / walks in fp32, the
+    estimate of the random-walk transition probability (walks that died stay in the denominator): in [0, 1], like
+    PathSim it does not saturate the softmax.  An (i, i) that no walk reached has value 0.
+    seed: 64 bits; the draw of (start node, walk, hop) is a counter-based hash of it (include/han_hip.h), so the result
+    is bitwise reproducible and rows = (r0, r1) returns exactly those rows of the whole graph, with global columns and
+    row_base = r0 -- the shard a rank hands to HANTrainer(graphs_local=True).  The H Hᵀ form of metapath_graph is
+    never used: a walk has no use for H."""
+    if weights not in SAMPLE_WEIGHTS:
+        raise ValueError(f"weights = {weights!r}: expected None, 'count' or 'prob'")
+    walks, fanout, seed = ops._walk_limits(walks, fanout, seed)
+    p = plan(relations, metapath)
+    if len(p["hops"]) > ops.WALK_MAX_HOPS:
+        raise ValueError(f"meta-path {metapath!r}: {len(p['hops'])} hops, at most {ops.WALK_MAX_HOPS} are walked")
+    if self_loops and metapath[0] != metapath[-1]:
+        raise ValueError(f"meta-path {metapath!r}: self_loops needs a path that ends on the type it starts from")
+    ops._walk_rows(rows, p["sizes"][metapath[0]])
+    for key, _ in p["hops"]:
+        ops.require_gpu(relations[key].rowptr, f"relations[{key!r}]")
+    hops = [relations[k].transpose() if t else relations[k] for k, t in p["hops"]]
+    g, visits = ops.metapath_walk(hops, walks, fanout, seed=seed, diag=self_loops, rows=rows)
+    if weights is None:
+        return g
+    values = visits.to(torch.float32)
+    if weights == "prob":
+        values = values / torch.tensor(float(walks), dtype=torch.float32, device=values.device)
+    return CSRGraph(g.rowptr, g.colidx, g.n_cols, validate=False, values=values, row_base=g.row_base)

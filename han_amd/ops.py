@@ -965,6 +965,87 @@ def csr_row_topk(graph: CSRGraph, k: int, keep_diag: bool = True) -> CSRGraph:
     return CSRGraph(rowptr, colidx, graph.n_cols, validate=False, values=values)
 
 
+WALK_MAX_HOPS = 8          # HAN_WALK_MAX_HOPS
+WALK_MAX_WALKS = 4096      # HAN_WALK_MAX_WALKS
+
+
+def _walk_limits(walks, fanout, seed):
+    """(walks, fanout, seed) as ints, fanout None = walks; ValueError outside 1 <= fanout <= walks <= WALK_MAX_WALKS
+    or a seed that is not 64 bits."""
+    _chk_int(walks, "walks", 1, WALK_MAX_WALKS)
+    if fanout is None:
+        fanout = walks
+    _chk_int(fanout, "fanout", 1, int(walks))
+    _chk_int(seed, "seed", 0, (1 << 64) - 1)
+    return int(walks), int(fanout), int(seed)
+
+
+def _walk_rows(rows, n):
+    """The start-row range (r0, r1) of `rows` (None: all n)."""
+    if rows is None:
+        return 0, n
+    try:
+        r0, r1 = rows
+        ok = all(not isinstance(r, bool) and int(r) == r for r in (r0, r1))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not 0 <= r0 <= r1 <= n:
+        raise ValueError(f"rows = {rows!r}: expected a range (r0, r1) with 0 <= r0 <= r1 <= {n}")
+    return int(r0), int(r1)
+
+
+def metapath_walk(hops, walks: int, fanout=None, seed: int = 0, diag: bool = False, rows=None):
+    """Sampled meta-path neighbours (han_metapath_walk_*): from every start node of `rows` = (r0, r1) (default: every
+    row of hops[0]) `walks` random walks along the chain `hops` (1 to 8 CSRGraphs, hops[k].n_cols == hops[k+1].n_rows;
+    a repeated stored entry is as many parallel edges, a node without entries ends the walk), and per start row the
+    `fanout` (None = walks) most visited end points, ties to the smaller column.  diag=True (square chains): (i, i) is
+    always kept, with its own visit count (possibly 0), beside the fanout best of the others.  Returns (graph, visits):
+    a CSRGraph of r1 - r0 rows (row_base = r0, global columns, strictly increasing per row, values None) and the visit
+    count of every entry, int32.  The draws depend on (seed, global start node, walk, hop) only -- include/han_hip.h
+    states them --, so a row range returns exactly its rows of the whole result.  Count and fill launches; the one
+    host sync reads nnz."""
+    hops = list(hops)
+    if not 1 <= len(hops) <= WALK_MAX_HOPS:
+        raise ValueError(f"metapath_walk: {len(hops)} hops, expected 1 to {WALK_MAX_HOPS}")
+    for k, g in enumerate(hops):
+        if not isinstance(g, CSRGraph):
+            raise ValueError(f"hops[{k}]: expected a CSRGraph, got {type(g)}")
+    for k in range(len(hops) - 1):
+        if hops[k].n_cols != hops[k + 1].n_rows:
+            raise ValueError(f"hops[{k}] has {hops[k].n_cols} columns, hops[{k + 1}] has {hops[k + 1].n_rows} rows")
+    walks, fanout, seed = _walk_limits(walks, fanout, seed)
+    n, n_cols = hops[0].n_rows, hops[-1].n_cols
+    if diag and n != n_cols:
+        raise ValueError(f"diag needs a square result, got {n} x {n_cols}")
+    r0, r1 = _walk_rows(rows, n)
+    for k, g in enumerate(hops):
+        require_gpu(g.rowptr, f"hops[{k}]")
+        if g.device != hops[0].device:
+            raise ValueError(f"hops[{k}] on {g.device}, hops[0] on {hops[0].device}")
+        if g.nnz >= 1 << 32 and int(g.degrees().max()) >= 1 << 32:      # (only such a graph costs a sync of its own)
+            raise ValueError(f"hops[{k}] has a row of 2^32 entries or more: the draw is a 32-bit word")
+    lib, dev, st, L, m = _lib.load(), hops[0].device, _stream(), len(hops), r1 - r0
+    rowptr = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    if m == 0:
+        return (CSRGraph(rowptr, torch.zeros(0, dtype=torch.int32, device=dev), n_cols, validate=False, row_base=r0),
+                torch.zeros(0, dtype=torch.int32, device=dev))
+    rps = (ctypes.c_void_p * L)(*[g.rowptr.data_ptr() for g in hops])
+    cis = (ctypes.c_void_p * L)(*[g.colidx.data_ptr() if g.nnz else None for g in hops])
+    nrs = (ctypes.c_int64 * L)(*[g.n_rows for g in hops])
+    args = (ctypes.cast(rps, ctypes.c_void_p), ctypes.cast(cis, ctypes.c_void_p), ctypes.cast(nrs, ctypes.c_void_p),
+            L, n_cols, r0, m, walks, fanout, seed, int(bool(diag)))
+    counts = torch.empty(m, dtype=torch.int64, device=dev)
+    _lib.check(lib.han_metapath_walk_count(*args, counts.data_ptr(), st), "han_metapath_walk_count")
+    torch.cumsum(counts, 0, out=rowptr[1:])
+    nnz = int(rowptr[-1])
+    colidx = torch.empty(nnz, dtype=torch.int32, device=dev)
+    visits = torch.empty(nnz, dtype=torch.int32, device=dev)
+    if nnz:
+        _lib.check(lib.han_metapath_walk_fill(*args, rowptr.data_ptr(), colidx.data_ptr(), visits.data_ptr(), st),
+                   "han_metapath_walk_fill")
+    return CSRGraph(rowptr, colidx, n_cols, validate=False, row_base=r0), visits
+
+
 # ------------------------------------------------- evaluation of the embeddings
 KNN_MAX_K = 16             # neighbours per query of han_knn_topk
 EVAL_MAX_D = 512           # embedding width of han_knn_topk / han_kmeans_step

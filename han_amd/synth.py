@@ -251,6 +251,10 @@ HETERO = {
     "dblp-like": dict(A=4057, P=14328, C=20, T=8000),
     # PAP at scale: three authors per paper (a repeated draw counts once), author popularity ~ rank^-0.5
     "pap-3m": dict(P=3_000_000, A=1_000_000),
+    # a hub type on the path: the pap-3m paper-author relation (bitwise) plus one venue per paper, venue popularity
+    # ~ rank^-1 over 4000 venues (the largest holds ~ 11 % of the papers).  APCPA of this preset is never formed: a
+    # venue of m papers alone contributes ~ (3 m)^2 author pairs -- metapath.metapath_sample draws its neighbours
+    "hub-1m": dict(P=3_000_000, A=1_000_000, C=4000),
 }
 
 
@@ -292,20 +296,27 @@ def hetero_relations(name: str, seed: int = 0, device="cpu"):
     """Typed relations of a synthetic heterogeneous graph, the input of han_amd.metapath: returns (relations,
     sizes) -- relations maps an ordered type pair to its CSRGraph (rows = nodes of the first type), sizes the node
     count per type.  "dblp-like": {"AP", "PC", "PT"} (APA / APCPA / APTPA as in the DBLP experiments of the
-    reference); "pap-3m": {"PA"} (PAP).  Block-seeded over the papers, like the rest of this module."""
+    reference); "pap-3m": {"PA"} (PAP); "hub-1m": {"PA", "PC"} (APCPA through Zipf-distributed venues, to be sampled).
+    Block-seeded over the papers, like the rest of this module."""
     from .metapath import relation
     if name not in HETERO:
         raise ValueError(f"unknown heterogeneous workload {name!r}: expected one of {sorted(HETERO)}")
     cfg = HETERO[name]
     n_p, n_a = cfg["P"], cfg["A"]
-    if name == "pap-3m":
+    if name in ("pap-3m", "hub-1m"):
         cdf = _zipf_cdf(n_a, 0.5, device)
         src, dst = [], []
         for b, lo, hi in _blocks(0, n_p):
             gen = _block_generator(seed, 41, b, device)
             src.append(torch.arange(b * ROW_BLOCK + lo, b * ROW_BLOCK + hi, device=device).repeat_interleave(3))
             dst.append(_zipf_draw(cdf, (hi - lo) * 3, gen, device))
-        return {"PA": relation(torch.cat(src), torch.cat(dst), n_p, n_a)}, dict(cfg)
+        rel = {"PA": relation(torch.cat(src), torch.cat(dst), n_p, n_a)}
+        if name == "hub-1m":
+            v_cdf = _zipf_cdf(cfg["C"], 1.0, device)
+            venue = [_zipf_draw(v_cdf, hi - lo, _block_generator(seed, 43, b, device), device)
+                     for b, lo, hi in _blocks(0, n_p)]
+            rel["PC"] = relation(torch.arange(n_p, device=device), torch.cat(venue), n_p, cfg["C"])
+        return rel, dict(cfg)
     n_c, n_t, areas = cfg["C"], cfg["T"], 4
     per_area = (n_a + areas - 1) // areas          # author a belongs to area a % 4
     a_cdf, t_cdf = _zipf_cdf(per_area, 0.8, device), _zipf_cdf(n_t, 1.1, device)

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HAN_ABI_VERSION 10
+#define HAN_ABI_VERSION 11
 
 #define HAN_E_BADARG   (-1)   /* null pointer, negative size, inconsistent shape.  The forward
                               * entry points return 0 at once for N == 0 (empty tensors may
@@ -501,6 +501,44 @@ int han_csr_row_topk_count(const int64_t *rowptr, const int32_t *colidx, int64_t
 int han_csr_row_topk_fill(const int64_t *rowptr, const int32_t *colidx, const float *values, int64_t n_rows,
                           int64_t k, int keep_diag, const int64_t *out_rowptr, int32_t *out_colidx,
                           float *out_values, void *stream);
+
+/* ---- K0: sampled meta-path neighbours (ABI 11) ------------------------------
+ * Meta-path-guided random walks instead of the product: from every start node `walks` walks along the chain of
+ * n_hops graphs (1 <= n_hops <= HAN_WALK_MAX_HOPS), the end points counted per start row, and the `fanout` most
+ * visited kept -- a CSR row of at most fanout + 1 entries whatever the product would hold.
+ * hop h (rows = current nodes, columns = next nodes): hop_rowptr[h] (hop_rows[h] + 1) int64, hop_colidx[h] int32 --
+ * HOST arrays of n_hops DEVICE pointers (read during the call, not kept); hop_rows: host array of the row counts;
+ * a hop_colidx[h] may be NULL when its graph has no entries.  Columns need not be sorted or unique: a repeated
+ * stored entry is as many parallel edges.  n_cols: the columns of the last hop.
+ * Start node i = row_base + r, r in [0, n_rows) (row_base + n_rows <= hop_rows[0]); walk w in [0, walks),
+ * 1 <= walks <= HAN_WALK_MAX_WALKS: cur = i, and for h = 0 .. n_hops - 1
+ *     deg = the stored entries of row cur of hop h; deg == 0: the walk dies and counts nowhere;
+ *     (x, y) = han_rand64(seed, stream 3, a = (uint32) i, b = w * ((n_hops + 1) / 2) + (h >> 1));
+ *     r = (h & 1) ? y : x;   e = ((uint64) r * deg) >> 32;   cur = colidx[rowptr[cur] + e].
+ * The draw depends on (seed, i, w, h) alone: not on the launch shape, the row range or the lane that walks.  The
+ * multiply-high map picks an entry with probability within 2^-32 of 1 / deg (relative bias below deg / 2^32).  Not
+ * checked: deg < 2^32 (the caller's; the low 32 bits are used, nothing is read out of bounds).  A column outside the
+ * next hop's rows (or outside [0, n_cols) at the end) ends the walk like a dead end.
+ * Row r of the result: c_j = walks of i that end in j.  diag == 0: the 1 <= fanout <= walks columns of largest c_j,
+ * ties to the smaller column.  diag != 0 (n_cols == hop_rows[0]): (i, i) is always stored with its own visit count,
+ * possibly 0, and does not compete: the fanout best of the OTHER columns are kept beside it.  Columns strictly
+ * ascending; a row whose walks all died is empty (diag: (i, i) alone, count 0).
+ *   han_metapath_walk_count: counts (n_rows) int64, the entries of every row; the caller scans them into c_rowptr
+ *       (n_rows + 1, local rows) and allocates c_colidx / c_visits (c_rowptr[n_rows] entries each);
+ *   han_metapath_walk_fill: the same walks again (same arguments), c_colidx int32 and c_visits int32 = c_j.
+ * A wave per start row; end points, their sort, the run lengths and a histogram of the counts stay in LDS: nothing of
+ * n_rows x walks words exists in device memory, integer LDS adds only, so the result is bitwise reproducible.
+ * Both run on `stream`, allocate nothing and never synchronise.  No seed_dev variant: building a graph is never
+ * captured into a hipGraph.                                                                                         */
+#define HAN_WALK_MAX_HOPS 8
+#define HAN_WALK_MAX_WALKS 4096
+int han_metapath_walk_count(const int64_t *const *hop_rowptr, const int32_t *const *hop_colidx,
+                            const int64_t *hop_rows, int n_hops, int64_t n_cols, int64_t row_base, int64_t n_rows,
+                            int walks, int fanout, uint64_t seed, int diag, int64_t *counts, void *stream);
+int han_metapath_walk_fill(const int64_t *const *hop_rowptr, const int32_t *const *hop_colidx,
+                           const int64_t *hop_rows, int n_hops, int64_t n_cols, int64_t row_base, int64_t n_rows,
+                           int walks, int fanout, uint64_t seed, int diag, const int64_t *c_rowptr,
+                           int32_t *c_colidx, int32_t *c_visits, void *stream);
 
 /* ---- evaluation of the embeddings (ABI 9) -----------------------------------
  * The reference scores final_embed on the host with scikit-learn: my_KNN (jhyexp.py:20-51) and my_Kmeans

@@ -18,12 +18,21 @@ One JSON line per (preset, meta-path):
 count_ms (weights="count"), pathsim_ms, pathsim_topk_ms (weights="pathsim", top_k=--top-k), count_over_bool, and
 scipy_count_s = scipy's int64 product of the same chain (+ the stored diagonal, indices sorted), count_exact = the GPU
 counts equal it, count_vs_scipy = scipy_count_s / count_ms.
+--sample: the sampler (metapath.metapath_sample, han_metapath_walk_*) -- per DBLP-like hub meta-path sample_ms
+(--walks, --fanout, weights="prob") beside pathsim_topk_ms of the same process and median, and recall@W for W = 64 / 256 /
+1024: the share of the exact `fanout` strongest neighbours by random-walk transition probability (scipy on the host: the
+product of the row-normalised relations, ties to the smaller column) that the sampled rows hold; for the hub preset
+(10^6 authors, APCPA never formed) sample_ms at --walks / --hub-fanout, nnz, reads_per_pass = 2 x rows x walks x hops
+(row pointers and the drawn entry of every hop; count and fill are a pass each), and -- unless --no-train -- epochs/s of
+HANTrainer on four such graphs beside the regular SYN-1M graphs of bench.py in the same process.
 
     python tools/metapath_bench.py [--out FILE]
     python tools/metapath_bench.py --sweep [--out FILE]
     python tools/metapath_bench.py --no-scipy            # GPU only (the rocprofv3 run)
     python tools/metapath_bench.py --weights [--out FILE]
     python tools/metapath_bench.py --weights --no-scipy --presets pap-3m --reps 1     # (the rocprofv3 run)
+    python tools/metapath_bench.py --sample --presets dblp-like,hub-1m [--out FILE]
+    python tools/metapath_bench.py --sample --no-scipy --no-train --presets hub-1m --reps 1   # (the rocprofv3 run)
 """
 import argparse
 import json
@@ -39,7 +48,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from han_amd import metapath, ops, synth  # noqa: E402
 from han_amd.graph import CSRGraph  # noqa: E402
 
-PRESETS = {"dblp-like": ("APA", "APCPA", "APTPA"), "pap-3m": ("PAP",)}
+PRESETS = {"dblp-like": ("APA", "APCPA", "APTPA"), "pap-3m": ("PAP",), "hub-1m": ("APCPA",)}
 
 
 def fresh(rel):
@@ -47,7 +56,7 @@ def fresh(rel):
     return {k: CSRGraph(g.rowptr, g.colidx, g.n_cols, validate=False) for k, g in rel.items()}
 
 
-def gpu_time(rel, mp, reps, **kw):
+def gpu_time(rel, mp, reps, build=metapath.metapath_graph, **kw):
     ts, out = [], None
     for i in range(2 + reps):
         r = fresh(rel)
@@ -55,7 +64,7 @@ def gpu_time(rel, mp, reps, **kw):
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        out = metapath.metapath_graph(r, mp, **kw)
+        out = build(r, mp, **kw)
         e1.record()
         torch.cuda.synchronize()
         if i >= 2:
@@ -139,6 +148,89 @@ def weights_line(rel, host, preset, mp, plan, reps, top_k):
     return d
 
 
+def exact_top(host, hops, fanout):
+    """Per row the `fanout` off-diagonal columns of largest random-walk transition probability (the product of the
+    row-normalised relations along `hops`, float64, ties to the smaller column): a list of int arrays."""
+    p = None
+    for key, t in hops:
+        m = sp.csr_matrix(host[key].T if t else host[key], dtype=np.float64)
+        deg = np.asarray(m.sum(1)).ravel()
+        m = sp.diags(np.divide(1.0, deg, out=np.zeros_like(deg), where=deg > 0)) @ m
+        p = m if p is None else p @ m
+    p = sp.csr_matrix(p)
+    p.sort_indices()
+    top = []
+    for i in range(p.shape[0]):
+        cols, vals = p.indices[p.indptr[i]:p.indptr[i + 1]], p.data[p.indptr[i]:p.indptr[i + 1]]
+        off = cols != i
+        cols, vals = cols[off], vals[off]
+        top.append(cols[np.lexsort((cols, -vals))[:fanout]])
+    return top
+
+
+def recall(g, top):
+    rp, ci = g.rowptr.cpu().numpy(), g.colidx.cpu().numpy()
+    hit = sum(np.intersect1d(ci[rp[i]:rp[i + 1]], t, assume_unique=True).size for i, t in enumerate(top))
+    return hit / max(1, sum(t.size for t in top))
+
+
+def epochs_per_s(x, graphs, labels, train_mask, val_mask, dev, warmup=3, steps=30):
+    """bench.py's model and trainer settings (eager, one stream) on `graphs`: epochs per second."""
+    from han_amd.gat import HeteGAT_multi
+    from han_amd.trainer import HANTrainer
+    model = HeteGAT_multi().build(len(graphs), x.shape[1], 4, (8,), (8, 1), 128, device=dev,
+                                  generator=torch.Generator().manual_seed(0))
+    tr = HANTrainer(model, [x] * len(graphs), graphs, labels, train_mask, val_mask, lr=0.005, l2_coef=0.001,
+                    attn_drop=0.6, ffd_drop=0.6)
+    for _ in range(warmup):
+        tr.epoch()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        last = tr.epoch()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert np.isfinite(float(last[0]))
+    return steps / dt
+
+
+def sample_line(rel, host, preset, mp, plan, args, dev):
+    hub = preset == "hub-1m"
+    fanout = args.hub_fanout if hub else args.fanout
+    n = plan["sizes"][mp[0]]
+    d = dict(preset=preset, metapath=mp, rows=n, walks=args.walks, fanout=fanout)
+    g, ts = gpu_time(rel, mp, args.reps, build=metapath.metapath_sample, walks=args.walks, fanout=fanout,
+                     weights="prob")
+    d.update(sample_ms=round(float(np.median(ts)), 4), sample_ms_all=[round(t, 4) for t in ts], nnz=g.nnz,
+             max_row=int(g.degrees().max()), reads_per_pass=2 * n * args.walks * len(plan["hops"]))
+    del g
+    if not hub:
+        g, ts = gpu_time(rel, mp, args.reps, weights="pathsim", top_k=fanout)
+        d.update(pathsim_topk_ms=round(float(np.median(ts)), 4), pathsim_topk_ms_all=[round(t, 4) for t in ts],
+                 nnz_pathsim_topk=g.nnz)
+        d["pathsim_topk_over_sample"] = round(d["pathsim_topk_ms"] / d["sample_ms"], 2)
+        del g
+        if host is not None:
+            top = exact_top(host, plan["hops"], fanout)
+            for w in (64, 256, 1024):
+                s = metapath.metapath_sample(rel, mp, walks=w, fanout=min(fanout, w))
+                d[f"recall_at_{w}"] = round(recall(s, top), 4)
+    elif not args.no_train:
+        graphs = [metapath.metapath_sample(rel, mp, walks=args.walks, fanout=fanout, seed=s) for s in range(4)]
+        wl = synth.make_workload("syn-1m", device=dev)
+        assert wl["n"] == n
+        d["epochs_per_s_sampled"] = round(epochs_per_s(wl["x"], graphs, wl["labels"], wl["train_mask"], wl["val_mask"],
+                                                       dev), 2)
+        d["nnz_train_graphs"] = sum(g.nnz for g in graphs)
+        del graphs
+        torch.cuda.empty_cache()
+        d["epochs_per_s_syn1m"] = round(epochs_per_s(wl["x"], wl["graphs"], wl["labels"], wl["train_mask"],
+                                                     wl["val_mask"], dev), 2)
+        d["nnz_syn1m"] = sum(g.nnz for g in wl["graphs"])
+    torch.cuda.empty_cache()
+    return d
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--presets", default="dblp-like,pap-3m")
@@ -146,6 +238,11 @@ def main():
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--weights", action="store_true")
     ap.add_argument("--top-k", type=int, default=32)
+    ap.add_argument("--sample", action="store_true")
+    ap.add_argument("--walks", type=int, default=256)
+    ap.add_argument("--fanout", type=int, default=32)
+    ap.add_argument("--hub-fanout", type=int, default=49)
+    ap.add_argument("--no-train", action="store_true")
     ap.add_argument("--no-scipy", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -161,9 +258,13 @@ def main():
 
     for preset in args.presets.split(","):
         rel, sizes = synth.hetero_relations(preset, device=dev)
-        host = None if (args.no_scipy or args.sweep) else {k: to_scipy(g) for k, g in rel.items()}
+        host = None if (args.no_scipy or args.sweep or preset == "hub-1m") else {k: to_scipy(g) for k, g in rel.items()}
         for mp in PRESETS[preset]:
             plan = metapath.plan(rel, mp)
+            if args.sample:
+                if mp != "APA":                # (the hub meta-paths: APA is small as a product)
+                    emit(sample_line(rel, host, preset, mp, plan, args, dev))
+                continue
             if args.sweep:
                 for S in (256, 1024, 4096):
                     for T in (1 << 15, 1 << 17, 1 << 19):
