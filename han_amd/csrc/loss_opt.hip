@@ -25,6 +25,19 @@ struct ClsArgs {
     int C, HC;
 };
 
+// Sum over an aligned group of 16 lanes as a butterfly (lane distances 1, 2, 4, 8): every lane adds the same pairs in the
+// same order, so all 16 hold the SAME bits.  han_row16_sum ends in two row rotations instead, after which the four quads
+// of a group hold differently associated sums (an ulp apart).  Here lane c stores logit c while lane 0 takes the
+// argmax and the loss from its own copies: with the rotations two classes with identical weights got different stored
+// logits, and the argmax of the stored row could differ from the one the accuracy counted.  Same four DPP adds.
+__device__ __forceinline__ float cls_row16_sum(float v) {
+    v += han_dpp_xor16<1>(v);
+    v += han_dpp_xor16<2>(v);
+    v += han_dpp_xor16<4>(v);
+    v += han_dpp_xor16<8>(v);
+    return v;
+}
+
 // CM = compile-time bound on the class count (4, 8 or 16): every per-class loop is
 // unrolled to CM, so small C does not pay for 16 shuffle reductions per row.
 // NV = float4 column groups per lane: the embedding width is D = 64*NV (lane q of a 16-lane
@@ -83,7 +96,7 @@ __global__ __launch_bounds__(256) void classifier_kernel(const ClsArgs a) {
             float s = 0.f;
 #pragma unroll
             for (int t = 0; t < NT; ++t) s += z[t] * wq[t][c];
-            s = han_row16_sum(s);
+            s = cls_row16_sum(s);
             lg[c] = c < C ? s + bq[c] : HAN_NEG_BIG;
         }
         if (q < C) {
