@@ -13,6 +13,7 @@
 // input dropout (layers.py:18-19 sits inside the per-head call) forces one
 // masked MFMA per head per 16-column tile.
 #include "han_b6.h"
+#include "han_k1_epilogue.h"
 
 namespace {
 
@@ -21,104 +22,30 @@ constexpr int BK = 32;      // K-step
 constexpr int XS_LD = 34;   // LDS leading dims chosen conflict-free for the MFMA fragment reads
 constexpr int WS_LD = 80;
 
-struct ProjFwdArgs {
+// the stored-row half (H, scores, projected-row dropout key: han_k1_epilogue.h) plus what the main loops read
+struct ProjFwdArgs : K1Epilogue {
     const unsigned char *wimg;   // bf16 x 6 kernels: the pre-split, LDS-ready image of W (project_wimage_kernel), in the workspace
     const void *X;      // fp32 or bf16 (x_bf16), row stride ldx ELEMENTS
     int64_t ldx;
     const float *W;
-    void *H;            // fp32 or bf16 (h_bf16), 64 elements per row
-    int x_bf16, h_bf16;
-    int64_t N;
-    int F;
-    uint32_t seed_lo, seed_hi, thr_in, thr_fts;   // thr_fts < 2^16: stamp keep bits into H
-    uint32_t fts_stream;                          // HAN_STREAM_FTS + 4 * slice (HAN_FLAG_FTS_SLICE: slices of a wide head)
-    const uint64_t *seed_dev;
+    int x_bf16, F;
+    uint32_t thr_in;    // input dropout (its seed is the epilogue's)
     float inv_keep_in;
-    int64_t row_offset;
-    // split-F for short inputs (few row blocks, long reduction): blockIdx.y owns the
-    // features [y*f_chunk, (y+1)*f_chunk) and writes a raw partial tile to `partial`
-    // ([nsplit][N][64] fp32); project_finish_kernel sums them in a fixed order.
+    // split-F for short inputs (few row blocks, long reduction): blockIdx.y owns the features [y*f_chunk, (y+1)*f_chunk)
+    // and writes a raw partial tile to `partial` ([nsplit][N][64] fp32); project_finish_kernel sums them in a fixed
+    // order and runs the epilogue (f1 is null in the main kernel then)
     int f_chunk;        // multiple of BK; >= F when not split
     float *partial;     // null when not split
-    // attention scores in the epilogue (layers.py:23-24), from the values exactly as stored; null f1 = not fused
-    // (split-F: project_scores_kernel runs after the finish kernel)
-    const float *a1, *a2, *b1, *b2;
-    float *f1, *f2;
     // keep table of the per-head input dropout for the backward (han_hip.h: han_project_keep_bytes), or null
     uint8_t *keep;
 };
-
-// f1 = H_k . a1_k + b1_k, f2 likewise, for the row whose stored elements (row, 16t + l15), t < 4, this lane
-// holds in vst[]: the F' columns of a head sit in min(F',16) consecutive lanes of a 16-lane group and in
-// max(1, F'/16) column tiles.  Epilogue code (once per output element), not a hot loop.
-template <int FP>
-__device__ __forceinline__ void tile_scores(const ProjFwdArgs &a, int64_t row, bool row_ok, const float (&vst)[4],
-                                            const float (&a1c)[4], const float (&a2c)[4], int l15) {
-    constexpr int K = HAN_D / FP;
-    constexpr int NT = FP >= 16 ? FP / 16 : 1;       // column tiles per head
-    constexpr int NL = FP >= 16 ? 16 : FP;           // lanes per head inside a tile
-    float r1[4 / NT], r2[4 / NT];
-#pragma unroll
-    for (int u = 0; u < 4 / NT; ++u) {
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int t = u * NT; t < (u + 1) * NT; ++t) {
-            s1 += vst[t] * a1c[t];
-            s2 += vst[t] * a2c[t];
-        }
-        // butterfly over the head's NL lanes on DPP operands (bitwise the __shfl_xor butterfly, without its 3-4
-        // ds_bpermute round trips per sum: the fused eval kernel issued 1024 of them per wave)
-        if (NL > 1) { s1 += han_dpp_xor16<1>(s1); s2 += han_dpp_xor16<1>(s2); }
-        if (NL > 2) { s1 += han_dpp_xor16<2>(s1); s2 += han_dpp_xor16<2>(s2); }
-        if (NL > 4) { s1 += han_dpp_xor16<4>(s1); s2 += han_dpp_xor16<4>(s2); }
-        if (NL > 8) { s1 += han_dpp_xor16<8>(s1); s2 += han_dpp_xor16<8>(s2); }
-        r1[u] = s1;
-        r2[u] = s2;
-    }
-    if (FP == 8) {
-        // lanes 0 / 8 of the group hold heads 2u / 2u+1: bring the odd heads over and let lane 0 write the
-        // row's 8 scores as two 16-byte stores (16 scattered 4-byte stores per row cost as much as the
-        // separate scores kernel they replaced)
-        float4_t o1[2], o2[2];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const float e1 = han_dpp_xor16<8>(r1[u]), e2 = han_dpp_xor16<8>(r2[u]);
-            o1[u >> 1][2 * (u & 1)] = r1[u] + a.b1[2 * u];
-            o1[u >> 1][2 * (u & 1) + 1] = e1 + a.b1[2 * u + 1];
-            o2[u >> 1][2 * (u & 1)] = r2[u] + a.b2[2 * u];
-            o2[u >> 1][2 * (u & 1) + 1] = e2 + a.b2[2 * u + 1];
-        }
-        if (row_ok && l15 == 0) {
-            float4_t *p1 = reinterpret_cast<float4_t *>(a.f1 + row * K), *p2 = reinterpret_cast<float4_t *>(a.f2 + row * K);
-            p1[0] = o1[0]; p1[1] = o1[1];
-            p2[0] = o2[0]; p2[1] = o2[1];
-        }
-        return;
-    }
-#pragma unroll
-    for (int u = 0; u < 4 / NT; ++u) {
-        const int head = FP >= 16 ? u : (16 * u + l15) / FP;
-        if (row_ok && (l15 % NL) == 0) {
-            a.f1[row * K + head] = r1[u] + a.b1[head];
-            a.f2[row * K + head] = r2[u] + a.b2[head];
-        }
-    }
-}
 
 __device__ __forceinline__ float load_x1(const void *X, int bf, int64_t idx) {
     if (bf) return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t *>(X)[idx] << 16);
     return reinterpret_cast<const float *>(X)[idx];
 }
 __device__ __forceinline__ float4_t load_x4(const void *X, int bf, int64_t idx) {   // idx % 4 == 0, aligned
-    if (bf) {
-        const uint2 w = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(X) + idx);
-        float4_t v;
-        v[0] = __uint_as_float(w.x << 16);
-        v[1] = __uint_as_float(w.x & 0xFFFF0000u);
-        v[2] = __uint_as_float(w.y << 16);
-        v[3] = __uint_as_float(w.y & 0xFFFF0000u);
-        return v;
-    }
+    if (bf) return han_widen_bf16x4(*reinterpret_cast<const uint2 *>(reinterpret_cast<const uint16_t *>(X) + idx));
     return *reinterpret_cast<const float4_t *>(reinterpret_cast<const float *>(X) + idx);
 }
 
@@ -134,10 +61,7 @@ __device__ __forceinline__ float4_t load_x4_tail(const void *X, int bf, int64_t 
     if (nvalid >= 4) {
         if (bf) {
             const uint2_u w = *reinterpret_cast<const uint2_u *>(reinterpret_cast<const uint16_t *>(X) + idx);
-            v[0] = __uint_as_float(w[0] << 16);
-            v[1] = __uint_as_float(w[0] & 0xFFFF0000u);
-            v[2] = __uint_as_float(w[1] << 16);
-            v[3] = __uint_as_float(w[1] & 0xFFFF0000u);
+            v = han_widen_bf16x4(make_uint2(w[0], w[1]));
         } else {
             const float4_u w = *reinterpret_cast<const float4_u *>(reinterpret_cast<const float *>(X) + idx);
 #pragma unroll
@@ -155,9 +79,8 @@ __device__ __forceinline__ float4_t load_x4_tail(const void *X, int bf, int64_t 
 template <int FP>
 struct HeadsPerTile { static constexpr int value = FP >= 16 ? 1 : 16 / FP; };
 
-// MT = 16-row MFMA tiles per wave (block = 64*MT rows); X is loaded in quads of 4
-// elements (load_x4_tail).  With dropout every head a tile covers gets its own
-// accumulator: the A fragment is masked per head and the columns of the other
+// MT = 16-row MFMA tiles per wave (block = 64*MT rows); X is loaded in quads of 4 elements (load_x4_tail).  With dropout
+// every head a tile covers gets its own accumulator: the A fragment is masked per head and the columns of the other
 // heads are simply not read back.
 template <int FP, bool DROP, int MT>
 __global__ __launch_bounds__(256) void project_fwd_kernel(const ProjFwdArgs a_in) {
@@ -256,13 +179,7 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(const ProjFwdArgs a_in
     // C/D layout of 16x16x4: col = lane & 15, row = (lane >> 4) * 4 + reg
     const int myhh = HPT > 1 ? l15 / FP : 0;   // which head accumulator holds this lane's column
     float a1c[4], a2c[4];
-    if (a.f1) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            a1c[t] = a.a1[16 * t + l15];
-            a2c[t] = a.a2[16 * t + l15];
-        }
-    }
+    if (a.f1) k1_tile_coeffs(a, l15, a1c, a2c);
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
 #pragma unroll
@@ -280,26 +197,7 @@ __global__ __launch_bounds__(256) void project_fwd_kernel(const ProjFwdArgs a_in
                     if (row < a.N) a.partial[((int64_t)blockIdx.y * a.N + row) * HAN_D + 16 * t + l15] = v;
                     continue;
                 }
-                uint32_t keepbit = 0, stamp = 0;
-                if (a.thr_fts < HAN_KEEP_ALL) {
-                    // projected-row dropout (layers.py:31-32): the keep bit rides in the lowest
-                    // mantissa bit of the STORED element (fp32 bit 0 / bf16 bit 0)
-                    const int d = 16 * t + l15;
-                    const HanRand64 rn = han_rand64(a.seed_lo, a.seed_hi, a.fts_stream,
-                                                    (uint32_t)(row + a.row_offset), (uint32_t)(d >> 2));
-                    keepbit = rn.field(d & 3) < a.thr_fts ? 1u : 0u;
-                    stamp = 1;
-                }
-                if (a.h_bf16) {
-                    uint32_t b = han_f32_to_bf16_bits(v);
-                    if (stamp) b = (b & ~1u) | keepbit;
-                    if (row < a.N) reinterpret_cast<uint16_t *>(a.H)[row * HAN_D + 16 * t + l15] = (uint16_t)b;
-                    vst[t] = __uint_as_float(b << 16);
-                } else {
-                    if (stamp) v = __uint_as_float((__float_as_uint(v) & ~1u) | keepbit);
-                    if (row < a.N) reinterpret_cast<float *>(a.H)[row * HAN_D + 16 * t + l15] = v;
-                    vst[t] = v;
-                }
+                vst[t] = k1_store_elem(a, row, t, l15, v);
             }
             if (a.f1) tile_scores<FP>(a, row, row < a.N, vst, a1c, a2c, l15);
         }
@@ -548,13 +446,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void project_fwd_b6_kerne
     // epilogue: C/D layout col = lane & 15, row = (lane >> 4) * 4 + reg (as the fp32 kernel's)
     const int myhh = HPT > 1 ? l15 / 8 : 0;
     float a1c[4], a2c[4];
-    if (DROP && a.f1) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            a1c[t] = a.a1[16 * t + l15];
-            a2c[t] = a.a2[16 * t + l15];
-        }
-    }
+    if (DROP && a.f1) k1_tile_coeffs(a, l15, a1c, a2c);
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
 #pragma unroll
@@ -566,24 +458,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void project_fwd_b6_kerne
                 float v = acc[m][t][0][r];
                 if (HPT > 1) v = myhh ? acc[m][t][HPT - 1][r] : v;
                 if (DROP) v *= a.inv_keep_in;
-                uint32_t keepbit = 0, stamp = 0;
-                if (a.thr_fts < HAN_KEEP_ALL) {
-                    const int d = 16 * t + l15;
-                    const HanRand64 rn = han_rand64(a.seed_lo, a.seed_hi, a.fts_stream,
-                                                    (uint32_t)(row + a.row_offset), (uint32_t)(d >> 2));
-                    keepbit = rn.field(d & 3) < a.thr_fts ? 1u : 0u;
-                    stamp = 1;
-                }
-                if (a.h_bf16) {
-                    uint32_t b = han_f32_to_bf16_bits(v);
-                    if (stamp) b = (b & ~1u) | keepbit;
-                    if (row < a.N) reinterpret_cast<uint16_t *>(a.H)[row * HAN_D + 16 * t + l15] = (uint16_t)b;
-                    vst[t] = __uint_as_float(b << 16);
-                } else {
-                    if (stamp) v = __uint_as_float((__float_as_uint(v) & ~1u) | keepbit);
-                    if (row < a.N) reinterpret_cast<float *>(a.H)[row * HAN_D + 16 * t + l15] = v;
-                    vst[t] = v;
-                }
+                vst[t] = k1_store_elem(a, row, t, l15, v);
             }
             if (DROP && a.f1) tile_scores<8>(a, row, row < a.N, vst, a1c, a2c, l15);
         }
@@ -693,17 +568,11 @@ __global__ __launch_bounds__(512) void project_fwd_b6_multi_kernel(const ProjMul
 #pragma unroll
     for (int pi = 0; pi < NP; ++pi) {
         const int p = p0 + pi;
-        ProjFwdArgs pa;       // what tile_scores reads
-        pa.f1 = a.f1 + (int64_t)p * a.N * a.K; pa.f2 = a.f2 + (int64_t)p * a.N * a.K;
-        pa.b1 = a.b1 + p * a.K; pa.b2 = a.b2 + p * a.K;
+        K1Epilogue e;         // the scores half of meta-path p (eval: nothing is stamped, the stores below are plain)
+        e.f1 = a.f1 + (int64_t)p * a.N * a.K; e.f2 = a.f2 + (int64_t)p * a.N * a.K;
+        e.a1 = a.a1 + p * HAN_D; e.a2 = a.a2 + p * HAN_D; e.b1 = a.b1 + p * a.K; e.b2 = a.b2 + p * a.K;
         float a1c[4], a2c[4];
-        if (a.fuse_scores) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                a1c[t] = a.a1[p * HAN_D + 16 * t + l15];
-                a2c[t] = a.a2[p * HAN_D + 16 * t + l15];
-            }
-        }
+        if (a.fuse_scores) k1_tile_coeffs(e, l15, a1c, a2c);
 #pragma unroll
         for (int mr = 0; mr < MT * 4; ++mr) {
             const int m = mr >> 2, r = mr & 3;
@@ -722,15 +591,14 @@ __global__ __launch_bounds__(512) void project_fwd_b6_multi_kernel(const ProjMul
                     vst[t] = v;
                 }
             }
-            if (a.fuse_scores) tile_scores<8>(pa, row, row < a.N, vst, a1c, a2c, l15);
+            if (a.fuse_scores) tile_scores<8>(e, row, row < a.N, vst, a1c, a2c, l15);
         }
     }
 }
 
-// split-F epilogue: H[row] = sum over the f-chunks (fixed order), then the same keep-bit
-// stamping / bf16 rounding as the unsplit kernel's epilogue -- and the attention scores f1 / f2
-// (layers.py:23-24) from the row exactly as stored, in the same pass (round 3: one launch per
-// projection less on the short inputs, whose epochs are launch-bound).
+// split-F epilogue: H[row] = sum over the f-chunks (fixed order), then the row form of han_k1_epilogue.h: stamp,
+// round, store, and the attention scores f1 / f2 (layers.py:23-24) from the row as stored, in the same pass
+// (round 3: one launch per projection less on the short inputs, whose epochs are launch-bound).
 template <int FP, bool BF>
 __global__ __launch_bounds__(256) void project_finish_kernel(const ProjFwdArgs a_in, int nsplit, float *f1, float *f2) {
     ProjFwdArgs a = a_in;
@@ -740,8 +608,8 @@ __global__ __launch_bounds__(256) void project_finish_kernel(const ProjFwdArgs a
     const int head = (4 * q) / FP;
     const int64_t grp0 = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
     const int64_t ngrp = (int64_t)gridDim.x * 16;
-    const float4_t a14 = *reinterpret_cast<const float4_t *>(a.a1 + 4 * q);
-    const float4_t a24 = *reinterpret_cast<const float4_t *>(a.a2 + 4 * q);
+    float4_t a14, a24;
+    k1_row_coeffs(a, 4 * q, a14, a24);
     const float b1 = a.b1[head], b2 = a.b2[head];
     // all 16 lanes of a group run the same trip count -> the in-head shuffles are safe
     for (int64_t row = grp0; row < a.N; row += ngrp) {
@@ -751,35 +619,12 @@ __global__ __launch_bounds__(256) void project_finish_kernel(const ProjFwdArgs a
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] += pv[e];
         }
-        HanRand64 rn = {0u, 0u};
-        if (a.thr_fts < HAN_KEEP_ALL)      // layers.py:31-32, d = 4q + e -> counter d/4 = q, field e
-            rn = han_rand64(a.seed_lo, a.seed_hi, a.fts_stream, (uint32_t)(row + a.row_offset), (uint32_t)q);
+        const HanRand64 rn = k1_row_draws(a, row, q);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const uint32_t keepbit = rn.field(e) < a.thr_fts ? 1u : 0u;
-            if (BF) {
-                uint32_t b = han_f32_to_bf16_bits(v[e]);
-                if (a.thr_fts < HAN_KEEP_ALL) b = (b & ~1u) | keepbit;
-                v[e] = __uint_as_float(b << 16);          // the value as stored (what the scores see)
-            } else if (a.thr_fts < HAN_KEEP_ALL) {
-                v[e] = __uint_as_float((__float_as_uint(v[e]) & ~1u) | keepbit);
-            }
-        }
-        if (BF) {      // already rounded: pack the high halves
-            uint2 w;
-            w.x = (__float_as_uint(v[0]) >> 16) | (__float_as_uint(v[1]) & 0xFFFF0000u);
-            w.y = (__float_as_uint(v[2]) >> 16) | (__float_as_uint(v[3]) & 0xFFFF0000u);
-            *reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(a.H) + row * 64 + 4 * q) = w;
-        } else {
-            *reinterpret_cast<float4_t *>(reinterpret_cast<float *>(a.H) + row * 64 + 4 * q) = v;
-        }
-        float s1 = v[0] * a14[0] + v[1] * a14[1] + v[2] * a14[2] + v[3] * a14[3];
-        float s2 = v[0] * a24[0] + v[1] * a24[1] + v[2] * a24[2] + v[3] * a24[3];
-#pragma unroll
-        for (int o = 1; o < FP / 4; o <<= 1) {
-            s1 += __shfl_xor(s1, o, 64);
-            s2 += __shfl_xor(s2, o, 64);
-        }
+        for (int i = 0; i < 4; ++i) v = k1_row_stamp<BF>(a, rn, v, i);
+        k1_row_store<BF>(a, row, 4 * q, v);
+        float s1, s2;
+        k1_row_scores<FP>(v, a14, a24, s1, s2);
         if ((4 * q) % FP == 0) {
             f1[row * K + head] = s1 + b1;
             f2[row * K + head] = s2 + b2;
@@ -787,15 +632,9 @@ __global__ __launch_bounds__(256) void project_finish_kernel(const ProjFwdArgs a
     }
 }
 
-// Row-local epilogue: f1 = H_k.a1 + b1, f2 = H_k.a2 + b2 (layers.py:23-24), taken from
-// the rows exactly as stored (i.e. including the keep bits stamped in training).
-struct ScoreArgs {
-    const void *H;
-    const float *a1, *a2, *b1, *b2;
-    float *f1, *f2;
-    int64_t N;
-};
-
+// f1 = H_k.a1 + b1, f2 = H_k.a2 + b2 (layers.py:23-24) of rows that are already stored (i.e. including the keep
+// bits stamped in training): the scores half of the row form (the sum spelled out: k1_row_scores costs it a register)
+struct ScoreArgs : K1Epilogue {};
 template <int FP, bool BF>
 __global__ __launch_bounds__(256) void project_scores_kernel(const ScoreArgs a) {
     constexpr int K = HAN_D / FP;
@@ -803,8 +642,8 @@ __global__ __launch_bounds__(256) void project_scores_kernel(const ScoreArgs a) 
     const int head = (4 * q) / FP;
     const int64_t grp0 = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
     const int64_t ngrp = (int64_t)gridDim.x * 16;
-    const float4_t a14 = *reinterpret_cast<const float4_t *>(a.a1 + 4 * q);
-    const float4_t a24 = *reinterpret_cast<const float4_t *>(a.a2 + 4 * q);
+    float4_t a14, a24;
+    k1_row_coeffs(a, 4 * q, a14, a24);
     const float b1 = a.b1[head], b2 = a.b2[head];
     for (int64_t row = grp0; row < a.N; row += ngrp) {
         const float4_t h4 = han_load_row4<BF>(a.H, row, q);
@@ -1299,8 +1138,6 @@ static bool x_vec(const void *X, int64_t ldx, int F, bool x_bf16) {
     return (F % 4 == 0) && (ldx % 4 == 0) && (((uintptr_t)X & (x_bf16 ? 7 : 15)) == 0);
 }
 
-static bool k1_dtype(int code) { return code == HAN_DTYPE_F32 || code == HAN_DTYPE_BF16; }
-
 // bf16 x 6 matrix-pipe kernel (fp32-class accuracy, see project_fwd_b6_kernel) for one meta-path: whole-F blocks
 // of 128 rows with 16-byte X loads; with dropout it is built for the reference head shape (8 x 8).
 // Used for the training forward (measured at SYN-1M in one process: 0.77 ms against 0.96 ms for the
@@ -1321,9 +1158,6 @@ static bool use_fused(const K1Plan &p, bool vec, int P, float in_drop, float fts
     return in_drop == 0.f && fts_drop == 0.f && P >= 2 && vec && p.pipe_shape && !(flags & HAN_FLAG_K1_EXACT_PIPE);
 }
 
-// the parameter, output and keep-table pointers of one meta-path
-struct K1Path { const float *W, *a1, *a2, *b1, *b2; void *H; float *f1, *f2; uint8_t *keep; };
-
 // meta-path p of the contiguous (P, ...) tensors `all`; hb / kb: bytes of one H table / keep table (0: none)
 static K1Path path_of(const K1Path &all, size_t p, int64_t N, int F, int K, size_t hb, size_t kb) {
     return {all.W + p * F * HAN_D, all.a1 + p * HAN_D, all.a2 + p * HAN_D, all.b1 + p * K, all.b2 + p * K,
@@ -1342,7 +1176,8 @@ static int launch_wimage(const float *W, void *workspace, size_t workspace_bytes
 // f1 / f2 from the stored rows.  The lane map of the scores follows the head width for both storage types (a bf16
 // table with F' != 8 through the 8 x 8 instantiation wrote f1 / f2 out of bounds for K < 8 and a wrong layout for K = 16)
 static int launch_scores(const K1Path &q, int64_t N, int FP, bool h_bf16, hipStream_t st) {
-    const ScoreArgs s = {q.H, q.a1, q.a2, q.b1, q.b2, q.f1, q.f2, N};
+    ScoreArgs s;
+    static_cast<K1Epilogue &>(s) = han_k1_epilogue(q, true, h_bf16 ? HAN_DTYPE_BF16 : HAN_DTYPE_F32, N, 0, nullptr, 0.f, 0, 0);
     const int sgrid = han_grid_for(N, 16, 256 * 8);
     HAN_DISPATCH_FP_BF(FP, h_bf16, project_scores_kernel<FPC, BF><<<sgrid, 256, 0, st>>>(s));
     HAN_CHECK_LAUNCH();
@@ -1375,24 +1210,20 @@ extern "C" int han_project_fwd(const void *X, int x_dtype, int64_t ldx, const fl
                                const uint64_t *seed_dev, int64_t row_offset, uint8_t *keep, int flags,
                                void *stream) {
     if (N == 0) return 0;   // nothing to do; row pointers of empty tensors may be null
-    if (!X || !W || !a1 || !a2 || !b1 || !b2 || !H || !f1 || !f2 || N < 0 || F <= 0 || ldx < F) return HAN_E_BADARG;
-    if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
-    if (!k1_dtype(x_dtype) || !k1_dtype(table_dtype)) return HAN_E_UNSUPPORTED;
-    if (in_drop < 0.f || in_drop >= 1.f || fts_drop < 0.f || fts_drop >= 1.f) return HAN_E_BADARG;
+    const bool drop = in_drop > 0.f;
+    const K1Path q = {W, a1, a2, b1, b2, H, f1, f2, drop ? keep : nullptr};   // a keep pointer without dropout is ignored
+    const int bad = han_k1_check_fwd(X, q, N, F, ldx >= F, true, K, FP, x_dtype, table_dtype, in_drop, fts_drop);
+    if (bad != 0) return bad;
     if ((flags & HAN_FLAG_K1_EXACT_PIPE) && (flags & HAN_FLAG_K1_MATRIX_PIPE)) return HAN_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     const K1Plan plan = k1_plan(N, F, ldx, K, FP, 1);
-    const bool split = plan.nsplit > 1, drop = in_drop > 0.f;
-    const K1Path q = {W, a1, a2, b1, b2, H, f1, f2, drop ? keep : nullptr};   // a keep pointer without dropout is ignored
+    const bool split = plan.nsplit > 1;
     ProjFwdArgs a;
-    a.X = X; a.ldx = ldx; a.W = W; a.H = H; a.N = N; a.F = F;
-    a.x_bf16 = x_dtype == HAN_DTYPE_BF16; a.h_bf16 = table_dtype == HAN_DTYPE_BF16;
-    han_set_dropout(a, seed, seed_dev, in_drop, a.thr_in, a.inv_keep_in);
-    a.thr_fts = han_drop_threshold(fts_drop);
-    a.fts_stream = HAN_STREAM_FTS + 4u * (uint32_t)HAN_FLAG_FTS_SLICE_OF(flags);
-    a.row_offset = row_offset; a.keep = q.keep; a.f_chunk = plan.f_chunk;
-    a.a1 = a1; a.a2 = a2; a.b1 = b1; a.b2 = b2;
-    a.f1 = split ? nullptr : f1; a.f2 = split ? nullptr : f2;      // scores fused into the epilogue, except on the split-F path
+    // scores fused into the epilogue, except on the split-F path (the finish kernel gets f1 / f2 itself)
+    static_cast<K1Epilogue &>(a) = han_k1_epilogue(q, !split, table_dtype, N, seed, seed_dev, fts_drop, flags, row_offset);
+    a.X = X; a.ldx = ldx; a.W = W; a.F = F; a.x_bf16 = x_dtype == HAN_DTYPE_BF16;
+    a.thr_in = han_drop_threshold(in_drop); a.inv_keep_in = 1.f / (1.f - in_drop);
+    a.keep = q.keep; a.f_chunk = plan.f_chunk;
     if (split && (!workspace || workspace_bytes < plan.fwd_bytes)) return HAN_E_WORKSPACE;
     a.partial = split ? (float *)workspace : nullptr;
     const bool b6 = use_b6(plan, x_vec(X, ldx, F, a.x_bf16), a.x_bf16, in_drop, K, FP, flags);
@@ -1454,14 +1285,14 @@ extern "C" int han_project_fwd_multi(const void *X, int x_dtype, int64_t ldx, co
                                      uint8_t *keep, int flags, void *stream) {
     if (P <= 0 || (in_drop > 0.f && !seeds)) return HAN_E_BADARG;
     if (N == 0) return 0;
-    if (!X || !W || !a1 || !a2 || !b1 || !b2 || !H || !f1 || !f2 || N < 0 || F <= 0 || ldx < F) return HAN_E_BADARG;
-    if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
-    if (!k1_dtype(x_dtype) || !k1_dtype(table_dtype)) return HAN_E_UNSUPPORTED;
+    // (the dropout range is han_project_fwd's check: the fused kernel runs without dropout; made here it returns the same)
+    const K1Path all = {W, a1, a2, b1, b2, H, f1, f2, keep};
+    const int bad = han_k1_check_fwd(X, all, N, F, ldx >= F, true, K, FP, x_dtype, table_dtype, in_drop, fts_drop);
+    if (bad != 0) return bad;
     hipStream_t st = (hipStream_t)stream;
     const bool x_bf16 = x_dtype == HAN_DTYPE_BF16, h_bf16 = table_dtype == HAN_DTYPE_BF16;
     const K1Plan plan = k1_plan(N, F, ldx, K, FP, P);
     const size_t hb = (size_t)N * HAN_D * (h_bf16 ? 2 : 4), kb = plan.keep_table ? (size_t)N * (size_t)F + 128 : 0;
-    const K1Path all = {W, a1, a2, b1, b2, H, f1, f2, keep};
     int done = 0;
     if (use_fused(plan, x_vec(X, ldx, F, x_bf16), P, in_drop, fts_drop, flags)) {
         int rc = launch_wimage(W, workspace, workspace_bytes, F, P, st);
@@ -1500,7 +1331,7 @@ extern "C" int han_project_bwd(const void *X, int x_dtype, int64_t ldx, const fl
                                void *stream) {
     if (!X || !dH || !dW || !workspace || N < 0 || F <= 0 || ldx < F) return HAN_E_BADARG;
     if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
-    if (!k1_dtype(x_dtype)) return HAN_E_UNSUPPORTED;
+    if (!han_k1_dtype(x_dtype)) return HAN_E_UNSUPPORTED;
     if (in_drop < 0.f || in_drop >= 1.f) return HAN_E_BADARG;
     if (workspace_bytes < han_project_bwd_workspace(N, F, K, FP)) return HAN_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;

@@ -13,24 +13,18 @@
 // entries brings its indices in with one coalesced load, and four steps are issued back to back, so a wave has 16
 // row gathers in flight (sparse_gather_sum).  The four groups' partial rows are added in a fixed order at the end:
 // bitwise reproducible, no atomics.
-#include "han_common.h"
+#include "han_k1_epilogue.h"
 
 namespace {
 
-struct SparseFwdArgs {
+// the stored-row half (han_k1_epilogue.h) plus the CSR triple and the input dropout
+struct SparseFwdArgs : K1Epilogue {
     const int64_t *rowptr;
     const int32_t *colidx;
     const float *vals;      // null: every stored entry is 1
     const float *W;
-    void *H;                // fp32 or bf16 (template), 64 elements per row
-    const float *a1, *a2, *b1, *b2;
-    float *f1, *f2;
-    int64_t N;
-    uint32_t seed_lo, seed_hi, thr_in, thr_fts;   // thr_fts < 2^16: stamp keep bits into H
-    uint32_t fts_stream;                          // HAN_STREAM_FTS + 4 * slice
-    const uint64_t *seed_dev;
+    uint32_t thr_in;        // input dropout (its seed is the epilogue's)
     float inv_keep_in;
-    int64_t row_offset;
 };
 
 // sum_e vals[e] * keep(.) * table[idx[e]][4q .. 4q+3] over the entries [beg, end) of one output row, for the whole
@@ -98,8 +92,7 @@ __device__ __forceinline__ float4_t sparse_gather_sum(const int32_t *idx, const 
     return s;
 }
 
-// one wave per row; the epilogue is project_finish_kernel's: scale, stamp the projected-row dropout keep bit, round
-// for a bf16 table, scores from the row as stored
+// one wave per row; scale, then the row form of han_k1_epilogue.h (lane group 0 stores)
 template <int FP, bool BF, bool DROP>
 __global__ __launch_bounds__(256) void project_sparse_fwd_kernel(const SparseFwdArgs a_in) {
     SparseFwdArgs a = a_in;
@@ -115,39 +108,14 @@ __global__ __launch_bounds__(256) void project_sparse_fwd_kernel(const SparseFwd
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] *= a.inv_keep_in;
     }
-    HanRand64 rn = {0u, 0u};
-    if (a.thr_fts < HAN_KEEP_ALL)      // layers.py:31-32, d = 4q + e -> counter d/4 = q, field e
-        rn = han_rand64(a.seed_lo, a.seed_hi, a.fts_stream, (uint32_t)(row + a.row_offset), (uint32_t)q);
+    const HanRand64 rn = k1_row_draws(a, row, q);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const uint32_t keepbit = rn.field(e) < a.thr_fts ? 1u : 0u;
-        if (BF) {
-            uint32_t b = han_f32_to_bf16_bits(v[e]);
-            if (a.thr_fts < HAN_KEEP_ALL) b = (b & ~1u) | keepbit;
-            v[e] = __uint_as_float(b << 16);          // the value as stored (what the scores see)
-        } else if (a.thr_fts < HAN_KEEP_ALL) {
-            v[e] = __uint_as_float((__float_as_uint(v[e]) & ~1u) | keepbit);
-        }
-    }
-    if (g == 0) {
-        if (BF) {      // already rounded: pack the high halves
-            uint2 w;
-            w.x = (__float_as_uint(v[0]) >> 16) | (__float_as_uint(v[1]) & 0xFFFF0000u);
-            w.y = (__float_as_uint(v[2]) >> 16) | (__float_as_uint(v[3]) & 0xFFFF0000u);
-            *reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(a.H) + row * 64 + 4 * q) = w;
-        } else {
-            *reinterpret_cast<float4_t *>(reinterpret_cast<float *>(a.H) + row * 64 + 4 * q) = v;
-        }
-    }
-    const float4_t a14 = *reinterpret_cast<const float4_t *>(a.a1 + 4 * q);
-    const float4_t a24 = *reinterpret_cast<const float4_t *>(a.a2 + 4 * q);
-    float s1 = v[0] * a14[0] + v[1] * a14[1] + v[2] * a14[2] + v[3] * a14[3];
-    float s2 = v[0] * a24[0] + v[1] * a24[1] + v[2] * a24[2] + v[3] * a24[3];
-#pragma unroll
-    for (int o = 1; o < FP / 4; o <<= 1) {      // the whole wave is here: the in-head shuffles are safe
-        s1 += __shfl_xor(s1, o, 64);
-        s2 += __shfl_xor(s2, o, 64);
-    }
+    for (int i = 0; i < 4; ++i) v = k1_row_stamp<BF>(a, rn, v, i);
+    if (g == 0) k1_row_store<BF>(a, row, 4 * q, v);
+    float4_t a14, a24;
+    k1_row_coeffs(a, 4 * q, a14, a24);
+    float s1, s2;
+    k1_row_scores<FP>(v, a14, a24, s1, s2);      // the whole wave is here: the in-head shuffles are safe
     if (g == 0 && (4 * q) % FP == 0) {
         a.f1[row * K + head] = s1 + a.b1[head];
         a.f2[row * K + head] = s2 + a.b2[head];
@@ -238,18 +206,15 @@ extern "C" int han_project_sparse_fwd(const int64_t *rowptr, const int32_t *coli
                                       float in_drop, float fts_drop, uint64_t seed, const uint64_t *seed_dev,
                                       int64_t row_offset, int flags, void *stream) {
     if (N == 0) return 0;   // nothing to do; pointers of empty tensors may be null
-    if (!rowptr || !W || !a1 || !a2 || !b1 || !b2 || !H || !f1 || !f2 || N < 0 || F <= 0) return HAN_E_BADARG;
-    if (N >= ((int64_t)1 << 31)) return HAN_E_UNSUPPORTED;      // (a matrix without entries may carry a null colidx)
-    if (!han_fp_supported(K, FP)) return HAN_E_UNSUPPORTED;
-    if (table_dtype != HAN_DTYPE_F32 && table_dtype != HAN_DTYPE_BF16) return HAN_E_UNSUPPORTED;
-    if (in_drop < 0.f || in_drop >= 1.f || fts_drop < 0.f || fts_drop >= 1.f) return HAN_E_BADARG;
+    // (a matrix without entries may carry a null colidx; the values are fp32)
+    const K1Path q = {W, a1, a2, b1, b2, H, f1, f2, nullptr};
+    const int bad = han_k1_check_fwd(rowptr, q, N, F, true, N < ((int64_t)1 << 31), K, FP, HAN_DTYPE_F32, table_dtype,
+                                     in_drop, fts_drop);
+    if (bad != 0) return bad;
     SparseFwdArgs a;
-    a.rowptr = rowptr; a.colidx = colidx; a.vals = vals; a.W = W; a.H = H; a.N = N;
-    a.a1 = a1; a.a2 = a2; a.b1 = b1; a.b2 = b2; a.f1 = f1; a.f2 = f2;
-    han_set_dropout(a, seed, seed_dev, in_drop, a.thr_in, a.inv_keep_in);
-    a.thr_fts = han_drop_threshold(fts_drop);
-    a.fts_stream = HAN_STREAM_FTS + 4u * (uint32_t)HAN_FLAG_FTS_SLICE_OF(flags);
-    a.row_offset = row_offset;
+    static_cast<K1Epilogue &>(a) = han_k1_epilogue(q, true, table_dtype, N, seed, seed_dev, fts_drop, flags, row_offset);
+    a.rowptr = rowptr; a.colidx = colidx; a.vals = vals; a.W = W;
+    a.thr_in = han_drop_threshold(in_drop); a.inv_keep_in = 1.f / (1.f - in_drop);
     const unsigned grid = (unsigned)((N + 3) / 4);
     const bool bf = table_dtype == HAN_DTYPE_BF16;
     HAN_DISPATCH_BOOL(DROP, in_drop > 0.f, HAN_DISPATCH_FP_BF(FP, bf,

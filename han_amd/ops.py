@@ -289,16 +289,9 @@ def project_fwd(X, W, a1, a2, b1, b2, in_drop=0.0, fts_drop=0.0, seed=0, row_off
     return H, f1, f2
 
 
-def _project_fwd_setup(X, W, a1, a2, b1, b2, lead, in_drop, fts_drop, table_dtype, flags, want_keep, ws_bytes):
-    """What project_fwd (lead = ()) and project_fwd_multi (lead = (P,)) share: the argument checks, the outputs
-    H lead + (N,D), f1 / f2 lead + (N,K), the workspace of ws_bytes(N, F, K, FP, *lead) bytes (> 0 only for short
-    inputs: split-F) and the keep table lead + (han_project_keep_bytes(),), or None when this call has none."""
-    _chk(X, "X", contiguous=False, dtype=X.dtype)
-    xcode = _dtype_code(X, "X")
-    if X.stride(1) != 1:
-        raise ValueError("X: rows must be contiguous")
-    N, F = X.shape
-    dev = X.device
+def _project_fwd_outputs(N, F, dev, W, a1, a2, b1, b2, lead, in_drop, fts_drop, table_dtype):
+    """What every K1 forward shares once its input has given (N, F) and the device: the parameter checks, in their
+    order, and the outputs H lead + (N,D), f1 / f2 lead + (N,K)."""
     K, FP = a1.shape[len(lead):]
     if table_dtype not in DTYPE_CODE:
         raise ValueError(f"table_dtype {table_dtype}: expected float32 or bfloat16")
@@ -313,6 +306,21 @@ def _project_fwd_setup(X, W, a1, a2, b1, b2, lead, in_drop, fts_drop, table_dtyp
     H = torch.empty(lead + (N, D), dtype=table_dtype, device=dev)
     f1 = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
     f2 = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
+    return K, FP, in_drop, fts_drop, H, f1, f2
+
+
+def _project_fwd_setup(X, W, a1, a2, b1, b2, lead, in_drop, fts_drop, table_dtype, flags, want_keep, ws_bytes):
+    """The dense project_fwd (lead = ()) and project_fwd_multi (lead = (P,)): the checks of X, _project_fwd_outputs,
+    the workspace of ws_bytes(N, F, K, FP, *lead) bytes (> 0 only for short inputs: split-F) and the keep table
+    lead + (han_project_keep_bytes(),), or None when this call has none."""
+    _chk(X, "X", contiguous=False, dtype=X.dtype)
+    xcode = _dtype_code(X, "X")
+    if X.stride(1) != 1:
+        raise ValueError("X: rows must be contiguous")
+    N, F = X.shape
+    dev = X.device
+    K, FP, in_drop, fts_drop, H, f1, f2 = _project_fwd_outputs(N, F, dev, W, a1, a2, b1, b2, lead, in_drop, fts_drop,
+                                                               table_dtype)
     nbytes = ws_bytes(N, F, K, FP, *lead)
     ws = _ws(nbytes, dev, "projf") if nbytes else None
     ldx = _ld(X, F)
@@ -331,21 +339,8 @@ def _project_sparse_fwd(X, W, a1, a2, b1, b2, lead, in_drop, fts_drop, seeds, ro
     if not X.is_cuda:
         raise ValueError(f"X: must be on a GPU (han_amd has no CPU path); got {X.device}")
     N, F = X.shape
-    dev = X.device
-    K, FP = a1.shape[len(lead):]
-    if table_dtype not in DTYPE_CODE:
-        raise ValueError(f"table_dtype {table_dtype}: expected float32 or bfloat16")
-    _check_heads(K, FP)
-    _chk(W, "W", lead + (F, D), device=dev)
-    _chk(a1, "a1", lead + (K, FP), device=dev)
-    _chk(a2, "a2", lead + (K, FP), device=dev)
-    _chk(b1, "b1", lead + (K,), device=dev)
-    _chk(b2, "b2", lead + (K,), device=dev)
-    in_drop = _check_drop(in_drop, "in_drop")
-    fts_drop = _check_drop(fts_drop, "fts_drop")
-    H = torch.empty(lead + (N, D), dtype=table_dtype, device=dev)
-    f1 = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
-    f2 = torch.empty(lead + (N, K), dtype=torch.float32, device=dev)
+    K, FP, in_drop, fts_drop, H, f1, f2 = _project_fwd_outputs(N, F, X.device, W, a1, a2, b1, b2, lead, in_drop,
+                                                               fts_drop, table_dtype)
     sel = (lambda t, p: t[p]) if lead else (lambda t, p: t)
     for p in range(lead[0] if lead else 1):
         _lib.check(lib.han_project_sparse_fwd(

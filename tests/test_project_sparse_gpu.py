@@ -12,6 +12,7 @@ import torch
 
 from han_amd import SparseFeatures, ops, synth
 from han_amd import rng as hrng
+from tests import k1_cases as kc
 from tests import rng_ref
 from tests.helpers import rel_err
 
@@ -158,6 +159,83 @@ def test_forward_bf16_table(dev, drop, binary):
     for got, a, b in ((f1, a1, b1), (f2, a2, b2)):
         ref = (Hk * a.astype(np.float64)[None]).sum(-1) + b.astype(np.float64)
         assert np.abs(got.cpu().numpy() - ref).max() < 1e-5
+
+
+# ------------------------------------------------------------------------------------------------ 3b
+@functools.lru_cache(maxsize=None)
+def _grid_problem(f, path, K, FP, bf16_table):
+    """An exact-grid forward case of tests/k1_cases.py (its generators and units) with about 5 % of X kept and two
+    score coefficients per head: the CSR triple, the dense matrix and the parameters, as float64 arrays holding exactly
+    the values the kernels get."""
+    c = kc.Case("fwd", 130, f, path, K=K, FP=FP, drop=0.5, fts=0.5, bf16_table=bf16_table, row_offset=1000)
+    x, W, a1, a2, b1, b2 = kc.fwd_inputs(c)              # asserts the precondition for the full matrix
+    pat = np.random.default_rng([c.n, f, 5]).random((c.n, f)) < 0.05
+    pat[0] = False                                       # a row without entries
+    x = x * pat
+    # The scores are sums over the rows AS STORED, and a stamped keep bit takes an fp32 element one unit in its last
+    # place off the grid: a sum of three or more such terms rounds differently in different orders (the tile form adds
+    # a head's products in a tree over its lanes, the row form four per lane in sequence first).  Two coefficients per
+    # head, each a power of two: every product is exact and a head's sum is ONE rounded addition, the same in any
+    # order, so the equality asserted below holds for every kernel that keeps the contract.
+    arng = np.random.default_rng([f, K, 7])
+    for a in (a1, a2):
+        kept = np.zeros((K, FP), dtype=bool)
+        for k in range(K):
+            kept[k, arng.choice(FP, 2, replace=False)] = True
+        a[0] = np.where(kept, np.where(a[0] == 0, kc.GA, a[0]), 0.0)
+        m = np.abs(a[0][kept]) / kc.GA
+        assert ((a[0] != 0).sum(-1) == 2).all() and np.isin(m, (1, 2)).all()
+    # the precondition of k1_cases.fwd_inputs again, for the matrix as used: in float64, from the inputs alone, all
+    # keep draws taken as "kept" -- every product and partial sum of H, in any order, is an integer below 2^24 units
+    S = 2 * (np.abs(x) @ np.abs(W[0])) / (kc.GX * kc.GW)
+    assert S.max() < kc.TWO24 and np.array_equal(x, x.astype(np.float32).astype(np.float64))
+    Sst = S * (1 + 2.0 ** -8) if bf16_table else S
+    for a, b in ((a1, b1), (a2, b2)):
+        sc = (Sst.reshape(c.n, K, FP) * np.abs(a[0] / kc.GA)).sum(-1) + np.abs(b[0]) / (kc.GX * kc.GW * kc.GA)
+        assert sc.max() < kc.TWO24
+    rowptr = np.zeros(c.n + 1, dtype=np.int64)
+    np.cumsum(pat.sum(1), out=rowptr[1:])
+    return c, rowptr, np.nonzero(pat)[1].astype(np.int32), x[pat].astype(np.float32), x, (W[0], a1[0], a2[0], b1[0], b2[0])
+
+
+@pytest.mark.parametrize("bf16_table", [False, True], ids=["f32tab", "bf16tab"])
+@pytest.mark.parametrize("K,FP", [(8, 8), (4, 16)])
+@pytest.mark.parametrize("f,path", [(77, "plain"), (300, "split")])
+def test_sparse_equals_dense_on_the_grid(dev, f, path, K, FP, bf16_table):
+    """The stored-row contract across both lane layouts (han_k1_epilogue.h): on exact-grid inputs the CSR forward and
+    the dense forward of the densified matrix -- F = 77: project_fwd_kernel, tile form; F = 300: split-F +
+    project_finish_kernel, row form -- must store the same bits of H and the same f1 / f2, with both dropouts, a row
+    offset and the keep bits of column slice 1.
+
+    H is exact on the grid in any order; the score sums are made order-free by the inputs (_grid_problem: two
+    power-of-two coefficients per head), since the stamped bits take fp32 elements off the grid.  With all F' coefficients
+    of a head non-zero the two forms' scores differ in the last bits of about one in ten on the F = 77 route with an
+    fp32 table (98 + 113 of 2 x 1040 scores at 8 x 8 on an MI355X, before and after the epilogue moved into the header):
+    a property of the two summation orders, not of the contract."""
+    c, rowptr, colidx, vals, dense, params = _grid_problem(f, path, K, FP, bf16_table)
+    assert kc.forward_path(c.n, f) == path
+    sf = SparseFeatures.from_arrays(rowptr, colidx, vals, f, device=dev)
+    tdt = torch.bfloat16 if bf16_table else torch.float32
+    W, a1, a2, b1, b2 = (_t(v, dev) for v in params)
+    kw = dict(in_drop=c.drop, fts_drop=c.fts, seed=c.seed, row_offset=c.row_offset, table_dtype=tdt,
+              flags=ops.flag_fts_slice(1))
+    Hs, f1s, f2s = ops.project_fwd(sf, W, a1, a2, b1, b2, **kw)
+    Hd, f1d, f2d = ops.project_fwd(_t(dense, dev), W, a1, a2, b1, b2, **kw)
+    it = torch.int16 if bf16_table else torch.int32
+    bits = (Hs.view(it).to(torch.int32) & 1).cpu().numpy()
+    assert np.array_equal(bits, rng_ref.fts_mask(c.seed, c.n, 64, c.fts, c.row_offset, slice_index=1).astype(np.int32))
+    diff = [int((a != b).sum()) for a, b in ((Hs.view(it), Hd.view(it)), (f1s, f1d), (f2s, f2d))]
+    print(f"sparse vs dense {path} ({K},{FP}) {'bf16' if bf16_table else 'fp32'} table: "
+          f"differing elements H {diff[0]} f1 {diff[1]} f2 {diff[2]}")
+    assert Hs.any() and torch.equal(Hs.view(it), Hd.view(it))
+    assert torch.equal(f1s, f1d) and torch.equal(f2s, f2d)
+    # and both are the scores of the rows as stored: the head's two products (exact), one fp32 addition, then b
+    st = Hs.float().cpu().numpy().reshape(c.n, K, FP)
+    for got, a, b in ((f1s, params[1], params[3]), (f2s, params[2], params[4])):
+        cols = np.argsort(a == 0, axis=-1, kind="stable")[:, :2]                  # the two kept columns of each head
+        p = np.take_along_axis(st, cols[None].repeat(c.n, 0), -1) * np.take_along_axis(a, cols, -1).astype(np.float32)[None]
+        want = ((p[..., 0] + p[..., 1]).astype(np.float32) + b.astype(np.float32)[None]).astype(np.float32)
+        assert np.array_equal(got.cpu().numpy(), want) and (want != b.astype(np.float32)[None]).any()
 
 
 # ------------------------------------------------------------------------------------------------ 4
