@@ -31,6 +31,7 @@ import time
 import torch
 import torch.distributed as dist
 
+from . import csr
 from .graph import CSRGraph
 
 
@@ -115,19 +116,14 @@ class NodePartition:
         rows_local = _row_block(g, self.row_start, self.row_end, self.n_table)
         # the transposed shard straight from the global graph, no collective: the edges whose source
         # column is local, their destination rows recovered from rowptr by binary search, one
-        # stable sort of E/G elements
-        dev = g.device
+        # stable sort of E/G elements (destinations stay ascending per source)
         col = g.colidx
         sel = torch.nonzero((col >= self.row_start) & (col < self.row_end)).flatten()
         dst = (torch.searchsorted(g.rowptr, sel, right=True) - 1).to(torch.int32)
-        src = (col[sel] - self.row_start).long()
-        order = torch.sort(src, stable=True).indices          # destinations stay ascending per source
-        rowidx = dst[order].contiguous()
-        counts = torch.bincount(src, minlength=self.n_local)
-        colptr = torch.zeros(self.n_local + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts, 0, out=colptr[1:])
+        colptr, order = csr.group_by((col[sel] - self.row_start).long(), self.n_local)
         vals = g.values[sel][order].contiguous() if g.values is not None else None
-        return rows_local, CSRGraph(colptr, rowidx, self.n_table, validate=False, values=vals, row_base=self.row_start)
+        return rows_local, CSRGraph(colptr, dst[order].contiguous(), self.n_table, validate=False, values=vals,
+                                    row_base=self.row_start)
 
     def shard_local_graph(self, rows_local: CSRGraph) -> tuple[CSRGraph, CSRGraph]:
         """rows_local: CSR of THIS rank's destination rows [row_start, row_end) with GLOBAL column ids.
@@ -139,14 +135,12 @@ class NodePartition:
         Collective: every rank must call it for the same meta-path in the same order."""
         if rows_local.n_rows != self.n_local:
             raise ValueError(f"expected this rank's {self.n_local} rows, got {rows_local.n_rows}")
-        dev = rows_local.device
         rows_local = CSRGraph(rows_local.rowptr, rows_local.colidx, self.n_table, validate=False,
                               values=rows_local.values, row_base=self.row_start)
         col = rows_local.colidx
         if col.numel() and (int(col.min()) < 0 or int(col.max()) >= self.n_global):
             raise ValueError("rows_local.colidx must hold global node ids")
-        dst = torch.repeat_interleave(torch.arange(self.row_start, self.row_end, device=dev, dtype=torch.int32),
-                                      rows_local.degrees())
+        dst = csr.row_ids(rows_local.rowptr, torch.int32, base=self.row_start)
         owner = torch.div(col, self.shard, rounding_mode="floor").long()
         order = torch.sort(owner, stable=True).indices          # grouped by owner, local edge order kept
         send_counts = torch.bincount(owner, minlength=self.world)
@@ -167,13 +161,8 @@ class NodePartition:
         del order
         # arrivals are ordered by sender rank (ascending row blocks) and, within a sender, by its CSR
         # order (ascending destination): a stable sort by source leaves each source's destinations ascending
-        src = (edges[:, 1] - self.row_start).long()
-        order2 = torch.sort(src, stable=True).indices
-        rowidx = edges[:, 0][order2].contiguous()
-        counts = torch.bincount(src, minlength=self.n_local)
-        colptr = torch.zeros(self.n_local + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts, 0, out=colptr[1:])
-        cols_local = CSRGraph(colptr, rowidx, self.n_table, validate=False,
+        colptr, order2 = csr.group_by((edges[:, 1] - self.row_start).long(), self.n_local)
+        cols_local = CSRGraph(colptr, edges[:, 0][order2].contiguous(), self.n_table, validate=False,
                               values=vals[order2].contiguous() if vals is not None else None, row_base=self.row_start)
         return rows_local, cols_local
 

@@ -11,6 +11,8 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import csr
+
 _LIM = 1 << 31
 
 
@@ -53,14 +55,11 @@ class SparseFeatures:
         return (f"SparseFeatures(shape={self.shape}, nnz={self.nnz}, "
                 f"{'binary' if self.values is None else 'float32'}, device={self.device})")
 
-    def _row_ids(self) -> torch.Tensor:
-        return torch.repeat_interleave(torch.arange(self.n_rows, device=self.device), self.rowptr[1:] - self.rowptr[:-1])
-
     def to_dense(self) -> torch.Tensor:
         """(N, F) fp32 -- for tests."""
         out = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
         vals = self.values if self.values is not None else torch.ones(self.nnz, dtype=torch.float32, device=self.device)
-        out[self._row_ids(), self.colidx.long()] = vals
+        out[csr.row_ids(self.rowptr), self.colidx.long()] = vals
         return out
 
     def rows(self, r0: int, r1: int) -> "SparseFeatures":
@@ -84,34 +83,21 @@ class SparseFeatures:
         hit = self._t.get(chunk)
         if hit is not None:
             return hit
-        dev, F = self.device, self.n_cols
-        cols = self.colidx.long()
         # the rows are stored in ascending order, so a stable sort by column leaves every column's rows ascending
-        order = torch.sort(cols, stable=True).indices
-        rowidx = self._row_ids()[order].to(torch.int32).contiguous()
+        colptr, order = csr.group_by(self.colidx.long(), self.n_cols)
+        rowidx = csr.row_ids(self.rowptr)[order].to(torch.int32).contiguous()
         values_t = self.values[order].contiguous() if self.values is not None else None
-        colptr = torch.zeros(F + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(torch.bincount(cols, minlength=F), 0, out=colptr[1:])
-        lens = colptr[1:] - colptr[:-1]
-        long_cols = torch.nonzero(lens > chunk).flatten()
-        t = dict(colptr=colptr, rowidx=rowidx, values_t=values_t, col_chunk=chunk, n_long=int(long_cols.numel()),
-                 n_chunks=0, long_cols=None, long_ptr=None, chunk_col=None, chunk_start=None, chunk_end=None)
-        if t["n_long"]:
-            nch = (lens[long_cols] + chunk - 1) // chunk
-            long_ptr = torch.zeros(long_cols.numel() + 1, dtype=torch.int64, device=dev)
-            torch.cumsum(nch, 0, out=long_ptr[1:])
-            n_chunks = int(long_ptr[-1])
-            chunk_long = torch.repeat_interleave(torch.arange(long_cols.numel(), device=dev), nch)
-            within = torch.arange(n_chunks, device=dev) - long_ptr[:-1][chunk_long]
-            chunk_start = (colptr[long_cols][chunk_long] + within * chunk).contiguous()
-            chunk_end = torch.minimum(chunk_start + chunk, colptr[long_cols + 1][chunk_long]).contiguous()
-            t.update(n_chunks=n_chunks, long_cols=long_cols.to(torch.int32).contiguous(), long_ptr=long_ptr,
-                     chunk_col=long_cols[chunk_long].to(torch.int32).contiguous(), chunk_start=chunk_start,
-                     chunk_end=chunk_end)
-        if dev.type == "cuda":
+        t = dict(colptr=colptr, rowidx=rowidx, values_t=values_t, col_chunk=chunk, n_long=0, n_chunks=0,
+                 long_cols=None, long_ptr=None, chunk_col=None, chunk_start=None, chunk_end=None)
+        c = csr.chunk_table(colptr, chunk, chunk)
+        if c is not None:       # the index arrays in the int32 that han_project_sparse_bwd reads
+            t.update(n_long=c["n_long"], n_chunks=c["n_chunks"], long_cols=c["long"].to(torch.int32),
+                     long_ptr=c["long_ptr"], chunk_col=c["long"][c["chunk_long"]].to(torch.int32),
+                     chunk_start=c["chunk_start"], chunk_end=c["chunk_end"])
+        if self.is_cuda:
             # the image is shared by every later launch, whichever stream it runs on (one stream per meta-path in a
             # captured epoch): it is complete before anybody sees it.  (Built outside a capture: the warm-up epoch.)
-            torch.cuda.current_stream(dev).synchronize()
+            torch.cuda.current_stream(self.device).synchronize()
         self._t[chunk] = t
         return t
 
@@ -150,10 +136,7 @@ class SparseFeatures:
             elif vals is not None:
                 vals = vals[order]
             rows, cols = torch.div(uniq, n_cols, rounding_mode="floor"), uniq % n_cols
-        rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
-        if n_rows:
-            torch.cumsum(torch.bincount(rows, minlength=n_rows), 0, out=rowptr[1:])
-        return SparseFeatures(rowptr, cols.to(torch.int32).contiguous(),
+        return SparseFeatures(csr.scan(torch.bincount(rows, minlength=n_rows)), cols.to(torch.int32).contiguous(),
                               vals.contiguous() if vals is not None else None, n_cols)
 
     @staticmethod
@@ -175,7 +158,7 @@ class SparseFeatures:
         if deg.numel() and bool((deg < 0).any()):
             bad = int(torch.nonzero(deg < 0).flatten()[0])
             raise ValueError(f"rowptr must be non-decreasing: rowptr[{bad + 1}] = {int(rp[bad + 1])} < rowptr[{bad}] = {int(rp[bad])}")
-        rows = torch.repeat_interleave(torch.arange(deg.numel(), device=rp.device), deg)
+        rows = csr.row_ids(rp)
         vals = as_t(values, torch.float32) if values is not None else None
         return SparseFeatures._from_coo(rows, ci, vals, deg.numel(), n_cols)
 

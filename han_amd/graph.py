@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, csr
 
 EDGE_THRESHOLD = -1e8   # an entry of bias_mat is an edge iff it is > -1e8
 
@@ -120,27 +120,12 @@ class CSRGraph:
         else a dict of device tensors; cached per (split_deg, chunk)."""
         key = (int(split_deg), int(chunk))
         if key not in self._split:
-            deg = self.degrees()
-            long_rows = torch.nonzero(deg > split_deg).flatten()
-            if long_rows.numel() == 0:
-                self._split[key] = None
-            else:
-                ldeg = deg[long_rows]
-                nch = (ldeg + chunk - 1) // chunk
-                long_ptr = torch.zeros(long_rows.numel() + 1, dtype=torch.int64, device=self.device)
-                torch.cumsum(nch, 0, out=long_ptr[1:])
-                n_chunks = int(long_ptr[-1])
-                chunk_long = torch.repeat_interleave(
-                    torch.arange(long_rows.numel(), device=self.device, dtype=torch.int32), nch)
-                within = torch.arange(n_chunks, device=self.device) - long_ptr[:-1][chunk_long.long()]
-                base = self.rowptr[long_rows][chunk_long.long()]
-                chunk_start = (base + within * chunk).contiguous()
-                chunk_end = torch.minimum(chunk_start + chunk,
-                                          self.rowptr[long_rows + 1][chunk_long.long()]).contiguous()
-                self._split[key] = dict(split_deg=int(split_deg), n_long=int(long_rows.numel()),
-                                        n_chunks=n_chunks, long_rows=long_rows.contiguous(),
-                                        long_ptr=long_ptr, chunk_long=chunk_long.contiguous(),
-                                        chunk_start=chunk_start, chunk_end=chunk_end)
+            t = csr.chunk_table(self.rowptr, key[0], key[1])
+            if t is not None:
+                t = dict(split_deg=key[0], n_long=t["n_long"], n_chunks=t["n_chunks"], long_rows=t["long"],
+                         long_ptr=t["long_ptr"], chunk_long=t["chunk_long"].to(torch.int32),       # (HanRowSplit reads
+                         chunk_start=t["chunk_start"], chunk_end=t["chunk_end"])                   # int32 chunk_long)
+            self._split[key] = t
         return self._split[key]
 
     def row_bins(self, short_deg: int = 16, split_deg: int = 1024):
@@ -186,21 +171,23 @@ class CSRGraph:
     # ---- transposition (CSC) ------------------------------------------------
     def transpose(self) -> "CSRGraph":
         """The transposed graph: for every source j the destinations i, in
-        ascending i (stable), as a CSRGraph with n_rows = n_cols of self."""
-        if self._t is None:
-            rows = torch.repeat_interleave(
-                torch.arange(self.n_rows, device=self.device, dtype=torch.int32), self.degrees())
-            cols = self.colidx.long()
+        ascending i (stable), as a CSRGraph with n_rows = n_cols of self.  Cached."""
+        return self._t if self._t is not None else self.transpose_with()[0]
+
+    def transpose_with(self, *per_entry: torch.Tensor):
+        """(transpose(), every (nnz,) tensor of `per_entry` in the entry order of the transposed graph): what rides
+        along goes through the one stable sort that builds the graph.  The order is not kept: beside a cached
+        transpose it is sorted again."""
+        cols = self.colidx.long()
+        if self._t is not None:
             order = torch.sort(cols, stable=True).indices
-            rowidx = rows[order].contiguous()
-            counts = torch.bincount(cols, minlength=self.n_cols)
-            colptr = torch.zeros(self.n_cols + 1, dtype=torch.int64, device=self.device)
-            torch.cumsum(counts, 0, out=colptr[1:])
-            t = CSRGraph(colptr, rowidx, n_cols=self.n_rows, validate=False,
-                         values=self.values[order] if self.values is not None else None)
+        else:
+            colptr, order = csr.group_by(cols, self.n_cols)
+            t = CSRGraph(colptr, csr.row_ids(self.rowptr, torch.int32)[order].contiguous(), n_cols=self.n_rows,
+                         validate=False, values=self.values[order] if self.values is not None else None)
             t._t = self
             self._t = t
-        return self._t
+        return (self._t,) + tuple(a[order] for a in per_entry)
 
     # ---- constructors ---------------------------------------------------------
     @staticmethod
@@ -221,21 +208,15 @@ class CSRGraph:
             b = b.to(torch.float32)
             if b.stride(1) != 1:
                 b = b.contiguous()
-            counts = torch.empty(n, dtype=torch.int64, device=b.device)
-            _lib.check(lib.han_bias_row_counts(b.data_ptr(), n, b.stride(0), counts.data_ptr(),
-                                               _stream()), "han_bias_row_counts")
-            rowptr = torch.zeros(n + 1, dtype=torch.int64, device=b.device)
-            torch.cumsum(counts, 0, out=rowptr[1:])
-            nnz = int(rowptr[-1])
-            colidx = torch.empty(nnz, dtype=torch.int32, device=b.device)
-            _lib.check(lib.han_bias_fill_csr(b.data_ptr(), n, b.stride(0), rowptr.data_ptr(),
-                                             colidx.data_ptr(), _stream()), "han_bias_fill_csr")
+            rowptr, colidx = csr.two_pass(
+                n, b.device, (torch.int32,),
+                lambda counts: _lib.check(lib.han_bias_row_counts(b.data_ptr(), n, b.stride(0), counts.data_ptr(),
+                                                                  _stream()), "han_bias_row_counts"),
+                lambda rowptr, colidx: _lib.check(lib.han_bias_fill_csr(b.data_ptr(), n, b.stride(0), rowptr.data_ptr(),
+                                                                        colidx.data_ptr(), _stream()), "han_bias_fill_csr"))
             return CSRGraph(rowptr, colidx, n, validate=False)
         keep = b > EDGE_THRESHOLD
-        rowptr = torch.zeros(n + 1, dtype=torch.int64)
-        torch.cumsum(keep.sum(1), 0, out=rowptr[1:])
-        colidx = keep.nonzero()[:, 1].to(torch.int32)
-        return CSRGraph(rowptr, colidx, n, validate=False)
+        return CSRGraph(csr.scan(keep.sum(1)), keep.nonzero()[:, 1].to(torch.int32), n, validate=False)
 
     @staticmethod
     def from_adjacency(adj, add_self_loops: bool = True, device=None) -> "CSRGraph":
@@ -273,18 +254,14 @@ class CSRGraph:
             if t.shape[0] != 1:
                 raise ValueError("batch size must be 1 (utils/layers.py:110-113)")
             idx = idx[1:]
-        n = t.shape[-2]
-        order = torch.argsort(idx[0] * t.shape[-1] + idx[1])
-        rows, cols = idx[0][order], idx[1][order]
-        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=t.device)
-        torch.cumsum(torch.bincount(rows, minlength=n), 0, out=rowptr[1:])
+        key, order = torch.sort(idx[0] * t.shape[-1] + idx[1])
+        rowptr, cols = csr.from_sorted_keys(key, t.shape[-2], t.shape[-1])
         return CSRGraph(rowptr, cols.to(torch.int32), t.shape[-1], values=vals_of(t.values()[order]))
 
     def to_bias(self, dtype=torch.float32) -> torch.Tensor:
         """Back to the reference's dense additive mask (1,N,N) -- tests only."""
         b = torch.full((self.n_rows, self.n_cols), -1e9, dtype=dtype, device=self.device)
-        rows = torch.repeat_interleave(torch.arange(self.n_rows, device=self.device), self.degrees())
-        b[rows, self.colidx.long()] = 0.0
+        b[csr.row_ids(self.rowptr), self.colidx.long()] = 0.0
         return b[None]
 
 

@@ -26,7 +26,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import ops
+from . import csr, ops
 from .graph import CSRGraph
 
 
@@ -41,12 +41,9 @@ def _ids(x, name, device):
     return t.to(torch.int64)
 
 
-def _from_keys(key, n_rows, n_cols, device) -> CSRGraph:
+def _from_keys(key, n_rows, n_cols) -> CSRGraph:
     """CSR of the sorted, unique entry keys row * n_cols + col."""
-    rows = key // n_cols if key.numel() else key
-    cols = key - rows * n_cols
-    rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=device)
-    torch.cumsum(torch.bincount(rows, minlength=n_rows), 0, out=rowptr[1:])
+    rowptr, cols = csr.from_sorted_keys(key, n_rows, n_cols)
     return CSRGraph(rowptr, cols.to(torch.int32), n_cols, validate=False)
 
 
@@ -66,7 +63,7 @@ def relation(src, dst, n_src: int, n_dst: int, device=None) -> CSRGraph:
             lo, hi = int(t.min()), int(t.max())
             if lo < 0 or hi >= n:
                 raise ValueError(f"{name} ids outside [0, {n}): [{lo}, {hi}]")
-    return _from_keys(torch.unique(s * n_dst + d), n_src, n_dst, s.device)
+    return _from_keys(torch.unique(s * n_dst + d), n_src, n_dst)
 
 
 WEIGHTS = (None, "count", "pathsim")
@@ -108,16 +105,15 @@ def _compose(graphs, self_loops, counted):
     every product fed the counts of the one before as operand values)."""
     if len(graphs) == 1:       # no product: the graph itself, sorted and unique (+ I)
         g = graphs[0]
-        rows = torch.repeat_interleave(torch.arange(g.n_rows, device=g.device), g.degrees())
-        key = rows * g.n_cols + g.colidx.long()
+        key = csr.row_ids(g.rowptr) * g.n_cols + g.colidx.long()
         n_stored = key.numel()
         if self_loops:
             key = torch.cat([key, torch.arange(g.n_rows, device=g.device) * (g.n_cols + 1)])
         if not counted:
-            return _from_keys(torch.unique(key), g.n_rows, g.n_cols, g.device), None
+            return _from_keys(torch.unique(key), g.n_rows, g.n_cols), None
         key, inv = torch.unique(key, return_inverse=True)
         counts = torch.bincount(inv[:n_stored], minlength=key.numel())      # an added (i, i) counts 0
-        return _from_keys(key, g.n_rows, g.n_cols, g.device), counts
+        return _from_keys(key, g.n_rows, g.n_cols), counts
     c, counts = graphs[0], None
     for k, g in enumerate(graphs[1:]):
         diag = self_loops and k == len(graphs) - 2
@@ -182,9 +178,8 @@ def plan(relations: dict, metapath: str) -> dict:
 
 
 def _transposed(g: CSRGraph, counts):
-    """(gᵀ, its counts): CSRGraph.transpose carries fp32 values only, the int64 counts take the same stable order."""
-    order = torch.sort(g.colidx.long(), stable=True).indices
-    return g.transpose(), counts[order]
+    """(gᵀ, its counts): the int64 counts ride through the sort that builds gᵀ (its fp32 values would round them)."""
+    return g.transpose_with(counts)
 
 
 def metapath_graph(relations: dict, metapath: str, self_loops: bool = True, weights=None, top_k=None) -> CSRGraph:

@@ -11,7 +11,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, csr
 from .features import SparseFeatures
 from .graph import CSRGraph
 
@@ -58,6 +58,11 @@ K2_TIMING: list | None = None
 def _ptr(t):
     """Device pointer of an optional tensor (NULL for None)."""
     return t.data_ptr() if t is not None else None
+
+
+def _ptr_nonempty(t):
+    """Device pointer of an optional tensor that may be empty, as the graphs K0 takes (NULL for None or no elements)."""
+    return t.data_ptr() if t is not None and t.numel() else None
 
 
 class _k2_timed:
@@ -849,8 +854,7 @@ def _spgemm_structure(A: CSRGraph, B: CSRGraph, diag: bool):
         return CSRGraph(torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev),
                         B.n_cols, validate=False), None
     flags = SPGEMM_DIAG if diag else 0
-    st = _stream()
-    ptr = lambda t: t.data_ptr() if t.numel() else None
+    st, ptr = _stream(), _ptr_nonempty
     ub = torch.empty(n, dtype=torch.int64, device=dev)
     _lib.check(lib.han_spgemm_row_bounds(A.rowptr.data_ptr(), ptr(A.colidx), B.rowptr.data_ptr(), n, A.n_cols, flags,
                                          ub.data_ptr(), st), "han_spgemm_row_bounds")
@@ -860,15 +864,14 @@ def _spgemm_structure(A: CSRGraph, B: CSRGraph, diag: bool):
     n_long = (ub > SPGEMM_SHORT).sum().reshape(1)
     args = (A.rowptr.data_ptr(), ptr(A.colidx), B.rowptr.data_ptr(), ptr(B.colidx), n, A.n_cols, B.n_cols,
             rows.data_ptr(), n_long.data_ptr(), SPGEMM_SHORT, SPGEMM_TILE, flags)
-    counts = torch.empty(n, dtype=torch.int64, device=dev)
-    _lib.check(lib.han_spgemm_count(*args, counts.data_ptr(), st), "han_spgemm_count")
-    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, out=rowptr[1:])
-    nnz = int(rowptr[-1])
-    colidx = torch.empty(nnz, dtype=torch.int32, device=dev)
-    _lib.check(lib.han_spgemm_fill(*args, rowptr.data_ptr(), ptr(colidx), st), "han_spgemm_fill")
+    rowptr, colidx = csr.two_pass(
+        n, dev, (torch.int32,),
+        lambda counts: _lib.check(lib.han_spgemm_count(*args, counts.data_ptr(), st), "han_spgemm_count"),
+        lambda rowptr, colidx: _lib.check(lib.han_spgemm_fill(*args, rowptr.data_ptr(), colidx.data_ptr(), st),
+                                          "han_spgemm_fill"))
     if SPGEMM_STATS is not None:
-        SPGEMM_STATS.append(dict(rows=n, cols=B.n_cols, nnz_a=A.nnz, nnz=nnz, candidates=ub.sum(), n_long=n_long))
+        SPGEMM_STATS.append(dict(rows=n, cols=B.n_cols, nnz_a=A.nnz, nnz=colidx.numel(), candidates=ub.sum(),
+                                 n_long=n_long))
     return CSRGraph(rowptr, colidx, B.n_cols, validate=False), (rows, n_long, SPGEMM_SHORT, SPGEMM_TILE, flags)
 
 
@@ -899,8 +902,7 @@ def csr_count_matmul(A: CSRGraph, B: CSRGraph, a_counts=None, b_counts=None, dia
     C, bins = _spgemm_structure(A, B, diag)
     counts = torch.empty(C.nnz, dtype=torch.int64, device=C.device)
     if C.nnz:
-        rows, n_long, short_max, tile_cols, flags = bins
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        (rows, n_long, short_max, tile_cols, flags), ptr = bins, _ptr_nonempty
         _lib.check(_lib.load().han_spgemm_values(
             A.rowptr.data_ptr(), ptr(A.colidx), ptr(a_counts), B.rowptr.data_ptr(), ptr(B.colidx), ptr(b_counts),
             A.n_rows, A.n_cols, B.n_cols, rows.data_ptr(), n_long.data_ptr(), short_max, tile_cols, flags,
@@ -943,20 +945,14 @@ def csr_row_topk(graph: CSRGraph, k: int, keep_diag: bool = True) -> CSRGraph:
         raise ValueError("csr_row_topk: the diagonal of a row shard (row_base != 0) is not supported")
     require_gpu(graph.rowptr, "graph")
     lib, k, n, dev, st = _lib.load(), int(k), graph.n_rows, graph.device, _stream()
-    ptr = lambda t: t.data_ptr() if t.numel() else None
-    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    if n:
-        counts = torch.empty(n, dtype=torch.int64, device=dev)
-        _lib.check(lib.han_csr_row_topk_count(graph.rowptr.data_ptr(), ptr(graph.colidx), n, k, int(keep_diag),
-                                              counts.data_ptr(), st), "han_csr_row_topk_count")
-        torch.cumsum(counts, 0, out=rowptr[1:])
-    nnz = int(rowptr[-1])
-    colidx = torch.empty(nnz, dtype=torch.int32, device=dev)
-    values = torch.empty(nnz, dtype=torch.float32, device=dev)
-    if nnz:
-        _lib.check(lib.han_csr_row_topk_fill(graph.rowptr.data_ptr(), graph.colidx.data_ptr(), graph.values.data_ptr(),
-                                             n, k, int(keep_diag), rowptr.data_ptr(), colidx.data_ptr(),
-                                             values.data_ptr(), st), "han_csr_row_topk_fill")
+    rowptr, colidx, values = csr.two_pass(
+        n, dev, (torch.int32, torch.float32),
+        lambda counts: _lib.check(lib.han_csr_row_topk_count(
+            graph.rowptr.data_ptr(), _ptr_nonempty(graph.colidx), n, k, int(keep_diag), counts.data_ptr(), st),
+            "han_csr_row_topk_count"),
+        lambda rowptr, colidx, values: _lib.check(lib.han_csr_row_topk_fill(
+            graph.rowptr.data_ptr(), graph.colidx.data_ptr(), graph.values.data_ptr(), n, k, int(keep_diag),
+            rowptr.data_ptr(), colidx.data_ptr(), values.data_ptr(), st), "han_csr_row_topk_fill"))
     return CSRGraph(rowptr, colidx, graph.n_cols, validate=False, values=values)
 
 
@@ -1020,24 +1016,16 @@ def metapath_walk(hops, walks: int, fanout=None, seed: int = 0, diag: bool = Fal
         if g.nnz >= 1 << 32 and int(g.degrees().max()) >= 1 << 32:      # (only such a graph costs a sync of its own)
             raise ValueError(f"hops[{k}] has a row of 2^32 entries or more: the draw is a 32-bit word")
     lib, dev, st, L, m = _lib.load(), hops[0].device, _stream(), len(hops), r1 - r0
-    rowptr = torch.zeros(m + 1, dtype=torch.int64, device=dev)
-    if m == 0:
-        return (CSRGraph(rowptr, torch.zeros(0, dtype=torch.int32, device=dev), n_cols, validate=False, row_base=r0),
-                torch.zeros(0, dtype=torch.int32, device=dev))
     rps = (ctypes.c_void_p * L)(*[g.rowptr.data_ptr() for g in hops])
     cis = (ctypes.c_void_p * L)(*[g.colidx.data_ptr() if g.nnz else None for g in hops])
     nrs = (ctypes.c_int64 * L)(*[g.n_rows for g in hops])
     args = (ctypes.cast(rps, ctypes.c_void_p), ctypes.cast(cis, ctypes.c_void_p), ctypes.cast(nrs, ctypes.c_void_p),
             L, n_cols, r0, m, walks, fanout, seed, int(bool(diag)))
-    counts = torch.empty(m, dtype=torch.int64, device=dev)
-    _lib.check(lib.han_metapath_walk_count(*args, counts.data_ptr(), st), "han_metapath_walk_count")
-    torch.cumsum(counts, 0, out=rowptr[1:])
-    nnz = int(rowptr[-1])
-    colidx = torch.empty(nnz, dtype=torch.int32, device=dev)
-    visits = torch.empty(nnz, dtype=torch.int32, device=dev)
-    if nnz:
-        _lib.check(lib.han_metapath_walk_fill(*args, rowptr.data_ptr(), colidx.data_ptr(), visits.data_ptr(), st),
-                   "han_metapath_walk_fill")
+    rowptr, colidx, visits = csr.two_pass(
+        m, dev, (torch.int32, torch.int32),
+        lambda counts: _lib.check(lib.han_metapath_walk_count(*args, counts.data_ptr(), st), "han_metapath_walk_count"),
+        lambda rowptr, colidx, visits: _lib.check(lib.han_metapath_walk_fill(
+            *args, rowptr.data_ptr(), colidx.data_ptr(), visits.data_ptr(), st), "han_metapath_walk_fill"))
     return CSRGraph(rowptr, colidx, n_cols, validate=False, row_base=r0), visits
 
 

@@ -20,16 +20,8 @@ from __future__ import annotations
 
 import torch
 
+from . import csr
 from .graph import CSRGraph
-
-
-def _ragged_gather_index(starts: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
-    """Positions [starts[i], starts[i] + lens[i]) for every i, concatenated."""
-    total = int(lens.sum())
-    out_ptr = torch.zeros(lens.numel() + 1, dtype=torch.int64, device=lens.device)
-    torch.cumsum(lens, 0, out=out_ptr[1:])
-    seg = torch.repeat_interleave(starts - out_ptr[:-1], lens)
-    return seg + torch.arange(total, device=lens.device)
 
 
 def permute_graph(g: CSRGraph, perm: torch.Tensor, inv: torch.Tensor | None = None) -> CSRGraph:
@@ -42,14 +34,12 @@ def permute_graph(g: CSRGraph, perm: torch.Tensor, inv: torch.Tensor | None = No
         inv = torch.empty_like(perm)
         inv[perm] = torch.arange(perm.numel(), device=g.device)
     deg = g.degrees()[perm]
-    rowptr = torch.zeros(g.n_rows + 1, dtype=torch.int64, device=g.device)
-    torch.cumsum(deg, 0, out=rowptr[1:])
-    src = _ragged_gather_index(g.rowptr[:-1][perm], deg)
+    rowptr = csr.scan(deg)
+    src = csr.ragged_index(g.rowptr[:-1][perm], deg)
     cols = inv[g.colidx[src].long()]
     vals = g.values[src] if g.values is not None else None
     # sort the columns inside each row (keeps the kernels' coalesced index loads monotone)
-    rows = torch.repeat_interleave(torch.arange(g.n_rows, device=g.device), deg)
-    order = torch.sort(rows * g.n_rows + cols).indices
+    order = torch.sort(csr.row_ids(rowptr) * g.n_rows + cols).indices
     return CSRGraph(rowptr, cols[order].to(torch.int32).contiguous(), g.n_cols, validate=False,
                     values=vals[order].contiguous() if vals is not None else None)
 
@@ -63,10 +53,9 @@ def bfs_order(graphs, start: int | None = None) -> torch.Tensor:
     seed is found with a monotone cursor over the ids (one small slice per lookup), not a pass over all n."""
     g0 = graphs[0]
     n, dev = g0.n_rows, g0.device
-    ids = torch.arange(n, device=dev)
     has_nb = torch.zeros(n, dtype=torch.bool, device=dev)
     for g in graphs:
-        rows = torch.repeat_interleave(ids, g.degrees())
+        rows = csr.row_ids(g.rowptr)
         has_nb[rows[g.colidx.long() != rows]] = True
     isolated = torch.nonzero(~has_nb).flatten()
     visited = ~has_nb                       # isolated nodes are placed at the end
@@ -91,7 +80,7 @@ def bfs_order(graphs, start: int | None = None) -> torch.Tensor:
             cand = []
             for g in graphs:
                 lens = g.degrees()[frontier]
-                idx = _ragged_gather_index(g.rowptr[:-1][frontier], lens)
+                idx = csr.ragged_index(g.rowptr[:-1][frontier], lens)
                 cand.append(g.colidx[idx].long())
             c = torch.cat(cand)
             c = c[~visited[c]]

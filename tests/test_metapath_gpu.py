@@ -97,6 +97,39 @@ def test_bool_matmul_degenerate_inputs(dev):
         ops.csr_bool_matmul(A, B, diag=True)
 
 
+def test_two_pass_builders_without_entries(dev):
+    """The count / scan / fill builders (csr.two_pass) on results without entries: no fill launch, empty arrays of the
+    dtypes a full result has, an all-zero row pointer."""
+    def check(g, n_rows, n_cols, *more):
+        assert (g.n_rows, g.n_cols, g.nnz) == (n_rows, n_cols, 0)
+        assert g.rowptr.dtype == torch.int64 and g.rowptr.tolist() == [0] * (n_rows + 1)
+        assert g.colidx.dtype == torch.int32 and g.colidx.shape == (0,)
+        for t, dtype in more:
+            assert t.dtype == dtype and t.shape == (0,) and t.device == g.device
+        assert g.rowptr.device == g.colidx.device == torch.device(dev)
+
+    g = CSRGraph.from_bias(torch.full((4, 4), -1e9, device=dev))
+    check(g, 4, 4)
+    assert g.values is None
+    A = CSRGraph(torch.zeros(4, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev), 2)
+    B = _graph([[0, 3], [1]], 4, dev)
+    C = ops.csr_bool_matmul(A, B)
+    check(C, 3, 4)
+    assert C.values is None
+    C, counts = ops.csr_count_matmul(A, B)
+    check(C, 3, 4, (counts, torch.int64))
+    V = CSRGraph(torch.zeros(4, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev), 3,
+                 values=torch.zeros(0, dtype=torch.float32, device=dev))
+    T = ops.csr_row_topk(V, 2)
+    check(T, 3, 3, (T.values, torch.float32))
+    hop = CSRGraph(torch.zeros(4, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int32, device=dev), 3)
+    g, visits = ops.metapath_walk([hop], 8, 2)
+    check(g, 3, 3, (visits, torch.int32))
+    g, visits = ops.metapath_walk([hop], 8, 2, diag=True)          # the lone (i, i), never visited
+    assert g.rowptr.tolist() == [0, 1, 2, 3] and g.colidx.tolist() == [0, 1, 2] and g.colidx.dtype == torch.int32
+    assert visits.dtype == torch.int32 and visits.tolist() == [0, 0, 0]
+
+
 @pytest.fixture(scope="module")
 def dblp():
     dev = torch.device("cuda:0")
