@@ -41,6 +41,8 @@ def main():
     ap.add_argument("--eval-device", choices=("cpu", "gpu"), default="cpu",
                     help="where final_embed is scored: cpu = scikit-learn on the host, as the reference; gpu = the "
                          "evaluation kernels (the embeddings are not copied to the host)")
+    ap.add_argument("--silhouette", action="store_true",
+                    help="also report the silhouette score of the k-means labels (the data/exp.py form of my_Kmeans)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(args.seed)
@@ -110,7 +112,7 @@ def main():
         sel = masks[2].bool().cpu().numpy()
         emb, lab, eval_dev = final_embed.cpu().numpy()[sel], labels.cpu().numpy()[sel], None
     evaluate.my_KNN(emb, lab, seed=args.seed, device=eval_dev)                     # ex_acm3025.py:288
-    evaluate.my_Kmeans(emb, lab, k=nb_classes, seed=args.seed, device=eval_dev)    # :289
+    evaluate.my_Kmeans(emb, lab, k=nb_classes, seed=args.seed, device=eval_dev, silhouette=args.silhouette)    # :289
 
 
 if __name__ == "__main__":

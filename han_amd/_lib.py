@@ -102,9 +102,11 @@ SIGNATURES = {
     "han_contingency": (c_int, [P, P, I64, c_int, c_int, P, P]),
     "han_kmeans_step_workspace": (c_size_t, [I64, c_int, c_int]),
     "han_kmeans_step": (c_int, [P, I64, P, P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, P]),
+    "han_silhouette_workspace": (c_size_t, [I64, c_int, c_int]),
+    "han_silhouette": (c_int, [P, I64, P, I64, c_int, c_int, P, P, P, P, P, c_size_t, P]),
 }
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 _lib = None
 
 

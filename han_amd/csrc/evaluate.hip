@@ -1,11 +1,12 @@
 // Evaluation of the final embeddings on the GPU (jhyexp.py:20-86): brute-force k nearest neighbours with a
-// majority vote, contingency tables for F1 / NMI / ARI, and one Lloyd iteration of k-means.
+// majority vote, contingency tables for F1 / NMI / ARI, one Lloyd iteration of k-means, and the silhouette score of a
+// clustering (data/exp.py:46-49).
 //
 // Distances are d2 = |q|^2 + |t|^2 - 2 q.t.  The q.t term runs on the exact-fp32 matrix pipe
 // (v_mfma_f32_16x16x4_f32) in tiles of 64 x 64 pairs per workgroup step; the distance matrix never exists in
 // memory: a lane sees its 16 candidates of a tile in registers and keeps a sorted list of the best ones.
 //
-// Tile layout (both kernels).  A workgroup of 4 waves stages 64 "column" rows (queries / data rows) and 64 "row"
+// Tile layout (all three tile kernels).  A workgroup of 4 waves stages 64 "column" rows (queries / data rows) and 64 "row"
 // rows (train rows / centres), 64 embedding columns at a time, into LDS as [64][kLd] fp32, zero-filled past the
 // matrix edges and past D (so a D that is no multiple of 4 is padded in LDS, never in memory).  Wave w owns the
 // column rows 16 w .. 16 w + 15 and walks all 64 row rows as four 16 x 16 accumulators.  The MFMA sums over its K
@@ -359,6 +360,155 @@ __global__ __launch_bounds__(kBlock) void kmeans_finish(const double *slab, int 
     }
 }
 
+// ---- silhouette (data/exp.py:46-49) -----------------------------------------------------------------------------
+// S(i, c) = sum over the rows j of cluster c of |x_i - x_j|, for a row tile of 64 rows i against the column rows
+// [blockIdx.y * split_rows, + split_rows).  The rows are grouped by cluster, so the column tiles are cut at the segment
+// (and split) boundaries and a tile holds rows of ONE cluster: a lane adds the (at most 16) distances it sees of a
+// tile in fp32 in a fixed order, adds that to its double sum of the cluster, and at the end of the cluster the four
+// lanes of a row are added in a fixed order.  No accumulator is indexed by a label.
+struct SilArgs {
+    const float *X, *xn;
+    const int64_t *seg;      // (k + 1) segment bounds
+    int64_t ldx, N, split_rows;
+    int D, k;
+    double *slab;            // [split][k][N] partial S(i, c); NULL with one split: a and b are formed here
+    double *ab;              // [2][N]: a, then b
+};
+
+// a and b of a row from its sums: n_own rows in its cluster (itself included), `best` the smallest mean distance to
+// another non-empty cluster (+inf: there is none)
+__device__ __forceinline__ void sil_ab(double s_own, int64_t n_own, double best, double *a, double *b) {
+    *a = n_own > 1 ? s_own / (double)(n_own - 1) : 0.0;
+    *b = best < __builtin_inf() ? best : 0.0;
+}
+
+__global__ __launch_bounds__(kBlock) void sil_tiles(const SilArgs a) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * kTile * kLd];
+    __shared__ float tns[kTile];
+    __shared__ int64_t segs[kMaxCentres + 1];
+    float *Rs = smem, *Cs = smem + kTile * kLd;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    if (threadIdx.x <= a.k) segs[threadIdx.x] = a.seg[threadIdx.x];
+    const int64_t q0 = (int64_t)blockIdx.x * kTile;
+    const int64_t t_begin = (int64_t)blockIdx.y * a.split_rows;
+    const int64_t t_end = min(a.N, t_begin + a.split_rows);
+    const int64_t myq = q0 + 16 * w + n;
+    const float qnorm = myq < a.N ? a.xn[myq] : 0.f;
+    const int nch = (a.D + kChunk - 1) / kChunk;
+    double s_own = 0.0, best = __builtin_inf();
+    int64_t n_own = 0;
+    bool staged = false;                                     // the row tile is in Cs (one chunk: staged once)
+    __syncthreads();
+    for (int c = 0; c < a.k; ++c) {
+        const int64_t c0 = segs[c], c1 = segs[c + 1];
+        const int64_t lo = max(c0, t_begin), hi = min(c1, t_end);      // inside [0, N) whatever seg holds
+        double S = 0.0;
+        for (int64_t t0 = lo; t0 < hi; t0 += kTile) {
+            const int nj = (int)((min(hi - t0, (int64_t)kTile) + 15) >> 4);
+            float4_t acc[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = float4_t{0.f, 0.f, 0.f, 0.f};
+            for (int ch = 0; ch < nch; ++ch) {
+                __syncthreads();
+                stage_tile(Rs, a.X, a.ldx, t0, hi, ch * kChunk, a.D);
+                if (nch > 1 || !staged) stage_tile(Cs, a.X, a.ldx, q0, a.N, ch * kChunk, a.D);
+                if (ch == 0 && threadIdx.x < kTile) tns[threadIdx.x] = t0 + threadIdx.x < hi ? a.xn[t0 + threadIdx.x] : 0.f;
+                __syncthreads();
+                mma_chunk(acc, Rs, Cs, w, lane, nj);
+            }
+            staged = true;
+            float part = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int tl = 16 * j + 4 * g + r;
+                    if (t0 + tl < hi) {
+                        const float d2 = (qnorm + tns[tl]) - 2.f * acc[j][r];
+                        part += t0 + tl == myq ? 0.f : sqrtf(fmaxf(d2, 0.f));      // the pair (i, i) by its index
+                    }
+                }
+            S += (double)part;
+        }
+        S += __shfl_xor(S, 16, 64);                          // (g0 + g1) + (g2 + g3) in every lane of the row
+        S += __shfl_xor(S, 32, 64);
+        if (a.slab) {
+            if (g == 0 && myq < a.N) a.slab[((size_t)blockIdx.y * a.k + c) * a.N + myq] = S;
+        } else if (myq >= c0 && myq < c1) {
+            s_own = S;
+            n_own = c1 - c0;
+        } else if (c1 > c0) {
+            best = fmin(best, S / (double)(c1 - c0));
+        }
+    }
+    if (!a.slab && g == 0 && myq < a.N) sil_ab(s_own, n_own, best, &a.ab[myq], &a.ab[a.N + myq]);
+}
+
+// a thread per row: a and b (from the slabs of the splits, added in order, when there are any), s, and the sum of
+// the workgroup's s in row order
+__global__ __launch_bounds__(kBlock) void sil_finish(const int64_t *seg, int k, int64_t N, const double *slab, int nsplit,
+                                                    const double *ab, float *a_out, float *b_out, float *s_out,
+                                                    double *part) {
+    __shared__ int64_t segs[kMaxCentres + 1];
+    __shared__ double ps[kBlock];
+    if (threadIdx.x <= k) segs[threadIdx.x] = seg[threadIdx.x];
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    double s = 0.0;
+    if (i < N) {
+        double av, bv, s_own = 0.0, best = __builtin_inf();
+        int64_t n_own = 0;
+        bool other = false;                                  // another cluster has rows
+        for (int c = 0; c < k; ++c) {
+            const int64_t c0 = segs[c], c1 = segs[c + 1];
+            if (c1 <= c0) continue;
+            const bool own = i >= c0 && i < c1;
+            if (own) n_own = c1 - c0;
+            else other = true;
+            if (slab) {
+                double S = 0.0;
+                for (int sp = 0; sp < nsplit; ++sp) S += slab[((size_t)sp * k + c) * N + i];
+                if (own) s_own = S;
+                else best = fmin(best, S / (double)(c1 - c0));
+            }
+        }
+        if (slab) {
+            sil_ab(s_own, n_own, best, &av, &bv);
+        } else {
+            av = ab[i];
+            bv = ab[N + i];
+        }
+        const double m = fmax(av, bv);
+        s = (n_own > 1 && other && m > 0.0) ? (bv - av) / m : 0.0;
+        const float sf = (float)s;
+        s = (double)sf;                                      // the sum is that of the fp32 values written
+        if (a_out) a_out[i] = (float)av;
+        if (b_out) b_out[i] = (float)bv;
+        if (s_out) s_out[i] = sf;
+    }
+    ps[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int e = 0; e < kBlock; ++e) t += ps[e];
+        part[blockIdx.x] = t;
+    }
+}
+
+// one workgroup: the partials of sil_finish, each thread its own in order, then the 256 threads in order
+__global__ __launch_bounds__(kBlock) void sil_total(const double *part, int64_t nparts, double *sum) {
+    __shared__ double ps[kBlock];
+    double t = 0.0;
+    for (int64_t e = threadIdx.x; e < nparts; e += kBlock) t += part[e];
+    ps[threadIdx.x] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int e = 0; e < kBlock; ++e) s += ps[e];
+        *sum = s;
+    }
+}
+
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // train-set splits of a KNN call: enough workgroups to fill the device when there are few queries
@@ -403,6 +553,24 @@ inline KmeansPlan kmeans_plan(int64_t N, int D, int k) {
 }
 
 inline int norms_grid(int64_t n) { return han_grid_for(n, kBlock / 16, 8192); }
+
+// the column range of a silhouette call is split like the train set of a KNN call; slabs only with more than one split
+struct SilPlan {
+    int64_t split_rows, finish_blocks;
+    int nsplit;
+    size_t off_ab, off_part, off_slab, bytes;
+};
+
+inline SilPlan sil_plan(int64_t N, int k) {
+    SilPlan p;
+    p.nsplit = knn_splits(N, N, &p.split_rows);
+    p.finish_blocks = (N + kBlock - 1) / kBlock;
+    p.off_ab = align256((size_t)N * sizeof(float));
+    p.off_part = p.off_ab + align256((size_t)2 * N * sizeof(double));
+    p.off_slab = p.off_part + align256((size_t)p.finish_blocks * sizeof(double));
+    p.bytes = p.off_slab + (p.nsplit > 1 ? align256((size_t)p.nsplit * k * N * sizeof(double)) : 0);
+    return p;
+}
 
 }  // namespace
 
@@ -528,6 +696,39 @@ extern "C" int han_kmeans_step(const float *X, int64_t ldx, const float *C, cons
     kmeans_finish<<<(k * D + kBlock - 1) / kBlock, kBlock, 0, st>>>(slab, p.sum_blocks, p.dp, C, D, k,
                                                                   (const unsigned long long *)counts, new_centres, part,
                                                                   p.assign_blocks, inertia);
+    HAN_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" size_t han_silhouette_workspace(int64_t N, int D, int k) {
+    if (N <= 0 || D < 1 || D > kMaxD || k < 2 || k > kMaxCentres || N > 0x7FFFFFFF) return 0;
+    return sil_plan(N, k).bytes;
+}
+
+extern "C" int han_silhouette(const float *X, int64_t ldx, const int64_t *seg_ptr, int64_t N, int D, int k, float *a,
+                              float *b, float *s, double *sum, void *workspace, size_t workspace_bytes, void *stream) {
+    if (N < 0 || D < 1 || k < 2 || ldx < D) return HAN_E_BADARG;
+    if (k > kMaxCentres || D > kMaxD || N > 0x7FFFFFFF) return HAN_E_UNSUPPORTED;
+    if (!sum) return HAN_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) return (int)hipMemsetAsync(sum, 0, sizeof(double), st);
+    if (!X || !seg_ptr || !workspace) return HAN_E_BADARG;
+    const SilPlan p = sil_plan(N, k);
+    if (workspace_bytes < p.bytes) return HAN_E_WORKSPACE;
+    char *ws = (char *)workspace;
+    float *xn = (float *)ws;
+    double *ab = (double *)(ws + p.off_ab), *part = (double *)(ws + p.off_part);
+    double *slab = p.nsplit > 1 ? (double *)(ws + p.off_slab) : nullptr;
+    row_norms<<<norms_grid(N), kBlock, 0, st>>>(X, ldx, N, D, xn);
+    HAN_CHECK_LAUNCH();
+    SilArgs t;
+    t.X = X; t.xn = xn; t.seg = seg_ptr; t.ldx = ldx; t.N = N; t.split_rows = p.split_rows; t.D = D; t.k = k;
+    t.slab = slab; t.ab = ab;
+    sil_tiles<<<dim3((unsigned)((N + kTile - 1) / kTile), (unsigned)p.nsplit), kBlock, 0, st>>>(t);
+    HAN_CHECK_LAUNCH();
+    sil_finish<<<(unsigned)p.finish_blocks, kBlock, 0, st>>>(seg_ptr, k, N, slab, p.nsplit, ab, a, b, s, part);
+    HAN_CHECK_LAUNCH();
+    sil_total<<<1, kBlock, 0, st>>>(part, p.finish_blocks, sum);
     HAN_CHECK_LAUNCH();
     return 0;
 }

@@ -9,6 +9,10 @@ With ``device=`` given, ``my_KNN`` / ``my_Kmeans`` run on the GPU instead (the `
 ``kmeans``): the embeddings stay on the device and only the small count tables come back.  The scores are formed
 on the host in float64 from those tables (``f1_from_table``, ``nmi_ari_from_table``: scikit-learn's conventions).
 
+``data/exp.py:25-62`` is the reference's second copy of the clustering evaluation; it adds the silhouette score of
+the k-means labels (``data/exp.py:46-49``).  ``silhouette_samples`` / ``silhouette_score`` are that number on the
+host (scikit-learn) or on the device (``han_silhouette``), and ``my_Kmeans(..., silhouette=True)`` is that form.
+
 Random streams: the reference draws its shuffles from NumPy's GLOBAL legacy generator
 (``np.random.permutation``, jhyexp.py:33) and lets scikit-learn's KMeans fall back on the
 same global generator (``random_state=None``, jhyexp.py:62).  Here both use ONE
@@ -53,29 +57,41 @@ def my_KNN(x, y, k=5, split_list=(0.2, 0.4, 0.6, 0.8), time=10, shuffle=True, se
     return out
 
 
-def my_Kmeans(x, y, k=4, time=10, seed=None, verbose=True, device=None):
+def my_Kmeans(x, y, k=4, time=10, seed=None, verbose=True, device=None, silhouette=False):
     """jhyexp.py:54-86.  Returns (NMI, ARI) averaged over `time` fits.
     device=None: scikit-learn on the host, as the reference.  With a device: `time` fits of kmeans() (k-means++
     seeding, Lloyd on the GPU) drawing from ONE RandomState, scored by nmi_ari; the random stream is not
-    scikit-learn's, so the clusterings are equally good, not identical."""
+    scikit-learn's, so the clusterings are equally good, not identical.
+    silhouette=True is the data/exp.py:25-54 form: (NMI, ARI, silhouette), the third the silhouette_score of each
+    fit's labels averaged likewise.  It draws nothing from the RandomState, so NMI and ARI do not depend on it."""
     if device is not None:
-        return _my_kmeans_device(x, y, k, time, seed, verbose, device)
+        return _my_kmeans_device(x, y, k, time, seed, verbose, device, silhouette)
     from sklearn.cluster import KMeans
     from sklearn.metrics import adjusted_rand_score, normalized_mutual_info_score
+    from sklearn.metrics import silhouette_score as sk_silhouette_score
     x = np.squeeze(np.array(x))
     y = np.array(y)
     if y.ndim > 1:
         y = np.argmax(y, axis=1)
-    nmi, ari = [], []
+    nmi, ari, sil = [], [], []
     rs = np.random.RandomState(seed) if not isinstance(seed, np.random.RandomState) else seed
     est = KMeans(n_clusters=k, random_state=rs)          # ONE estimator, library defaults (jhyexp.py:62)
     for i in range(time):
         pred = est.fit(x, y).predict(x)                  # re-fitted `time` times (jhyexp.py:67-68)
         nmi.append(normalized_mutual_info_score(y, pred))
         ari.append(adjusted_rand_score(y, pred))
+        if silhouette:                                   # data/exp.py:47-48
+            sil.append(sk_silhouette_score(x, est.labels_, metric="euclidean"))
+    return _kmeans_result(nmi, ari, sil, silhouette, verbose)
+
+
+def _kmeans_result(nmi, ari, sil, silhouette, verbose):
     res = float(np.mean(nmi)), float(np.mean(ari))
-    if verbose:
-        print("NMI (10 avg): {:.4f} , ARI (10avg): {:.4f}".format(*res))
+    if silhouette:
+        res += (float(np.mean(sil)),)
+    if verbose:                                          # jhyexp.py:86 / data/exp.py:54
+        print(("NMI (10 avg): {:.4f} , ARI (10avg): {:.4f}, silhouette(10avg): {:.4f}" if silhouette else
+               "NMI (10 avg): {:.4f} , ARI (10avg): {:.4f}").format(*res))
     return res
 
 
@@ -313,6 +329,92 @@ def kmeans(x, k, init=None, seed=None, n_init=1, max_iter=300, tol=1e-4, device=
     return best
 
 
+SILHOUETTE_MAX_K = 64   # han_silhouette
+SILHOUETTE_MAX_D = 512
+
+
+def _on_host(device, *arrays):
+    return device is None and not any(_is_tensor(a) and a.is_cuda for a in arrays)
+
+
+def _host_array(a, dtype=None):
+    return np.asarray(a.numpy() if _is_tensor(a) else a, dtype=dtype)
+
+
+def _silhouette_device(x, labels, device):
+    """(s in the caller's row order, its sum (1,) float64) on the device.  The distinct labels, any integers, become
+    codes 0 .. k - 1; a stable sort of the codes groups the rows, one gather of x puts them in that order for
+    ops.silhouette, and its rows are scattered back."""
+    import torch
+    from . import ops
+    n, d = _shape2(x, "x")
+    dev = _pick_device(device, x, labels)
+    lab = labels if _is_tensor(labels) else torch.as_tensor(np.array(labels))
+    if lab.dim() != 1 or lab.shape[0] != n:
+        raise ValueError(f"labels: shape {tuple(lab.shape)} for {n} rows")
+    if lab.is_floating_point() or lab.dtype == torch.bool:
+        raise ValueError(f"labels: expected integers, got {lab.dtype}")
+    uniq, codes = torch.unique(lab.to(device=dev, dtype=torch.int64), return_inverse=True)
+    k = int(uniq.numel())
+    if not 2 <= k <= n - 1:                                  # scikit-learn's check_number_of_labels
+        raise ValueError(f"Number of labels is {k}. Valid values are 2 to n_samples - 1 (inclusive)")
+    if k > SILHOUETTE_MAX_K:
+        raise ValueError(f"{k} distinct labels: the device path takes at most {SILHOUETTE_MAX_K}")
+    if d > SILHOUETTE_MAX_D:
+        raise ValueError(f"x has width {d}: the device path takes at most {SILHOUETTE_MAX_D} columns")
+    order = torch.sort(codes, stable=True).indices
+    seg = torch.zeros(k + 1, dtype=torch.int64, device=dev)
+    seg[1:] = torch.cumsum(torch.bincount(codes, minlength=k), 0)
+    r = ops.silhouette(_embed(x, dev)[order], seg)
+    s = torch.empty_like(r["s"])
+    s[order] = r["s"]
+    return s, r["sum"]
+
+
+def _sample(x, labels, sample_size, seed):
+    """scikit-learn's sample_size: the rows RandomState(seed).permutation(n)[:sample_size] (seed=None: NumPy's
+    global generator, a RandomState: that one)."""
+    n = _shape2(x, "x")[0]
+    rs = seed if isinstance(seed, np.random.RandomState) else \
+        np.random.mtrand._rand if seed is None else np.random.RandomState(seed)
+    idx = rs.permutation(n)[:sample_size]
+
+    def pick(a):
+        if _is_tensor(a):
+            import torch
+            return a[torch.as_tensor(idx, device=a.device)]
+        return np.asarray(a)[idx]
+    return pick(x), pick(labels)
+
+
+def silhouette_samples(x, labels, device=None):
+    """sklearn.metrics.silhouette_samples(x, labels, metric="euclidean"): per row (b - a) / max(a, b), a the mean
+    distance to the other rows of its cluster and b the smallest mean distance to another cluster; 0 for a cluster
+    of one row.  labels are any integers.  With device=None and no GPU tensor among the arguments: scikit-learn on
+    the host in float64, the array it returns.  Otherwise han_silhouette on the device: the (n,) fp32 values in the
+    caller's row order, as a tensor on the device.  ValueError unless 2 <= distinct labels <= n - 1; on the device
+    also for more than 64 distinct labels or more than 512 columns."""
+    if _on_host(device, x, labels):
+        from sklearn.metrics import silhouette_samples as sk_samples
+        return sk_samples(_host_array(x, np.float64), _host_array(labels), metric="euclidean")
+    return _silhouette_device(x, labels, device)[0]
+
+
+def silhouette_score(x, labels, sample_size=None, seed=None, device=None):
+    """sklearn.metrics.silhouette_score(x, labels, metric="euclidean", sample_size=sample_size, random_state=seed)
+    (data/exp.py:48): the mean of silhouette_samples, a Python float; with sample_size, over the rows
+    RandomState(seed).permutation(n)[:sample_size] only.  Host or device as silhouette_samples; on the device the
+    mean is formed from the kernel's float64 sum (one small read)."""
+    if _on_host(device, x, labels):
+        from sklearn.metrics import silhouette_score as sk_score
+        return float(sk_score(_host_array(x, np.float64), _host_array(labels), metric="euclidean", sample_size=sample_size,
+                              random_state=seed))
+    if sample_size is not None:
+        x, labels = _sample(x, labels, sample_size, seed)
+    total = _silhouette_device(x, labels, device)[1]
+    return float(total) / _shape2(x, "x")[0]
+
+
 def _my_knn_device(x, y, k, split_list, time, shuffle, seed, verbose, device):
     import torch
     rng = np.random.RandomState(seed) if not isinstance(seed, np.random.RandomState) else seed
@@ -341,7 +443,7 @@ def _my_knn_device(x, y, k, split_list, time, shuffle, seed, verbose, device):
     return out
 
 
-def _my_kmeans_device(x, y, k, time, seed, verbose, device):
+def _my_kmeans_device(x, y, k, time, seed, verbose, device, silhouette):
     import torch
     dev = torch.device(device)
     x = _embed(x, dev)
@@ -349,13 +451,12 @@ def _my_kmeans_device(x, y, k, time, seed, verbose, device):
         x = x.squeeze()
     y = _labels(y, dev)
     rs = np.random.RandomState(seed) if not isinstance(seed, np.random.RandomState) else seed
-    nmi, ari = [], []
+    nmi, ari, sil = [], [], []
     for _ in range(time):
         fit = kmeans(x, k, seed=rs, device=dev)
         s = nmi_ari(y, fit["labels"])
         nmi.append(s[0])
         ari.append(s[1])
-    res = float(np.mean(nmi)), float(np.mean(ari))
-    if verbose:
-        print("NMI (10 avg): {:.4f} , ARI (10avg): {:.4f}".format(*res))
-    return res
+        if silhouette:
+            sil.append(silhouette_score(x, fit["labels"], device=dev))
+    return _kmeans_result(nmi, ari, sil, silhouette, verbose)

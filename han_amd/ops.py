@@ -1033,6 +1033,7 @@ def metapath_walk(hops, walks: int, fanout=None, seed: int = 0, diag: bool = Fal
 KNN_MAX_K = 16             # neighbours per query of han_knn_topk
 EVAL_MAX_D = 512           # embedding width of han_knn_topk / han_kmeans_step
 KMEANS_MAX_K = 64          # centres of han_kmeans_step
+SILHOUETTE_MAX_K = 64      # clusters of han_silhouette
 CONTINGENCY_MAX_CELLS = 4096
 
 
@@ -1133,3 +1134,26 @@ def kmeans_step(x, centres, prev=None, want_d2=True):
                                    _ptr(d2), counts.data_ptr(), new.data_ptr(), inertia.data_ptr(), changed.data_ptr(),
                                    ws.data_ptr(), ws.numel(), n, d, k, _stream()), "han_kmeans_step")
     return dict(labels=labels, d2=d2, counts=counts, centres=new, inertia=inertia, changed=changed)
+
+
+def silhouette(x, seg_ptr):
+    """scikit-learn's silhouette_samples (Euclidean) of rows GROUPED BY CLUSTER (han_silhouette): rows
+    [seg_ptr[c], seg_ptr[c + 1]) of x are cluster c, seg_ptr a (k + 1,) int64 GPU tensor with seg_ptr[0] = 0 and
+    seg_ptr[k] = N, 2 <= k <= 64; a cluster may be empty.  Returns dict(a (N,) fp32 -- the mean distance to the other
+    rows of the own cluster, 0 for a cluster of one row --, b (N,) fp32 -- the smallest mean distance to another
+    non-empty cluster --, s (N,) fp32 = (b - a) / max(a, b), 0 for a cluster of one row, sum (1,) float64 -- the sum
+    of s).  Everything stays on the device; the pair distances are never stored."""
+    ldx = _chk_rows(x, "x")
+    n, d = x.shape
+    _chk(seg_ptr, "seg_ptr", (None,), dtype=torch.int64, device=x.device)
+    k = _chk_int(seg_ptr.shape[0] - 1, "k", 2, SILHOUETTE_MAX_K)
+    if n >= 2 ** 31:
+        raise ValueError("x: at most 2^31 - 1 rows")
+    lib, dev = _lib.load(), x.device
+    a, b, s = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+    total = torch.empty(1, dtype=torch.float64, device=dev)
+    ws = _ws(lib.han_silhouette_workspace(n, d, k), dev, "silhouette")
+    _lib.check(lib.han_silhouette(x.data_ptr() if n else None, ldx, seg_ptr.data_ptr(), n, d, k, _ptr_nonempty(a),
+                                  _ptr_nonempty(b), _ptr_nonempty(s), total.data_ptr(), ws.data_ptr(), ws.numel(),
+                                  _stream()), "han_silhouette")
+    return dict(a=a, b=b, s=s, sum=total)

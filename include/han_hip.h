@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HAN_ABI_VERSION 11
+#define HAN_ABI_VERSION 12
 
 #define HAN_E_BADARG   (-1)   /* null pointer, negative size, inconsistent shape.  The forward
                               * entry points return 0 at once for N == 0 (empty tensors may
@@ -579,6 +579,30 @@ size_t han_kmeans_step_workspace(int64_t N, int D, int k);
 int han_kmeans_step(const float *X, int64_t ldx, const float *C, const int32_t *prev, int32_t *labels, float *d2,
                     int64_t *counts, float *new_centres, double *inertia, int64_t *changed, void *workspace,
                     size_t workspace_bytes, int64_t N, int D, int k, void *stream);
+
+/* ---- silhouette of a clustering of the embeddings (ABI 12) ------------------
+ * The second copy of the reference's clustering evaluation (data/exp.py:25-62) also reports
+ * silhouette_score(x, estimator.labels_, metric='euclidean') of every k-means fit (data/exp.py:46-49).  This is
+ * scikit-learn's silhouette_samples on the device, O(N^2 D) on the exact-fp32 matrix pipe with the tiles of
+ * han_knn_topk; distances are sqrt(max(0, |x_i|^2 + |x_j|^2 - 2 x_i.x_j)), no pair matrix is stored, and every result
+ * is bitwise the same from run to run (no floating-point atomics; sums that cross a tile are carried in double and
+ * added in a fixed order).
+ *
+ * X (N, D) fp32 with leading dimension ldx >= D, 1 <= D <= 512, N < 2^31.  The rows are GROUPED BY CLUSTER: rows
+ * [seg_ptr[c], seg_ptr[c + 1]) are cluster c, seg_ptr (k + 1) int64 on the device, seg_ptr[0] = 0, seg_ptr[k] = N,
+ * 2 <= k <= 64; a cluster may be empty.  A seg_ptr that is not such a sequence gives meaningless numbers (reads stay
+ * inside X).  With n_c the size of cluster c, L the cluster of row i and S(i, c) the sum of |x_i - x_j| over the rows
+ * j of c (the pair j = i contributes exactly 0, by its index):
+ *   a[i] = S(i, L) / (n_L - 1), 0 when n_L = 1;   b[i] = min over c != L with n_c > 0 of S(i, c) / n_c (0 when there
+ *   is no such cluster);   s[i] = (b - a) / max(a, b), and 0 when n_L = 1, when max(a, b) = 0 or when no other
+ *   cluster has rows;   *sum (double, on the device) = the sum of the fp32 s[i], added in double in a fixed order.
+ * a, b, s are (N) fp32 and may each be NULL.  N == 0 returns 0 with *sum = 0.  k < 2, ldx < D, a NULL X / seg_ptr /
+ * sum / workspace: HAN_E_BADARG; k > 64, D > 512 or N >= 2^31: HAN_E_UNSUPPORTED.  workspace:
+ * han_silhouette_workspace() bytes (row norms, a and b in double, the partial sums; with few row tiles the column
+ * range is split over workgroups and the per-(row, cluster) partial sums are merged from it).                */
+size_t han_silhouette_workspace(int64_t N, int D, int k);
+int han_silhouette(const float *X, int64_t ldx, const int64_t *seg_ptr, int64_t N, int D, int k, float *a, float *b,
+                   float *s, double *sum, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -18,10 +18,22 @@ Synthetic 64-wide embeddings of four overlapping classes, seeded.  One JSON line
   agree           share of queries whose prediction equals scikit-learn's (knn), or of rows whose label does (kmeans).
 
     python tools/evaluate_bench.py [--out FILE] [--sizes 3025,100000,1000000]
+
+--silhouette measures evaluate.silhouette_score (han_silhouette) instead.  The process that is started does not touch
+the GPU: it runs one child process per case, each under `timeout` (a case that fails or runs out of time ends the
+run), with at most 16 host threads, and appends one JSON line per case to profiles/r14_silhouette_bench.jsonl (or
+--out).  Cases: --sil-sklearn (default 20000) rows x 64, k = 4, the device against
+sklearn.metrics.silhouette_score on the same host; --sil-device (default 262144) rows, the device alone.  Per case:
+  gpu_ms / pairs_per_s   ops.silhouette on rows already grouped (all launches of the call), pairs = N^2 distances;
+  score_ms               the whole evaluate.silhouette_score: label codes, sort, gather, the kernels, one read;
+  knn_ms / knn_pairs_per_s  ops.knn_topk(x, x, 5) on the same rows in the same run: the same N^2 pair products on the
+                         same pipe -- the yardstick of the pair rate;  vs_knn = pairs_per_s / knn_pairs_per_s;
+  sklearn_s, score_diff, speedup_vs_sklearn   the sklearn case only (one host run; speed-up of the whole score call).
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -64,16 +76,83 @@ def rates(d, pairs, ts):
     return d
 
 
+SIL_OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "r14_silhouette_bench.jsonl")
+HOST_THREADS = 16
+
+
+def silhouette_case(n, with_sklearn, reps):
+    """One case, in a process of its own; returns the record."""
+    torch.set_num_threads(min(HOST_THREADS, torch.get_num_threads()))
+    dev = torch.device("cuda:0")
+    x, y = embeddings(n)
+    xt, yt = torch.as_tensor(x).to(dev), torch.as_tensor(y).to(dev)
+    order = torch.sort(yt.long(), stable=True).indices
+    seg = torch.zeros(5, dtype=torch.int64, device=dev)
+    seg[1:] = torch.cumsum(torch.bincount(yt.long(), minlength=4), 0)
+    xg = xt[order].contiguous()
+    res, ts = gpu_time(lambda: ops.silhouette(xg, seg), reps)
+    d = rates(dict(n=n, d=D, stage="silhouette", k=4), n * n, ts)
+    score, ts = gpu_time(lambda: evaluate.silhouette_score(xt, yt), reps)
+    d.update(score=score, score_ms=round(float(np.median(ts)), 4))
+    assert abs(score - float(res["sum"].cpu()[0]) / n) < 1e-12
+    _, ts = gpu_time(lambda: ops.knn_topk(xt, xt, 5), reps)
+    knn = rates({}, n * n, ts)
+    d.update(knn_ms=knn["gpu_ms"], knn_pairs_per_s=knn["pairs_per_s"],
+             vs_knn=round(d["pairs_per_s"] / knn["pairs_per_s"], 4))
+    if with_sklearn:
+        from sklearn.metrics import silhouette_score
+        t0 = time.perf_counter()
+        ref = float(silhouette_score(x, y, metric="euclidean"))
+        d["sklearn_s"] = round(time.perf_counter() - t0, 4)
+        d["host_threads"] = int(os.environ.get("OMP_NUM_THREADS", HOST_THREADS))
+        d["score_diff"] = abs(ref - score)
+        d["speedup_vs_sklearn"] = round(d["sklearn_s"] * 1e3 / d["score_ms"], 1)
+    return d
+
+
+def silhouette_driver(args):
+    """One child per case under `timeout`; nothing more is started after a case that fails."""
+    env = dict(os.environ)
+    for var in ("OMP_NUM_THREADS", "MKL_NUM_THREADS", "OPENBLAS_NUM_THREADS"):
+        env[var] = str(min(HOST_THREADS, int(env.get(var) or HOST_THREADS)))
+    path = args.out or SIL_OUT
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as out:
+        for n, sk in ((args.sil_sklearn, 1), (args.sil_device, 0)):
+            if n <= 0:
+                continue
+            cmd = ["timeout", "-k", "10", str(args.sil_timeout), sys.executable, os.path.abspath(__file__),
+                   "--silhouette-case", f"{n},{sk}", "--reps", str(args.reps)]
+            r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True)
+            if r.returncode != 0:
+                raise SystemExit(f"silhouette case n={n} ended with status {r.returncode}; stopping")
+            line = r.stdout.strip().splitlines()[-1]
+            print(line, flush=True)
+            out.write(line + "\n")
+            out.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--silhouette", action="store_true", help="measure evaluate.silhouette_score (one child per case)")
+    ap.add_argument("--sil-sklearn", type=int, default=20000, help="rows of the case run against scikit-learn (0: skip)")
+    ap.add_argument("--sil-device", type=int, default=262144, help="rows of the device-only case (0: skip)")
+    ap.add_argument("--sil-timeout", type=int, default=300, help="seconds per silhouette case")
+    ap.add_argument("--silhouette-case", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--sizes", default="3025,100000,1000000")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--sklearn-max", type=int, default=100000)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.silhouette:
+        return silhouette_driver(args)
     if not torch.cuda.is_available():
         raise SystemExit("evaluate_bench needs a GPU: there is nothing to measure without one")
+    if args.silhouette_case:
+        n, sk = (int(v) for v in args.silhouette_case.split(","))
+        print(json.dumps(silhouette_case(n, bool(sk), args.reps)), flush=True)
+        return
     dev = torch.device("cuda:0")
     out = open(args.out, "w") if args.out else None
 
