@@ -27,16 +27,24 @@ def _note(tag, ratios):
     print(tag, {k: f"{v:.3g}" for k, v in ratios.items()})
 
 
-def restate32(case, mutation=None):
+def restate32(case, mutation=None, columnwise=False):
     """The classifier + masked loss in plain fp32 (torch CPU).  Returns logits, (loss, acc), (dZ, dWc, dbc) as NumPy.
-    `mutation` plants one of the faults the bounds must catch."""
+    `mutation` plants one of the faults the bounds must catch.  `columnwise` forms the logits one rounded product and
+    one rounded addition per term, the same sequence for every class: two classes with identical weights then get
+    identical bits on any host (a BLAS may treat the columns of a 7-wide matrix differently by position)."""
     Z, Wc, bc = (torch.from_numpy(case[k]) for k in ("Z", "Wc", "bc"))
     lab = torch.from_numpy(case["labels"].astype(np.int64))
     live = torch.from_numpy(case["mask"] != 0)
     N, HC, C = Z.shape[0], Wc.shape[0], Wc.shape[2]
     invh = torch.tensor(1.0 / HC, dtype=torch.float32)
     Wm, bm = Wc.sum(0) * invh, bc.sum(0) * invh
-    lg = Z @ Wm + bm
+    if columnwise:
+        lg = torch.zeros((N, C), dtype=torch.float32)
+        for d in range(Z.shape[1]):
+            lg = lg + Z[:, d:d + 1] * Wm[d]
+        lg = lg + bm
+    else:
+        lg = Z @ Wm + bm
     rows = torch.arange(N)
     w = torch.where(live, torch.tensor(case["row_weight"], dtype=torch.float32), torch.tensor(0.0))
     if mutation == "skip_32768":
@@ -165,10 +173,11 @@ def test_tie_cases_pair_is_maximum(D, C, HC, j1, j2):
     case = R.tie_case(D, C, HC, j1, j2)
     acc, e_acc, ok = R.tie_expected_acc(case, j1, j2)
     assert ok and 0.55 < acc < 0.8
-    lg, la, _ = restate32(case)
+    lg, la, _ = restate32(case, columnwise=True)
     assert np.array_equal(lg[:, j1], lg[:, j2])
     assert abs(la[1] - acc) <= e_acc
-    _, la_last, _ = restate32(case, "argmax_last")            # the last maximum: every j1 row is lost
+    assert max(R.classifier_ratios(R.classifier_ref(**case), lg, la).values()) <= 1.0
+    _, la_last, _ = restate32(case, "argmax_last", columnwise=True)     # the last maximum: every j1 row is lost
     assert abs(la_last[1] - acc) > 0.1 > 1000 * e_acc
 
 
