@@ -43,6 +43,9 @@ def main():
                          "evaluation kernels (the embeddings are not copied to the host)")
     ap.add_argument("--silhouette", action="store_true",
                     help="also report the silhouette score of the k-means labels (the data/exp.py form of my_Kmeans)")
+    ap.add_argument("--tsne", metavar="PATH", default=None,
+                    help="save the two-dimensional t-SNE coordinates of the scored embeddings and their labels as an .npz "
+                         "(evaluate.tsne: scikit-learn exact t-SNE on the host, the han_tsne kernels with --eval-device gpu)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(args.seed)
@@ -113,6 +116,12 @@ def main():
         emb, lab, eval_dev = final_embed.cpu().numpy()[sel], labels.cpu().numpy()[sel], None
     evaluate.my_KNN(emb, lab, seed=args.seed, device=eval_dev)                     # ex_acm3025.py:288
     evaluate.my_Kmeans(emb, lab, k=nb_classes, seed=args.seed, device=eval_dev, silhouette=args.silhouette)    # :289
+    if args.tsne:                                                                  # the picture of jhyexp.py:16
+        import numpy as np
+        coords, info = evaluate.tsne(emb, seed=args.seed, device=eval_dev, return_info=True)
+        np.savez(args.tsne, coords=coords.cpu().numpy() if eval_dev is not None else coords,
+                 labels=lab.cpu().numpy() if eval_dev is not None else lab)
+        print(f"t-SNE: {info['n_iter']} iterations, KL divergence {info['kl_divergence']:.4f} -> {args.tsne}")
 
 
 if __name__ == "__main__":

@@ -104,9 +104,13 @@ SIGNATURES = {
     "han_kmeans_step": (c_int, [P, I64, P, P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, P]),
     "han_silhouette_workspace": (c_size_t, [I64, c_int, c_int]),
     "han_silhouette": (c_int, [P, I64, P, I64, c_int, c_int, P, P, P, P, P, c_size_t, P]),
+    "han_tsne_workspace": (c_size_t, [I64, c_int]),
+    "han_tsne_calibrate": (c_int, [P, I64, I64, c_int, c_float, c_float, c_int, c_int, P, P, P, P, P, P, c_size_t, P]),
+    "han_tsne_step": (c_int, [P, I64, P, P, P, P, P, P, P, P, I64, c_int, c_float, c_float, c_float, c_float, c_int, P,
+                              c_size_t, P]),
 }
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 _lib = None
 
 

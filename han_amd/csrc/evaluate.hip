@@ -1,6 +1,6 @@
 // Evaluation of the final embeddings on the GPU (jhyexp.py:20-86): brute-force k nearest neighbours with a
-// majority vote, contingency tables for F1 / NMI / ARI, one Lloyd iteration of k-means, and the silhouette score of a
-// clustering (data/exp.py:46-49).
+// majority vote, contingency tables for F1 / NMI / ARI, one Lloyd iteration of k-means, the silhouette score of a
+// clustering (data/exp.py:46-49), and exact t-SNE in two dimensions (sklearn.manifold, jhyexp.py:16).
 //
 // Distances are d2 = |q|^2 + |t|^2 - 2 q.t.  The q.t term runs on the exact-fp32 matrix pipe
 // (v_mfma_f32_16x16x4_f32) in tiles of 64 x 64 pairs per workgroup step; the distance matrix never exists in
@@ -509,6 +509,382 @@ __global__ __launch_bounds__(kBlock) void sil_total(const double *part, int64_t 
     }
 }
 
+// ---- t-SNE (jhyexp.py:16, data/exp.py:20: sklearn.manifold, method="exact") ---------------------------------------
+// Row tile i against the column rows [blockIdx.y * split_rows, + split_rows), as sil_tiles walks them.  Nothing of
+// N x N is stored: a calibration pass and a gradient step both form d2 per pair again, and the step forms p_ij from
+// three floats per row (beta, the row minimum m of d2, the sum Z of that row's kernel).  A lane adds the at most 16
+// pairs it sees of a tile in fp32, carries its sums in double across tiles, and the four lanes of a row are added in a
+// fixed order; every (row, split) sum goes to a slab and the per-row kernels add the slabs in split order.
+constexpr int kTsneSums = 5;       // per row and split: A (2), R (2), W
+constexpr int kTsneSumsKL = 7;     // + sum e p (log e p - log w), sum e p
+constexpr float kLog2e = 1.44269504088896340736f;
+constexpr float kFltMax = 3.402823466e+38f, kFltMin = 1.175494351e-38f;
+
+struct TsneTiles {
+    const float *X, *xn;
+    int64_t ldx, N, split_rows;
+    int D;
+};
+
+// the one form of a pair's d2 in every t-SNE kernel (the row minimum must be the minimum of what the later passes see)
+__device__ __forceinline__ float tsne_d2(float qn, float tn, float dot) {
+    return fmaxf(__builtin_fmaf(-2.f, dot, qn + tn), 0.f);
+}
+
+// the beta a pass evaluates for the bisection state `next` (negative: a closed row's), inside the finite fp32 range
+__device__ __forceinline__ float tsne_beta32(double next) {
+    return fminf(fmaxf((float)fabs(next), kFltMin), kFltMax);
+}
+
+// beta * log2(e), finite: exp(-beta x) = exp2(-(this) x), and 0 * this = 0 for the nearest neighbour
+__device__ __forceinline__ float tsne_bl2(float beta) { return fminf(beta * kLog2e, kFltMax); }
+
+// acc = (column rows [t0, min(t0 + 64, t_end))) x (row tile q0) as mma_chunk leaves it, their norms in tns; `extra`
+// stages what else the epilogue reads per column row between the same two barriers.  Returns the row tiles in use.
+template <class Extra>
+__device__ __forceinline__ int tsne_product(float4_t (&acc)[4], float *smem, float *tns, const TsneTiles &a, int64_t q0,
+                                            int64_t t0, int64_t t_end, bool &staged, Extra extra) {
+    float *Rs = smem, *Cs = smem + kTile * kLd;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nch = (a.D + kChunk - 1) / kChunk;
+    const int nj = (int)((min(t_end - t0, (int64_t)kTile) + 15) >> 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = float4_t{0.f, 0.f, 0.f, 0.f};
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();
+        stage_tile(Rs, a.X, a.ldx, t0, t_end, ch * kChunk, a.D);
+        if (nch > 1 || !staged) stage_tile(Cs, a.X, a.ldx, q0, a.N, ch * kChunk, a.D);
+        if (ch == 0) {
+            if (threadIdx.x < kTile) tns[threadIdx.x] = t0 + threadIdx.x < t_end ? a.xn[t0 + threadIdx.x] : 0.f;
+            extra();
+        }
+        __syncthreads();
+        mma_chunk(acc, Rs, Cs, w, lane, nj);
+    }
+    staged = true;
+    return nj;
+}
+
+// (g0 + g1) + (g2 + g3) of the four lanes of a row, in every one of them
+__device__ __forceinline__ double tsne_row4(double v) {
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+// m_i = min over j != i of d2_ij, per split
+__global__ __launch_bounds__(kBlock) void tsne_rowmin_tiles(const TsneTiles a, float *slab /* [split][N] */) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * kTile * kLd];
+    __shared__ float tns[kTile];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    const int64_t q0 = (int64_t)blockIdx.x * kTile;
+    const int64_t t_begin = (int64_t)blockIdx.y * a.split_rows;
+    const int64_t t_end = min(a.N, t_begin + a.split_rows);
+    const int64_t myq = q0 + 16 * w + n;
+    const float qnorm = myq < a.N ? a.xn[myq] : 0.f;
+    float best = __builtin_inff();
+    bool staged = false;
+    for (int64_t t0 = t_begin; t0 < t_end; t0 += kTile) {
+        float4_t acc[4];
+        tsne_product(acc, smem, tns, a, q0, t0, t_end, staged, [] {});
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int tl = 16 * j + 4 * g + r;
+                if (t0 + tl < t_end && t0 + tl != myq) best = fminf(best, tsne_d2(qnorm, tns[tl], acc[j][r]));
+            }
+    }
+    best = fminf(best, __shfl_xor(best, 16, 64));
+    best = fminf(best, __shfl_xor(best, 32, 64));
+    if (g == 0 && myq < a.N) slab[(size_t)blockIdx.y * a.N + myq] = best;
+}
+
+// a thread per row: the minimum over the splits, and the bisection's start (beta = 1, no bound yet)
+__global__ __launch_bounds__(kBlock) void tsne_calib_init(const float *slab, int nsplit, int64_t N, float *dmin, double *state) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= N) return;
+    float m = __builtin_inff();
+    for (int sp = 0; sp < nsplit; ++sp) m = fminf(m, slab[(size_t)sp * N + i]);
+    dmin[i] = m;
+    state[i] = 1.0;
+    state[N + i] = -__builtin_inf();
+    state[2 * N + i] = __builtin_inf();
+}
+
+// Z_i = sum_j exp(-beta_i (d2_ij - m_i)) and E_i = sum_j (d2_ij - m_i) exp(..) at the beta the state asks for
+__global__ __launch_bounds__(kBlock) void tsne_calib_tiles(const TsneTiles a, const double *state, const float *dmin,
+                                                           double *slab /* [split][2][N] */) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * kTile * kLd];
+    __shared__ float tns[kTile];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    const int64_t q0 = (int64_t)blockIdx.x * kTile;
+    const int64_t t_begin = (int64_t)blockIdx.y * a.split_rows;
+    const int64_t t_end = min(a.N, t_begin + a.split_rows);
+    const int64_t myq = q0 + 16 * w + n;
+    const bool mine = myq < a.N;
+    const float qnorm = mine ? a.xn[myq] : 0.f;
+    const float m = mine ? dmin[myq] : 0.f;
+    const float nbl2 = mine ? -tsne_bl2(tsne_beta32(state[myq])) : 0.f;
+    double Z = 0.0, E = 0.0;
+    bool staged = false;
+    for (int64_t t0 = t_begin; t0 < t_end; t0 += kTile) {
+        float4_t acc[4];
+        tsne_product(acc, smem, tns, a, q0, t0, t_end, staged, [] {});
+        float z = 0.f, e = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int tl = 16 * j + 4 * g + r;
+                if (t0 + tl < t_end && t0 + tl != myq) {
+                    const float x = fmaxf(tsne_d2(qnorm, tns[tl], acc[j][r]) - m, 0.f);
+                    const float t = __builtin_amdgcn_exp2f(nbl2 * x);
+                    z += t;
+                    e = __builtin_fmaf(x, t, e);
+                }
+            }
+        Z += (double)z;
+        E += (double)e;
+    }
+    Z = tsne_row4(Z);
+    E = tsne_row4(E);
+    if (g == 0 && mine) {
+        slab[((size_t)blockIdx.y * 2 + 0) * a.N + myq] = Z;
+        slab[((size_t)blockIdx.y * 2 + 1) * a.N + myq] = E;
+    }
+}
+
+// a thread per open row: Z and E from the slabs in split order, H = log Z + beta E / Z, one step of
+// _binary_search_perplexity in double.  A row within tol of the target is closed: state[0] = -beta.  beta / zsum get
+// the beta this pass evaluated and its Z; *open_rows (cleared before) counts the rows still open.
+__global__ __launch_bounds__(kBlock) void tsne_calib_update(const double *slab, int nsplit, int64_t N, double log_perp, double tol,
+                                                            double *state, float *beta, float *zsum,
+                                                            unsigned long long *open_rows) {
+    __shared__ int cnt;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const double next = i < N ? state[i] : -1.0;
+    if (next > 0.0) {
+        double Z = 0.0, E = 0.0;
+        for (int sp = 0; sp < nsplit; ++sp) {
+            Z += slab[((size_t)sp * 2 + 0) * N + i];
+            E += slab[((size_t)sp * 2 + 1) * N + i];
+        }
+        const float bf = tsne_beta32(next);
+        const double diff = (log(Z) + (double)bf * E / Z) - log_perp;
+        beta[i] = bf;
+        zsum[i] = (float)Z;
+        if (fabs(diff) <= tol) {
+            state[i] = -(double)bf;
+        } else {
+            double lo = state[N + i], hi = state[2 * N + i], b = next;
+            if (diff > 0.0) {
+                lo = b;
+                b = hi == __builtin_inf() ? b * 2.0 : (b + hi) * 0.5;
+            } else {
+                hi = b;
+                b = lo == -__builtin_inf() ? b * 0.5 : (b + lo) * 0.5;
+            }
+            state[i] = b;
+            state[N + i] = lo;
+            state[2 * N + i] = hi;
+            atomicAdd(&cnt, 1);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && cnt) atomicAdd(open_rows, (unsigned long long)cnt);
+}
+
+struct TsneStepArgs {
+    TsneTiles t;
+    const float *beta, *dmin, *zsum, *Y;
+    float scale, floor;      // e / (2 N) and e 2^-52: e p_ij = max((c_ij + c_ji) scale, floor)
+    double *slab;            // [split][kTsneSums or kTsneSumsKL][N]
+};
+
+// what a lane adds up over its pairs of one tile
+struct TsnePairSums {
+    float a0, a1, r0, r1, w, k1, k2;
+};
+
+// One pair of the step.  Every rounding is written out, so the sums of the KL form are bit for bit those of the
+// plain form.  cj: (bl2, m, 1 / Z) of the column row; on = false for the pair (i, i) and past the last row.
+template <bool KL>
+__device__ __forceinline__ void tsne_pair(TsnePairSums &s, float d2, float nbl2_i, float m_i, float iz_i, float nbl2_j, float m_j,
+                                          float iz_j, float dy0, float dy1, bool on, float scale, float floor) {
+#pragma clang fp contract(off)
+    const float ei = __builtin_amdgcn_exp2f(nbl2_i * fmaxf(d2 - m_i, 0.f));
+    const float ej = __builtin_amdgcn_exp2f(nbl2_j * fmaxf(d2 - m_j, 0.f));
+    const float ep = fmaxf(__builtin_fmaf(ei, iz_i, ej * iz_j) * scale, floor);
+    const float w = on ? __builtin_amdgcn_rcpf(__builtin_fmaf(dy0, dy0, __builtin_fmaf(dy1, dy1, 1.f))) : 0.f;
+    const float pw = ep * w, w2 = w * w;
+    s.a0 = __builtin_fmaf(pw, dy0, s.a0);
+    s.a1 = __builtin_fmaf(pw, dy1, s.a1);
+    s.r0 = __builtin_fmaf(w2, dy0, s.r0);
+    s.r1 = __builtin_fmaf(w2, dy1, s.r1);
+    s.w += w;
+    if (KL && on) {
+        s.k1 = __builtin_fmaf(ep, __logf(ep) - __logf(w), s.k1);
+        s.k2 += ep;
+    }
+}
+
+template <bool KL>
+__global__ __launch_bounds__(kBlock) void tsne_step_tiles(const TsneStepArgs a) {
+    constexpr int NS = KL ? kTsneSumsKL : kTsneSums;
+    __shared__ __attribute__((aligned(16))) float smem[2 * kTile * kLd];
+    __shared__ __attribute__((aligned(16))) float cp[6][kTile];      // column rows: norm, -beta log2 e, m, 1 / Z, y0, y1
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    const int64_t N = a.t.N;
+    const int64_t q0 = (int64_t)blockIdx.x * kTile;
+    const int64_t t_begin = (int64_t)blockIdx.y * a.t.split_rows;
+    const int64_t t_end = min(N, t_begin + a.t.split_rows);
+    const int64_t myq = q0 + 16 * w + n;
+    const bool mine = myq < N;
+    const float qnorm = mine ? a.t.xn[myq] : 0.f;
+    const float nbl2 = mine ? -tsne_bl2(a.beta[myq]) : 0.f, m = mine ? a.dmin[myq] : 0.f;
+    const float iz = mine ? 1.f / a.zsum[myq] : 0.f;
+    const float y0 = mine ? a.Y[2 * myq] : 0.f, y1 = mine ? a.Y[2 * myq + 1] : 0.f;
+    double sum[NS];
+#pragma unroll
+    for (int e = 0; e < NS; ++e) sum[e] = 0.0;
+    bool staged = false;
+    for (int64_t t0 = t_begin; t0 < t_end; t0 += kTile) {
+        float4_t acc[4];
+        const int nj = tsne_product(acc, smem, cp[0], a.t, q0, t0, t_end, staged, [&] {
+            const int r = threadIdx.x & 63;
+            const int64_t row = t0 + r;
+            const bool in = row < t_end;
+            if (w == 1) {
+                cp[1][r] = in ? -tsne_bl2(a.beta[row]) : 0.f;
+                cp[2][r] = in ? a.dmin[row] : 0.f;
+            } else if (w == 2) {
+                cp[3][r] = in ? 1.f / a.zsum[row] : 0.f;
+            } else if (w == 3) {
+                cp[4][r] = in ? a.Y[2 * row] : 0.f;
+                cp[5][r] = in ? a.Y[2 * row + 1] : 0.f;
+            }
+        });
+        TsnePairSums s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= nj) break;
+            float4_t c[6];
+#pragma unroll
+            for (int e = 0; e < 6; ++e) c[e] = *reinterpret_cast<const float4_t *>(&cp[e][16 * j + 4 * g]);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t col = t0 + 16 * j + 4 * g + r;
+                tsne_pair<KL>(s, tsne_d2(qnorm, c[0][r], acc[j][r]), nbl2, m, iz, c[1][r], c[2][r], c[3][r], y0 - c[4][r],
+                              y1 - c[5][r], col < t_end && col != myq, a.scale, a.floor);
+            }
+        }
+        sum[0] += (double)s.a0;
+        sum[1] += (double)s.a1;
+        sum[2] += (double)s.r0;
+        sum[3] += (double)s.r1;
+        sum[4] += (double)s.w;
+        if (KL) {
+            sum[5] += (double)s.k1;
+            sum[6] += (double)s.k2;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < NS; ++e) {
+        const double v = tsne_row4(sum[e]);
+        if (g == 0 && mine) a.slab[((size_t)blockIdx.y * NS + e) * N + myq] = v;
+    }
+}
+
+// W_i from the slabs in split order, and the sum of a workgroup's rows in row order
+__global__ __launch_bounds__(kBlock) void tsne_rowsum_parts(const double *slab, int nsplit, int ns, int64_t N, double *part) {
+    __shared__ double ps[kBlock];
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    double s = 0.0;
+    if (i < N)
+        for (int sp = 0; sp < nsplit; ++sp) s += slab[((size_t)sp * ns + 4) * N + i];
+    ps[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int e = 0; e < kBlock; ++e) t += ps[e];
+        part[blockIdx.x] = t;
+    }
+}
+
+// workgroup b: out[b] = the partials part[b * nparts ..), each thread its own in order, then the 256 threads in order
+__global__ __launch_bounds__(kBlock) void tsne_total(const double *part, int64_t nparts, double *out) {
+    __shared__ double ps[kBlock];
+    double t = 0.0;
+    for (int64_t e = threadIdx.x; e < nparts; e += kBlock) t += part[(int64_t)blockIdx.x * nparts + e];
+    ps[threadIdx.x] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int e = 0; e < kBlock; ++e) s += ps[e];
+        out[blockIdx.x] = s;
+    }
+}
+
+// _gradient_descent's update of one coordinate, every product and sum rounded on its own; returns gains * grad
+__device__ __forceinline__ float tsne_descend(float g, float *y, float *upd, float *gain, float momentum, float lr, float min_gain) {
+#pragma clang fp contract(off)
+    const float u = *upd;
+    float gn = *gain;
+    gn = __fmul_rn(u, g) < 0.f ? __fadd_rn(gn, 0.2f) : __fmul_rn(gn, 0.8f);
+    gn = fmaxf(gn, min_gain);
+    const float gg = __fmul_rn(gn, g);
+    const float un = __fsub_rn(__fmul_rn(momentum, u), __fmul_rn(lr, gg));
+    *gain = gn;
+    *upd = un;
+    *y = __fadd_rn(*y, un);
+    return gg;
+}
+
+struct TsneUpdateArgs {
+    const double *slab, *zq;
+    int nsplit, ns;
+    int64_t N, nparts;
+    float *Y, *update, *gains, *grad;
+    float momentum, lr, min_gain;
+    double *part;            // [2][nparts]: sum of (gains * grad)^2, KL terms
+};
+
+// a thread per row: A and R from the slabs in split order, grad = 4 (A - R / Z_q), the update rule, and the
+// workgroup's partials of |gains * grad|^2 and of the KL sum in row order
+__global__ __launch_bounds__(kBlock) void tsne_update(const TsneUpdateArgs a) {
+    __shared__ double pn[kBlock], pk[kBlock];
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    double nrm = 0.0, kl = 0.0;
+    if (i < a.N) {
+        double s[kTsneSumsKL] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int sp = 0; sp < a.nsplit; ++sp)
+#pragma unroll
+            for (int e = 0; e < kTsneSumsKL; ++e)
+                if (e != 4 && e < a.ns) s[e] += a.slab[((size_t)sp * a.ns + e) * a.N + i];
+        const double zq = *a.zq;
+        for (int c = 0; c < 2; ++c) {
+            const float g = (float)(4.0 * (s[c] - s[2 + c] / zq));
+            if (a.grad) a.grad[2 * i + c] = g;
+            const float gg = tsne_descend(g, a.Y + 2 * i + c, a.update + 2 * i + c, a.gains + 2 * i + c, a.momentum, a.lr,
+                                          a.min_gain);
+            nrm += (double)gg * (double)gg;
+        }
+        kl = s[5] + log(zq) * s[6];
+    }
+    pn[threadIdx.x] = nrm;
+    pk[threadIdx.x] = kl;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0, u = 0.0;
+        for (int e = 0; e < kBlock; ++e) { t += pn[e]; u += pk[e]; }
+        a.part[blockIdx.x] = t;
+        a.part[a.nparts + blockIdx.x] = u;
+    }
+}
+
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // train-set splits of a KNN call: enough workgroups to fill the device when there are few queries
@@ -569,6 +945,23 @@ inline SilPlan sil_plan(int64_t N, int k) {
     p.off_part = p.off_ab + align256((size_t)2 * N * sizeof(double));
     p.off_slab = p.off_part + align256((size_t)p.finish_blocks * sizeof(double));
     p.bytes = p.off_slab + (p.nsplit > 1 ? align256((size_t)p.nsplit * k * N * sizeof(double)) : 0);
+    return p;
+}
+
+// t-SNE: the column range is split as in han_silhouette; every (row, split) sum goes through a slab
+struct TsnePlan {
+    int64_t split_rows, row_blocks;
+    int nsplit;
+    size_t off_part, off_slab, bytes;
+};
+
+inline TsnePlan tsne_plan(int64_t N) {
+    TsnePlan p;
+    p.nsplit = knn_splits(N, N, &p.split_rows);
+    p.row_blocks = (N + kBlock - 1) / kBlock;
+    p.off_part = align256((size_t)N * sizeof(float));
+    p.off_slab = p.off_part + align256((size_t)2 * p.row_blocks * sizeof(double));
+    p.bytes = p.off_slab + align256((size_t)p.nsplit * kTsneSumsKL * N * sizeof(double));
     return p;
 }
 
@@ -729,6 +1122,90 @@ extern "C" int han_silhouette(const float *X, int64_t ldx, const int64_t *seg_pt
     sil_finish<<<(unsigned)p.finish_blocks, kBlock, 0, st>>>(seg_ptr, k, N, slab, p.nsplit, ab, a, b, s, part);
     HAN_CHECK_LAUNCH();
     sil_total<<<1, kBlock, 0, st>>>(part, p.finish_blocks, sum);
+    HAN_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" size_t han_tsne_workspace(int64_t N, int D) {
+    if (N <= 0 || D < 1 || D > kMaxD || N > 0x7FFFFFFF) return 0;
+    return tsne_plan(N).bytes;
+}
+
+extern "C" int han_tsne_calibrate(const float *X, int64_t ldx, int64_t N, int D, float perplexity, float tol, int steps,
+                                  int restart, float *beta, float *dmin, float *zsum, double *state, int64_t *open_rows,
+                                  void *workspace, size_t workspace_bytes, void *stream) {
+    if (N < 0 || D < 1 || ldx < D || steps < 0) return HAN_E_BADARG;
+    if (D > kMaxD || N > 0x7FFFFFFF) return HAN_E_UNSUPPORTED;
+    if (N <= 1) return 0;
+    if (!(perplexity >= 1.f) || !((double)perplexity < (double)N) || !(tol >= 0.f)) return HAN_E_BADARG;      // NaN: neither
+    if (!X || !beta || !dmin || !zsum || !state || !open_rows || !workspace) return HAN_E_BADARG;
+    const TsnePlan p = tsne_plan(N);
+    if (workspace_bytes < p.bytes) return HAN_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    float *xn = (float *)ws;
+    double *slab = (double *)(ws + p.off_slab);
+    TsneTiles t;
+    t.X = X; t.xn = xn; t.ldx = ldx; t.N = N; t.split_rows = p.split_rows; t.D = D;
+    const dim3 grid((unsigned)((N + kTile - 1) / kTile), (unsigned)p.nsplit);
+    row_norms<<<norms_grid(N), kBlock, 0, st>>>(X, ldx, N, D, xn);
+    HAN_CHECK_LAUNCH();
+    if (restart) {
+        tsne_rowmin_tiles<<<grid, kBlock, 0, st>>>(t, (float *)slab);
+        HAN_CHECK_LAUNCH();
+        tsne_calib_init<<<(unsigned)p.row_blocks, kBlock, 0, st>>>((const float *)slab, p.nsplit, N, dmin, state);
+        HAN_CHECK_LAUNCH();
+    }
+    for (int s = 0; s < steps; ++s) {
+        tsne_calib_tiles<<<grid, kBlock, 0, st>>>(t, state, dmin, slab);
+        HAN_CHECK_LAUNCH();
+        const hipError_t e = hipMemsetAsync(open_rows, 0, sizeof(int64_t), st);
+        if (e != hipSuccess) return (int)e;
+        tsne_calib_update<<<(unsigned)p.row_blocks, kBlock, 0, st>>>(slab, p.nsplit, N, log((double)perplexity), (double)tol,
+                                                                    state, beta, zsum, (unsigned long long *)open_rows);
+        HAN_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+extern "C" int han_tsne_step(const float *X, int64_t ldx, const float *beta, const float *dmin, const float *zsum, float *Y,
+                             float *update, float *gains, float *grad, double *stats, int64_t N, int D,
+                             float exaggeration, float momentum, float lr, float min_gain, int want_kl, void *workspace,
+                             size_t workspace_bytes, void *stream) {
+    if (N < 0 || D < 1 || ldx < D) return HAN_E_BADARG;
+    if (D > kMaxD || N > 0x7FFFFFFF) return HAN_E_UNSUPPORTED;
+    if (N <= 1) return 0;
+    if (!(exaggeration > 0.f) || !(exaggeration < kFltMax)) return HAN_E_BADARG;
+    if (!X || !beta || !dmin || !zsum || !Y || !update || !gains || !stats || !workspace) return HAN_E_BADARG;
+    const TsnePlan p = tsne_plan(N);
+    if (workspace_bytes < p.bytes) return HAN_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    float *xn = (float *)ws;
+    double *part = (double *)(ws + p.off_part), *slab = (double *)(ws + p.off_slab);
+    const int ns = want_kl ? kTsneSumsKL : kTsneSums;
+    TsneStepArgs a;
+    a.t.X = X; a.t.xn = xn; a.t.ldx = ldx; a.t.N = N; a.t.split_rows = p.split_rows; a.t.D = D;
+    a.beta = beta; a.dmin = dmin; a.zsum = zsum; a.Y = Y; a.slab = slab;
+    a.scale = (float)((double)exaggeration / (2.0 * (double)N));
+    a.floor = exaggeration * 0x1p-52f;
+    const dim3 grid((unsigned)((N + kTile - 1) / kTile), (unsigned)p.nsplit);
+    row_norms<<<norms_grid(N), kBlock, 0, st>>>(X, ldx, N, D, xn);
+    HAN_CHECK_LAUNCH();
+    if (want_kl) tsne_step_tiles<true><<<grid, kBlock, 0, st>>>(a);
+    else tsne_step_tiles<false><<<grid, kBlock, 0, st>>>(a);
+    HAN_CHECK_LAUNCH();
+    tsne_rowsum_parts<<<(unsigned)p.row_blocks, kBlock, 0, st>>>(slab, p.nsplit, ns, N, part);
+    HAN_CHECK_LAUNCH();
+    tsne_total<<<1, kBlock, 0, st>>>(part, p.row_blocks, stats);
+    HAN_CHECK_LAUNCH();
+    TsneUpdateArgs u;
+    u.slab = slab; u.zq = stats; u.nsplit = p.nsplit; u.ns = ns; u.N = N; u.nparts = p.row_blocks;
+    u.Y = Y; u.update = update; u.gains = gains; u.grad = grad;
+    u.momentum = momentum; u.lr = lr; u.min_gain = min_gain; u.part = part;
+    tsne_update<<<(unsigned)p.row_blocks, kBlock, 0, st>>>(u);
+    HAN_CHECK_LAUNCH();
+    tsne_total<<<want_kl ? 2 : 1, kBlock, 0, st>>>(part, p.row_blocks, stats + 1);
     HAN_CHECK_LAUNCH();
     return 0;
 }

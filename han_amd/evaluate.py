@@ -13,6 +13,10 @@ on the host in float64 from those tables (``f1_from_table``, ``nmi_ari_from_tabl
 the k-means labels (``data/exp.py:46-49``).  ``silhouette_samples`` / ``silhouette_score`` are that number on the
 host (scikit-learn) or on the device (``han_silhouette``), and ``my_Kmeans(..., silhouette=True)`` is that form.
 
+Both evaluation modules of the reference import ``sklearn.manifold`` (``jhyexp.py:16``, ``data/exp.py:20``) for the
+t-SNE picture of the embeddings; ``tsne`` is scikit-learn's exact t-SNE on the host or ``han_tsne_calibrate`` /
+``han_tsne_step`` on the device.
+
 Random streams: the reference draws its shuffles from NumPy's GLOBAL legacy generator
 (``np.random.permutation``, jhyexp.py:33) and lets scikit-learn's KMeans fall back on the
 same global generator (``random_state=None``, jhyexp.py:62).  Here both use ONE
@@ -413,6 +417,114 @@ def silhouette_score(x, labels, sample_size=None, seed=None, device=None):
         x, labels = _sample(x, labels, sample_size, seed)
     total = _silhouette_device(x, labels, device)[1]
     return float(total) / _shape2(x, "x")[0]
+
+
+TSNE_MAX_D = 512        # han_tsne_calibrate / han_tsne_step
+TSNE_EXPLORATION = 250  # exaggerated iterations (sklearn.manifold.TSNE._EXPLORATION_MAX_ITER)
+TSNE_CHECK = 50         # iterations between two reads of the KL divergence and the gradient norm (_N_ITER_CHECK)
+
+
+def _tsne_init(x, init, seed, dev):
+    """The (N, 2) fp32 start on the device.  "random": the numbers scikit-learn draws; "pca": the top two principal
+    components (eigh of the D x D covariance in float64), the first with standard deviation 1e-4; else as given."""
+    import torch
+    n = x.shape[0]
+    if isinstance(init, str):
+        if init == "random":
+            rs = seed if isinstance(seed, np.random.RandomState) else np.random.RandomState(seed)
+            return torch.as_tensor(np.float32(1e-4) * rs.standard_normal(size=(n, 2)).astype(np.float32)).to(dev)
+        if init != "pca":
+            raise ValueError(f"init = {init!r}: expected 'pca', 'random' or an (n, 2) array")
+        xc = x.to(torch.float64)
+        xc = xc - xc.mean(0, keepdim=True)
+        vec = torch.linalg.eigh(xc.T @ xc)[1]                # ascending eigenvalues
+        if vec.shape[1] < 2:
+            vec = torch.cat([torch.zeros_like(vec), vec], 1)
+        y = xc @ vec[:, [-1, -2]]
+        return (y / y[:, 0].std(unbiased=False) * 1e-4).to(torch.float32).contiguous()
+    y = _embed(init, dev)
+    if tuple(y.shape) != (n, 2):
+        raise ValueError(f"init: shape {tuple(y.shape)}, expected ({n}, 2)")
+    return y.clone().contiguous()
+
+
+def _tsne_device(x, perplexity, early_exaggeration, learning_rate, max_iter, init, seed, n_iter_without_progress,
+                 min_grad_norm, device, return_info):
+    import torch
+    from . import ops
+    n, d = _shape2(x, "x")
+    if _is_tensor(x) and not x.is_cuda:
+        raise ValueError("x: a CPU tensor with device= set; pass a GPU tensor or a NumPy array")
+    if not perplexity < n:
+        raise ValueError(f"perplexity ({perplexity}) must be less than n_samples ({n})")
+    if d > TSNE_MAX_D:
+        raise ValueError(f"x has width {d}: the device path takes at most {TSNE_MAX_D} columns")
+    dev = _pick_device(device, x)
+    x = _embed(x, dev)
+    if isinstance(learning_rate, str) and learning_rate != "auto":
+        raise ValueError(f"learning_rate = {learning_rate!r}: expected 'auto' or a number")
+    lr = max(n / early_exaggeration / 4.0, 50.0) if isinstance(learning_rate, str) else float(learning_rate)
+    y = _tsne_init(x, init, seed, dev)
+    calib = ops.tsne_calibrate(x, perplexity)
+    update, gains = torch.zeros_like(y), torch.ones_like(y)
+    kl = float("nan")
+
+    def descend(it, end, exaggeration, momentum, patience):
+        """_gradient_descent from iteration `it` to `end`: the error and the norm are read every TSNE_CHECK steps"""
+        nonlocal kl
+        best, best_it = float("inf"), it
+        i = it
+        for i in range(it, end):
+            check = (i + 1) % TSNE_CHECK == 0
+            r = ops.tsne_step(x, calib, y, update, gains, exaggeration, momentum, lr, want_kl=check or i == end - 1)
+            if check or i == end - 1:
+                stats = r["stats"].cpu()                     # the one synchronisation
+                kl = float(stats[2])
+            if check:
+                if kl < best:
+                    best, best_it = kl, i
+                elif i - best_it > patience:
+                    break
+                if float(stats[1]) ** 0.5 <= min_grad_norm:
+                    break
+        return i + 1
+
+    it = descend(0, min(TSNE_EXPLORATION, max_iter), early_exaggeration, 0.5, TSNE_EXPLORATION) if max_iter > 0 else 0
+    if it < max_iter:
+        update.zero_()
+        gains.fill_(1.0)
+        it = descend(it, max_iter, 1.0, 0.8, n_iter_without_progress)
+    if return_info:
+        return y, dict(kl_divergence=kl, n_iter=it, calibration_passes=int(calib["passes"]),
+                       open_rows=int(calib["open_rows"].cpu()[0]))
+    return y
+
+
+def tsne(x, perplexity=30.0, early_exaggeration=12.0, learning_rate="auto", max_iter=1000, init="pca", seed=None,
+         n_iter_without_progress=300, min_grad_norm=1e-7, device=None, return_info=False):
+    """The two-dimensional t-SNE picture of the embeddings (sklearn.manifold, jhyexp.py:16 / data/exp.py:20):
+    scikit-learn's TSNE(n_components=2, method="exact", ...).fit_transform(x).
+    device=None: that call on the host, the (n, 2) array it returns (init / seed are its init / random_state).
+    With a device: han_tsne_calibrate and han_tsne_step, the same schedule -- learning_rate "auto" is
+    max(n / early_exaggeration / 4, 50); 250 exaggerated iterations at momentum 0.5, the rest at 0.8; the KL
+    divergence and the gradient norm are read every 50 iterations, and the run stops on min_grad_norm or after
+    n_iter_without_progress iterations without a better KL -- and the (n, 2) fp32 coordinates stay on the device.
+    init: "random" (1e-4 * RandomState(seed).standard_normal((n, 2)).astype(float32), scikit-learn's numbers), "pca" (top two
+    principal components, the first with standard deviation 1e-4) or an (n, 2) array / tensor, used as given.
+    return_info=True adds dict(kl_divergence, n_iter): the KL divergence at the last iterate the loop evaluated and the
+    iterations run (on the host scikit-learn's kl_divergence_ and n_iter_, the index of the last one); on the device also
+    calibration_passes and open_rows.  The optimisation is chaotic: host and device runs from one start end in
+    different pictures of the same quality.  ValueError for perplexity >= n and, on the device, for more than 512
+    columns or a CPU tensor."""
+    if device is None:
+        from sklearn.manifold import TSNE
+        est = TSNE(n_components=2, method="exact", perplexity=perplexity, early_exaggeration=early_exaggeration,
+                   learning_rate=learning_rate, max_iter=max_iter, init=init if isinstance(init, str) else _host_array(init, np.float32),
+                   random_state=seed, n_iter_without_progress=n_iter_without_progress, min_grad_norm=min_grad_norm)
+        y = est.fit_transform(_host_array(x))
+        return (y, dict(kl_divergence=float(est.kl_divergence_), n_iter=int(est.n_iter_))) if return_info else y
+    return _tsne_device(x, float(perplexity), float(early_exaggeration), learning_rate, int(max_iter), init, seed,
+                        n_iter_without_progress, min_grad_norm, device, return_info)
 
 
 def _my_knn_device(x, y, k, split_list, time, shuffle, seed, verbose, device):

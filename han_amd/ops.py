@@ -1157,3 +1157,68 @@ def silhouette(x, seg_ptr):
                                   _ptr_nonempty(b), _ptr_nonempty(s), total.data_ptr(), ws.data_ptr(), ws.numel(),
                                   _stream()), "han_silhouette")
     return dict(a=a, b=b, s=s, sum=total)
+
+
+def tsne_calibrate(x, perplexity, tol=1e-5, max_passes=100, check_every=8):
+    """scikit-learn's _binary_search_perplexity for TSNE(method="exact") (han_tsne_calibrate): per row of x the beta
+    whose conditional distribution has entropy log(perplexity).  All rows bisect together, one pass over all pairs per
+    step; the passes run in batches of `check_every` and the count of open rows is read between batches (the one
+    synchronisation), until no row is open or max_passes have run.  Returns dict(beta (N,), dmin (N,) -- the smallest
+    d2 to another row --, zsum (N,) -- the sum of exp(-beta (d2 - dmin)) --, all fp32; state (3, N) float64 -- the
+    bisection's next beta (negative: closed), lower and upper bound --; passes, a 0-d int64 host tensor; open_rows (1,)
+    int64 on the device).  Nothing of N x N is stored."""
+    ldx = _chk_rows(x, "x")
+    n, d = x.shape
+    perplexity, tol = float(perplexity), float(tol)
+    max_passes, check_every = _chk_int(max_passes, "max_passes", 1), _chk_int(check_every, "check_every", 1)
+    if n >= 2 ** 31:
+        raise ValueError("x: at most 2^31 - 1 rows")
+    if n > 1 and not 1.0 <= perplexity < n:
+        raise ValueError(f"perplexity = {perplexity}: expected 1 <= perplexity < {n} rows")
+    if not tol >= 0.0:
+        raise ValueError(f"tol = {tol}: expected a tolerance >= 0")
+    lib, dev = _lib.load(), x.device
+    beta, dmin, zsum = (torch.zeros(n, dtype=torch.float32, device=dev) for _ in range(3))
+    state = torch.zeros((3, n), dtype=torch.float64, device=dev)
+    open_rows = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = _ws(lib.han_tsne_workspace(n, d), dev, "tsne")
+    passes = 0
+    while n > 1 and passes < max_passes:
+        steps = min(check_every, max_passes - passes)
+        _lib.check(lib.han_tsne_calibrate(x.data_ptr(), ldx, n, d, perplexity, tol, steps, int(passes == 0), beta.data_ptr(),
+                                          dmin.data_ptr(), zsum.data_ptr(), state.data_ptr(), open_rows.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), _stream()), "han_tsne_calibrate")
+        passes += steps
+        if int(open_rows.cpu()[0]) == 0:
+            break
+    return dict(beta=beta, dmin=dmin, zsum=zsum, state=state, passes=torch.tensor(passes, dtype=torch.int64),
+                open_rows=open_rows)
+
+
+def tsne_step(x, calib, y, update, gains, exaggeration, momentum, lr, min_gain=0.01, want_grad=False, want_kl=False):
+    """One iteration of scikit-learn's exact t-SNE in two dimensions (han_tsne_step): the gradient of _kl_divergence
+    at y with the joint probabilities formed again per pair from calib (tsne_calibrate's dict), times `exaggeration`,
+    then _gradient_descent's update rule IN PLACE on y, update and gains ((N, 2) fp32 each).  Returns dict(stats (3,)
+    float64 on the device: Z_q, the squared norm of gains * grad, the KL divergence at the y that came in -- NaN
+    without want_kl --; grad (N, 2) fp32, the gradient before the gains, or None without want_grad)."""
+    ldx = _chk_rows(x, "x")
+    n, d = x.shape
+    dev = x.device
+    for name in ("beta", "dmin", "zsum"):
+        _chk(calib[name], "calib." + name, (n,), device=dev)
+    for t, name in ((y, "y"), (update, "update"), (gains, "gains")):
+        _chk(t, name, (n, 2), device=dev)
+    if n >= 2 ** 31:
+        raise ValueError("x: at most 2^31 - 1 rows")
+    exaggeration = float(exaggeration)
+    if not 0.0 < exaggeration < float("inf"):
+        raise ValueError(f"exaggeration = {exaggeration}: expected a positive number")
+    lib = _lib.load()
+    stats = torch.full((3,), float("nan") if n > 1 else 0.0, dtype=torch.float64, device=dev)      # [2] stays NaN without want_kl
+    grad = torch.zeros((n, 2), dtype=torch.float32, device=dev) if want_grad else None
+    ws = _ws(lib.han_tsne_workspace(n, d), dev, "tsne")
+    _lib.check(lib.han_tsne_step(x.data_ptr() if n else None, ldx, _ptr_nonempty(calib["beta"]), _ptr_nonempty(calib["dmin"]),
+                                 _ptr_nonempty(calib["zsum"]), _ptr_nonempty(y), _ptr_nonempty(update), _ptr_nonempty(gains),
+                                 _ptr_nonempty(grad), stats.data_ptr(), n, d, exaggeration, float(momentum), float(lr),
+                                 float(min_gain), int(bool(want_kl)), ws.data_ptr(), ws.numel(), _stream()), "han_tsne_step")
+    return dict(stats=stats, grad=grad)

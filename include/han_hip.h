@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HAN_ABI_VERSION 12
+#define HAN_ABI_VERSION 13
 
 #define HAN_E_BADARG   (-1)   /* null pointer, negative size, inconsistent shape.  The forward
                               * entry points return 0 at once for N == 0 (empty tensors may
@@ -603,6 +603,51 @@ int han_kmeans_step(const float *X, int64_t ldx, const float *C, const int32_t *
 size_t han_silhouette_workspace(int64_t N, int D, int k);
 int han_silhouette(const float *X, int64_t ldx, const int64_t *seg_ptr, int64_t N, int D, int k, float *a, float *b,
                    float *s, double *sum, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- t-SNE of the embeddings (ABI 13) ---------------------------------------
+ * Both evaluation modules of the reference import sklearn.manifold (jhyexp.py:16, data/exp.py:20) for the
+ * two-dimensional t-SNE picture of final_embed.  These entry points are scikit-learn's TSNE(n_components=2,
+ * method="exact") on the device: _utils._binary_search_perplexity and _joint_probabilities (han_tsne_calibrate),
+ * _kl_divergence with one degree of freedom and one iteration of _gradient_descent (han_tsne_step).  Pair distances are
+ * d2 = max(0, |x_i|^2 + |x_j|^2 - 2 x_i.x_j) on the exact-fp32 matrix pipe with the tiles of han_knn_topk, the pair
+ * j = i is excluded by its index, and NO N x N array is stored at any N: a step forms p_ij again from three floats per
+ * row.  Every result is bitwise the same from run to run (no floating-point atomics; a lane adds the pairs of a tile in
+ * fp32, sums that cross a tile are carried in double and added in a fixed order).
+ *
+ * X (N, D) fp32 with leading dimension ldx >= D, 1 <= D <= 512, N < 2^31.
+ * han_tsne_calibrate: per row i the beta_i with entropy H(P_i) = log(perplexity).  Distances are shifted by the row
+ *   minimum m_i = min over j != i of d2_ij (the one departure from scikit-learn: the same P, no underflow of the sum):
+ *   Z_i = sum_j exp(-beta_i (d2_ij - m_i)),  E_i = sum_j (d2_ij - m_i) exp(..),  H = log Z_i + beta_i E_i / Z_i.
+ *   restart != 0 finds dmin (N) = m and starts the bisection (beta = 1, no bounds); then `steps` bisection passes run
+ *   back to back on the stream -- all rows together, one pass over all pairs each --: double or halve while a bound is
+ *   infinite, else move to the midpoint; a row with |H - log perplexity| <= tol is closed and keeps its beta.
+ *   state (3, N) double: the next beta (NEGATIVE: minus the beta of a closed row), the lower and the upper bound; beta
+ *   is clamped to the finite fp32 range when a pass evaluates it.  beta (N) / zsum (N) fp32 always hold the last
+ *   EVALUATED beta and its Z (what scikit-learn's P is built from when a row never closes); *open_rows (int64, on the
+ *   device) the rows not closed after the last pass; steps == 0 leaves beta, zsum and *open_rows as they are (after a
+ *   restart alone nothing has been evaluated yet).  perplexity must be finite, >= 1 and < N, tol >= 0.
+ * han_tsne_step: one iteration.  c_ij = exp(-beta_i (d2_ij - m_i)) / Z_i,  p_ij = max((c_ij + c_ji) / (2 N), 2^-52),
+ *   dy = y_i - y_j,  w = 1 / (1 + |dy|^2),  e = exaggeration:
+ *     A_i = sum_j e p_ij w dy,  R_i = sum_j w^2 dy,  W_i = sum_j w,  Z_q = sum_i W_i,  grad_i = 4 (A_i - R_i / Z_q),
+ *     KL = sum_ij e p_ij (log(e p_ij) - log w + log Z_q)        (scikit-learn's floor on q is not reproduced).
+ *   Then, per element of (N, 2), every product and sum rounded on its own in fp32:
+ *     gains = max(update * grad < 0 ? gains + 0.2 : gains * 0.8, min_gain);
+ *     update = momentum * update - lr * (gains * grad);   Y += update.
+ *   Y, update, gains (N, 2) fp32 in/out; grad (N, 2) fp32 or NULL: the gradient BEFORE the gains are applied.
+ *   stats (3) double on the device: [0] Z_q, [1] the sum of (gains * grad)^2 (the squared norm scikit-learn compares
+ *   with min_grad_norm), [2] KL when want_kl != 0, untouched otherwise; want_kl and grad change no other output bit.
+ * N <= 1 returns 0 and launches nothing.  A NULL pointer (but grad), ldx < D, D < 1, a bad perplexity / tol /
+ * exaggeration: HAN_E_BADARG; D > 512 or N >= 2^31: HAN_E_UNSUPPORTED; all decided before anything touches the
+ * device.  workspace: han_tsne_workspace() bytes for both (row norms, the per-split slabs, the partial sums); 0 for an
+ * unsupported shape.  Both run on `stream` and never synchronise.                                                   */
+size_t han_tsne_workspace(int64_t N, int D);
+int han_tsne_calibrate(const float *X, int64_t ldx, int64_t N, int D, float perplexity, float tol, int steps,
+                       int restart, float *beta, float *dmin, float *zsum, double *state, int64_t *open_rows,
+                       void *workspace, size_t workspace_bytes, void *stream);
+int han_tsne_step(const float *X, int64_t ldx, const float *beta, const float *dmin, const float *zsum, float *Y,
+                  float *update, float *gains, float *grad, double *stats, int64_t N, int D, float exaggeration,
+                  float momentum, float lr, float min_gain, int want_kl, void *workspace, size_t workspace_bytes,
+                  void *stream);
 
 #ifdef __cplusplus
 }

@@ -29,6 +29,27 @@ sklearn.metrics.silhouette_score on the same host; --sil-device (default 262144)
   knn_ms / knn_pairs_per_s  ops.knn_topk(x, x, 5) on the same rows in the same run: the same N^2 pair products on the
                          same pipe -- the yardstick of the pair rate;  vs_knn = pairs_per_s / knn_pairs_per_s;
   sklearn_s, score_diff, speedup_vs_sklearn   the sklearn case only (one host run; speed-up of the whole score call).
+
+--tsne measures evaluate.tsne (han_tsne_calibrate / han_tsne_step) and writes profiles/r15_tsne_bench.jsonl (or --out).
+ONE child process under `timeout` runs every size of --tsne-sizes (default 3025,4057,20000; perplexity 30), so all the
+rates of the file come from one process.  Per size:
+  calibrate_ms / passes  the whole ops.tsne_calibrate (row minima, the bisection passes, the reads between batches);
+  step_ms, step_kl_ms    one ops.tsne_step without / with the KL sums (median of --reps runs of 20 steps each);
+  pairs_per_s            N^2 / step_ms;  sil_pairs_per_s: ops.silhouette on the same rows in the same process, the same
+                         N^2 pair products;  vs_silhouette their ratio;
+  step_ms_by_width       the step on x repeated to 128, 256 and 512 columns: the tile kernel stages and multiplies one
+                         64-column chunk after another (a narrower x is zero-padded to a whole chunk in LDS and costs
+                         the same LDS fills and MFMAs, so timing a narrow x isolates nothing), and each further chunk
+                         adds one X-tile product -- the LDS fill of both operands and 16 MFMAs per 16 x 16 sub-tile --
+                         and nothing of the epilogue;
+  chunk_ms               the least-squares slope of step time over chunks (1, 2, 4, 8): what an X-tile product costs
+                         where it is NOT hidden.  It is no share of the 64-column step: with one chunk the row tile is
+                         staged once per workgroup, with more it is staged again for every column tile, and co-resident
+                         workgroups overlap one's product with another's epilogue;
+  full_s, n_iter, kl     the whole evaluate.tsne call from a random start (host clock, synchronised);
+  sklearn_bh_s           N <= --tsne-bh-max: TSNE(method="barnes_hut"), the host's practical choice, one run.
+And records of stage "tsne_exact": per size of --tsne-exact (default 1000,2000,3025: up to where scikit-learn's exact
+method ends in about a minute), the device's full call against TSNE(method="exact") on the same host.
 """
 import argparse
 import json
@@ -132,8 +153,106 @@ def silhouette_driver(args):
             out.flush()
 
 
+TSNE_OUT = os.path.join(os.path.dirname(SIL_OUT), "r15_tsne_bench.jsonl")
+
+
+def _steps_ms(xt, calib, want_kl, reps, steps=20):
+    """median ms of one ops.tsne_step over `reps` runs of `steps` steps from the same start"""
+    y0 = torch.as_tensor(np.float32(1e-4) * np.random.RandomState(1).standard_normal((xt.shape[0], 2)).astype(np.float32)).to(xt.device)
+    lr = max(xt.shape[0] / 48.0, 50.0)
+
+    def run():
+        y, u, g = y0.clone(), torch.zeros_like(y0), torch.ones_like(y0)
+        for _ in range(steps):
+            ops.tsne_step(xt, calib, y, u, g, 12.0, 0.5, lr, want_kl=want_kl)
+    return round(float(np.median(gpu_time(run, reps)[1])) / steps, 4)
+
+
+def _wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t0
+
+
+def tsne_cases(sizes, exact_sizes, bh_max, reps):
+    """Every t-SNE record, in this one process."""
+    from sklearn.manifold import TSNE
+    torch.set_num_threads(min(HOST_THREADS, torch.get_num_threads()))
+    dev = torch.device("cuda:0")
+    for n in sizes:
+        x, y = embeddings(n)
+        xt, yt = torch.as_tensor(x).to(dev), torch.as_tensor(y).to(dev)
+        ops.tsne_calibrate(xt, 30.0)                          # warm-up
+        calib, t = min((_wall(lambda: ops.tsne_calibrate(xt, 30.0)) for _ in range(reps)), key=lambda r: r[1])
+        d = dict(n=n, d=D, stage="tsne", perplexity=30.0, calibrate_ms=round(t * 1e3, 3), passes=int(calib["passes"]),
+                 open_rows=int(calib["open_rows"].cpu()[0]))
+        d["step_ms"], d["step_kl_ms"] = _steps_ms(xt, calib, False, reps), _steps_ms(xt, calib, True, reps)
+        d["pairs_per_s"] = float("%.4g" % (n * n / (d["step_ms"] * 1e-3)))
+        by_width = {D: d["step_ms"]}
+        for k in (2, 4, 8):
+            xw = torch.cat([xt] * k, 1).contiguous()
+            by_width[k * D] = _steps_ms(xw, ops.tsne_calibrate(xw, 30.0), False, reps)
+            del xw
+        d["step_ms_by_width"] = {str(w): t for w, t in by_width.items()}
+        d["chunk_ms"] = round(float(np.polyfit([w // D for w in by_width], list(by_width.values()), 1)[0]), 4)
+        order = torch.sort(yt.long(), stable=True).indices
+        seg = torch.zeros(5, dtype=torch.int64, device=dev)
+        seg[1:] = torch.cumsum(torch.bincount(yt.long(), minlength=4), 0)
+        xg = xt[order].contiguous()
+        sil = rates({}, n * n, gpu_time(lambda: ops.silhouette(xg, seg), reps)[1])
+        d.update(sil_ms=sil["gpu_ms"], sil_pairs_per_s=sil["pairs_per_s"],
+                 vs_silhouette=round(d["pairs_per_s"] / sil["pairs_per_s"], 4))
+        (_, info), t = _wall(lambda: evaluate.tsne(xt, init="random", seed=0, device=dev, return_info=True))
+        d.update(full_s=round(t, 4), n_iter=info["n_iter"], kl=round(info["kl_divergence"], 6))
+        if n <= bh_max:
+            t0 = time.perf_counter()
+            TSNE(n_components=2, method="barnes_hut", init="random", random_state=0).fit_transform(x)
+            d["sklearn_bh_s"] = round(time.perf_counter() - t0, 3)
+            d["host_threads"] = int(os.environ.get("OMP_NUM_THREADS", HOST_THREADS))
+        print(json.dumps(d), flush=True)
+    for exact_n in exact_sizes:
+        x, _ = embeddings(exact_n)
+        xt = torch.as_tensor(x).to(dev)
+        (_, info), t = _wall(lambda: evaluate.tsne(xt, init="random", seed=0, device=dev, return_info=True))
+        t0 = time.perf_counter()
+        est = TSNE(n_components=2, method="exact", init="random", random_state=0)
+        est.fit_transform(x)
+        host = time.perf_counter() - t0
+        print(json.dumps(dict(n=exact_n, d=D, stage="tsne_exact", full_s=round(t, 4), n_iter=info["n_iter"],
+                              kl=round(info["kl_divergence"], 6), sklearn_exact_s=round(host, 3),
+                              sklearn_kl=round(float(est.kl_divergence_), 6), sklearn_n_iter=int(est.n_iter_),
+                              host_threads=int(os.environ.get("OMP_NUM_THREADS", HOST_THREADS)),
+                              speedup_vs_sklearn=round(host / t, 1))), flush=True)
+
+
+def tsne_driver(args):
+    """One child under `timeout` for all sizes; its lines are the file."""
+    env = dict(os.environ)
+    for var in ("OMP_NUM_THREADS", "MKL_NUM_THREADS", "OPENBLAS_NUM_THREADS"):
+        env[var] = str(min(HOST_THREADS, int(env.get(var) or HOST_THREADS)))
+    path = args.out or TSNE_OUT
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    cmd = ["timeout", "-k", "10", str(args.tsne_timeout), sys.executable, os.path.abspath(__file__), "--tsne-case",
+           f"{args.tsne_sizes};{args.tsne_exact};{args.tsne_bh_max}", "--reps", str(args.reps)]
+    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    print("\n".join(lines), flush=True)
+    if r.returncode != 0:
+        raise SystemExit(f"the t-SNE cases ended with status {r.returncode}; nothing written")
+    with open(path, "w") as out:
+        out.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--tsne", action="store_true", help="measure evaluate.tsne (one child for all sizes)")
+    ap.add_argument("--tsne-sizes", default="3025,4057,20000")
+    ap.add_argument("--tsne-exact", default="1000,2000,3025", help="sizes also run through scikit-learn exact ('': none)")
+    ap.add_argument("--tsne-bh-max", type=int, default=4057, help="largest size also run through scikit-learn Barnes-Hut")
+    ap.add_argument("--tsne-timeout", type=int, default=540, help="seconds for the t-SNE child")
+    ap.add_argument("--tsne-case", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--silhouette", action="store_true", help="measure evaluate.silhouette_score (one child per case)")
     ap.add_argument("--sil-sklearn", type=int, default=20000, help="rows of the case run against scikit-learn (0: skip)")
     ap.add_argument("--sil-device", type=int, default=262144, help="rows of the device-only case (0: skip)")
@@ -147,12 +266,17 @@ def main():
     args = ap.parse_args()
     if args.silhouette:
         return silhouette_driver(args)
+    if args.tsne:
+        return tsne_driver(args)
     if not torch.cuda.is_available():
         raise SystemExit("evaluate_bench needs a GPU: there is nothing to measure without one")
     if args.silhouette_case:
         n, sk = (int(v) for v in args.silhouette_case.split(","))
         print(json.dumps(silhouette_case(n, bool(sk), args.reps)), flush=True)
         return
+    if args.tsne_case:
+        sizes, exact, bh_max = ([int(v) for v in part.split(",") if v] for part in args.tsne_case.split(";"))
+        return tsne_cases(sizes, exact, bh_max[0], args.reps)
     dev = torch.device("cuda:0")
     out = open(args.out, "w") if args.out else None
 
