@@ -5,6 +5,7 @@ full-graph with early stopping, restore the best weights, report the test metric
 KNN / KMeans scores of ``final_embed``.
 
     python examples/ex_acm3025.py [--mat ACM3025.mat] [--epochs 200] [--graph] [--eval-device gpu] [--sparse-features]
+                                  [--batch-size B]
 
 Hyper-parameters are the reference's (ex_acm3025.py:16-31): lr 0.005, l2 0.001,
 hid_units [8], n_heads [8, 1], dropout 0.6/0.6, patience 100, mp_att_size 128.
@@ -19,6 +20,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from han_amd import SparseFeatures, evaluate, process, synth  # noqa: E402
 from han_amd.gat import HeteGAT_multi  # noqa: E402
+from han_amd.minibatch import MiniBatchTrainer  # noqa: E402
 from han_amd.trainer import HANTrainer  # noqa: E402
 
 
@@ -37,6 +39,9 @@ def main():
     ap.add_argument("--sparse-features", action="store_true",
                     help="feed the features as a CSR matrix (han_amd.SparseFeatures): the first-layer projection then "
                          "visits the stored entries only; without --mat, a generated bag-of-words of the ACM shape")
+    ap.add_argument("--batch-size", type=int, default=None, metavar="B",
+                    help="train in mini-batches of B training nodes on the ego block of each batch "
+                         "(han_amd.minibatch.MiniBatchTrainer) instead of one full-graph step per epoch")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eval-device", choices=("cpu", "gpu"), default="cpu",
                     help="where final_embed is scored: cpu = scikit-learn on the host, as the reference; gpu = the "
@@ -82,9 +87,16 @@ def main():
           f"edges {[g.nnz for g in graphs]}")
 
     model = HeteGAT_multi().build(len(graphs), ft, nb_classes, (8,), (8, 1), 128, device=dev)
-    tr = HANTrainer(model, xs, graphs, labels, masks[0], masks[1], lr=0.005, l2_coef=0.001,
-                    attn_drop=0.6, ffd_drop=0.6, patience=args.patience, use_graph=args.graph,
-                    overlap_eval=args.graph and args.overlap_eval)
+    if args.batch_size is not None:
+        if args.graph:
+            ap.error("--batch-size: the block shapes change per batch, there is no epoch to capture (--graph)")
+        tr = MiniBatchTrainer(model, xs, graphs, labels, masks[0], masks[1], batch_size=args.batch_size, lr=0.005,
+                              l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6, seed=args.seed, patience=args.patience)
+        tr.overlap_eval = False
+    else:
+        tr = HANTrainer(model, xs, graphs, labels, masks[0], masks[1], lr=0.005, l2_coef=0.001,
+                        attn_drop=0.6, ffd_drop=0.6, patience=args.patience, use_graph=args.graph,
+                        overlap_eval=args.graph and args.overlap_eval)
     t0 = time.perf_counter()
     for epoch in range(args.epochs):
         tl, ta, vl, va = (float(v) for v in tr.epoch())
@@ -102,8 +114,11 @@ def main():
     dt = time.perf_counter() - t0
     print(f"{epoch + 1} epochs in {dt:.2f} s ({(epoch + 1) / dt:.1f} epochs/s)")
     tr.restore_best()
-    w_test = 1.0 / max(int(masks[2].sum()), 1)
-    tl, ta = tr.eval_step(masks[2].to(torch.uint8).contiguous(), w_test)
+    if args.batch_size is not None:
+        tl, ta = tr.evaluate(masks[2])
+    else:
+        w_test = 1.0 / max(int(masks[2].sum()), 1)
+        tl, ta = tr.eval_step(masks[2].to(torch.uint8).contiguous(), w_test)
     print(f"test loss {float(tl):.5f}  test accuracy {float(ta):.5f}")
     with torch.no_grad():
         _, final_embed, att = model.inference(xs, nb_classes, n, False, 0.0, 0.0, graphs, [8], [8, 1])

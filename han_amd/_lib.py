@@ -14,7 +14,8 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_uint64, c_void
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhan_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("node_attn.hip", "project.hip", "project_sparse.hip", "sem_attn.hip", "loss_opt.hip", "metapath.hip", "evaluate.hip")
+SOURCES = ("node_attn.hip", "project.hip", "project_sparse.hip", "sem_attn.hip", "loss_opt.hip", "metapath.hip", "evaluate.hip",
+           "ego_block.hip")
 # node_attn.hip: the dense K2 kernels (node_attn_dense.h) keep 8-16 fp32 MFMA accumulators in a rolled loop; with the
 # default AGPR form hipcc shuffles them through v_accvgpr_read / _mov / _write every iteration (each a wait for the
 # matrix pipe); the VGPR form of the MFMA destination has no such traffic
@@ -96,6 +97,9 @@ SIGNATURES = {
     "han_csr_row_topk_fill": (c_int, [P, P, P, I64, I64, c_int, P, P, P, P]),
     "han_metapath_walk_count": (c_int, [P, P, P, c_int, I64, I64, I64, c_int, c_int, c_uint64, c_int, P, P]),
     "han_metapath_walk_fill": (c_int, [P, P, P, c_int, I64, I64, I64, c_int, c_int, c_uint64, c_int, P, P, P, P]),
+    "han_ego_expand": (c_int, [P, P, I64, c_int, I64, I64, P, P, P, P, P, P]),
+    "han_ego_count": (c_int, [P, P, P, c_int, I64, I64, P, P]),
+    "han_ego_fill": (c_int, [P, P, P, P, P, c_int, P, I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P]),
     "han_knn_topk_workspace": (c_size_t, [I64, I64, c_int, c_int]),
     "han_knn_topk": (c_int, [P, I64, P, I64, P, P, P, c_size_t, I64, I64, c_int, c_int, P]),
     "han_knn_vote": (c_int, [P, P, P, I64, c_int, I64, P]),
@@ -110,7 +114,7 @@ SIGNATURES = {
                               c_size_t, P]),
 }
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 _lib = None
 
 

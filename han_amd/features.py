@@ -71,6 +71,29 @@ class SparseFeatures:
         return SparseFeatures(self.rowptr[r0:r1 + 1] - b, self.colidx[b:e],
                               self.values[b:e] if self.values is not None else None, self.n_cols)
 
+    def take(self, ids) -> "SparseFeatures":
+        """The rows `ids` (1-D integer tensor or array; any order, repeats allowed) as a new matrix, in the given
+        order: the features of the nodes of an ego block (minibatch.EgoBlock.take).  GPU only: the count / fill
+        kernels of the block graphs with every row kept and no column map (han_ego_count / han_ego_fill), one host
+        read for the new nnz (csr.two_pass) and one for the range of `ids`."""
+        from . import ops
+        ops.require_gpu(self.rowptr, "SparseFeatures.take")
+        ids = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids))
+        if ids.dim() != 1 or ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+            raise ValueError(f"ids: expected a 1-D integer array of row ids, got {tuple(ids.shape)} {ids.dtype}")
+        ids = ids.to(device=self.device, dtype=torch.int64).contiguous()
+        if ids.numel():
+            lo, hi = torch.stack([ids.min(), ids.max()]).tolist()
+            if lo < 0 or hi >= self.n_rows:
+                raise ValueError(f"ids outside [0, {self.n_rows}): [{lo}, {hi}]")
+        dtypes = (torch.int32,) if self.values is None else (torch.int32, torch.float32)
+        out = csr.two_pass(
+            ids.numel(), self.device, dtypes,
+            lambda counts: ops.ego_count(self.rowptr, ids, counts),
+            lambda rowptr, colidx, values=None: ops.ego_fill(self.rowptr, self.colidx, self.values, ids, self.n_cols,
+                                                             rowptr, colidx, values))
+        return SparseFeatures(out[0], out[1], out[2] if self.values is not None else None, self.n_cols)
+
     # ---- the transposed image of the backward ------------------------------------
     def transposed(self) -> dict:
         """The CSC image dW gathers through (ops.project_bwd), built once with torch ops on the first backward and

@@ -1,0 +1,330 @@
+"""Ego blocks: mini-batch inference and training on the neighbourhood of a batch of seed nodes.
+
+The reference's loop is a batch loop that runs once (``ex_acm3025.py:176-191``, ``batch_size = 1`` graph): the model
+only ever sees the whole graph.  :func:`ego_block` cuts out of the P meta-path graphs the block a batch needs -- the
+seeds and every node within ``hops`` steps of one over the UNION of the graphs -- with the nodes renumbered in
+ascending order.  A node closer than ``hops`` keeps its whole stored row; a node at distance ``hops`` (the rim) keeps
+one entry, (r, r).  The relabelling preserves order, so a kept row is summed in the order of the full graph; a kept
+row's neighbours are all in the block; a rim row only feeds rows whose output nobody reads.  For a model of ``hops``
+node-attention layers the rows ``seed_pos`` of every output on the block are therefore the rows ``seeds`` of the
+full-graph outputs, with the model code unchanged::
+
+    blk = ego_block(graphs, seeds, hops=1)
+    logits, embed, att = model.forward([blk.take(x)] * P, blk.graphs)      # rows blk.seed_pos answer the seeds
+
+:func:`predict` runs eval inference block by block, :class:`MiniBatchTrainer` the training step of ``HANTrainer`` on
+the block of each batch.  Fan-out is bounded beforehand (``metapath_graph(top_k=)``, ``metapath_sample(fanout=)``).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import csr, layers, ops, rng
+from .base_gattn import TFAdam
+from .features import SparseFeatures, as_features
+from .graph import CSRGraph, as_graph
+
+CHUNK = 1024       # input rows with more entries are walked and copied in chunks of this many, a wave each
+
+
+@dataclass
+class EgoBlock:
+    """nodes (n_b,) int64 ascending global ids; level (n_b,) int32 breadth-first distance from the seed set over the
+    union of the graphs (seeds 0); seed_pos (B,) int64 with nodes[seed_pos[i]] == seeds[i]; graphs: P CSRGraphs
+    n_b x n_b (module docstring); n: the nodes of the graphs the block was cut from."""
+    nodes: torch.Tensor
+    level: torch.Tensor
+    seed_pos: torch.Tensor
+    graphs: list
+    n: int
+
+    def take(self, x):
+        """What the block's nodes hold of `x`: x[nodes] of a dense (N, ...) / (1, N, F) tensor -- features, labels,
+        masks --, x.take(nodes) of sparse features (a SparseFeatures or a torch sparse tensor)."""
+        x = as_features(x)
+        if isinstance(x, SparseFeatures):
+            if x.n_rows != self.n:
+                raise ValueError(f"features have {x.n_rows} rows, the block was cut from {self.n} nodes")
+            return x.take(self.nodes)
+        if x.dim() == 3 and x.shape[0] == 1:
+            x = x[0]
+        if x.dim() < 1 or x.shape[0] != self.n:
+            raise ValueError(f"expected a per-node tensor with {self.n} rows, got shape {tuple(x.shape)}")
+        return x.index_select(0, self.nodes.to(x.device))
+
+
+def _host_seeds(seeds, n):
+    """Seeds given on the host as a checked int64 array: 1-D integers, B >= 1, distinct, inside [0, n)."""
+    s = np.asarray(seeds)
+    if s.size == 0:
+        raise ValueError("seeds: empty")
+    if s.ndim != 1 or s.dtype.kind not in "iu":
+        raise ValueError(f"seeds: expected a 1-D integer array of node ids, got shape {s.shape} {s.dtype}")
+    s = s.astype(np.int64)
+    if int(s.min()) < 0 or int(s.max()) >= n:
+        raise ValueError(f"seeds outside [0, {n}): [{int(s.min())}, {int(s.max())}]")
+    if np.unique(s).size != s.size:
+        raise ValueError("seeds: repeated node ids")
+    return s
+
+
+def _check_block_args(graphs, seeds, hops):
+    """Everything ego_block can refuse without a device: (graphs, n, host seeds or None for a device tensor)."""
+    graphs = list(graphs)
+    if isinstance(hops, bool) or int(hops) != hops or hops < 1:
+        raise ValueError(f"hops = {hops!r}: expected an integer >= 1")
+    if not graphs:
+        raise ValueError("ego_block: no graphs")
+    for p, g in enumerate(graphs):
+        if not isinstance(g, CSRGraph):
+            raise ValueError(f"graphs[{p}] is a {type(g)}, expected a CSRGraph")
+        if g.n_rows != g.n_cols:
+            raise ValueError(f"graphs[{p}] is {g.n_rows} x {g.n_cols}: an ego block needs square graphs")
+        if g.n_rows != graphs[0].n_rows:
+            raise ValueError(f"graphs[{p}] has {g.n_rows} nodes, graphs[0] has {graphs[0].n_rows}")
+        if g.row_base != 0:
+            raise ValueError(f"graphs[{p}] is a row shard (row_base = {g.row_base}): blocks are cut from whole graphs")
+    n = graphs[0].n_rows
+    if isinstance(seeds, torch.Tensor):
+        if seeds.dim() != 1 or seeds.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"seeds: expected a 1-D int32 / int64 tensor, got {tuple(seeds.shape)} {seeds.dtype}")
+        if seeds.numel() == 0:
+            raise ValueError("seeds: empty")
+        host = None
+    else:
+        host = _host_seeds(seeds, n)
+    dev = graphs[0].device
+    for p, g in enumerate(graphs):
+        ops.require_gpu(g.rowptr, f"graphs[{p}]")
+        if g.device != dev:
+            raise ValueError(f"graphs[{p}] on {g.device}, graphs[0] on {dev}")
+    if host is None:
+        ops.require_gpu(seeds, "seeds")
+        if seeds.device != dev:
+            raise ValueError(f"seeds on {seeds.device}, the graphs on {dev}")
+    return graphs, n, host
+
+
+def ego_block(graphs, seeds, hops: int = 1) -> EgoBlock:
+    """The block of `seeds` (B >= 1 distinct node ids; an int32 / int64 tensor on the graphs' GPU, or a host array)
+    in P square CSRGraphs over the same N nodes on one GPU (values optional, row_base 0), for a model of `hops` >= 1
+    node-attention layers: see EgoBlock and the module docstring.  Raises ValueError, before any launch, for repeated,
+    out-of-range or empty seeds, hops < 1, a non-square graph, graphs of different N, a row shard, and graphs or a
+    seed tensor on the CPU (there is no CPU path).
+
+    Launches: hops x P han_ego_expand (the graphs of a hop one after another on the stream), a scan of level >= 0
+    for the local ids, then han_ego_count / han_ego_fill per graph (csrc/ego_block.hip).  HOST READS PER BLOCK: 2,
+    whatever B, N, P and hops are -- n_b with the node list, then the P entry counts in one read -- and one more when
+    the seeds come as a device tensor (their range and distinctness, in one read).  Rows longer than CHUNK entries
+    are served by the input graph's own chunk table (CSRGraph.row_split), built on a graph's first block and cached
+    with it.  Bitwise reproducible: integer stores only, every writer of a word writes the same value."""
+    graphs, n, host = _check_block_args(graphs, seeds, hops)
+    hops, P, dev = int(hops), len(graphs), graphs[0].device
+    if host is not None:
+        s = torch.as_tensor(host).to(dev)
+    else:
+        s = seeds.to(torch.int64)
+        srt = torch.sort(s).values
+        lo, hi, repeated = torch.stack([srt[0], srt[-1], (srt[1:] == srt[:-1]).any().to(torch.int64)]).tolist()
+        if lo < 0 or hi >= n:
+            raise ValueError(f"seeds outside [0, {n}): [{lo}, {hi}]")
+        if repeated:
+            raise ValueError("seeds: repeated node ids")
+    splits = [g.row_split(CHUNK, CHUNK) for g in graphs]
+    level = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    level[s] = 0
+    for h in range(hops):
+        for g, sp in zip(graphs, splits):
+            ops.ego_expand(g, level, h, sp)
+    nodes = torch.nonzero(level >= 0).flatten()                               # host read 1: n_b
+    n_b = nodes.numel()
+    local = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    local[nodes] = torch.arange(n_b, dtype=torch.int32, device=dev)
+    counts = torch.empty(P * n_b, dtype=torch.int64, device=dev)
+    for p, g in enumerate(graphs):
+        ops.ego_count(g.rowptr, nodes, counts[p * n_b:(p + 1) * n_b], level, hops)
+    ptr = csr.scan(counts)                                                    # the P row pointers end to end
+    offs = ptr[::n_b].tolist()                                                # host read 2: the P entry counts
+    out = []
+    for p, (g, sp) in enumerate(zip(graphs, splits)):
+        nnz = offs[p + 1] - offs[p]
+        rowptr = ptr[p * n_b:(p + 1) * n_b + 1] - offs[p]
+        colidx = torch.empty(nnz, dtype=torch.int32, device=dev)
+        values = torch.empty(nnz, dtype=torch.float32, device=dev) if g.values is not None else None
+        if nnz:
+            ops.ego_fill(g.rowptr, g.colidx, g.values, nodes, n, rowptr, colidx, values, level, hops, local, sp)
+        out.append(CSRGraph(rowptr, colidx, n_b, validate=False, values=values))
+    return EgoBlock(nodes=nodes, level=level[nodes], seed_pos=local[s].long(), graphs=out, n=n)
+
+
+# ---- using a block ---------------------------------------------------------------------------------------------------
+def _model_hops(model) -> int:
+    return 1 + len(model.extra)
+
+
+def _inputs(model, xs, graphs):
+    """(xs, graphs) as the model methods take them: features squeezed / converted once, graphs on the model's GPU."""
+    if not model._built:
+        raise RuntimeError("build the model first (model.build(...))")
+    if model.partition is not None:
+        raise NotImplementedError("ego blocks under a node partition are not supported")
+    dev = model.flat.device
+    xs = [layers._squeeze_batch(x, f"xs[{i}]") for i, x in enumerate(xs)]
+    xs = [x if isinstance(x, SparseFeatures) else x.contiguous() for x in xs]
+    graphs = [as_graph(g, dev) for g in graphs]
+    if len(xs) != len(graphs) or len(graphs) != model.P:
+        raise ValueError(f"{len(xs)} feature inputs and {len(graphs)} graphs for a model of {model.P} meta-paths")
+    for x, g in zip(xs, graphs):
+        if x.shape[0] != g.n_rows:
+            raise ValueError(f"graph has {g.n_rows} rows, features have {x.shape[0]}")
+    return xs, graphs
+
+
+def _take_each(blk: EgoBlock, xs):
+    """blk.take of every input, an input shared by several meta-paths taken once."""
+    done = {}
+    return [done[id(x)] if id(x) in done else done.setdefault(id(x), blk.take(x)) for x in xs]
+
+
+def predict(model, xs, graphs, rows=None, batch_size: int = 4096):
+    """Eval inference of the nodes `rows` (default: all N; a 1-D integer tensor or array, repeats allowed), block by
+    block: (logits (R, C), final_embed (R, D_out), att_val (R, P)) of exactly those rows, in their order -- the rows
+    a full-graph model.inference returns for them.  hops is the model's node-attention layer count; the distinct
+    rows are served in ascending batches of `batch_size` seeds, so peak memory follows the block, not N."""
+    xs, graphs = _inputs(model, xs, graphs)
+    if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError(f"batch_size = {batch_size!r}: expected an integer >= 1")
+    dev, n, hops = model.flat.device, graphs[0].n_rows, _model_hops(model)
+    if rows is None:
+        uniq, inverse = torch.arange(n, device=dev), None
+    else:
+        r = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.asarray(rows))
+        if r.dim() != 1 or r.dtype.is_floating_point or r.dtype.is_complex or r.dtype == torch.bool:
+            raise ValueError(f"rows: expected a 1-D integer array of node ids, got {tuple(r.shape)} {r.dtype}")
+        uniq, inverse = torch.unique(r.to(device=dev, dtype=torch.int64), return_inverse=True)
+    outs = ([], [], [])
+    for b0 in range(0, uniq.numel(), int(batch_size)):
+        blk = ego_block(graphs, uniq[b0:b0 + int(batch_size)], hops)
+        with torch.no_grad():
+            M = model.node_level(_take_each(blk, xs), blk.graphs, 0.0, 0.0, False, ops.ACT_ELU)
+            Z, att = model.semantic(M)
+            logits = model.classify(Z)
+        for o, t in zip(outs, (logits, Z, att)):
+            o.append(t[blk.seed_pos])
+    if not outs[0]:
+        return (torch.empty((0, model.C), device=dev), torch.empty((0, model.D_out), device=dev),
+                torch.empty((0, model.P), device=dev))
+    res = tuple(torch.cat(o) for o in outs)
+    return res if inverse is None else tuple(t[inverse] for t in res)
+
+
+def epoch_batches(ids, batch_size: int, seed: int, epoch: int):
+    """The batches of one epoch: `ids` (host array of node ids) in the order of a host permutation drawn from
+    (seed, epoch), cut into runs of `batch_size`; the short last batch is kept.  Every id exactly once."""
+    ids = np.asarray(ids, dtype=np.int64)
+    if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError(f"batch_size = {batch_size!r}: expected an integer >= 1")
+    order = ids[np.random.default_rng([int(seed) & ((1 << 64) - 1), int(epoch)]).permutation(ids.size)]
+    return [order[b0:b0 + int(batch_size)] for b0 in range(0, ids.size, int(batch_size))]
+
+
+class MiniBatchTrainer:
+    """The training loop of HANTrainer on ego blocks: an epoch visits the training nodes once, in batches
+    (epoch_batches), and every batch is one step of HANTrainer.train_step on the block of its seeds -- node_level
+    (train=True), semantic, classifier_loss with the mask on seed_pos and weight 1 / B, backward, TFAdam.step -- with
+    the trainer and the model code as they are.  Dropout draws are keyed by LOCAL node id: another, equally valid
+    assignment than the full graph's (as under reorder's relabelling).  The dropout seed stream is the trainer's own
+    (started from `seed`), so two trainers with equal seeds and equal initial parameters stay bit-equal.  Single
+    process, eager (the shapes change per batch: nothing to capture)."""
+
+    def __init__(self, model, xs, graphs, labels, train_mask, val_mask=None, batch_size: int = 1024, lr=0.005,
+                 l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6, seed: int = 0, patience: int = 100):
+        self.model = model
+        self.xs, self.graphs = _inputs(model, xs, graphs)
+        model.direct_grads(True)
+        dev = model.flat.device
+        self.hops = _model_hops(model)
+        self.labels = labels.to(device=dev, dtype=torch.int32).contiguous()
+        self.train_mask = train_mask.to(device=dev, dtype=torch.uint8).contiguous()
+        self.val_mask = (val_mask if val_mask is not None else train_mask).to(device=dev, dtype=torch.uint8).contiguous()
+        self.train_ids = torch.nonzero(self.train_mask).flatten().cpu().numpy()
+        if self.train_ids.size == 0:
+            raise ValueError("train_mask selects no node")
+        epoch_batches(self.train_ids[:1], batch_size, seed, 0)          # checks batch_size
+        self.batch_size, self.seed = int(batch_size), int(seed)
+        self.opt = TFAdam(model.flat, model.flat_grad, lr=lr, l2_coef=l2_coef)
+        self._one = torch.ones((), dtype=torch.float32, device=dev)
+        self.attn_drop, self.ffd_drop = float(attn_drop), float(ffd_drop)
+        self._rng = {"seed": self.seed & ((1 << 64) - 1), "counter": 0}      # this trainer's rng._state
+        self.epochs_done = 0
+        self.patience = patience
+        self.vlss_mn, self.vacc_mx, self.curr_step = float("inf"), 0.0, 0
+        self.best_state = None
+
+    def batches(self):
+        """The seed batches of the next epoch (host arrays)."""
+        return epoch_batches(self.train_ids, self.batch_size, self.seed, self.epochs_done)
+
+    def train_step(self, seeds):
+        """One optimiser step on the block of `seeds`; returns device scalars (loss, accuracy) over the seeds."""
+        m = self.model
+        blk = ego_block(self.graphs, seeds, self.hops)
+        xs = _take_each(blk, self.xs)
+        labels = blk.take(self.labels)
+        mask = torch.zeros(blk.nodes.numel(), dtype=torch.uint8, device=labels.device)
+        mask[blk.seed_pos] = 1
+        saved = dict(rng._state)
+        rng._state.update(self._rng)
+        try:
+            m.zero_grad_flat()
+            with torch.enable_grad():
+                M = m.node_level(xs, blk.graphs, self.attn_drop, self.ffd_drop, True, ops.ACT_ELU)
+                Z, _ = m.semantic(M)
+                loss, acc, _ = m.classifier_loss(Z, labels, mask, 1.0 / blk.seed_pos.numel())
+            loss.backward(self._one)
+        finally:
+            self._rng = dict(rng._state)
+            rng._state.update(saved)
+        self.opt.step()
+        return loss.detach(), acc
+
+    def evaluate(self, mask=None):
+        """(loss, accuracy) over the nodes of `mask` (default: val_mask) with the current parameters, through
+        predict: the masked softmax cross-entropy and accuracy of HANTrainer.eval_step, as device scalars."""
+        mask = self.val_mask if mask is None else mask
+        ids = torch.nonzero(mask.to(self.labels.device)).flatten()
+        if ids.numel() == 0:
+            raise ValueError("the mask selects no node")
+        logits, _, _ = predict(self.model, self.xs, self.graphs, ids, self.batch_size)
+        labels = self.labels[ids].long()
+        loss = torch.nn.functional.cross_entropy(logits, labels)
+        return loss, (logits.argmax(1) == labels).to(torch.float32).mean()
+
+    def epoch(self):
+        """One pass over the training nodes, then the validation pair: (train loss, train accuracy -- the batch
+        figures averaged over the training nodes --, val loss, val accuracy), device scalars."""
+        tl = ta = 0.0
+        for b in self.batches():
+            loss, acc = self.train_step(b)
+            tl, ta = tl + loss * (b.size / self.train_ids.size), ta + acc * (b.size / self.train_ids.size)
+        self.epochs_done += 1
+        vl, va = self.evaluate()
+        return tl, ta, vl, va
+
+    def early_stopping(self, val_loss: float, val_acc: float) -> bool:
+        """HANTrainer.early_stopping (ex_acm3025.py:225-240): True to stop."""
+        if val_acc >= self.vacc_mx or val_loss <= self.vlss_mn:
+            if val_acc >= self.vacc_mx and val_loss <= self.vlss_mn:
+                self.best_state = self.model.flat.detach().clone()
+            self.vacc_mx, self.vlss_mn = max(val_acc, self.vacc_mx), min(val_loss, self.vlss_mn)
+            self.curr_step = 0
+            return False
+        self.curr_step += 1
+        return self.curr_step == self.patience
+
+    def restore_best(self):
+        if self.best_state is not None:
+            self.model.flat.copy_(self.best_state)

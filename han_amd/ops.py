@@ -1029,6 +1029,43 @@ def metapath_walk(hops, walks: int, fanout=None, seed: int = 0, diag: bool = Fal
     return CSRGraph(rowptr, colidx, n_cols, validate=False, row_base=r0), visits
 
 
+# ------------------------------------------------- K0: ego blocks (han_ego_*, csrc/ego_block.hip)
+def _long_rows_arg(split):
+    """The chunk-table arguments of han_ego_expand / han_ego_fill from CSRGraph.row_split's dict (None: no long row)."""
+    if split is None:
+        return (0, 0, None, None, None, None)
+    return (split["split_deg"], split["n_chunks"], split["long_rows"].data_ptr(), split["chunk_long"].data_ptr(),
+            split["chunk_start"].data_ptr(), split["chunk_end"].data_ptr())
+
+
+def ego_expand(graph: CSRGraph, level: torch.Tensor, h: int, split=None):
+    """One breadth-first hop over `graph`, in place: every row with level == h writes h + 1 into the level of its
+    unvisited (-1) columns.  level: (n,) int32 on the graph's device; split: graph.row_split(...) or None."""
+    _chk(level, "level", (graph.n_rows,), dtype=torch.int32, device=graph.device)
+    _lib.check(_lib.load().han_ego_expand(graph.rowptr.data_ptr(), _ptr_nonempty(graph.colidx), graph.n_rows, int(h),
+                                          *_long_rows_arg(split), level.data_ptr(), _stream()), "han_ego_expand")
+
+
+def ego_count(rowptr: torch.Tensor, rows: torch.Tensor, counts: torch.Tensor, level=None, hops: int = 1):
+    """counts[r] = the entries of output row r: those of row rows[r] of `rowptr` where it is kept (level None: always;
+    else 0 <= level[rows[r]] < hops), 1 on the rim.  rows (n_out,) int64, counts (n_out,) int64, written in place."""
+    _chk(rows, "rows", dtype=torch.int64, device=rowptr.device)
+    _chk(counts, "counts", (rows.numel(),), dtype=torch.int64, device=rowptr.device)
+    _lib.check(_lib.load().han_ego_count(rowptr.data_ptr(), _ptr_nonempty(rows), _ptr(level), int(hops),
+                                         rowptr.numel() - 1, rows.numel(), _ptr_nonempty(counts), _stream()),
+               "han_ego_count")
+
+
+def ego_fill(rowptr, colidx, values, rows, n_cols, out_rowptr, out_colidx, out_values, level=None, hops: int = 1,
+             local=None, split=None):
+    """The output rows counted by ego_count: row rows[r] as stored (columns through `local` when given), (r, r) on the
+    rim; out_values None or (nnz,) fp32 (1.0 where `values` is None or on the rim)."""
+    _lib.check(_lib.load().han_ego_fill(
+        rowptr.data_ptr(), _ptr_nonempty(colidx), _ptr_nonempty(values), _ptr_nonempty(rows), _ptr(level), int(hops),
+        _ptr(local), rowptr.numel() - 1, int(n_cols), rows.numel(), *_long_rows_arg(split), out_rowptr.data_ptr(),
+        _ptr_nonempty(out_colidx), _ptr_nonempty(out_values), _stream()), "han_ego_fill")
+
+
 # ------------------------------------------------- evaluation of the embeddings
 KNN_MAX_K = 16             # neighbours per query of han_knn_topk
 EVAL_MAX_D = 512           # embedding width of han_knn_topk / han_kmeans_step

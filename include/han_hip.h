@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HAN_ABI_VERSION 13
+#define HAN_ABI_VERSION 14
 
 #define HAN_E_BADARG   (-1)   /* null pointer, negative size, inconsistent shape.  The forward
                               * entry points return 0 at once for N == 0 (empty tensors may
@@ -539,6 +539,42 @@ int han_metapath_walk_fill(const int64_t *const *hop_rowptr, const int32_t *cons
                            const int64_t *hop_rows, int n_hops, int64_t n_cols, int64_t row_base, int64_t n_rows,
                            int walks, int fanout, uint64_t seed, int diag, const int64_t *c_rowptr,
                            int32_t *c_colidx, int32_t *c_visits, void *stream);
+
+/* ---- K0: ego blocks (ABI 14) --------------------------------------------------
+ * The neighbourhood of a batch of seed nodes cut out of square graphs over the same n nodes (han_amd/minibatch.py):
+ * a breadth-first level per node, then the block's rows with their columns renumbered.  Graphs are CSR as everywhere
+ * (rowptr int64, colidx int32; columns need not be sorted or unique), a colidx / values pointer may be NULL when the
+ * graph has no entries.  Integer loads and stores only: results are bitwise the same from run to run.
+ * The chunk table (split_deg, n_chunks, long_rows, chunk_long, chunk_start, chunk_end) is han_row_split_t's, of the
+ * INPUT graph: rows with more than split_deg entries are left to their chunks, a wave each; n_chunks == 0 (pointers
+ * may be NULL): every row is walked by one wave, whatever its length.  Not checked: that the table describes rowptr.
+ * han_ego_expand: one hop over one graph.  level (n) int32, -1 = unvisited: every row i with level[i] == h writes
+ *   h + 1 into level[c] of each of its columns c that is still unvisited (columns outside [0, n) are skipped).  All
+ *   writers of a word write the same value, a visited word never changes, so the outcome does not depend on timing.
+ *   The caller sets level = 0 on the seeds and issues the graphs of hop h one after another on the stream, then
+ *   hop h + 1: level becomes the breadth-first distance over the union of the graphs.
+ * han_ego_count: counts (n_out) int64, the entries of every output row r with source row v = rows[r] (int64): the
+ *   stored entries of row v where the row is kept, 1 where it is not (the rim), 0 for v outside [0, n_in).  A row is
+ *   kept iff 0 <= level[v] < hops; level == NULL keeps every row (hops is then ignored).
+ * han_ego_fill: out_rowptr (n_out + 1) int64 = the scanned counts.  A kept row is row v as stored -- order, repeated
+ *   entries and values as they are --, its columns c replaced by local[c] (int32 over n_cols; -1 for c outside
+ *   [0, n_cols)), or unchanged with local == NULL; a rim row holds (r, r) alone.  out_values (or NULL): the values,
+ *   1.0 on the rim and wherever values == NULL.  With a chunk table local must be given and invert rows on the kept
+ *   rows (local[rows[r]] == r): chunk c of row v lands at its offset inside row local[v].
+ * A NULL rowptr / level / rows / counts / out_rowptr / out_colidx, a negative size, hops < 1 beside a level array, a
+ * chunk table with a NULL array or split_deg < 1, and n (expand) or n_cols / n_out (fill) beyond INT32_MAX are
+ * HAN_E_BADARG, decided before any launch; n == 0 / n_out == 0 return 0 and launch nothing.  All three run on `stream`,
+ * allocate nothing and never synchronise.                                                                            */
+int han_ego_expand(const int64_t *rowptr, const int32_t *colidx, int64_t n, int h, int64_t split_deg,
+                   int64_t n_chunks, const int64_t *long_rows, const int32_t *chunk_long, const int64_t *chunk_start,
+                   const int64_t *chunk_end, int32_t *level, void *stream);
+int han_ego_count(const int64_t *rowptr, const int64_t *rows, const int32_t *level, int hops, int64_t n_in,
+                  int64_t n_out, int64_t *counts, void *stream);
+int han_ego_fill(const int64_t *rowptr, const int32_t *colidx, const float *values, const int64_t *rows,
+                 const int32_t *level, int hops, const int32_t *local, int64_t n_in, int64_t n_cols, int64_t n_out,
+                 int64_t split_deg, int64_t n_chunks, const int64_t *long_rows, const int32_t *chunk_long,
+                 const int64_t *chunk_start, const int64_t *chunk_end, const int64_t *out_rowptr, int32_t *out_colidx,
+                 float *out_values, void *stream);
 
 /* ---- evaluation of the embeddings (ABI 9) -----------------------------------
  * The reference scores final_embed on the host with scikit-learn: my_KNN (jhyexp.py:20-51) and my_Kmeans
