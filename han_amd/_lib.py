@@ -79,6 +79,9 @@ SIGNATURES = {
     "han_sem_attn_bwd_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
     "han_sem_attn_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int,
                                  c_int, c_int, P]),
+    "han_sem_attn_bwd_rows_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
+    "han_sem_attn_bwd_rows": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int,
+                                      c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "han_classifier_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
     "han_classifier_loss": (c_int, [P, P, P, P, P, c_float, P, P, P, P, P, P, c_size_t, I64,
                                     c_int, c_int, c_int, P]),
@@ -114,7 +117,8 @@ SIGNATURES = {
                               c_size_t, P]),
 }
 
-ABI_VERSION = 14
+ABI_VERSION = 15
+E_UNSUPPORTED = -2      # HAN_E_UNSUPPORTED
 _lib = None
 
 

@@ -1127,6 +1127,8 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_b6_kernel(const float *
     for (int i = threadIdx.x; i < 64 * A + 2 * A; i += 256) out[i] = red[i];
 }
 
+#include "sem_attn_fold.h"      // the same kernel with the row-local K2 backward in its epilogue (han_sem_attn_bwd_rows)
+
 // The same backward at A = 128 with TWO waves per SIMD.  One wave cannot keep the matrix pipe busy (a wave issues
 // an fp32 16x16x4 MFMA every ~51 cycles and a bf16 16x16x32 every ~27 where the pipe takes 32 / 16:
 // profiles/r04_ubench_mfma_valu_overlap.jsonl), and the kernel above needs 390 registers -- 128 of them the dW
@@ -1961,11 +1963,13 @@ hipError_t launch_fwd_wide(const K3Fwd &a) {
     return a.launch(sem_attn_fwd_wide_kernel<CA>, han_grid_for(a.N, ROWS / a.P, 256 * 4), 256, 0, a.P, a.D, a.A);
 }
 
+int bwd_wave_grid(const K3Bwd &a) { return han_grid_for(a.N * a.P, 64, kSemBwdBlocks); }
+
 template <int CA>
 hipError_t launch_bwd_wave(K3Bwd &a) {
     constexpr int A = 64 * CA;
     hipError_t e = hipSuccess;
-    a.grid = han_grid_for(a.N * a.P, 64, kSemBwdBlocks);
+    a.grid = bwd_wave_grid(a);
     if (k3_b6(a.N, a.P, a.flags)) {
         const size_t lds = B6BwdLds<A>::bytes;
         HAN_DISPATCH_P(a.P, {
@@ -1978,6 +1982,23 @@ hipError_t launch_bwd_wave(K3Bwd &a) {
     } else {
         HAN_DISPATCH_P(a.P, e = a.launch(sem_attn_bwd_wave_kernel<CA, PC>, 256, BwdLds<64, A>::bytes))
     }
+    return e;
+}
+
+// shapes of the fold (han_sem_attn_bwd_rows): the one-wave bf16-pipe kernel with a node's rows inside a lane group
+bool k3_fold_ok(int64_t N, int P, int D, int A, int flags) {
+    return D == 64 && (A == 64 || A == 128) && (P == 1 || P == 2 || P == 4) && k3_b6(N, P, flags) &&
+           !(flags & (HAN_FLAG_K3_PAIRS | HAN_FLAG_K3_G3_F32)) && N * kFoldRowBytes < ((int64_t)1 << 32);      // 32-bit table offsets
+}
+constexpr int k3_fold_slab_width(int P, int A) { return 64 * A + 2 * A + 64 * P; }
+
+template <int CA>
+hipError_t launch_bwd_fold(K3Bwd &a, const K3FoldArgs &fa) {
+    hipError_t e = hipSuccess;
+    a.grid = bwd_wave_grid(a);
+    const size_t lds = B6BwdLds<64 * CA>::bytes + (size_t)a.P * 64 * sizeof(float);      // + c
+    HAN_DISPATCH_P(a.P, if constexpr (PC <= 4) e = han_launch_lds(sem_attn_bwd_wave_b6_fold_kernel<CA, PC>, a.grid, 256, lds, a.st,
+                                                                 a.M, a.w, a.b, a.u, a.beta, a.dZ, a.slab, a.N, fa));
     return e;
 }
 
@@ -2063,5 +2084,44 @@ extern "C" int han_sem_attn_bwd(const float *M, const float *w_omega, const floa
     o.ptr[1] = db_omega; o.ptr[2] = du_omega;
     o.seg_end[0] = D * A; o.seg_end[1] = D * A + A; o.seg_end[2] = width;
     o.nseg = 3;
+    return (int)han_reduce_slabs(a.slab, a.grid, width, width, o, (hipStream_t)stream);
+}
+
+extern "C" size_t han_sem_attn_bwd_rows_workspace(int64_t N, int P, int D, int A) {
+    (void)N; (void)D;
+    return (size_t)kSemBwdBlocks * (size_t)k3_fold_slab_width(P > 0 ? P : 0, A > 0 ? A : 0) * sizeof(float);
+}
+
+extern "C" int han_sem_attn_bwd_rows(const float *M, const float *w_omega, const float *b_omega, const float *u_omega,
+                                     const float *beta, const float *dZ, const float *const *aggp,
+                                     const float *const *tsum, const float *const *f1, const float *const *lse,
+                                     const float *c, void *const *gs, float *const *df1, float *dw_omega,
+                                     float *db_omega, float *du_omega, float *dc, void *workspace,
+                                     size_t workspace_bytes, int64_t N, int P, int D, int A, int K, int FP,
+                                     int table_dtype, int activation, int flags, void *stream) {
+    if (!M || !w_omega || !b_omega || !u_omega || !beta || !dZ || !aggp || !tsum || !f1 || !lse || !c || !gs || !df1 ||
+        !dw_omega || !db_omega || !du_omega || !dc || !workspace || N < 0 || P <= 0)
+        return HAN_E_BADARG;
+    if (!k3_fold_ok(N, P, D, A, flags) || K != 8 || FP != 8 || table_dtype != HAN_DTYPE_F32 ||
+        (activation != HAN_ACT_ELU && activation != HAN_ACT_IDENTITY))
+        return HAN_E_UNSUPPORTED;
+    K3FoldArgs fa = {};
+    for (int p = 0; p < P; ++p) {
+        if (!aggp[p] || !tsum[p] || !f1[p] || !lse[p] || !gs[p] || !df1[p]) return HAN_E_BADARG;
+        fa.aggp[p] = aggp[p]; fa.tsum[p] = tsum[p]; fa.f1[p] = f1[p]; fa.lse[p] = lse[p];
+        fa.gs[p] = (char *)gs[p]; fa.df1[p] = df1[p];
+    }
+    fa.c = c;
+    fa.act = activation;
+    if (workspace_bytes < han_sem_attn_bwd_rows_workspace(N, P, D, A)) return HAN_E_WORKSPACE;
+    K3Bwd a = {M, w_omega, b_omega, u_omega, beta, dZ, nullptr, (float *)workspace, N, P, D, A, flags, (hipStream_t)stream, 0};
+    hipError_t e = hipSuccess;
+    HAN_DISPATCH_CA(A, if constexpr (CA <= 2) e = launch_bwd_fold<CA>(a, fa));
+    if (e != hipSuccess) return (int)e;
+    const int wpar = D * A + 2 * A, width = k3_fold_slab_width(P, A);
+    HanReduceOut o = han_reduce_to(dw_omega, width);
+    o.ptr[1] = db_omega; o.ptr[2] = du_omega; o.ptr[3] = dc;
+    o.seg_end[0] = D * A; o.seg_end[1] = D * A + A; o.seg_end[2] = wpar; o.seg_end[3] = width;
+    o.nseg = 4;
     return (int)han_reduce_slabs(a.slab, a.grid, width, width, o, (hipStream_t)stream);
 }

@@ -93,6 +93,9 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         self.path_streams = None              # one stream per meta-path (HANTrainer(use_graph=True)): layers._each_path
         self.path_order = "index"             # "heavy": the per-meta-path chains of a captured epoch are issued largest graph first (layers._path_order)
         self.overlap_branch = None            # HANTrainer(overlap_eval=True): the eval forward riding in the captured training step (trainer._EvalBranch)
+        self.fold_k3 = False                  # the K3 backward also runs the row-local half of the last layer's K2 backward (layers.FoldTail):
+                                              # set by HANTrainer; off for free-form use, because it relies on M having no consumer but semantic()
+        self._fold_handover = None            # (M, FoldTail) of the last node_level() call, taken by semantic(M)
         self.side_stream = None               # second stream of the eager training step on large graphs (layers.NodeLevelAttention.backward):
                                               # dW of meta-path p runs beside the backward gather of meta-path p + 1
         self._graph_cache: dict = {}
@@ -260,6 +263,8 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         then projects the whole table on every rank instead of exchanging it (replicated projection)."""
         P = len(graphs)
         layers._no_sparse_under_partition(self.partition is not None or xs_full is not None, xs, xs_full)
+        self._fold_handover = None
+        fold = [] if (self.fold_k3 and train and post is None) else None      # FoldTail of the LAST node-attention call
 
         def act(M, K, FP):
             if post is None:
@@ -298,9 +303,11 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
             sd = seeds(layer)
             wide = FP > GROUP
             groups = [(k, k + 1) for k in range(K)] if wide else _head_groups(K, FP)
+            if fold is not None:
+                fold.clear()
             if len(groups) == 1 and K * FP == GROUP:      # the reference shapes: no slicing, direct gradients
                 return layers.NodeLevelAttention.apply(Xin, W, a1, b1, a2, b2, c, Wr, br, xs_, tuple(graphs),
-                                                       run(layer, sd, coef_sink=sink, coef_mean=True))
+                                                       run(layer, sd, coef_sink=sink, coef_mean=True, fold_sink=fold))
             fn = layers.WideHeadAttention if wide else layers.NodeLevelAttention
             FPk = -(-FP // GROUP) * GROUP if wide else _kernel_head_width(FP)      # width a head runs at (zero-weight columns beyond FP)
             kg = max(GROUP // FPk, 1)                                              # head slots of a group
@@ -335,12 +342,16 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         M = act(layer_fwd(0, None, tuple(xs), self.K, self.FP, coef_sink), self.K, self.FP)
         for i, (Ki, FPi) in enumerate(self.extra, start=1):                     # gat.py:48-57
             M = act(layer_fwd(i, M, None, Ki, FPi, None), Ki, FPi)
+        if fold:
+            self._fold_handover = (M, fold[0])
         return M
 
     def semantic(self, M):
         """models/gat.py:61-63: SimpleAttLayer over the stacked meta-path embeddings M (N,P,D_out) ->
         (final_embed (N,D_out), att_val (N,P)); any width (layers.semantic_attention)."""
-        return layers.semantic_attention(M, self.w_omega, self.b_omega, self.u_omega)
+        h, self._fold_handover = self._fold_handover, None
+        tail = h[1] if (h is not None and h[0] is M) else None      # M itself, straight from node_level()
+        return layers.semantic_attention(M, self.w_omega, self.b_omega, self.u_omega, tail=tail)
 
     def classify(self, Z):
         """models/gat.py:65-72: logits (N,C) = mean over the output heads of Z Wc[h] + bc[h]."""

@@ -180,6 +180,7 @@ class LayerRun:
     overlap: object = None            # trainer._EvalBranch riding in this call's fork / join sections
     coef_sink: list | None = None     # receives per meta-path the coefficients of this call as data -- (E,K), or their
     coef_mean: bool = False           # head mean (E,) with coef_mean (return_coef of layers.py:43-44 / models/gat.py:143-172; single GPU only)
+    fold_sink: list | None = None     # HeteGAT_multi.fold_k3: receives this call's FoldTail when its row-local backward may run in the K3 backward
 
     @functools.cached_property
     def multi(self) -> bool:
@@ -220,6 +221,32 @@ class LayerRun:
         if masked and self.masked_bwd is not None and self.masked_bwd[p] is not None:
             return self.masked_bwd[p], "bm"      # opt-in: only the live rows are read / travel
         return self._source(self.plans_b, p, graph_t), "b"
+
+
+class FoldTail:
+    """Hand-over between NodeLevelAttention and SemanticAttention when M goes from the one straight into the other
+    (HeteGAT_multi.fold_k3): the K3 backward then runs the row-local half of the K2 backward of every meta-path in its
+    epilogue (ops.sem_attn_bwd_rows) -- dM is never written or read back -- and leaves the [g | stats] tables, df1 and dc
+    here for NodeLevelAttention.backward, which goes on from the exchange of the tables.  Valid only while M has no
+    other consumer: NodeLevelAttention.backward raises when the gradient it receives is not the placeholder the K3
+    backward returned (_no_grad_of) -- autograd has then added another consumer's gradient to it."""
+    __slots__ = ("saved", "c", "dc", "act", "K", "FP", "gs", "df1")
+
+    def __init__(self, saved, c, dc, act, K, FP):
+        self.saved, self.c, self.dc, self.act, self.K, self.FP = saved, c, dc, act, K, FP
+        self.gs = self.df1 = None      # filled by SemanticAttention.backward
+
+
+_ZERO: dict = {}
+
+
+def _no_grad_of(M):
+    """The gradient a folded K3 backward returns for M: zeros that take no memory and no launch (one cached scalar per
+    device, expanded); NodeLevelAttention.backward does not read it."""
+    z = _ZERO.get(M.device)
+    if z is None:
+        z = _ZERO[M.device] = torch.zeros((), dtype=M.dtype, device=M.device)
+    return z.expand(M.shape)
 
 
 class _SavedPath(NamedTuple):
@@ -387,6 +414,11 @@ class NodeLevelAttention(torch.autograd.Function):
         # their results there and autograd gets None (no copy / accumulate launches)
         plist = (W, a1, b1, a2, b2, c) + ((Wr, br) if Wr is not None else ())
         ctx.direct = tuple(p.grad for p in plist) if all(_direct(p) for p in plist) else None
+        ctx.tail = None
+        if (run.fold_sink is not None and train and W.is_cuda and Wr is None and run.streams is None
+                and tdt == torch.float32):
+            ctx.tail = FoldTail(saved, c, ctx.direct[5] if ctx.direct is not None else None, run.act, K, FP)
+            run.fold_sink.append(ctx.tail)
         # M, the output, is backward state too (the pre-activation is recovered from it): saved through autograd, so
         # that an in-place change of M between forward and backward raises instead of giving wrong gradients
         ctx.save_for_backward(W, a1, b1, a2, b2, c, *((Wr,) if Wr is not None else ()), *((M,) if train else ()))
@@ -404,7 +436,14 @@ class NodeLevelAttention(torch.autograd.Function):
         dbr = torch.empty_like(c) if Wr is not None else None
         P = len(graphs)
         K, FP = a1.shape[1], a1.shape[2]
-        dM = dM.contiguous()
+        tail, ctx.tail = ctx.tail, None
+        folded = tail is not None and tail.gs is not None      # the K3 backward has run the row-local half (FoldTail)
+        if folded:
+            if dM.data_ptr() != _no_grad_of(dM).data_ptr() or any(dM.stride()):
+                raise RuntimeError("fold_k3: M has a consumer besides semantic(); its gradient cannot be folded into the K3 "
+                                   "backward (set model.fold_k3 = False for free-form use of the model)")
+        else:
+            dM = dM.contiguous()
         graphs_t = run.transposed(graphs)
         in_drop, coef_drop, row_offset, seed_dev = run.drop_in, run.drop_coef, run.row_offset, run.seed_dev
         direct = ctx.direct
@@ -415,7 +454,7 @@ class NodeLevelAttention(torch.autograd.Function):
             dW = torch.empty_like(W)
             da1, da2 = torch.empty_like(a1), torch.empty_like(a2)
             db1, db2 = torch.empty_like(b1), torch.empty_like(b2)
-            dc = torch.empty_like(c)
+            dc = tail.dc if folded else torch.empty_like(c)
         dXin = None
         if ctx.xin_shape is not None and ctx.needs_input_grad[0]:
             dXin = torch.empty(ctx.xin_shape, dtype=torch.float32, device=W.device)
@@ -430,6 +469,10 @@ class NodeLevelAttention(torch.autograd.Function):
 
         def rows_path(p):      # row-local halves first; their tables go out while we continue
             sv = ctx.saved_per_p[p]
+            if folded:
+                src, kind = srcs[p]
+                rows[p] = (src.exchange(tail.gs[p], run.tag(kind, p)), tail.df1[p])
+                return
             gs, df1, dcp = ops.node_attn_bwd_rows(dM[:, p, :], Mout[:, p, :], sv.aggp, sv.tsum, sv.f1, sv.lse, c[p],
                                                   activation=run.act, K=K, FP=FP,
                                                   table_dtype=sv.H.dtype, res=sv.R, dc_out=dc[p])
@@ -630,9 +673,12 @@ class SemanticAttention(torch.autograd.Function):
     """K3: M (N,P,D) -> (Z (N,D), beta (N,P)); utils/layers.py:152-159."""
 
     @staticmethod
-    def forward(ctx, M, w_omega, b_omega, u_omega):
+    def forward(ctx, M, w_omega, b_omega, u_omega, *tail):
+        """tail: nothing, or the FoldTail of the NodeLevelAttention call whose output M is (semantic_attention)."""
         M = M.contiguous()
         Z, beta = ops.sem_attn_fwd(M, w_omega, b_omega, u_omega)
+        ctx.n_tail = len(tail)
+        ctx.tail = tail[0] if tail else None
         ctx.set_materialize_grads(False)      # no zero-filled gradient for beta (a fill launch per step)
         plist = (w_omega, b_omega, u_omega)
         ctx.direct = tuple(p.grad for p in plist) if all(_direct(p) for p in plist) else None
@@ -645,10 +691,23 @@ class SemanticAttention(torch.autograd.Function):
         M, w, b, u, beta = ctx.saved_tensors
         if dZ is None:
             dZ = torch.zeros((M.shape[0], M.shape[2]), dtype=M.dtype, device=M.device)
+        tail, ctx.tail = ctx.tail, None
+        none = (None,) * ctx.n_tail
+        if tail is not None:      # the row-local K2 backward in this kernel's epilogue; None: not a shape of the fused kernel
+            dc = tail.dc if tail.dc is not None else torch.empty_like(tail.c)
+            r = ops.sem_attn_bwd_rows(M, w, b, u, beta, dZ.contiguous(),
+                                      [(sv.aggp, sv.tsum, sv.f1, sv.lse) for sv in tail.saved], tail.c.contiguous(), dc,
+                                      activation=tail.act, K=tail.K, FP=tail.FP, table_dtype=tail.saved[0].H.dtype,
+                                      out=ctx.direct)
+            if r is not None:
+                tail.gs, tail.df1, tail.dc = r[0], r[1], dc
+                if ctx.direct is not None:
+                    return (_no_grad_of(M), None, None, None) + none
+                return (_no_grad_of(M),) + tuple(r[2:]) + none
         dM, dw, db, du = ops.sem_attn_bwd(M, w, b, u, beta, dZ.contiguous(), out=ctx.direct)
         if ctx.direct is not None:
-            return dM, None, None, None
-        return dM, dw, db, du
+            return (dM, None, None, None) + none
+        return (dM, dw, db, du) + none
 
 
 class ClassifierLoss(torch.autograd.Function):
@@ -724,7 +783,7 @@ def _pad_to(n: int) -> int:
     return 64 * ((n + 63) // 64)
 
 
-def semantic_attention(M, w_omega, b_omega, u_omega):
+def semantic_attention(M, w_omega, b_omega, u_omega, tail=None):
     """utils/layers.py:152-159 for any embedding width D and attention size A, always on the K3 kernels.
     Widths that are not multiples of 64 are zero-padded -- padded columns of w_omega / u_omega contribute
     tanh(.) * 0 = 0 to the scores and padded embedding columns are 0 -- which is exact.  D in {64, 128} with
@@ -732,8 +791,8 @@ def semantic_attention(M, w_omega, b_omega, u_omega):
     mp_att_size = 512, ...) the run-time-width kernels of sem_attn.hip (round 3: no torch branch is left)."""
     d, a = M.shape[2], w_omega.shape[1]
     dm, am = _pad_to(d), _pad_to(a)
-    if dm == d and am == a:
-        return SemanticAttention.apply(M.contiguous(), w_omega, b_omega, u_omega)
+    if dm == d and am == a:      # tail: M is the output of the NodeLevelAttention call that made it (FoldTail); padded, it is not
+        return SemanticAttention.apply(M.contiguous(), w_omega, b_omega, u_omega, *((tail,) if tail is not None else ()))
     Z, att = SemanticAttention.apply(
         torch.nn.functional.pad(M, (0, dm - d)), torch.nn.functional.pad(w_omega, (0, am - a, 0, dm - d)),
         torch.nn.functional.pad(b_omega, (0, am - a)), torch.nn.functional.pad(u_omega, (0, am - a)))

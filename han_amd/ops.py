@@ -740,6 +740,51 @@ def sem_attn_bwd(M, w_omega, b_omega, u_omega, beta, dZ, out=None, flags=0):
     return dM, dw, db, du
 
 
+def sem_attn_bwd_rows(M, w_omega, b_omega, u_omega, beta, dZ, paths, c, dc, activation=ACT_ELU, K=8, FP=8,
+                      table_dtype=torch.float32, out=None, flags=0, gs_out=None, df1_out=None):
+    """sem_attn_bwd with node_attn_bwd_rows of every meta-path in its epilogue, for an M (N,P,D) that is the K2 output
+    of P node_attn_fwd calls and has no other consumer: no dM.  paths: per meta-path (aggp, tsum, f1, lse) as
+    node_attn_bwd_rows takes them; c (P,D).  Returns (gs list, df1 list, dw, db, du) [dw, db, du written to the tensors
+    of `out` when given] and writes dc (P,D) -- or None, with nothing launched, when the library does not take the shape
+    (han_hip.h: han_sem_attn_bwd_rows decides, before any launch; the rule is written down there and nowhere else); the
+    caller then runs the two ops.  gs_out / df1_out: optional lists of P
+    preallocated destinations (N, row_bytes) uint8 / (N,K)."""
+    lib = _lib.load()
+    N, P, Dm = M.shape
+    A = w_omega.shape[1]
+    dev = M.device
+    _chk(M, "M", (N, P, Dm))
+    _chk(beta, "beta", (N, P), device=dev)
+    _chk(dZ, "dZ", (N, Dm), device=dev)
+    _chk(c, "c", (P, D), device=dev)
+    _chk(dc, "dc", (P, D), device=dev)
+    if len(paths) != P:
+        raise ValueError(f"paths: expected {P} entries, got {len(paths)}")
+    for aggp, tsum, f1, lse in paths:
+        for t, n, s in ((aggp, "aggp", (N, D)), (tsum, "tsum", (N, K)), (f1, "f1", (N, K)), (lse, "lse", (N, K))):
+            _chk(t, n, s, device=dev)
+    o = out if out is not None else (None,) * 3
+    dw = _out(o[0], "dw", tuple(w_omega.shape), dev)
+    db = _out(o[1], "db", tuple(b_omega.shape), dev)
+    du = _out(o[2], "du", tuple(u_omega.shape), dev)
+    _check_heads(K, FP)
+    rb = gs_row_bytes(K, FP, table_dtype)
+    gs = [torch.empty((N, rb), dtype=torch.uint8, device=dev) if gs_out is None else
+          _chk(gs_out[p], "gs_out", (N, rb), dtype=torch.uint8, device=dev) for p in range(P)]
+    df1 = [_out(None if df1_out is None else df1_out[p], "df1_out", (N, K), dev) for p in range(P)]
+    ws = _ws(lib.han_sem_attn_bwd_rows_workspace(N, P, Dm, A), dev, "semrows")
+    arr = lambda ts: (ctypes.c_void_p * P)(*[t.data_ptr() for t in ts])
+    code = lib.han_sem_attn_bwd_rows(
+        M.data_ptr(), w_omega.data_ptr(), b_omega.data_ptr(), u_omega.data_ptr(), beta.data_ptr(), dZ.data_ptr(),
+        arr([p[0] for p in paths]), arr([p[1] for p in paths]), arr([p[2] for p in paths]), arr([p[3] for p in paths]),
+        c.data_ptr(), arr(gs), arr(df1), dw.data_ptr(), db.data_ptr(), du.data_ptr(), dc.data_ptr(), ws.data_ptr(),
+        ws.numel(), N, P, Dm, A, K, FP, DTYPE_CODE[table_dtype], int(activation), int(flags), _stream())
+    if code == _lib.E_UNSUPPORTED:
+        return None
+    _lib.check(code, "han_sem_attn_bwd_rows")
+    return gs, df1, dw, db, du
+
+
 # ------------------------------------------------------------- classifier + loss
 def _classifier_args(Z, Wc, bc):
     """The checks classifier_loss and classifier_bwd share; returns (N, device, HC, D, C)."""

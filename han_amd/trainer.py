@@ -112,6 +112,9 @@ class HANTrainer:
         every rank): the forward passes named by `replicate` ("auto" = dist.replication_policy,
         "all", "eval", "none") then project the whole table on every rank instead of exchanging it;
         `xs` may then be None (the local rows are views of xs_full).
+        The trainer sets model.direct_grads(True) and model.fold_k3 = True and leaves them set: both describe ITS step
+        (every parameter used once, M consumed by semantic() alone).  A model used free-form afterwards with another
+        consumer of M raises in the backward (layers.FoldTail); set model.fold_k3 = False for that.
         masked_backward: OPT-IN (never the default, never the headline measurement): with a single node-attention
         layer the backward row g_i of every destination outside `train_mask` is identically zero, so the
         transposed-graph pass skips those destinations in place (bit-identical results, dist.MaskedBackwardPlan)
@@ -121,6 +124,7 @@ class HANTrainer:
             raise RuntimeError("build the model first (model.build(...))")
         self.model = model
         model.direct_grads(True)      # gradients land in model.flat_grad without copy/accumulate launches
+        model.fold_k3 = True          # M goes from node_level() straight into semantic(): the K3 backward runs the row-local K2 backward too
         self.part = part if (part is not None and part.active) else None
         layers._no_sparse_under_partition(self.part is not None or xs_full is not None, xs, xs_full)
         model.partition = self.part

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HAN_ABI_VERSION 14
+#define HAN_ABI_VERSION 15
 
 #define HAN_E_BADARG   (-1)   /* null pointer, negative size, inconsistent shape.  The forward
                               * entry points return 0 at once for N == 0 (empty tensors may
@@ -383,6 +383,23 @@ int han_sem_attn_bwd(const float *M, const float *w_omega, const float *b_omega,
                      const float *u_omega, const float *beta, const float *dZ, float *dM,
                      float *dw_omega, float *db_omega, float *du_omega, void *workspace,
                      size_t workspace_bytes, int64_t N, int P, int D, int A, int flags, void *stream);
+
+/* han_sem_attn_bwd with the row-local step of the K2 backward (han_node_attn_bwd_rows) of all P meta-paths in its
+ * epilogue, for an M that is the K2 output itself: row (n, p) of M is the output row n of meta-path p's
+ * han_node_attn_fwd, and nothing else consumes M.  dM is not written.  aggp, tsum, f1, lse, gs and df1 are HOST
+ * arrays of P DEVICE pointers, each as han_node_attn_bwd_rows takes it (gs: fp32 rows of han_gs_row_bytes(8, 8,
+ * HAN_DTYPE_F32) bytes); c (P,D) and dc (P,D) hold all meta-paths.  g, f1, lse, s and df1 are the bits the two
+ * calls give; dc is the same sum in another order.
+ * HAN_E_UNSUPPORTED, before any launch, unless D == 64, A in {64, 128}, P in {1, 2, 4}, N * P >= 65 536, K == 8,
+ * FP == 8, table_dtype == HAN_DTYPE_F32, activation is HAN_ACT_ELU or HAN_ACT_IDENTITY and flags holds none of
+ * HAN_FLAG_K3_EXACT_PIPE, HAN_FLAG_K3_PAIRS, HAN_FLAG_K3_G3_F32: the caller then runs the two calls.            */
+size_t han_sem_attn_bwd_rows_workspace(int64_t N, int P, int D, int A);
+int han_sem_attn_bwd_rows(const float *M, const float *w_omega, const float *b_omega, const float *u_omega,
+                          const float *beta, const float *dZ, const float *const *aggp, const float *const *tsum,
+                          const float *const *f1, const float *const *lse, const float *c, void *const *gs,
+                          float *const *df1, float *dw_omega, float *db_omega, float *du_omega, float *dc,
+                          void *workspace, size_t workspace_bytes, int64_t N, int P, int D, int A, int K, int FP,
+                          int table_dtype, int activation, int flags, void *stream);
 
 /* ---- classifier + masked loss ----------------------------------------------
  * models/gat.py:65-72: logits = (1/HC) sum_h (Z Wc[h] + bc[h]);  Wc (HC,D,C).
