@@ -5,7 +5,7 @@ full-graph with early stopping, restore the best weights, report the test metric
 KNN / KMeans scores of ``final_embed``.
 
     python examples/ex_acm3025.py [--mat ACM3025.mat] [--epochs 200] [--graph] [--eval-device gpu] [--sparse-features]
-                                  [--batch-size B]
+                                  [--batch-size B [--fanout 10 | --fanout 10,5]]
 
 Hyper-parameters are the reference's (ex_acm3025.py:16-31): lr 0.005, l2 0.001,
 hid_units [8], n_heads [8, 1], dropout 0.6/0.6, patience 100, mp_att_size 128.
@@ -42,6 +42,9 @@ def main():
     ap.add_argument("--batch-size", type=int, default=None, metavar="B",
                     help="train in mini-batches of B training nodes on the ego block of each batch "
                          "(han_amd.minibatch.MiniBatchTrainer) instead of one full-graph step per epoch")
+    ap.add_argument("--fanout", default=None, metavar="F[,F...]",
+                    help="with --batch-size: sample every step's block afresh, at most F neighbours per row and "
+                         "meta-path (one number, or one per node-attention layer: the seeds' rows first)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eval-device", choices=("cpu", "gpu"), default="cpu",
                     help="where final_embed is scored: cpu = scikit-learn on the host, as the reference; gpu = the "
@@ -87,11 +90,21 @@ def main():
           f"edges {[g.nnz for g in graphs]}")
 
     model = HeteGAT_multi().build(len(graphs), ft, nb_classes, (8,), (8, 1), 128, device=dev)
+    fanout = None
+    if args.fanout is not None:
+        if args.batch_size is None:
+            ap.error("--fanout samples the blocks of --batch-size")
+        try:
+            fanout = [int(v) for v in args.fanout.split(",")]
+        except ValueError:
+            ap.error(f"--fanout {args.fanout}: expected F or F,F,...")
+        fanout = fanout[0] if len(fanout) == 1 else fanout
     if args.batch_size is not None:
         if args.graph:
             ap.error("--batch-size: the block shapes change per batch, there is no epoch to capture (--graph)")
         tr = MiniBatchTrainer(model, xs, graphs, labels, masks[0], masks[1], batch_size=args.batch_size, lr=0.005,
-                              l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6, seed=args.seed, patience=args.patience)
+                              l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6, seed=args.seed, patience=args.patience,
+                              fanout=fanout)
         tr.overlap_eval = False
     else:
         tr = HANTrainer(model, xs, graphs, labels, masks[0], masks[1], lr=0.005, l2_coef=0.001,

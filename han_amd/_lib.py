@@ -103,6 +103,9 @@ SIGNATURES = {
     "han_ego_expand": (c_int, [P, P, I64, c_int, I64, I64, P, P, P, P, P, P]),
     "han_ego_count": (c_int, [P, P, P, c_int, I64, I64, P, P]),
     "han_ego_fill": (c_int, [P, P, P, P, P, c_int, P, I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P]),
+    "han_ego_sample_expand": (c_int, [P, P, I64, c_int, c_int, c_uint64, c_int, I64, I64, P, P, P, P, P, P]),
+    "han_ego_sample_count": (c_int, [P, P, c_int, P, I64, I64, P, P]),
+    "han_ego_sample_fill": (c_int, [P, P, P, P, P, c_int, P, I64, I64, c_uint64, c_int, I64, I64, P, P, P, P, P, P, P]),
     "han_knn_topk_workspace": (c_size_t, [I64, I64, c_int, c_int]),
     "han_knn_topk": (c_int, [P, I64, P, I64, P, P, P, c_size_t, I64, I64, c_int, c_int, P]),
     "han_knn_vote": (c_int, [P, P, P, I64, c_int, I64, P]),

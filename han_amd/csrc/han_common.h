@@ -30,7 +30,11 @@ typedef float float4_t __attribute__((ext_vector_type(4)));
 //             (2 + 4 * slice: the column slices of a head wider than 64 columns)
 //   stream 3  meta-path random walks (metapath.hip)  a = global start node, b = walk * ceil(L/2) + hop/2,
 //             word x for an even hop, y for an odd one (one 32-bit draw per hop, not a 16-bit field)
+//   stream 4 (p + 1)  sampled ego blocks (ego_block.hip), graph p: a = global row, b = stored position in the row,
+//             word x is the entry's sort key (a 32-bit draw).  The streams that are multiples of 4, from 4 on, are
+//             this family's; 2 + 4 * slice stays clear of them.
 // ---------------------------------------------------------------------------
+#define HAN_STREAM_EGO 4u
 #define HAN_STREAM_SEQ 0u
 #define HAN_STREAM_COEF 1u
 #define HAN_STREAM_FTS 2u

@@ -13,7 +13,10 @@ full-graph outputs, with the model code unchanged::
     logits, embed, att = model.forward([blk.take(x)] * P, blk.graphs)      # rows blk.seed_pos answer the seeds
 
 :func:`predict` runs eval inference block by block, :class:`MiniBatchTrainer` the training step of ``HANTrainer`` on
-the block of each batch.  Fan-out is bounded beforehand (``metapath_graph(top_k=)``, ``metapath_sample(fanout=)``).
+the block of each batch.  Fan-out can be bounded beforehand (``metapath_graph(top_k=)``, ``metapath_sample(fanout=)``:
+one deterministic cut of the graph) or per block: ``ego_block(..., fanout=f, seed=s)`` keeps in every row closer than
+``hops`` its self entries and a random ``f`` of its other entries, drawn on the GPU, so a block holds at most
+``B * prod(P * f)`` nodes whatever the degrees are, and every training step sees another subset.
 """
 from __future__ import annotations
 
@@ -71,11 +74,34 @@ def _host_seeds(seeds, n):
     return s
 
 
-def _check_block_args(graphs, seeds, hops):
-    """Everything ego_block can refuse without a device: (graphs, n, host seeds or None for a device tensor)."""
+def _is_int(x) -> bool:
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def _check_fanout(fanout, hops: int):
+    """None, or the fan-out of every level 0 .. hops - 1 as a list of ints >= 1."""
+    if fanout is None:
+        return None
+    fan = list(fanout) if isinstance(fanout, (list, tuple, np.ndarray)) else [fanout] * hops
+    if len(fan) != hops:
+        raise ValueError(f"fanout = {fanout!r}: expected one bound per level, {hops} for hops = {hops}")
+    for f in fan:
+        if not _is_int(f) or f < 1:
+            raise ValueError(f"fanout = {fanout!r}: expected an integer >= 1 or a sequence of {hops} of them")
+        if f > 2 ** 31 - 1:
+            raise ValueError(f"fanout = {fanout!r}: beyond int32")
+    return [int(f) for f in fan]
+
+
+def _check_block_args(graphs, seeds, hops, fanout=None, seed=0):
+    """Everything ego_block can refuse without a device: (graphs, n, host seeds or None for a device tensor, the
+    fan-out per level or None)."""
     graphs = list(graphs)
     if isinstance(hops, bool) or int(hops) != hops or hops < 1:
         raise ValueError(f"hops = {hops!r}: expected an integer >= 1")
+    fan = _check_fanout(fanout, int(hops))
+    if not _is_int(seed):
+        raise ValueError(f"seed = {seed!r}: expected an integer")
     if not graphs:
         raise ValueError("ego_block: no graphs")
     for p, g in enumerate(graphs):
@@ -105,10 +131,10 @@ def _check_block_args(graphs, seeds, hops):
         ops.require_gpu(seeds, "seeds")
         if seeds.device != dev:
             raise ValueError(f"seeds on {seeds.device}, the graphs on {dev}")
-    return graphs, n, host
+    return graphs, n, host, fan
 
 
-def ego_block(graphs, seeds, hops: int = 1) -> EgoBlock:
+def ego_block(graphs, seeds, hops: int = 1, fanout=None, seed: int = 0) -> EgoBlock:
     """The block of `seeds` (B >= 1 distinct node ids; an int32 / int64 tensor on the graphs' GPU, or a host array)
     in P square CSRGraphs over the same N nodes on one GPU (values optional, row_base 0), for a model of `hops` >= 1
     node-attention layers: see EgoBlock and the module docstring.  Raises ValueError, before any launch, for repeated,
@@ -120,8 +146,21 @@ def ego_block(graphs, seeds, hops: int = 1) -> EgoBlock:
     whatever B, N, P and hops are -- n_b with the node list, then the P entry counts in one read -- and one more when
     the seeds come as a device tensor (their range and distinctness, in one read).  Rows longer than CHUNK entries
     are served by the input graph's own chunk table (CSRGraph.row_split), built on a graph's first block and cached
-    with it.  Bitwise reproducible: integer stores only, every writer of a word writes the same value."""
-    graphs, n, host = _check_block_args(graphs, seeds, hops)
+    with it.  Bitwise reproducible: integer stores only, every writer of a word writes the same value.
+
+    `fanout` (None: the rule above, exactly) samples the rows: an int >= 1, or one per level 0 .. hops - 1 (seeds are
+    level 0).  A row at level l < hops keeps its self entries (column == row; they do not count) and, of its d other
+    entries, all when d <= fanout[l], else the fanout[l] of smallest (x, k): k the stored position in the row, x the
+    first word of han_rand64(seed, stream 4 (p + 1), row, k) for graph number p (tests/rng_ref.py restates the hash;
+    `seed` is taken mod 2^64).  Kept entries stay in stored order with their stored values, repeated entries are
+    entries of their own, and levels are breadth-first over the sampled rows.  The block is therefore, bit for bit,
+    ego_block(G', seeds, hops) of the graphs G' whose rows closer than hops are their selected entries -- the rows
+    seed_pos of a model's outputs on it are the rows `seeds` of full-graph inference on G'.  Values are NOT reweighted
+    (no importance weights): the attention softmax renormalises over the entries a row keeps.  Ties of x are decided
+    exactly; the same (graphs, seeds, hops, fanout, seed) give the same block, bit for bit; the host reads stay as
+    above.  Launches: hops x P han_ego_sample_expand, then han_ego_sample_count / han_ego_sample_fill per graph; a
+    row beyond CHUNK entries is served by a 256-thread workgroup."""
+    graphs, n, host, fan = _check_block_args(graphs, seeds, hops, fanout, seed)
     hops, P, dev = int(hops), len(graphs), graphs[0].device
     if host is not None:
         s = torch.as_tensor(host).to(dev)
@@ -136,16 +175,23 @@ def ego_block(graphs, seeds, hops: int = 1) -> EgoBlock:
     splits = [g.row_split(CHUNK, CHUNK) for g in graphs]
     level = torch.full((n,), -1, dtype=torch.int32, device=dev)
     level[s] = 0
+    dec = [ops.ego_sample_decision(g) for g in graphs] if fan is not None else None
     for h in range(hops):
-        for g, sp in zip(graphs, splits):
-            ops.ego_expand(g, level, h, sp)
+        for p, (g, sp) in enumerate(zip(graphs, splits)):
+            if fan is None:
+                ops.ego_expand(g, level, h, sp)
+            else:
+                ops.ego_sample_expand(g, level, h, fan[h], seed, p, dec[p], sp)
     nodes = torch.nonzero(level >= 0).flatten()                               # host read 1: n_b
     n_b = nodes.numel()
     local = torch.full((n,), -1, dtype=torch.int32, device=dev)
     local[nodes] = torch.arange(n_b, dtype=torch.int32, device=dev)
     counts = torch.empty(P * n_b, dtype=torch.int64, device=dev)
     for p, g in enumerate(graphs):
-        ops.ego_count(g.rowptr, nodes, counts[p * n_b:(p + 1) * n_b], level, hops)
+        if fan is None:
+            ops.ego_count(g.rowptr, nodes, counts[p * n_b:(p + 1) * n_b], level, hops)
+        else:
+            ops.ego_sample_count(nodes, counts[p * n_b:(p + 1) * n_b], level, hops, dec[p])
     ptr = csr.scan(counts)                                                    # the P row pointers end to end
     offs = ptr[::n_b].tolist()                                                # host read 2: the P entry counts
     out = []
@@ -154,8 +200,10 @@ def ego_block(graphs, seeds, hops: int = 1) -> EgoBlock:
         rowptr = ptr[p * n_b:(p + 1) * n_b + 1] - offs[p]
         colidx = torch.empty(nnz, dtype=torch.int32, device=dev)
         values = torch.empty(nnz, dtype=torch.float32, device=dev) if g.values is not None else None
-        if nnz:
+        if nnz and fan is None:
             ops.ego_fill(g.rowptr, g.colidx, g.values, nodes, n, rowptr, colidx, values, level, hops, local, sp)
+        elif nnz:
+            ops.ego_sample_fill(g, nodes, rowptr, colidx, values, level, hops, local, seed, p, dec[p], sp)
         out.append(CSRGraph(rowptr, colidx, n_b, validate=False, values=values))
     return EgoBlock(nodes=nodes, level=level[nodes], seed_pos=local[s].long(), graphs=out, n=n)
 
@@ -189,12 +237,15 @@ def _take_each(blk: EgoBlock, xs):
     return [done[id(x)] if id(x) in done else done.setdefault(id(x), blk.take(x)) for x in xs]
 
 
-def predict(model, xs, graphs, rows=None, batch_size: int = 4096):
+def predict(model, xs, graphs, rows=None, batch_size: int = 4096, fanout=None, seed: int = 0):
     """Eval inference of the nodes `rows` (default: all N; a 1-D integer tensor or array, repeats allowed), block by
     block: (logits (R, C), final_embed (R, D_out), att_val (R, P)) of exactly those rows, in their order -- the rows
     a full-graph model.inference returns for them.  hops is the model's node-attention layer count; the distinct
-    rows are served in ascending batches of `batch_size` seeds, so peak memory follows the block, not N."""
+    rows are served in ascending batches of `batch_size` seeds, so peak memory follows the block, not N.  With
+    `fanout` set (ego_block's fanout / seed) every block is sampled: APPROXIMATE inference -- the exact outputs of the
+    graphs thinned to each block's selected entries, not those of the full graphs."""
     xs, graphs = _inputs(model, xs, graphs)
+    _check_fanout(fanout, _model_hops(model))
     if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
         raise ValueError(f"batch_size = {batch_size!r}: expected an integer >= 1")
     dev, n, hops = model.flat.device, graphs[0].n_rows, _model_hops(model)
@@ -207,7 +258,7 @@ def predict(model, xs, graphs, rows=None, batch_size: int = 4096):
         uniq, inverse = torch.unique(r.to(device=dev, dtype=torch.int64), return_inverse=True)
     outs = ([], [], [])
     for b0 in range(0, uniq.numel(), int(batch_size)):
-        blk = ego_block(graphs, uniq[b0:b0 + int(batch_size)], hops)
+        blk = ego_block(graphs, uniq[b0:b0 + int(batch_size)], hops, fanout, seed)
         with torch.no_grad():
             M = model.node_level(_take_each(blk, xs), blk.graphs, 0.0, 0.0, False, ops.ACT_ELU)
             Z, att = model.semantic(M)
@@ -231,6 +282,13 @@ def epoch_batches(ids, batch_size: int, seed: int, epoch: int):
     return [order[b0:b0 + int(batch_size)] for b0 in range(0, ids.size, int(batch_size))]
 
 
+def block_seed(seed: int, step: int) -> int:
+    """The ego_block seed of training step `step` of a trainer seeded `seed`: splitmix64(splitmix64(seed) + step),
+    mod 2^64."""
+    m = (1 << 64) - 1
+    return rng._splitmix64((rng._splitmix64(int(seed) & m) + int(step)) & m)
+
+
 class MiniBatchTrainer:
     """The training loop of HANTrainer on ego blocks: an epoch visits the training nodes once, in batches
     (epoch_batches), and every batch is one step of HANTrainer.train_step on the block of its seeds -- node_level
@@ -238,15 +296,19 @@ class MiniBatchTrainer:
     the trainer and the model code as they are.  Dropout draws are keyed by LOCAL node id: another, equally valid
     assignment than the full graph's (as under reorder's relabelling).  The dropout seed stream is the trainer's own
     (started from `seed`), so two trainers with equal seeds and equal initial parameters stay bit-equal.  Single
-    process, eager (the shapes change per batch: nothing to capture)."""
+    process, eager (the shapes change per batch: nothing to capture).  `fanout` (ego_block's) samples every step's
+    block afresh: the block seed of a step is block_seed(seed, steps done) -- splitmix64, apart from the dropout seed
+    stream, which it does not consume: fanout=None, and a fan-out no degree exceeds, train bit for bit alike.
+    evaluate() stays exact (unsampled blocks)."""
 
     def __init__(self, model, xs, graphs, labels, train_mask, val_mask=None, batch_size: int = 1024, lr=0.005,
-                 l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6, seed: int = 0, patience: int = 100):
+                 l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6, seed: int = 0, patience: int = 100, fanout=None):
         self.model = model
         self.xs, self.graphs = _inputs(model, xs, graphs)
         model.direct_grads(True)
         dev = model.flat.device
         self.hops = _model_hops(model)
+        self.fanout, self.steps_done = _check_fanout(fanout, self.hops), 0
         self.labels = labels.to(device=dev, dtype=torch.int32).contiguous()
         self.train_mask = train_mask.to(device=dev, dtype=torch.uint8).contiguous()
         self.val_mask = (val_mask if val_mask is not None else train_mask).to(device=dev, dtype=torch.uint8).contiguous()
@@ -271,7 +333,8 @@ class MiniBatchTrainer:
     def train_step(self, seeds):
         """One optimiser step on the block of `seeds`; returns device scalars (loss, accuracy) over the seeds."""
         m = self.model
-        blk = ego_block(self.graphs, seeds, self.hops)
+        blk = ego_block(self.graphs, seeds, self.hops, self.fanout, block_seed(self.seed, self.steps_done))
+        self.steps_done += 1
         xs = _take_each(blk, self.xs)
         labels = blk.take(self.labels)
         mask = torch.zeros(blk.nodes.numel(), dtype=torch.uint8, device=labels.device)

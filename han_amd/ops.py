@@ -1111,6 +1111,56 @@ def ego_fill(rowptr, colidx, values, rows, n_cols, out_rowptr, out_colidx, out_v
         _ptr_nonempty(out_colidx), _ptr_nonempty(out_values), _stream()), "han_ego_fill")
 
 
+def _long_list_arg(split):
+    """The long-row list of the han_ego_sample_* entry points from CSRGraph.row_split's dict (None: no long row)."""
+    if split is None:
+        return (0, 0, None)
+    return (split["split_deg"], split["n_long"], split["long_rows"].data_ptr())
+
+
+def ego_sample_decision(graph: CSRGraph):
+    """(thr uint32 as int32 storage, need int32, kept int64), each (n,): the per-row decisions han_ego_sample_expand
+    writes for the rows it expands.  Uninitialised -- but kept is zeroed for a graph without entries, which the entry
+    point leaves alone."""
+    n, dev = graph.n_rows, graph.device
+    kept = (torch.zeros if graph.nnz == 0 else torch.empty)(n, dtype=torch.int64, device=dev)
+    return (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev), kept)
+
+
+def ego_sample_expand(graph: CSRGraph, level: torch.Tensor, h: int, fanout: int, seed: int, p: int, decision,
+                      split=None):
+    """ego_expand over the sampled entries of graph number `p`: every row with level == h keeps its self entries and
+    the `fanout` other entries of smallest (key, stored position) (include/han_hip.h), stores that decision and writes
+    h + 1 into the level of the unvisited columns it kept."""
+    _chk(level, "level", (graph.n_rows,), dtype=torch.int32, device=graph.device)
+    thr, need, kept = decision
+    _lib.check(_lib.load().han_ego_sample_expand(
+        graph.rowptr.data_ptr(), _ptr_nonempty(graph.colidx), graph.n_rows, int(h), int(fanout),
+        int(seed) & ((1 << 64) - 1), int(p), *_long_list_arg(split), level.data_ptr(), thr.data_ptr(), need.data_ptr(),
+        kept.data_ptr(), _stream()), "han_ego_sample_expand")
+
+
+def ego_sample_count(rows: torch.Tensor, counts: torch.Tensor, level: torch.Tensor, hops: int, decision):
+    """counts[r] = the entries of sampled block row r: the stored kept count where level[rows[r]] < hops, else 1."""
+    _chk(rows, "rows", dtype=torch.int64, device=level.device)
+    _chk(counts, "counts", (rows.numel(),), dtype=torch.int64, device=level.device)
+    _lib.check(_lib.load().han_ego_sample_count(_ptr_nonempty(rows), level.data_ptr(), int(hops),
+                                                decision[2].data_ptr(), level.numel(), rows.numel(),
+                                                _ptr_nonempty(counts), _stream()), "han_ego_sample_count")
+
+
+def ego_sample_fill(graph: CSRGraph, rows, out_rowptr, out_colidx, out_values, level, hops: int, local, seed: int,
+                    p: int, decision, split=None):
+    """The rows counted by ego_sample_count: the kept entries of row rows[r] in stored order, columns through `local`;
+    (r, r) on the rim; out_values None or (nnz,) fp32."""
+    thr, need, _ = decision
+    _lib.check(_lib.load().han_ego_sample_fill(
+        graph.rowptr.data_ptr(), _ptr_nonempty(graph.colidx), _ptr_nonempty(graph.values), _ptr_nonempty(rows),
+        level.data_ptr(), int(hops), local.data_ptr(), graph.n_rows, rows.numel(), int(seed) & ((1 << 64) - 1), int(p),
+        *_long_list_arg(split), thr.data_ptr(), need.data_ptr(), out_rowptr.data_ptr(), _ptr_nonempty(out_colidx),
+        _ptr_nonempty(out_values), _stream()), "han_ego_sample_fill")
+
+
 # ------------------------------------------------- evaluation of the embeddings
 KNN_MAX_K = 16             # neighbours per query of han_knn_topk
 EVAL_MAX_D = 512           # embedding width of han_knn_topk / han_kmeans_step

@@ -593,6 +593,42 @@ int han_ego_fill(const int64_t *rowptr, const int32_t *colidx, const float *valu
                  const int64_t *chunk_start, const int64_t *chunk_end, const int64_t *out_rowptr, int32_t *out_colidx,
                  float *out_values, void *stream);
 
+/* ---- K0: sampled ego blocks (added under ABI 15: new entry points only, nothing existing changed) ----
+ * The same block with a random fan-out: a row keeps its self entries (column == row) and at most `fanout` of its
+ * other entries.  The key of the entry at stored position k of row v of graph `graph` is the first word x of
+ * han_rand64(seed, stream 4 * (graph + 1), a = v, b = k) (csrc/han_common.h; tests/rng_ref.py).  A row with d <= fanout
+ * entries off the diagonal keeps them all; otherwise it keeps the `fanout` entries of smallest (x, k) -- equal keys go
+ * to the smaller stored position.  Kept entries stay in stored order with their values (no reweighting), repeated
+ * entries are entries of their own.  Rows of up to 2^31 - 1 entries.  Integer stores only, all writers of a word write
+ * the same value: bitwise the same from run to run.
+ * The long-row list (split_deg, n_long, long_rows) is han_row_split_t's of the INPUT graph: the rows with more than
+ * split_deg entries, a 256-thread workgroup each; every other row is served by a wave.  n_long == 0 (pointer may be
+ * NULL): every row by a wave.  Not checked: that the list describes rowptr.
+ * han_ego_sample_expand: one hop over one graph, as han_ego_expand, over the SELECTED entries: every row i with
+ *   level[i] == h is decided -- thr[i] (the fanout-th smallest key), need[i] (entries equal to thr still kept, in
+ *   stored order; -1: the whole row is kept) and kept[i] (entries of the sampled row), arrays of n elements that are
+ *   written and read for expanded rows only -- and writes h + 1 into the level of the unvisited columns of its
+ *   selected entries.  fanout may differ from hop to hop; a row is expanded once, at the hop of its level.
+ * han_ego_sample_count: counts[r] = kept[rows[r]] where 0 <= level[rows[r]] < hops, 1 on the rim, 0 for a row outside
+ *   [0, n_in).
+ * han_ego_sample_fill: the rows counted above from the stored decision and the keys drawn again; columns through
+ *   local (int32 over n_in), a rim row holds (r, r) alone; out_values (or NULL): the values, 1.0 on the rim and where
+ *   values == NULL.  local must invert rows on the kept rows.  No store lands at or beyond out_rowptr[r + 1].
+ * HAN_E_BADARG, before any launch: a NULL rowptr / level / thr / need / kept / local / rows / counts / out_rowptr /
+ * out_colidx, a negative size, n / n_in / n_out beyond INT32_MAX, fanout < 1, hops < 1, h < 0, graph < 0, a long-row
+ * list without its array or with split_deg < 1.  n == 0, a NULL colidx (no entries: the caller zeroes kept) and
+ * n_out == 0 return 0 and launch nothing.                                                                          */
+int han_ego_sample_expand(const int64_t *rowptr, const int32_t *colidx, int64_t n, int h, int fanout, uint64_t seed,
+                          int graph, int64_t split_deg, int64_t n_long, const int64_t *long_rows, int32_t *level,
+                          uint32_t *thr, int32_t *need, int64_t *kept, void *stream);
+int han_ego_sample_count(const int64_t *rows, const int32_t *level, int hops, const int64_t *kept, int64_t n_in,
+                         int64_t n_out, int64_t *counts, void *stream);
+int han_ego_sample_fill(const int64_t *rowptr, const int32_t *colidx, const float *values, const int64_t *rows,
+                        const int32_t *level, int hops, const int32_t *local, int64_t n_in, int64_t n_out,
+                        uint64_t seed, int graph, int64_t split_deg, int64_t n_long, const int64_t *long_rows,
+                        const uint32_t *thr, const int32_t *need, const int64_t *out_rowptr, int32_t *out_colidx,
+                        float *out_values, void *stream);
+
 /* ---- evaluation of the embeddings (ABI 9) -----------------------------------
  * The reference scores final_embed on the host with scikit-learn: my_KNN (jhyexp.py:20-51) and my_Kmeans
  * (jhyexp.py:54-86), called at ex_acm3025.py:288-289.  These entry points are the device side of both.

@@ -13,11 +13,18 @@ meta-path graphs, B seeds drawn from a seeded permutation, and `hops` layers:
   (c) training     MiniBatchTrainer.train_step on a batch of B next to HANTrainer.train_step on the whole graph
                    (dropout 0.6 / 0.6 on both).
 
+With --fanout F every (workload, B, hops) measures instead, in the same process and the same alternating windows, the
+SAMPLED block (ego_block(fanout=F, seed=): at most F neighbours per row, graph and hop, han_ego_sample_* kernels) next
+to the unsampled block and the full graph: extraction (sampled | whole), predict (sampled | whole | one full-graph eval
+forward) and the training step (sampled | whole | HANTrainer.train_step); the line also holds both blocks' sizes and
+whether entries <= kept rows x F + self entries + rim rows holds for every block graph.  Default --out then:
+profiles/r18_ego_sample_bench.jsonl.
+
 One JSON line per (workload, B, hops) with the block sizes (n_b, entries per graph) and median / min / max
 milliseconds over `reps` alternating windows after a warm-up; lines are appended as they are measured.
 
     python tools/ego_block_bench.py [--out profiles/r16_ego_block_bench.jsonl] [--workloads syn-1m,syn-1m-skew]
-                                    [--batches 1024,8192] [--hops 1,2] [--reps 5] [--n N] [--append]
+                                    [--batches 1024,8192] [--hops 1,2] [--reps 5] [--n N] [--append] [--fanout F]
 """
 import argparse
 import json
@@ -93,9 +100,57 @@ def timed(sides, reps, warmup=2):
             for k, v in ts.items()}
 
 
+def block_sizes(blk, hops):
+    return dict(n_b=int(blk.nodes.numel()), nnz=[g.nnz for g in blk.graphs], rim=int((blk.level == hops).sum()))
+
+
+def fanout_bound_holds(blk, hops, fanout):
+    """entries <= kept rows x fanout + self entries of the kept rows + one per rim row, for every block graph."""
+    kept = blk.level < hops
+    n_kept, n_rim = int(kept.sum()), int((~kept).sum())
+    ok = True
+    for g in blk.graphs:
+        rows = torch.repeat_interleave(torch.arange(g.n_rows, device=g.device), g.degrees())
+        n_self = int(((g.colidx == rows) & kept[rows]).sum())
+        ok = ok and g.nnz <= n_kept * fanout + n_self + n_rim
+    return bool(ok)
+
+
+def sampled_line(args, name, wl, model, full, full_eval, graphs, seeds, B, hops):
+    """The --fanout line of one (workload, B, hops): sampled block | unsampled block | full graph, one job."""
+    f, P = args.fanout, wl["p"]
+    xs, labels = [wl["x"]] * P, wl["labels"]
+    mini = {k: minibatch.MiniBatchTrainer(model, xs, graphs, labels, wl["train_mask"], wl["val_mask"], batch_size=B,
+                                          seed=1, fanout=fo) for k, fo in (("sampled", f), ("whole", None))}
+    blk = minibatch.ego_block(graphs, seeds, hops, fanout=f, seed=1)
+    sizes = dict(sampled=block_sizes(blk, hops), bound_holds=fanout_bound_holds(blk, hops, f))
+    reproducible = same_block(blk, minibatch.ego_block(graphs, seeds, hops, fanout=f, seed=1))
+    blk = minibatch.ego_block(graphs, seeds, hops)
+    sizes["whole"] = block_sizes(blk, hops)
+    del blk
+    t = {}
+    t.update({"extract_" + k: v for k, v in timed(
+        {"sampled": lambda: minibatch.ego_block(graphs, seeds, hops, fanout=f, seed=1),
+         "whole": lambda: minibatch.ego_block(graphs, seeds, hops)}, args.reps).items()})
+    t.update({"infer_" + k: v for k, v in timed(
+        {"sampled": lambda: minibatch.predict(model, full.xs, graphs, seeds, batch_size=B, fanout=f, seed=1),
+         "whole": lambda: minibatch.predict(model, full.xs, graphs, seeds, batch_size=B),
+         "full": full_eval}, args.reps).items()})
+    t.update({"train_" + k: v for k, v in timed(
+        {"sampled": lambda: mini["sampled"].train_step(seeds), "whole": lambda: mini["whole"].train_step(seeds),
+         "full": full.train_step}, args.reps).items()})
+    return dict(tool="ego_block_bench", mode="fanout", workload=name, N=wl["n"], P=P, B=B, hops=hops, fanout=f, **sizes,
+                full_nnz=[g.nnz for g in graphs], reproducible=reproducible, windows=args.reps, ms=t,
+                train_sampled_vs_whole=round(t["train_whole"]["median"] / t["train_sampled"]["median"], 3),
+                train_sampled_vs_full=round(t["train_full"]["median"] / t["train_sampled"]["median"], 3),
+                device=torch.cuda.get_device_name(0))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "r16_ego_block_bench.jsonl"))
+    ap.add_argument("--out", default=None, help="default: profiles/r16_ego_block_bench.jsonl, with --fanout "
+                                                "profiles/r18_ego_sample_bench.jsonl")
+    ap.add_argument("--fanout", type=int, default=None, help="measure sampled blocks of this fan-out per graph and hop")
     ap.add_argument("--workloads", default="syn-1m,syn-1m-skew")
     ap.add_argument("--batches", default="1024,8192")
     ap.add_argument("--hops", default="1,2")
@@ -103,6 +158,8 @@ def main():
     ap.add_argument("--n", type=int, default=None, help="override the node count (rehearsals)")
     ap.add_argument("--append", action="store_true", help="add to --out instead of starting it afresh")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join("profiles", "r18_ego_sample_bench.jsonl" if args.fanout else "r16_ego_block_bench.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("ego_block_bench needs a GPU: a CPU run gives no timing")
     dev = torch.device("cuda:0")
@@ -126,6 +183,13 @@ def main():
 
             for B in (int(v) for v in args.batches.split(",")):
                 seeds = perm[:B].contiguous()
+                if args.fanout:
+                    line = sampled_line(args, name, wl, model, full, full_eval, graphs, seeds, B, hops)
+                    print(json.dumps(line), flush=True)
+                    with open(args.out, "a") as fh:
+                        fh.write(json.dumps(line) + "\n")
+                    torch.cuda.empty_cache()
+                    continue
                 mini = minibatch.MiniBatchTrainer(model, [x] * wl["p"], graphs, wl["labels"], wl["train_mask"],
                                                   wl["val_mask"], batch_size=B, seed=1)
                 blk = minibatch.ego_block(graphs, seeds, hops)
