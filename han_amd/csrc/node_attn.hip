@@ -44,6 +44,16 @@ __device__ __forceinline__ float head_sum(float v) {
     return v;
 }
 
+// bitwise OR over the same lanes, the same way
+template <int FP>
+__device__ __forceinline__ uint32_t head_or(uint32_t v) {
+    if (FP >= 8) v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
+    if (FP >= 16) v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);
+    if (FP >= 32) v |= (uint32_t)__shfl_xor((int)v, 4, 64);
+    if (FP >= 64) v |= (uint32_t)__shfl_xor((int)v, 8, 64);
+    return v;
+}
+
 __device__ __forceinline__ float dot4(const float4_t &x, const float4_t &y) {
     return x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3];
 }
@@ -118,9 +128,11 @@ struct FwdArgs {
     float *split_ws;
 };
 
-// Backward tables: ONE fused row per destination i, [ g_i : D elements (fp32 or bf16) | (f1, lse, s, 0) x K : fp32 ],
+// Backward tables: ONE fused row per destination i, [ g_i : D elements (fp32 or bf16) | (f1, lse, s, z) x K : fp32 ],
 // padded to whole 128-B lines (fp32, K = 8: 256 + 128 = 384 B = 3 lines; bf16: 128 + 128 = 256 B), so that a
 // node partition moves ONE table per meta-path in the backward (one collective, one pack) instead of two.
+// z (han_hip.h): bits 0 = the head's g values may be anything, HAN_GS_Z_ALL_ZERO = all of them are +-0 (the whole row
+// of a destination outside the loss mask of a one-layer model); bwd_consume_pred reads it, nothing else does.
 template <int FP, bool BF>
 struct GsRow {
     static constexpr int K = HAN_D / FP;
@@ -985,6 +997,7 @@ __global__ __launch_bounds__(256) void node_attn_bwd_rows_kernel(const BwdRowsAr
         float4_t r4 = {0.f, 0.f, 0.f, 0.f};
         if (a.res) r4 = *reinterpret_cast<const float4_t *>(a.res + row * HAN_D + 4 * q);
         float sp = 0.f, dp = 0.f;
+        uint32_t zb = 0;      // the magnitude bits of the stored g values, ORed: 0 iff all are +-0
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             // ELU'(pre) and pre from the output: out > 0: 1, out;  out <= 0: out + 1 (= e^pre), log(out + 1).  An output
@@ -998,11 +1011,13 @@ __global__ __launch_bounds__(256) void node_attn_bwd_rows_kernel(const BwdRowsAr
             // row-local sums s_i and df1_i are formed from the rounded value too -- otherwise
             // sum_j dl_ij (gathered side) and df1_i (this side) disagree by the rounding of g
             if (BF) g4[t] = __uint_as_float(han_f32_to_bf16_bits(g4[t]) << 16);
+            zb |= __float_as_uint(g4[t]) << 1;
             sp += g4[t] * (pt - c4[t] - r4[t]);         // g . (the aggregate alone)
             dp += g4[t] * ap4[t];
         }
         sp = head_sum<FP>(sp);
         dp = head_sum<FP>(dp);
+        zb = head_or<FP>(zb);
         char *grow = reinterpret_cast<char *>(a.gs) + row * GsRow<FP, BF>::bytes;
         if (BF) {
             uint2 w;
@@ -1019,7 +1034,7 @@ __global__ __launch_bounds__(256) void node_attn_bwd_rows_kernel(const BwdRowsAr
             st[0] = a.f1[row * K + head];
             st[1] = a.lse[row * K + head];
             st[2] = sp;
-            st[3] = 0.f;
+            st[3] = __uint_as_float(zb == 0u ? HAN_GS_Z_ALL_ZERO : 0u);
             *reinterpret_cast<float4_t *>(grow + GsRow<FP, BF>::g_bytes + 16 * head) = st;
         }
     }
@@ -1047,6 +1062,7 @@ struct BwdColsArgs {
     const int32_t *gid;  // global id of each row of the gs table, or null
     const float *f2, *df1, *a1, *a2;
     int lsb_mask;
+    int zero_rows;       // HAN_FLAG_K2_ZERO_ROWS: most g rows are zero, MODE 3 honours z (host side only; sits in what was padding)
     float *dH, *df2;
     int64_t NS;
     const int32_t *rows;     // degree-binned launches: the n_work source rows of this launch (null: 0 .. n_work-1)
@@ -1173,12 +1189,20 @@ __device__ __forceinline__ void bwd_consume(const BwdColsArgs &a, const int (&i)
 // the bit for finite g: the roundings from the gathered values on are written out (dot4_unfused), because left to
 // itself the compiler fuses them differently from one arrangement of the loads to the next (what leads up to alpha is
 // the same expression in both and compiles alike today).  bwd_consume, the form of every other launch, is untouched.
+// The same holds for a head whose g values are all +-0, which its statistics record says in its fourth word (z, set by
+// whoever wrote the row): in the full gather w * g and am * dot are zeros of either sign there (for a finite w), and acc
+// and dfacc keep their bits.  MODE 3 (HAN_FLAG_K2_ZERO_ROWS) asks for the g piece of such a head no more than for a
+// dropped one -- on a one-layer model that is every head of every destination outside the loss mask.  Its g loads wait
+// for the statistics of their step, which costs 0.05 ms of 2.51 at N = 1M where no z is set and saves 0.73 ms where nine
+// rows in ten are zero; so it is the caller who says that most rows are zero, and MODE 1 and 2 do not look at z.
+// (Requesting the statistics of the next step ahead of a step's g loads was measured and is slower in both cases: 114
+// registers instead of 95, four waves per SIMD instead of five -- DESIGN.md section 3.)
 template <int FP, int U, bool VAL, bool FAST, bool ALLV, bool MASKED, int MODE>
 __device__ __forceinline__ void bwd_consume_pred(const BwdColsArgs &a, const int (&i)[U], const float (&ew)[U],
                                                  const bool (&valid)[U], const SrcRow &sr, const int q, const int head, const bool drop_c,
                                                  float (&acc)[4], float &dfacc) {
     constexpr int KQ = (HAN_D / FP + 3) / 4;
-    static_assert(MODE == 1 || MODE == 2, "MODE 0 is bwd_consume");
+    static_assert(MODE >= 1 && MODE <= 3, "MODE 0 is bwd_consume");
     float4_t gv[U], st[U];
     float am[U];
     // MASKED: a dead entry reads the statistics record of row 0 (one line that every wave shares) and drops it.
@@ -1204,7 +1228,7 @@ __device__ __forceinline__ void bwd_consume_pred(const BwdColsArgs &a, const int
 #pragma unroll
     for (int u = 0; u < U; ++u)
         gv[u] = gs_load_g4_if<FP>(a.gs, (MASKED && !valid[u]) ? (int64_t)0 : (int64_t)i[u], q, head,
-                                  (MODE == 2 || am[u] != 0.f) && (ALLV || valid[u]));
+                                  (MODE == 2 || (am[u] != 0.f && (MODE != 3 || __float_as_uint(st[u][3]) == 0u))) && (ALLV || valid[u]));
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         float x = st[u][0] + sr.f2h;
@@ -1226,12 +1250,13 @@ __device__ __forceinline__ void bwd_consume_pred(const BwdColsArgs &a, const int
             for (int t = 0; t < 4; ++t) acc[t] = __builtin_fmaf(w, gv[u][t], acc[t]);
         }
     }
-    // The fourth word of a statistics record is padding that nothing reads.  Left dead, its register goes to the hash,
-    // which then waits for the statistics to land before it may overwrite it -- and the g loads behind the hash wait
-    // with it, one memory latency after the other (read from the ISA; the form without this line was not timed).  This
-    // keeps the register taken until the step is done.
+    // MODE 1 and 2 do not read the fourth word of a statistics record.  Left dead, its register goes to the hash, which
+    // then waits for the statistics to land before it may overwrite it -- and the g loads behind the hash wait with it,
+    // one memory latency after the other (read from the ISA; the form without this line was not timed).  This keeps the
+    // register taken until the step is done.  MODE 3 reads the word, and its g loads wait for the statistics anyway.
 #pragma unroll
-    for (int u = 0; u < U; ++u) asm volatile("" ::"v"(st[u][3]));
+    for (int u = 0; u < U; ++u)
+        if (MODE != 3) asm volatile("" ::"v"(st[u][3]));
 }
 
 template <int FP>
@@ -1247,7 +1272,7 @@ __device__ __forceinline__ void write_src(const BwdColsArgs &a, const int64_t sr
     if ((4 * q) % FP == 0) a.df2[src * K + head] = dfacc;
 }
 
-// MODE: 0 = bwd_consume, 1 / 2 = bwd_consume_pred (the FAST fp32 launches: bwd_gather_mode)
+// MODE: 0 = bwd_consume, 1 / 2 / 3 = bwd_consume_pred (the FAST fp32 launches: bwd_gather_mode)
 template <int FP, int RPW, int U, bool BF, bool VAL, bool FAST, bool MASKED = false, bool DEDUP = false, int MODE = 0>
 __global__ __launch_bounds__(256) void node_attn_bwd_cols_kernel(const BwdColsArgs a_in) {
     BwdColsArgs a = a_in;
@@ -1893,10 +1918,10 @@ static void launch_fwd_v(const FwdArgs &a_in, bool train, bool low, bool has_spl
 // to leave out or measured slower: no attention dropout; bf16 tables (eight heads share a 128-byte line: 1.85 -> 1.94 ms
 // at N = 1M); a table of ids (the draw waits for the id lookup and the g loads wait for the draw, two latencies in a row:
 // 3.38 -> 3.72 ms); the masked backward, which already loads nothing for nine entries in ten (bench.py --masked-backward
-// 33.3 -> 31.2 epochs/s).  Otherwise 1, or 2 under HAN_FLAG_K2_FULL_GATHER.
+// 33.3 -> 31.2 epochs/s).  Otherwise 2 under HAN_FLAG_K2_FULL_GATHER, else 3 under HAN_FLAG_K2_ZERO_ROWS, else 1.
 static int bwd_gather_mode(const BwdColsArgs &a, bool bf) {
     if (bf || a.thr_coef >= HAN_KEEP_ALL || a.gid != nullptr || a.masked != 0) return 0;
-    return a.full_gather ? 2 : 1;
+    return a.full_gather ? 2 : (a.zero_rows ? 3 : 1);
 }
 
 template <int FPC, bool BF, bool VAL>
@@ -1911,6 +1936,7 @@ static void launch_bwd_rows(const BwdColsArgs &a, bool short_rows, hipStream_t s
         else if (mode == 0) HAN_DISPATCH_BOOL(FAST, fast, node_attn_bwd_cols_kernel<FPC, RPW, 4, BF, VAL, FAST><<<grid, 256, 0, st>>>(a));
         else if constexpr (!BF) {
             if (mode == 1) node_attn_bwd_cols_kernel<FPC, RPW, 4, false, VAL, true, false, false, 1><<<grid, 256, 0, st>>>(a);
+            else if (mode == 3) node_attn_bwd_cols_kernel<FPC, RPW, 4, false, VAL, true, false, false, 3><<<grid, 256, 0, st>>>(a);
             else node_attn_bwd_cols_kernel<FPC, RPW, 4, false, VAL, true, false, false, 2><<<grid, 256, 0, st>>>(a);
         }
     });
@@ -1933,6 +1959,7 @@ static void launch_bwd_cols_v(const BwdColsArgs &a_in, bool low, bool has_split,
         if (mode == 0) node_attn_bwd_chunk_kernel<FPC, 4, BF, VAL><<<attn_grid(a.n_chunks), 256, 0, st>>>(a);
         else if constexpr (!BF) {
             if (mode == 1) node_attn_bwd_chunk_kernel<FPC, 4, false, VAL, 1><<<attn_grid(a.n_chunks), 256, 0, st>>>(a);
+            else if (mode == 3) node_attn_bwd_chunk_kernel<FPC, 4, false, VAL, 3><<<attn_grid(a.n_chunks), 256, 0, st>>>(a);
             else node_attn_bwd_chunk_kernel<FPC, 4, false, VAL, 2><<<attn_grid(a.n_chunks), 256, 0, st>>>(a);
         }
         node_attn_bwd_finish_kernel<FPC, BF><<<(int)a.n_long, 256, 0, st>>>(a);
@@ -2099,6 +2126,7 @@ extern "C" int han_node_attn_bwd_cols(const int64_t *colptr, const int32_t *rowi
     a.masked = (flags & HAN_FLAG_MASKED_EDGES) ? 1 : 0;
     a.lean = (flags & HAN_FLAG_LEAN) ? 1 : 0;
     a.full_gather = (flags & HAN_FLAG_K2_FULL_GATHER) ? 1 : 0;
+    a.zero_rows = (flags & HAN_FLAG_K2_ZERO_ROWS) ? 1 : 0;
     a.only_if = nullptr;
     const bool has_split = fill_split(a, split);
     hipStream_t st = (hipStream_t)stream;

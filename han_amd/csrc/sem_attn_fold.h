@@ -13,7 +13,7 @@
 // coincide: a lane ends a tile with acc2[ft][reg] = dM[row g0 + reg][4 l15 + ft] and still holds mvc[reg] = M of the
 // same four elements -- the row pass's 16-lane group per row, q = l15, head = l15 >> 1.  Row g0 + reg is node
 // (g0 + reg) / P, meta-path reg % P (P divides 4).  So dM is not written: the epilogue forms g = dM ELU'(M), the head
-// sums s = g . (pre - c) and g . aggp, writes the [g | (f1, lse, s, 0) x 8] row of meta-path reg % P's table and
+// sums s = g . (pre - c) and g . aggp, writes the [g | (f1, lse, s, z) x 8] row of meta-path reg % P's table and
 // df1 = g . aggp - s tsum, and adds g to dc[p][4 l15 ..] in registers (lane groups -> waves -> P * 64 more floats of the
 // block's slab row at the end).  g, s and df1 are the row pass's bits: its
 // roundings (read from its ISA: both head sums are fma chains from 0, df1 is one fma) are written out.
@@ -24,7 +24,7 @@ struct K3FoldArgs {
     const float *c;                                    // (P,64)
     int act;                                           // HAN_ACT_ELU | HAN_ACT_IDENTITY
 };
-constexpr int kFoldRowBytes = 384;      // GsRow<8, false> of node_attn.hip: 64 fp32 g | 8 x (f1, lse, s, 0)
+constexpr int kFoldRowBytes = 384;      // GsRow<8, false> of node_attn.hip: 64 fp32 g | 8 x (f1, lse, s, z)
 constexpr int kFoldStatsAt = 256;
 
 // No dM; slab rows of 64 A + 2 A + 64 P floats; P * 256 more bytes of LDS than B6BwdLds.
@@ -299,6 +299,9 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_b6_fold_kernel(const fl
                 }
                 sp += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sp), 0xB1, 0xF, 0xF, true));    // the head's lane pair
                 dpv += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dpv), 0xB1, 0xF, 0xF, true));
+                // z of the record (han_hip.h): the magnitude bits of the head's eight g values, ORed -- 0 iff all are +-0
+                uint32_t zb = (__float_as_uint(g4[0]) | __float_as_uint(g4[1]) | __float_as_uint(g4[2]) | __float_as_uint(g4[3])) << 1;
+                zb |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)zb, 0xB1, 0xF, 0xF, true);
                 if (ok) {
                     dcacc[pp] = dcacc[pp] + g4;      // dc: this lane's partial sum, in row order
                     const uint32_t goff = nn * kFoldRowBytes;
@@ -308,7 +311,7 @@ __global__ __launch_bounds__(256) void sem_attn_bwd_wave_b6_fold_kernel(const fl
                         *reinterpret_cast<float *>(reinterpret_cast<char *>(fa.df1[pp]) + (nn * 8 + head) * 4) =
                             __builtin_fmaf(-sp, ts_n[reg], dpv);
                         *reinterpret_cast<float4_t *>(fa.gs[pp] + (goff + kFoldStatsAt + 16 * head)) =
-                            (float4_t){f1_n[reg], ls_n[reg], sp, 0.f};
+                            (float4_t){f1_n[reg], ls_n[reg], sp, __uint_as_float(zb == 0u ? HAN_GS_Z_ALL_ZERO : 0u)};
                     }
                 }
             }

@@ -174,6 +174,7 @@ class LayerRun:
     plans_b: list | None = None
     xs_full: tuple | None = None      # the features of ALL rows: replicated projection under a partition
     masked_bwd: list | None = None    # per meta-path dist.MaskedBackwardPlan, or None (the full pass)
+    zero_rows: bool = False           # at most half of the loss rows are live and this is the only node-attention layer: the backward gather honours z (HAN_FLAG_K2_ZERO_ROWS)
     streams: list | None = None       # one stream per meta-path (_each_path)
     side_stream: torch.cuda.Stream | None = None   # dW beside the next meta-path's backward gather (NodeLevelAttention.backward)
     path_order: str | None = None     # _path_order
@@ -492,7 +493,7 @@ class NodeLevelAttention(torch.autograd.Function):
             src = srcs[p][0]
             dH, df2 = ops.node_attn_bwd_cols(src.graph, gs_h.wait(), sv.H, sv.f2, df1, a1[p], a2[p], coef_drop=coef_drop,
                                              fts_drop=in_drop, seed=seed, src_offset=row_offset, dst_offset=0,
-                                             table_gid=src.gid, seed_dev=seed_dev)
+                                             table_gid=src.gid, seed_dev=seed_dev, **({"zero_rows": True} if run.zero_rows else {}))
             rows[p] = None
             ops.score_param_bwd(sv.H, df1, df2, K=K, FP=FP, out=(da1[p], da2[p], db1[p], db2[p]))
             if side is not None and dXin is None:

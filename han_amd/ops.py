@@ -24,6 +24,8 @@ K2_DEEP = False            # set by tools/k2_regimes.py --deep
 K2_SHARED_HASH = False     # tests / measurements: FLAG_K2_SHARED_HASH on every node_attn_fwd call
 K2_FULL_GATHER = False     # tests / measurements: FLAG_K2_FULL_GATHER on every node_attn_bwd_cols call
 FLAG_K2_FULL_GATHER = 2048 # HAN_FLAG_K2_FULL_GATHER: measurements only (the backward gather requests g rows whole, dropped heads included)
+FLAG_K2_ZERO_ROWS = 4096   # HAN_FLAG_K2_ZERO_ROWS: most rows of the gs table hold a zero gradient; the predicated backward gather honours z
+GS_Z_ALL_ZERO = 0x3F800000 # HAN_GS_Z_ALL_ZERO: fourth word of a head's statistics record when all g values of the head are +-0 (else 0)
 FLAG_MASKED_EDGES = 64     # HAN_FLAG_MASKED_EDGES: negative entries of the transposed graph are skipped in place
 FLAG_K1_EXACT_PIPE = 2     # HAN_FLAG_K1_EXACT_PIPE / _MATRIX_PIPE: force one of the two K1 forward kernels (tests, measurements)
 FLAG_K1_MATRIX_PIPE = 4
@@ -45,7 +47,7 @@ def flag_fts_slice(s: int) -> int:
 
 LEAKY_SLOPE = 0.2          # tf.nn.leaky_relu default (utils/layers.py:27)
 D = 64                     # K * F' of this build
-STATS_ROW_BYTES = 128      # per destination row: the (f1, lse, s, 0) records of the K = 8 heads inside the fused gs row (bench.py byte model)
+STATS_ROW_BYTES = 128      # per destination row: the (f1, lse, s, z) records of the K = 8 heads inside the fused gs row (bench.py byte model)
 
 _workspaces: dict = {}
 _retired_workspaces: list = []      # superseded buffers stay alive: a captured hipGraph may have baked their pointers in
@@ -583,7 +585,7 @@ def node_attn_coefs(graph: CSRGraph, f1, f2, coef_drop=0.0, seed=0, row_offset=0
 
 
 def gs_row_bytes(K=8, FP=8, table_dtype=torch.float32) -> int:
-    """Bytes of one fused backward row [g | (f1, lse, s, 0) x K] (han_gs_row_bytes)."""
+    """Bytes of one fused backward row [g | (f1, lse, s, z) x K] (han_gs_row_bytes)."""
     n = int(_lib.load().han_gs_row_bytes(K, FP, DTYPE_CODE[table_dtype]))
     if n == 0:
         raise NotImplementedError(f"no fused backward row for K={K}, FP={FP}, {table_dtype}")
@@ -602,7 +604,7 @@ def node_attn_bwd_rows(dOut, out, aggp, tsum, f1, lse, c, activation=ACT_ELU, K=
                        table_dtype=torch.float32, res=None, dc_out=None, gs_out=None):
     """Row-local half of the K2 backward.  dOut (N,D) view (unit inner stride); out (N,D) view: the forward's
     output rows (saved[0] of node_attn_fwd), from which the pre-activation is recovered.
-    Returns gs (N, row_bytes) uint8 -- the fused table [g | (f1, lse, s, 0) x K] the transposed-graph
+    Returns gs (N, row_bytes) uint8 -- the fused table [g | (f1, lse, s, z) x K] the transposed-graph
     pass gathers from (gs_views() splits it) --, df1 (N,K), dc (D,) [written to dc_out when given].
     gs_out: optional preallocated destination (e.g. the local block of an exchange table)."""
     lib = _lib.load()
@@ -635,11 +637,12 @@ def node_attn_bwd_rows(dOut, out, aggp, tsum, f1, lse, c, activation=ACT_ELU, K=
 
 
 def node_attn_bwd_cols(graph_t: CSRGraph, gs_tab, H, f2, df1, a1, a2, coef_drop=0.0,
-                       fts_drop=0.0, seed=0, src_offset=0, dst_offset=0, table_gid=None, seed_dev=None):
+                       fts_drop=0.0, seed=0, src_offset=0, dst_offset=0, table_gid=None, seed_dev=None, zero_rows=False):
     """Transposed-graph half of the K2 backward.  graph_t rows = local sources j,
     its colidx = destinations i indexing the fused table gs_tab (NT, row_bytes) uint8.
     H (NS,D) undropped local rows (keep bits in bit 0 when fts_drop > 0),
-    f2/df1 (NS,K).  Returns dH (NS,D), df2 (NS,K)."""
+    f2/df1 (NS,K).  zero_rows: a hint that most rows of gs_tab hold a zero gradient (HAN_FLAG_K2_ZERO_ROWS: the
+    g piece of a head whose record says so is not requested; same bits).  Returns dH (NS,D), df2 (NS,K)."""
     lib = _lib.load()
     K, FP = a1.shape
     _check_heads(K, FP)
@@ -668,7 +671,8 @@ def node_attn_bwd_cols(graph_t: CSRGraph, gs_tab, H, f2, df1, a1, a2, coef_drop=
             NS, graph_t.nnz, K, FP, LEAKY_SLOPE, _check_drop(coef_drop, "coef_drop"), fts_drop,
             int(seed), _dev_word(seed_dev), int(src_offset), int(dst_offset),
             (FLAG_XCD_ORDER if graph_t.has_locality() else 0) | (FLAG_MASKED_EDGES if graph_t.masked else 0)
-            | (FLAG_LEAN if lean_b else 0) | (FLAG_K2_FULL_GATHER if K2_FULL_GATHER else 0),
+            | (FLAG_LEAN if lean_b else 0) | (FLAG_K2_FULL_GATHER if K2_FULL_GATHER else 0)
+            | (FLAG_K2_ZERO_ROWS if zero_rows else 0),
             ctypes.byref(split) if split is not None else None,
             ctypes.byref(dense) if dense is not None else None, _stream()), "han_node_attn_bwd_cols")
     return dH, df2

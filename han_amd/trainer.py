@@ -175,6 +175,12 @@ class HANTrainer:
         # normaliser is a setup-time constant, summed over ranks once.
         self.w_train = 1.0 / max(self._global_count(self.train_mask), 1)
         self.w_val = 1.0 / max(self._global_count(self.val_mask), 1)
+        # a hint, not a plan: with one node-attention layer the g row of a destination outside the mask is zero, and the
+        # HIP backward gather skips what its producers flag as zero (HAN_FLAG_K2_ZERO_ROWS) -- a gain from half of the
+        # rows on, a small loss where every row is live.  Single GPU only in effect: under a node
+        # partition the backward tables come with an id table, those launches are not predicated and ignore the hint.
+        n_global = self._global_count(torch.ones_like(self.train_mask))
+        model.zero_rows = dev.type == "cuda" and not model.extra and 2 * self._global_count(self.train_mask) <= n_global
         self.opt = TFAdam(model.flat, model.flat_grad, lr=lr, l2_coef=l2_coef)
         # d loss = 1 handed to backward() instead of the ones_like() autograd would launch per step: in a captured epoch
         # of the small graphs that 1-element fill is a dependent 5-us launch between the loss and the K3 backward

@@ -63,7 +63,16 @@ extern "C" {
                                   the sums into NaN (the full gather multiplies it by zero), a non-finite g under a kept head
                                   still does.  Predicated are fp32 tables with attention dropout, table_gid NULL and no
                                   HAN_FLAG_MASKED_EDGES; every other launch gathers whole rows with or without this flag
-                                  (bf16 tables, table_gid, masked edges, the lean, one-lane-per-head and dense kernels).     */
+                                  (bf16 tables, table_gid, masked edges, the lean, one-lane-per-head and dense kernels).
+                                  This flag wins over HAN_FLAG_K2_ZERO_ROWS: the full gather ignores z.                      */
+#define HAN_FLAG_K2_ZERO_ROWS 4096 /* han_node_attn_bwd_cols, a hint: most rows of the gs table hold a zero gradient (a one-layer
+                                  model whose loss mask covers at most half of the rows).  The predicated launches (see above)
+                                  then also leave out the g piece of a head whose statistics record says that it holds only
+                                  zeros (z, see the gs row below): such a piece contributes exact zeros, so dH and df2 keep
+                                  their bits for finite g, lse and f1.  The g loads then wait for the statistics of their
+                                  edge: at N = 1M a loss of 0.05 ms (2.51 -> 2.56, +2 %) where no z is set and a gain of 0.73 ms
+                                  (2.51 -> 1.78, -29 %) where nine records in ten have it; hence a flag.  Launches that are
+                                  not predicated ignore it, and without it z is not read.                                   */
 #define HAN_FLAG_MASKED_EDGES 64 /* han_node_attn_bwd_cols: entries of rowidx below 0 are skipped IN PLACE (their destination's
                                   g row is identically zero -- a destination outside the loss mask of a one-layer model);
                                   the remaining terms are summed in the positions and order of the full pass, so the
@@ -314,10 +323,20 @@ int han_node_attn_coefs(const int64_t *rowptr, const int32_t *colidx, const floa
                         float coef_drop, uint64_t seed, const uint64_t *seed_dev, int64_t row_offset, void *stream);
 
 /* Backward tables: ONE fused row per destination i,
- *   [ g_i : D elements of table_dtype | (f1_i, lse_i, s_i, 0)[k] : 4 fp32 per head k ]
+ *   [ g_i : D elements of table_dtype | (f1_i, lse_i, s_i, z_i)[k] : 4 x 32 bits per head k ]
  * padded to whole 128-B lines; han_gs_row_bytes() gives the row size (K = 8, F' = 8: 384 B with
  * fp32 g, 256 B with bf16 g).  Under a node partition this is the ONLY table the backward moves
- * per meta-path (one collective instead of one for g and one for the statistics).            */
+ * per meta-path (one collective instead of one for g and one for the statistics).
+ * z, the fourth word of a record, is read as bits: 0 = the F' stored g values of head k in row i may be
+ * anything; any non-zero pattern = all of them are +0 or -0.  The library's producers write
+ * HAN_GS_Z_ALL_ZERO exactly where that holds, 0 elsewhere.  Under HAN_FLAG_K2_ZERO_ROWS the predicated
+ * launches of han_node_attn_bwd_cols do not request the g piece of a head whose z is set -- with finite
+ * statistics (f1, lse: a finite coefficient) it could only add zeros; with a non-finite coefficient the
+ * full gather yields NaN (inf * 0) where this form does not, as for a non-finite g under a dropped head.
+ * z is an optimisation only: 0 everywhere is always correct (it is what tables written before the word
+ * had a meaning hold).  A caller that builds gs rows itself writes 0 or, where it knows the head's g to
+ * be all zero, HAN_GS_Z_ALL_ZERO -- never garbage.                                             */
+#define HAN_GS_Z_ALL_ZERO 0x3F800000u   /* the bits of 1.0f: survives any float view of the record */
 size_t han_gs_row_bytes(int K, int FP, int table_dtype);
 
 /* Backward, step 1 (row-local): from dOut (N,D; row stride dout_stride), the forward's OUTPUT rows `out`
@@ -327,7 +346,8 @@ size_t han_gs_row_bytes(int K, int FP, int table_dtype);
  *   g = dOut * act'(pre)   (rounded to table_dtype; the sums below use the rounded value)
  *   s_i[k] = g_i[k] . (pre_i - c)[k]
  *   df1_i[k] = g_i[k] . aggp_i[k] - s_i[k] * tsum_i[k]        -> df1 (N,K)
- *   gs row i = [ g_i | (f1, lse, s, 0)[k] ]                    -> gs (N rows of han_gs_row_bytes())
+ *   z_i[k] = HAN_GS_Z_ALL_ZERO if every stored g_i[k] is +-0, else 0
+ *   gs row i = [ g_i | (f1, lse, s, z)[k] ]                    -> gs (N rows of han_gs_row_bytes())
  *   dc += sum_i g_i  (written, not accumulated; unrounded g)  -> dc (D)
  * workspace: han_node_attn_bwd_workspace() bytes.                          */
 size_t han_node_attn_bwd_workspace(int64_t N, int K, int FP);
