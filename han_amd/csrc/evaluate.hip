@@ -6,7 +6,7 @@
 // (v_mfma_f32_16x16x4_f32) in tiles of 64 x 64 pairs per workgroup step; the distance matrix never exists in
 // memory: a lane sees its 16 candidates of a tile in registers and keeps a sorted list of the best ones.
 //
-// Tile layout (all three tile kernels).  A workgroup of 4 waves stages 64 "column" rows (queries / data rows) and 64 "row"
+// Tile layout (all six tile kernels).  A workgroup of 4 waves stages 64 "column" rows (queries / data rows) and 64 "row"
 // rows (train rows / centres), 64 embedding columns at a time, into LDS as [64][kLd] fp32, zero-filled past the
 // matrix edges and past D (so a D that is no multiple of 4 is padded in LDS, never in memory).  Wave w owns the
 // column rows 16 w .. 16 w + 15 and walks all 64 row rows as four 16 x 16 accumulators.  The MFMA sums over its K
@@ -14,6 +14,21 @@
 // group g = lane >> 4 takes columns 16 g + 4 s .. + 3 in step s, one ds_read_b128 per operand and four MFMAs.
 // Result map: lane (n = lane & 15, g) holds, in acc[j][r], the product of column row 16 w + n and row row
 // 16 j + 4 g + r.
+//
+// Written once and shared (the roundings of this file are pinned bit for bit; a second copy is where one drifts):
+//   TilePos, pair_product   a lane's place, and one 64 x 64 tile of q.t over all stages of D with the row rows' norms:
+//                           knn_tiles, sil_tiles, tsne_rowmin / calib / step_tiles (kmeans_assign: see its comment)
+//   for_pairs               the walk of a lane's 16 pairs: knn_tiles, sil_tiles, tsne_rowmin_tiles, tsne_calib_tiles
+//                           (tsne_step_tiles and kmeans_assign: see there)
+//   d2_norms, tsne_d2       the two forms of a pair's distance; they round differently, on purpose
+//   row4_sum                the four lanes of a column row: sil_tiles, tsne_calib_tiles, tsne_step_tiles
+//   block_sums              the workgroup's sum in thread order: sil_finish, tsne_rowsum_parts, block_totals,
+//                           tsne_update (two values behind one barrier); kmeans_assign keeps its own (see there)
+// Host side: one plan per entry-point family (knn_plan, kmeans_plan, sil_plan, tsne_plan), laid out with Regions and
+// read by both the *_workspace function and the entry point; norms_and_grid launches row_norms and gives a tile
+// kernel's (row tiles, splits) grid.
+#include <utility>
+
 #include "han_common.h"
 
 namespace {
@@ -47,8 +62,7 @@ __device__ __forceinline__ void stage_tile(float *s, const float *M, int64_t ld,
 }
 
 // acc[j] += rows(16 j ..) of Rs  x  columns(16 w ..) of Cs over one staged chunk, for the first nj (uniform) row tiles
-__device__ __forceinline__ void mma_chunk(float4_t (&acc)[4], const float *Rs, const float *Cs, int w, int lane,
-                                          int nj = 4) {
+__device__ __forceinline__ void mma_chunk(float4_t (&acc)[4], const float *Rs, const float *Cs, int w, int lane, int nj) {
     const int n = lane & 15, g = lane >> 4;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -60,6 +74,104 @@ __device__ __forceinline__ void mma_chunk(float4_t (&acc)[4], const float *Rs, c
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[e], acc[j], 0, 0, 0);
         }
+    }
+}
+
+// a lane's place: workgroup (x, y) takes the column rows [q0, q0 + 64) against the row rows [t_begin, t_end) of n_rows,
+// this lane the column row myq
+struct TilePos {
+    int lane, w, n, g;
+    int64_t q0, t_begin, t_end, myq;
+    __device__ __forceinline__ TilePos(int64_t split_rows, int64_t n_rows)
+        : lane(threadIdx.x & 63), w(threadIdx.x >> 6), n(lane & 15), g(lane >> 4), q0((int64_t)blockIdx.x * kTile),
+          t_begin((int64_t)blockIdx.y * split_rows), t_end(min(n_rows, t_begin + split_rows)), myq(q0 + 16 * w + n) {}
+};
+
+// the operands of pair_product: row rows [.., end) of M with their norms, and the n column rows of M
+struct TileRows {
+    const float *M, *norms;
+    int64_t ld, end;
+};
+struct TileCols {
+    const float *M;
+    int64_t ld, n;
+};
+
+// acc = (row rows [t0, min(t0 + 64, R.end))) x (column tile q0) as mma_chunk leaves it, the row rows' norms in tns;
+// `extra` stages what else the epilogue reads per row row between the same two barriers.  `staged`: the column tile
+// is in LDS already (one stage: it is staged once per workgroup).  Returns the 16-row tiles in use; ALL4 issues all
+// four whatever the tail, as knn_tiles always has (a tail-dependent count in its MFMA loop is a change to measure).
+template <bool ALL4, class Extra>
+__device__ __forceinline__ int pair_product(float4_t (&acc)[4], float *smem, float *tns, const TileRows R, const TileCols C,
+                                            int D, int64_t q0, int64_t t0, bool &staged, Extra extra) {
+    float *Rs = smem, *Cs = smem + kTile * kLd;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nch = (D + kChunk - 1) / kChunk;
+    const int nj = ALL4 ? 4 : (int)((min(R.end - t0, (int64_t)kTile) + 15) >> 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = float4_t{0.f, 0.f, 0.f, 0.f};
+    for (int ch = 0; ch < nch; ++ch) {
+        __syncthreads();
+        stage_tile(Rs, R.M, R.ld, t0, R.end, ch * kChunk, D);
+        if (nch > 1 || !staged) stage_tile(Cs, C.M, C.ld, q0, C.n, ch * kChunk, D);
+        if (ch == 0) {
+            if (threadIdx.x < kTile) tns[threadIdx.x] = t0 + threadIdx.x < R.end ? R.norms[t0 + threadIdx.x] : 0.f;
+            extra();
+        }
+        __syncthreads();
+        mma_chunk(acc, Rs, Cs, w, lane, nj);
+    }
+    staged = true;
+    return nj;
+}
+
+// f(j, r, tl, t) for the 16 pairs of a lane of group g in the tile at t0 whose row row t = t0 + tl lies before `end`:
+// the product is acc[j][r], the row row's norm tns[tl]
+template <class F>
+__device__ __forceinline__ void for_pairs(int g, int64_t t0, int64_t end, F f) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int tl = 16 * j + 4 * g + r;
+            if (t0 + tl < end) f(j, r, tl, t0 + tl);
+        }
+}
+
+// The two forms of a pair's d2 from the norms and the product.  d2_norms, of KNN, k-means and the silhouette: the
+// plain expression, NOT clamped: the neighbours and the nearest centre are the smallest computed values under
+// (d2, index), and a clamp would turn what cancellation left slightly negative into ties (the silhouette clamps where
+// it takes the root).  tsne_d2, of every t-SNE kernel: an explicit fma, clamped at 0, because d2 - m feeds an exponent
+// and the row minimum m must be the minimum of what the later passes see.  The two may differ in the last bit and
+// each is pinned by bit-for-bit tests, so neither stands in for the other.
+__device__ __forceinline__ float d2_norms(float qn, float tn, float dot) { return (qn + tn) - 2.f * dot; }
+__device__ __forceinline__ float tsne_d2(float qn, float tn, float dot) {
+    return fmaxf(__builtin_fmaf(-2.f, dot, qn + tn), 0.f);
+}
+
+// (g0 + g1) + (g2 + g3) of the four lanes of a column row, in every one of them
+__device__ __forceinline__ double row4_sum(double v) {
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
+    return v;
+}
+
+// out[i * stride] = the workgroup's sum of v[i], the 256 threads in order (thread 0 adds them behind one barrier)
+template <int NV>
+__device__ __forceinline__ void block_sums(const double (&v)[NV], double *out, int64_t stride) {
+    __shared__ double ps[NV][kBlock];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) ps[i][threadIdx.x] = v[i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) t[i] = 0.0;
+        for (int e = 0; e < kBlock; ++e)
+#pragma unroll
+            for (int i = 0; i < NV; ++i) t[i] += ps[i][e];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) out[i * stride] = t[i];
     }
 }
 
@@ -115,35 +227,17 @@ template <int KC>
 __global__ __launch_bounds__(kBlock) void knn_tiles(const KnnArgs a) {
     __shared__ __attribute__((aligned(16))) float smem[2 * kTile * kLd];
     __shared__ float tns[kTile];
-    float *Rs = smem, *Cs = smem + kTile * kLd;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
-    const int64_t q0 = (int64_t)blockIdx.x * kTile;
-    const int64_t t_begin = (int64_t)blockIdx.y * a.split_rows;
-    const int64_t t_end = min(a.Nt, t_begin + a.split_rows);
-    const int64_t myq = q0 + 16 * w + n;
-    const float qnorm = myq < a.Nq ? a.qn[myq] : 0.f;
-    const int nch = (a.D + kChunk - 1) / kChunk;
+    const TilePos p(a.split_rows, a.Nt);
+    const float qnorm = p.myq < a.Nq ? a.qn[p.myq] : 0.f;
     TopList<KC> top;
     top.init();
-    for (int64_t t0 = t_begin; t0 < t_end; t0 += kTile) {
+    bool staged = false;
+    for (int64_t t0 = p.t_begin; t0 < p.t_end; t0 += kTile) {
         float4_t acc[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = float4_t{0.f, 0.f, 0.f, 0.f};
-        for (int c = 0; c < nch; ++c) {
-            __syncthreads();
-            stage_tile(Rs, a.T, a.ldt, t0, t_end, c * kChunk, a.D);
-            if (nch > 1 || t0 == t_begin) stage_tile(Cs, a.Q, a.ldq, q0, a.Nq, c * kChunk, a.D);
-            if (c == 0 && threadIdx.x < kTile) tns[threadIdx.x] = t0 + threadIdx.x < t_end ? a.tn[t0 + threadIdx.x] : 0.f;
-            __syncthreads();
-            mma_chunk(acc, Rs, Cs, w, lane);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int tl = 16 * j + 4 * g + r;
-                if (t0 + tl < t_end) top.offer((qnorm + tns[tl]) - 2.f * acc[j][r], (int)(t0 + tl));
-            }
+        pair_product<true>(acc, smem, tns, TileRows{a.T, a.tn, a.ldt, p.t_end}, TileCols{a.Q, a.ldq, a.Nq}, a.D, p.q0, t0,
+                           staged, [] {});
+        for_pairs(p.g, t0, p.t_end,
+                  [&](int j, int r, int tl, int64_t t) { top.offer(d2_norms(qnorm, tns[tl], acc[j][r]), (int)t); });
     }
     // the four lanes of a query: groups 1..3 hand their lists to group 0 through LDS
     __syncthreads();
@@ -153,13 +247,13 @@ __global__ __launch_bounds__(kBlock) void knn_tiles(const KnnArgs a) {
 #pragma unroll
     for (int j = 0; j < KC; ++j) { md[threadIdx.x * KC + j] = top.d[j]; mi[threadIdx.x * KC + j] = top.i[j]; }
     __syncthreads();
-    if (g == 0 && myq < a.Nq) {
+    if (p.g == 0 && p.myq < a.Nq) {
         for (int og = 1; og < 4; ++og) {
-            const int src = (64 * w + 16 * og + n) * KC;
+            const int src = (64 * p.w + 16 * og + p.n) * KC;
 #pragma unroll
             for (int j = 0; j < KC; ++j) top.offer(md[src + j], mi[src + j]);
         }
-        const int64_t o = ((int64_t)blockIdx.y * a.Nq + myq) * a.k;
+        const int64_t o = ((int64_t)blockIdx.y * a.Nq + p.myq) * a.k;
 #pragma unroll
         for (int j = 0; j < KC; ++j)
             if (j < a.k) { a.out_idx[o + j] = top.i[j]; a.out_d2[o + j] = top.d[j]; }
@@ -238,6 +332,11 @@ struct AssignArgs {
     double *inertia_part;      // one per workgroup
 };
 
+// The product loop here is its own and not pair_product: the roles are swapped.  A workgroup walks data tiles, so the
+// COLUMN operand (the data rows) is staged again for every tile, the row operand (all the centres: no tile of them to
+// walk, no split) is what stays in LDS with one stage, and the centres' norms are loaded once per workgroup.  A flag
+// for all that would make pair_product branch on its caller.  The walk and the ordered sum are spelled out too: on
+// for_pairs and block_sums the k-means line at 10^6 rows missed the parent's spread in one of two A/B jobs (DESIGN).
 __global__ __launch_bounds__(kBlock) void kmeans_assign(const AssignArgs a) {
     __shared__ __attribute__((aligned(16))) float smem[2 * kTile * kLd];
     __shared__ float cns[kMaxCentres];
@@ -277,7 +376,7 @@ __global__ __launch_bounds__(kBlock) void kmeans_assign(const AssignArgs a) {
             for (int r = 0; r < 4; ++r) {
                 const int ci = 16 * j + 4 * g + r;
                 if (ci < a.k) {
-                    const float d = (xnorm + cns[ci]) - 2.f * acc[j][r];
+                    const float d = d2_norms(xnorm, cns[ci], acc[j][r]);
                     if (pair_less(d, ci, best, bi)) { best = d; bi = ci; }
                 }
             }
@@ -360,6 +459,15 @@ __global__ __launch_bounds__(kBlock) void kmeans_finish(const double *slab, int 
     }
 }
 
+// the tile arguments of a call on X against itself (silhouette, t-SNE): both operands of pair_product
+struct SelfTiles {
+    const float *X, *xn;
+    int64_t ldx, N, split_rows;
+    int D;
+    __device__ __forceinline__ TileRows rows(int64_t end) const { return TileRows{X, xn, ldx, end}; }
+    __device__ __forceinline__ TileCols cols() const { return TileCols{X, ldx, N}; }
+};
+
 // ---- silhouette (data/exp.py:46-49) -----------------------------------------------------------------------------
 // S(i, c) = sum over the rows j of cluster c of |x_i - x_j|, for a row tile of 64 rows i against the column rows
 // [blockIdx.y * split_rows, + split_rows).  The rows are grouped by cluster, so the column tiles are cut at the segment
@@ -367,10 +475,9 @@ __global__ __launch_bounds__(kBlock) void kmeans_finish(const double *slab, int 
 // tile in fp32 in a fixed order, adds that to its double sum of the cluster, and at the end of the cluster the four
 // lanes of a row are added in a fixed order.  No accumulator is indexed by a label.
 struct SilArgs {
-    const float *X, *xn;
+    SelfTiles t;
     const int64_t *seg;      // (k + 1) segment bounds
-    int64_t ldx, N, split_rows;
-    int D, k;
+    int k;
     double *slab;            // [split][k][N] partial S(i, c); NULL with one split: a and b are formed here
     double *ab;              // [2][N]: a, then b
 };
@@ -386,54 +493,31 @@ __global__ __launch_bounds__(kBlock) void sil_tiles(const SilArgs a) {
     __shared__ __attribute__((aligned(16))) float smem[2 * kTile * kLd];
     __shared__ float tns[kTile];
     __shared__ int64_t segs[kMaxCentres + 1];
-    float *Rs = smem, *Cs = smem + kTile * kLd;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
+    const TilePos p(a.t.split_rows, a.t.N);
+    const int64_t N = a.t.N, myq = p.myq;
     if (threadIdx.x <= a.k) segs[threadIdx.x] = a.seg[threadIdx.x];
-    const int64_t q0 = (int64_t)blockIdx.x * kTile;
-    const int64_t t_begin = (int64_t)blockIdx.y * a.split_rows;
-    const int64_t t_end = min(a.N, t_begin + a.split_rows);
-    const int64_t myq = q0 + 16 * w + n;
-    const float qnorm = myq < a.N ? a.xn[myq] : 0.f;
-    const int nch = (a.D + kChunk - 1) / kChunk;
+    const float qnorm = myq < N ? a.t.xn[myq] : 0.f;
     double s_own = 0.0, best = __builtin_inf();
     int64_t n_own = 0;
-    bool staged = false;                                     // the row tile is in Cs (one chunk: staged once)
+    bool staged = false;
     __syncthreads();
     for (int c = 0; c < a.k; ++c) {
         const int64_t c0 = segs[c], c1 = segs[c + 1];
-        const int64_t lo = max(c0, t_begin), hi = min(c1, t_end);      // inside [0, N) whatever seg holds
+        const int64_t lo = max(c0, p.t_begin), hi = min(c1, p.t_end);      // inside [0, N) whatever seg holds
         double S = 0.0;
         for (int64_t t0 = lo; t0 < hi; t0 += kTile) {
-            const int nj = (int)((min(hi - t0, (int64_t)kTile) + 15) >> 4);
             float4_t acc[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = float4_t{0.f, 0.f, 0.f, 0.f};
-            for (int ch = 0; ch < nch; ++ch) {
-                __syncthreads();
-                stage_tile(Rs, a.X, a.ldx, t0, hi, ch * kChunk, a.D);
-                if (nch > 1 || !staged) stage_tile(Cs, a.X, a.ldx, q0, a.N, ch * kChunk, a.D);
-                if (ch == 0 && threadIdx.x < kTile) tns[threadIdx.x] = t0 + threadIdx.x < hi ? a.xn[t0 + threadIdx.x] : 0.f;
-                __syncthreads();
-                mma_chunk(acc, Rs, Cs, w, lane, nj);
-            }
-            staged = true;
+            pair_product<false>(acc, smem, tns, a.t.rows(hi), a.t.cols(), a.t.D, p.q0, t0, staged, [] {});
             float part = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int tl = 16 * j + 4 * g + r;
-                    if (t0 + tl < hi) {
-                        const float d2 = (qnorm + tns[tl]) - 2.f * acc[j][r];
-                        part += t0 + tl == myq ? 0.f : sqrtf(fmaxf(d2, 0.f));      // the pair (i, i) by its index
-                    }
-                }
+            for_pairs(p.g, t0, hi, [&](int j, int r, int tl, int64_t t) {
+                const float d2 = d2_norms(qnorm, tns[tl], acc[j][r]);
+                part += t == myq ? 0.f : sqrtf(fmaxf(d2, 0.f));      // the pair (i, i) by its index
+            });
             S += (double)part;
         }
-        S += __shfl_xor(S, 16, 64);                          // (g0 + g1) + (g2 + g3) in every lane of the row
-        S += __shfl_xor(S, 32, 64);
+        S = row4_sum(S);
         if (a.slab) {
-            if (g == 0 && myq < a.N) a.slab[((size_t)blockIdx.y * a.k + c) * a.N + myq] = S;
+            if (p.g == 0 && myq < N) a.slab[((size_t)blockIdx.y * a.k + c) * N + myq] = S;
         } else if (myq >= c0 && myq < c1) {
             s_own = S;
             n_own = c1 - c0;
@@ -441,7 +525,7 @@ __global__ __launch_bounds__(kBlock) void sil_tiles(const SilArgs a) {
             best = fmin(best, S / (double)(c1 - c0));
         }
     }
-    if (!a.slab && g == 0 && myq < a.N) sil_ab(s_own, n_own, best, &a.ab[myq], &a.ab[a.N + myq]);
+    if (!a.slab && p.g == 0 && myq < N) sil_ab(s_own, n_own, best, &a.ab[myq], &a.ab[N + myq]);
 }
 
 // a thread per row: a and b (from the slabs of the splits, added in order, when there are any), s, and the sum of
@@ -450,7 +534,6 @@ __global__ __launch_bounds__(kBlock) void sil_finish(const int64_t *seg, int k, 
                                                     const double *ab, float *a_out, float *b_out, float *s_out,
                                                     double *part) {
     __shared__ int64_t segs[kMaxCentres + 1];
-    __shared__ double ps[kBlock];
     if (threadIdx.x <= k) segs[threadIdx.x] = seg[threadIdx.x];
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -486,27 +569,14 @@ __global__ __launch_bounds__(kBlock) void sil_finish(const int64_t *seg, int k, 
         if (b_out) b_out[i] = (float)bv;
         if (s_out) s_out[i] = sf;
     }
-    ps[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int e = 0; e < kBlock; ++e) t += ps[e];
-        part[blockIdx.x] = t;
-    }
+    block_sums({s}, &part[blockIdx.x], 0);
 }
 
-// one workgroup: the partials of sil_finish, each thread its own in order, then the 256 threads in order
-__global__ __launch_bounds__(kBlock) void sil_total(const double *part, int64_t nparts, double *sum) {
-    __shared__ double ps[kBlock];
+// workgroup b: out[b] = the partials part[b * nparts ..), each thread its own in order, then the 256 threads in order
+__global__ __launch_bounds__(kBlock) void block_totals(const double *part, int64_t nparts, double *out) {
     double t = 0.0;
-    for (int64_t e = threadIdx.x; e < nparts; e += kBlock) t += part[e];
-    ps[threadIdx.x] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int e = 0; e < kBlock; ++e) s += ps[e];
-        *sum = s;
-    }
+    for (int64_t e = threadIdx.x; e < nparts; e += kBlock) t += part[(int64_t)blockIdx.x * nparts + e];
+    block_sums({t}, &out[blockIdx.x], 0);
 }
 
 // ---- t-SNE (jhyexp.py:16, data/exp.py:20: sklearn.manifold, method="exact") ---------------------------------------
@@ -520,17 +590,6 @@ constexpr int kTsneSumsKL = 7;     // + sum e p (log e p - log w), sum e p
 constexpr float kLog2e = 1.44269504088896340736f;
 constexpr float kFltMax = 3.402823466e+38f, kFltMin = 1.175494351e-38f;
 
-struct TsneTiles {
-    const float *X, *xn;
-    int64_t ldx, N, split_rows;
-    int D;
-};
-
-// the one form of a pair's d2 in every t-SNE kernel (the row minimum must be the minimum of what the later passes see)
-__device__ __forceinline__ float tsne_d2(float qn, float tn, float dot) {
-    return fmaxf(__builtin_fmaf(-2.f, dot, qn + tn), 0.f);
-}
-
 // the beta a pass evaluates for the bisection state `next` (negative: a closed row's), inside the finite fp32 range
 __device__ __forceinline__ float tsne_beta32(double next) {
     return fminf(fmaxf((float)fabs(next), kFltMin), kFltMax);
@@ -539,65 +598,25 @@ __device__ __forceinline__ float tsne_beta32(double next) {
 // beta * log2(e), finite: exp(-beta x) = exp2(-(this) x), and 0 * this = 0 for the nearest neighbour
 __device__ __forceinline__ float tsne_bl2(float beta) { return fminf(beta * kLog2e, kFltMax); }
 
-// acc = (column rows [t0, min(t0 + 64, t_end))) x (row tile q0) as mma_chunk leaves it, their norms in tns; `extra`
-// stages what else the epilogue reads per column row between the same two barriers.  Returns the row tiles in use.
-template <class Extra>
-__device__ __forceinline__ int tsne_product(float4_t (&acc)[4], float *smem, float *tns, const TsneTiles &a, int64_t q0,
-                                            int64_t t0, int64_t t_end, bool &staged, Extra extra) {
-    float *Rs = smem, *Cs = smem + kTile * kLd;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int nch = (a.D + kChunk - 1) / kChunk;
-    const int nj = (int)((min(t_end - t0, (int64_t)kTile) + 15) >> 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = float4_t{0.f, 0.f, 0.f, 0.f};
-    for (int ch = 0; ch < nch; ++ch) {
-        __syncthreads();
-        stage_tile(Rs, a.X, a.ldx, t0, t_end, ch * kChunk, a.D);
-        if (nch > 1 || !staged) stage_tile(Cs, a.X, a.ldx, q0, a.N, ch * kChunk, a.D);
-        if (ch == 0) {
-            if (threadIdx.x < kTile) tns[threadIdx.x] = t0 + threadIdx.x < t_end ? a.xn[t0 + threadIdx.x] : 0.f;
-            extra();
-        }
-        __syncthreads();
-        mma_chunk(acc, Rs, Cs, w, lane, nj);
-    }
-    staged = true;
-    return nj;
-}
-
-// (g0 + g1) + (g2 + g3) of the four lanes of a row, in every one of them
-__device__ __forceinline__ double tsne_row4(double v) {
-    v += __shfl_xor(v, 16, 64);
-    v += __shfl_xor(v, 32, 64);
-    return v;
-}
-
 // m_i = min over j != i of d2_ij, per split
-__global__ __launch_bounds__(kBlock) void tsne_rowmin_tiles(const TsneTiles a, float *slab /* [split][N] */) {
+__global__ __launch_bounds__(kBlock) void tsne_rowmin_tiles(const SelfTiles a, float *slab /* [split][N] */) {
     __shared__ __attribute__((aligned(16))) float smem[2 * kTile * kLd];
     __shared__ float tns[kTile];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
-    const int64_t q0 = (int64_t)blockIdx.x * kTile;
-    const int64_t t_begin = (int64_t)blockIdx.y * a.split_rows;
-    const int64_t t_end = min(a.N, t_begin + a.split_rows);
-    const int64_t myq = q0 + 16 * w + n;
+    const TilePos p(a.split_rows, a.N);
+    const int64_t myq = p.myq;
     const float qnorm = myq < a.N ? a.xn[myq] : 0.f;
     float best = __builtin_inff();
     bool staged = false;
-    for (int64_t t0 = t_begin; t0 < t_end; t0 += kTile) {
+    for (int64_t t0 = p.t_begin; t0 < p.t_end; t0 += kTile) {
         float4_t acc[4];
-        tsne_product(acc, smem, tns, a, q0, t0, t_end, staged, [] {});
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int tl = 16 * j + 4 * g + r;
-                if (t0 + tl < t_end && t0 + tl != myq) best = fminf(best, tsne_d2(qnorm, tns[tl], acc[j][r]));
-            }
+        pair_product<false>(acc, smem, tns, a.rows(p.t_end), a.cols(), a.D, p.q0, t0, staged, [] {});
+        for_pairs(p.g, t0, p.t_end, [&](int j, int r, int tl, int64_t t) {
+            if (t != myq) best = fminf(best, tsne_d2(qnorm, tns[tl], acc[j][r]));
+        });
     }
     best = fminf(best, __shfl_xor(best, 16, 64));
     best = fminf(best, __shfl_xor(best, 32, 64));
-    if (g == 0 && myq < a.N) slab[(size_t)blockIdx.y * a.N + myq] = best;
+    if (p.g == 0 && myq < a.N) slab[(size_t)blockIdx.y * a.N + myq] = best;
 }
 
 // a thread per row: the minimum over the splits, and the bisection's start (beta = 1, no bound yet)
@@ -613,43 +632,36 @@ __global__ __launch_bounds__(kBlock) void tsne_calib_init(const float *slab, int
 }
 
 // Z_i = sum_j exp(-beta_i (d2_ij - m_i)) and E_i = sum_j (d2_ij - m_i) exp(..) at the beta the state asks for
-__global__ __launch_bounds__(kBlock) void tsne_calib_tiles(const TsneTiles a, const double *state, const float *dmin,
+__global__ __launch_bounds__(kBlock) void tsne_calib_tiles(const SelfTiles a, const double *state, const float *dmin,
                                                            double *slab /* [split][2][N] */) {
     __shared__ __attribute__((aligned(16))) float smem[2 * kTile * kLd];
     __shared__ float tns[kTile];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
-    const int64_t q0 = (int64_t)blockIdx.x * kTile;
-    const int64_t t_begin = (int64_t)blockIdx.y * a.split_rows;
-    const int64_t t_end = min(a.N, t_begin + a.split_rows);
-    const int64_t myq = q0 + 16 * w + n;
+    const TilePos p(a.split_rows, a.N);
+    const int64_t myq = p.myq;
     const bool mine = myq < a.N;
     const float qnorm = mine ? a.xn[myq] : 0.f;
     const float m = mine ? dmin[myq] : 0.f;
     const float nbl2 = mine ? -tsne_bl2(tsne_beta32(state[myq])) : 0.f;
     double Z = 0.0, E = 0.0;
     bool staged = false;
-    for (int64_t t0 = t_begin; t0 < t_end; t0 += kTile) {
+    for (int64_t t0 = p.t_begin; t0 < p.t_end; t0 += kTile) {
         float4_t acc[4];
-        tsne_product(acc, smem, tns, a, q0, t0, t_end, staged, [] {});
+        pair_product<false>(acc, smem, tns, a.rows(p.t_end), a.cols(), a.D, p.q0, t0, staged, [] {});
         float z = 0.f, e = 0.f;
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int tl = 16 * j + 4 * g + r;
-                if (t0 + tl < t_end && t0 + tl != myq) {
-                    const float x = fmaxf(tsne_d2(qnorm, tns[tl], acc[j][r]) - m, 0.f);
-                    const float t = __builtin_amdgcn_exp2f(nbl2 * x);
-                    z += t;
-                    e = __builtin_fmaf(x, t, e);
-                }
+        for_pairs(p.g, t0, p.t_end, [&](int j, int r, int tl, int64_t col) {
+            if (col != myq) {
+                const float x = fmaxf(tsne_d2(qnorm, tns[tl], acc[j][r]) - m, 0.f);
+                const float t = __builtin_amdgcn_exp2f(nbl2 * x);
+                z += t;
+                e = __builtin_fmaf(x, t, e);
             }
+        });
         Z += (double)z;
         E += (double)e;
     }
-    Z = tsne_row4(Z);
-    E = tsne_row4(E);
-    if (g == 0 && mine) {
+    Z = row4_sum(Z);
+    E = row4_sum(E);
+    if (p.g == 0 && mine) {
         slab[((size_t)blockIdx.y * 2 + 0) * a.N + myq] = Z;
         slab[((size_t)blockIdx.y * 2 + 1) * a.N + myq] = E;
     }
@@ -698,7 +710,7 @@ __global__ __launch_bounds__(kBlock) void tsne_calib_update(const double *slab, 
 }
 
 struct TsneStepArgs {
-    TsneTiles t;
+    SelfTiles t;
     const float *beta, *dmin, *zsum, *Y;
     float scale, floor;      // e / (2 N) and e 2^-52: e p_ij = max((c_ij + c_ji) scale, floor)
     double *slab;            // [split][kTsneSums or kTsneSumsKL][N]
@@ -736,12 +748,9 @@ __global__ __launch_bounds__(kBlock) void tsne_step_tiles(const TsneStepArgs a) 
     constexpr int NS = KL ? kTsneSumsKL : kTsneSums;
     __shared__ __attribute__((aligned(16))) float smem[2 * kTile * kLd];
     __shared__ __attribute__((aligned(16))) float cp[6][kTile];      // column rows: norm, -beta log2 e, m, 1 / Z, y0, y1
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
-    const int64_t N = a.t.N;
-    const int64_t q0 = (int64_t)blockIdx.x * kTile;
-    const int64_t t_begin = (int64_t)blockIdx.y * a.t.split_rows;
-    const int64_t t_end = min(N, t_begin + a.t.split_rows);
-    const int64_t myq = q0 + 16 * w + n;
+    const TilePos p(a.t.split_rows, a.t.N);
+    const int w = p.w, g = p.g;
+    const int64_t N = a.t.N, t_end = p.t_end, myq = p.myq;
     const bool mine = myq < N;
     const float qnorm = mine ? a.t.xn[myq] : 0.f;
     const float nbl2 = mine ? -tsne_bl2(a.beta[myq]) : 0.f, m = mine ? a.dmin[myq] : 0.f;
@@ -751,9 +760,9 @@ __global__ __launch_bounds__(kBlock) void tsne_step_tiles(const TsneStepArgs a) 
 #pragma unroll
     for (int e = 0; e < NS; ++e) sum[e] = 0.0;
     bool staged = false;
-    for (int64_t t0 = t_begin; t0 < t_end; t0 += kTile) {
+    for (int64_t t0 = p.t_begin; t0 < t_end; t0 += kTile) {
         float4_t acc[4];
-        const int nj = tsne_product(acc, smem, cp[0], a.t, q0, t0, t_end, staged, [&] {
+        const int nj = pair_product<false>(acc, smem, cp[0], a.t.rows(t_end), a.t.cols(), a.t.D, p.q0, t0, staged, [&] {
             const int r = threadIdx.x & 63;
             const int64_t row = t0 + r;
             const bool in = row < t_end;
@@ -768,6 +777,7 @@ __global__ __launch_bounds__(kBlock) void tsne_step_tiles(const TsneStepArgs a) 
             }
         });
         TsnePairSums s = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        // not for_pairs: six column vectors are read once per 16-row tile, and the walk ends at the last tile in use
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j >= nj) break;
@@ -793,39 +803,18 @@ __global__ __launch_bounds__(kBlock) void tsne_step_tiles(const TsneStepArgs a) 
     }
 #pragma unroll
     for (int e = 0; e < NS; ++e) {
-        const double v = tsne_row4(sum[e]);
+        const double v = row4_sum(sum[e]);
         if (g == 0 && mine) a.slab[((size_t)blockIdx.y * NS + e) * N + myq] = v;
     }
 }
 
 // W_i from the slabs in split order, and the sum of a workgroup's rows in row order
 __global__ __launch_bounds__(kBlock) void tsne_rowsum_parts(const double *slab, int nsplit, int ns, int64_t N, double *part) {
-    __shared__ double ps[kBlock];
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     double s = 0.0;
     if (i < N)
         for (int sp = 0; sp < nsplit; ++sp) s += slab[((size_t)sp * ns + 4) * N + i];
-    ps[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int e = 0; e < kBlock; ++e) t += ps[e];
-        part[blockIdx.x] = t;
-    }
-}
-
-// workgroup b: out[b] = the partials part[b * nparts ..), each thread its own in order, then the 256 threads in order
-__global__ __launch_bounds__(kBlock) void tsne_total(const double *part, int64_t nparts, double *out) {
-    __shared__ double ps[kBlock];
-    double t = 0.0;
-    for (int64_t e = threadIdx.x; e < nparts; e += kBlock) t += part[(int64_t)blockIdx.x * nparts + e];
-    ps[threadIdx.x] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int e = 0; e < kBlock; ++e) s += ps[e];
-        out[blockIdx.x] = s;
-    }
+    block_sums({s}, &part[blockIdx.x], 0);
 }
 
 // _gradient_descent's update of one coordinate, every product and sum rounded on its own; returns gains * grad
@@ -855,7 +844,6 @@ struct TsneUpdateArgs {
 // a thread per row: A and R from the slabs in split order, grad = 4 (A - R / Z_q), the update rule, and the
 // workgroup's partials of |gains * grad|^2 and of the KL sum in row order
 __global__ __launch_bounds__(kBlock) void tsne_update(const TsneUpdateArgs a) {
-    __shared__ double pn[kBlock], pk[kBlock];
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     double nrm = 0.0, kl = 0.0;
     if (i < a.N) {
@@ -874,18 +862,20 @@ __global__ __launch_bounds__(kBlock) void tsne_update(const TsneUpdateArgs a) {
         }
         kl = s[5] + log(zq) * s[6];
     }
-    pn[threadIdx.x] = nrm;
-    pk[threadIdx.x] = kl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0, u = 0.0;
-        for (int e = 0; e < kBlock; ++e) { t += pn[e]; u += pk[e]; }
-        a.part[blockIdx.x] = t;
-        a.part[a.nparts + blockIdx.x] = u;
-    }
+    block_sums({nrm, kl}, a.part + blockIdx.x, a.nparts);
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// a workspace, region by region: add() gives the next region's offset; every region starts on a 256-byte boundary
+struct Regions {
+    size_t bytes = 0;
+    size_t add(size_t b) { return std::exchange(bytes, bytes + ((b + 255) & ~(size_t)255)); }
+};
+
+// |row|^2 of M's n rows into `out`; returns the grid of a tile kernel with them on the column axis: (row tiles, splits)
+inline dim3 norms_and_grid(const float *M, int64_t ld, int64_t n, int D, float *out, int nsplit, hipStream_t st) {
+    row_norms<<<han_grid_for(n, kBlock / 16, 8192), kBlock, 0, st>>>(M, ld, n, D, out);
+    return dim3((unsigned)((n + kTile - 1) / kTile), (unsigned)nsplit);
+}
 
 // train-set splits of a KNN call: enough workgroups to fill the device when there are few queries
 inline int knn_splits(int64_t Nq, int64_t Nt, int64_t *split_rows) {
@@ -900,6 +890,27 @@ inline int knn_splits(int64_t Nq, int64_t Nt, int64_t *split_rows) {
     return (int)((Nt + rows - 1) / rows);
 }
 
+// Every workspace starts with the norms of the column rows (offset 0).  KNN: then the train rows' norms and, with more
+// than one split, the splits' lists [split][Nq][k]: indices, then distances.
+struct KnnPlan {
+    int64_t split_rows;
+    int nsplit;
+    size_t off_tn, off_idx, off_d2, bytes;
+};
+
+inline KnnPlan knn_plan(int64_t Nq, int64_t Nt, int k) {
+    KnnPlan p;
+    Regions r;
+    p.nsplit = knn_splits(Nq, Nt, &p.split_rows);
+    const size_t lists = p.nsplit > 1 ? (size_t)p.nsplit * Nq * k * sizeof(float) : 0;
+    r.add((size_t)Nq * sizeof(float));
+    p.off_tn = r.add((size_t)Nt * sizeof(float));
+    p.off_idx = r.add(lists);
+    p.off_d2 = r.add(lists);
+    p.bytes = r.bytes;
+    return p;
+}
+
 struct KmeansPlan {
     int64_t tiles, tiles_per_block, rows_per_block;
     int assign_blocks, sum_blocks, dp;
@@ -908,6 +919,7 @@ struct KmeansPlan {
 
 inline KmeansPlan kmeans_plan(int64_t N, int D, int k) {
     KmeansPlan p;
+    Regions r;
     p.tiles = (N + kTile - 1) / kTile;
     p.assign_blocks = (int)(p.tiles < kAssignCap ? (p.tiles < 1 ? 1 : p.tiles) : kAssignCap);
     p.tiles_per_block = (p.tiles + p.assign_blocks - 1) / p.assign_blocks;
@@ -921,14 +933,13 @@ inline KmeansPlan kmeans_plan(int64_t N, int D, int k) {
     if (sb < 1) sb = 1;
     p.sum_blocks = (int)sb;
     p.rows_per_block = (N + sb - 1) / sb;
-    p.off_cn = align256((size_t)N * sizeof(float));
-    p.off_part = p.off_cn + align256(kMaxCentres * sizeof(float));
-    p.off_slab = p.off_part + align256((size_t)kAssignCap * sizeof(double));
-    p.bytes = p.off_slab + align256((size_t)p.sum_blocks * slab_bytes);
+    r.add((size_t)N * sizeof(float));
+    p.off_cn = r.add(kMaxCentres * sizeof(float));
+    p.off_part = r.add((size_t)kAssignCap * sizeof(double));
+    p.off_slab = r.add((size_t)p.sum_blocks * slab_bytes);
+    p.bytes = r.bytes;
     return p;
 }
-
-inline int norms_grid(int64_t n) { return han_grid_for(n, kBlock / 16, 8192); }
 
 // the column range of a silhouette call is split like the train set of a KNN call; slabs only with more than one split
 struct SilPlan {
@@ -939,12 +950,14 @@ struct SilPlan {
 
 inline SilPlan sil_plan(int64_t N, int k) {
     SilPlan p;
+    Regions r;
     p.nsplit = knn_splits(N, N, &p.split_rows);
     p.finish_blocks = (N + kBlock - 1) / kBlock;
-    p.off_ab = align256((size_t)N * sizeof(float));
-    p.off_part = p.off_ab + align256((size_t)2 * N * sizeof(double));
-    p.off_slab = p.off_part + align256((size_t)p.finish_blocks * sizeof(double));
-    p.bytes = p.off_slab + (p.nsplit > 1 ? align256((size_t)p.nsplit * k * N * sizeof(double)) : 0);
+    r.add((size_t)N * sizeof(float));
+    p.off_ab = r.add((size_t)2 * N * sizeof(double));
+    p.off_part = r.add((size_t)p.finish_blocks * sizeof(double));
+    p.off_slab = r.add(p.nsplit > 1 ? (size_t)p.nsplit * k * N * sizeof(double) : 0);
+    p.bytes = r.bytes;
     return p;
 }
 
@@ -957,11 +970,13 @@ struct TsnePlan {
 
 inline TsnePlan tsne_plan(int64_t N) {
     TsnePlan p;
+    Regions r;
     p.nsplit = knn_splits(N, N, &p.split_rows);
     p.row_blocks = (N + kBlock - 1) / kBlock;
-    p.off_part = align256((size_t)N * sizeof(float));
-    p.off_slab = p.off_part + align256((size_t)2 * p.row_blocks * sizeof(double));
-    p.bytes = p.off_slab + align256((size_t)p.nsplit * kTsneSumsKL * N * sizeof(double));
+    r.add((size_t)N * sizeof(float));
+    p.off_part = r.add((size_t)2 * p.row_blocks * sizeof(double));
+    p.off_slab = r.add((size_t)p.nsplit * kTsneSumsKL * N * sizeof(double));
+    p.bytes = r.bytes;
     return p;
 }
 
@@ -969,11 +984,7 @@ inline TsnePlan tsne_plan(int64_t N) {
 
 extern "C" size_t han_knn_topk_workspace(int64_t Nq, int64_t Nt, int D, int k) {
     if (Nq <= 0 || Nt <= 0 || D < 1 || k < 1) return 0;
-    int64_t rows;
-    const int ns = knn_splits(Nq, Nt, &rows);
-    size_t b = align256((size_t)Nq * sizeof(float)) + align256((size_t)Nt * sizeof(float));
-    if (ns > 1) b += 2 * align256((size_t)ns * Nq * k * sizeof(float));
-    return b;
+    return knn_plan(Nq, Nt, k).bytes;
 }
 
 extern "C" int han_knn_topk(const float *Q, int64_t ldq, const float *T, int64_t ldt, int32_t *idx, float *d2,
@@ -983,25 +994,18 @@ extern "C" int han_knn_topk(const float *Q, int64_t ldq, const float *T, int64_t
     if (k > kMaxK || D > kMaxD || Nt > 0x7FFFFFFF) return HAN_E_UNSUPPORTED;
     if (Nq == 0) return 0;
     if (!Q || !T || !idx || !d2 || !workspace) return HAN_E_BADARG;
-    if (workspace_bytes < han_knn_topk_workspace(Nq, Nt, D, k)) return HAN_E_WORKSPACE;
+    const KnnPlan p = knn_plan(Nq, Nt, k);
+    if (workspace_bytes < p.bytes) return HAN_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    int64_t rows;
-    const int ns = knn_splits(Nq, Nt, &rows);
+    const int ns = p.nsplit;
     char *ws = (char *)workspace;
-    float *qn = (float *)ws;
-    float *tn = (float *)(ws + align256((size_t)Nq * sizeof(float)));
-    char *parts = (char *)tn + align256((size_t)Nt * sizeof(float));
-    const size_t part_bytes = align256((size_t)ns * Nq * k * sizeof(float));
-    row_norms<<<norms_grid(Nq), kBlock, 0, st>>>(Q, ldq, Nq, D, qn);
+    float *qn = (float *)ws, *tn = (float *)(ws + p.off_tn);
+    const dim3 grid = norms_and_grid(Q, ldq, Nq, D, qn, ns, st);
     HAN_CHECK_LAUNCH();
-    row_norms<<<norms_grid(Nt), kBlock, 0, st>>>(T, ldt, Nt, D, tn);
+    norms_and_grid(T, ldt, Nt, D, tn, 1, st);
     HAN_CHECK_LAUNCH();
-    KnnArgs a;
-    a.Q = Q; a.T = T; a.qn = qn; a.tn = tn; a.ldq = ldq; a.ldt = ldt; a.Nq = Nq; a.Nt = Nt; a.split_rows = rows;
-    a.D = D; a.k = k;
-    a.out_idx = ns > 1 ? (int32_t *)parts : idx;
-    a.out_d2 = ns > 1 ? (float *)(parts + part_bytes) : d2;
-    const dim3 grid((unsigned)((Nq + kTile - 1) / kTile), (unsigned)ns);
+    const KnnArgs a = {Q, T, qn, tn, ldq, ldt, Nq, Nt, p.split_rows, D, k,
+                       ns > 1 ? (int32_t *)(ws + p.off_idx) : idx, ns > 1 ? (float *)(ws + p.off_d2) : d2};
     const int64_t mgrid = (Nq + kBlock - 1) / kBlock;
 #define HAN_KNN_LAUNCH(KC)                                                                                        \
     do {                                                                                                          \
@@ -1073,9 +1077,9 @@ extern "C" int han_kmeans_step(const float *X, int64_t ldx, const float *C, cons
     char *ws = (char *)workspace;
     float *xn = (float *)ws, *cn = (float *)(ws + p.off_cn);
     double *part = (double *)(ws + p.off_part), *slab = (double *)(ws + p.off_slab);
-    row_norms<<<norms_grid(N), kBlock, 0, st>>>(X, ldx, N, D, xn);
+    norms_and_grid(X, ldx, N, D, xn, 1, st);
     HAN_CHECK_LAUNCH();
-    row_norms<<<norms_grid(k), kBlock, 0, st>>>(C, D, k, D, cn);
+    norms_and_grid(C, D, k, D, cn, 1, st);
     HAN_CHECK_LAUNCH();
     AssignArgs a;
     a.X = X; a.C = C; a.xn = xn; a.cn = cn; a.ldx = ldx; a.N = N; a.tiles = p.tiles; a.tiles_per_block = p.tiles_per_block;
@@ -1112,16 +1116,14 @@ extern "C" int han_silhouette(const float *X, int64_t ldx, const int64_t *seg_pt
     float *xn = (float *)ws;
     double *ab = (double *)(ws + p.off_ab), *part = (double *)(ws + p.off_part);
     double *slab = p.nsplit > 1 ? (double *)(ws + p.off_slab) : nullptr;
-    row_norms<<<norms_grid(N), kBlock, 0, st>>>(X, ldx, N, D, xn);
+    const dim3 grid = norms_and_grid(X, ldx, N, D, xn, p.nsplit, st);
     HAN_CHECK_LAUNCH();
-    SilArgs t;
-    t.X = X; t.xn = xn; t.seg = seg_ptr; t.ldx = ldx; t.N = N; t.split_rows = p.split_rows; t.D = D; t.k = k;
-    t.slab = slab; t.ab = ab;
-    sil_tiles<<<dim3((unsigned)((N + kTile - 1) / kTile), (unsigned)p.nsplit), kBlock, 0, st>>>(t);
+    const SilArgs t = {{X, xn, ldx, N, p.split_rows, D}, seg_ptr, k, slab, ab};
+    sil_tiles<<<grid, kBlock, 0, st>>>(t);
     HAN_CHECK_LAUNCH();
     sil_finish<<<(unsigned)p.finish_blocks, kBlock, 0, st>>>(seg_ptr, k, N, slab, p.nsplit, ab, a, b, s, part);
     HAN_CHECK_LAUNCH();
-    sil_total<<<1, kBlock, 0, st>>>(part, p.finish_blocks, sum);
+    block_totals<<<1, kBlock, 0, st>>>(part, p.finish_blocks, sum);
     HAN_CHECK_LAUNCH();
     return 0;
 }
@@ -1145,10 +1147,8 @@ extern "C" int han_tsne_calibrate(const float *X, int64_t ldx, int64_t N, int D,
     char *ws = (char *)workspace;
     float *xn = (float *)ws;
     double *slab = (double *)(ws + p.off_slab);
-    TsneTiles t;
-    t.X = X; t.xn = xn; t.ldx = ldx; t.N = N; t.split_rows = p.split_rows; t.D = D;
-    const dim3 grid((unsigned)((N + kTile - 1) / kTile), (unsigned)p.nsplit);
-    row_norms<<<norms_grid(N), kBlock, 0, st>>>(X, ldx, N, D, xn);
+    const SelfTiles t = {X, xn, ldx, N, p.split_rows, D};
+    const dim3 grid = norms_and_grid(X, ldx, N, D, xn, p.nsplit, st);
     HAN_CHECK_LAUNCH();
     if (restart) {
         tsne_rowmin_tiles<<<grid, kBlock, 0, st>>>(t, (float *)slab);
@@ -1184,20 +1184,16 @@ extern "C" int han_tsne_step(const float *X, int64_t ldx, const float *beta, con
     float *xn = (float *)ws;
     double *part = (double *)(ws + p.off_part), *slab = (double *)(ws + p.off_slab);
     const int ns = want_kl ? kTsneSumsKL : kTsneSums;
-    TsneStepArgs a;
-    a.t.X = X; a.t.xn = xn; a.t.ldx = ldx; a.t.N = N; a.t.split_rows = p.split_rows; a.t.D = D;
-    a.beta = beta; a.dmin = dmin; a.zsum = zsum; a.Y = Y; a.slab = slab;
-    a.scale = (float)((double)exaggeration / (2.0 * (double)N));
-    a.floor = exaggeration * 0x1p-52f;
-    const dim3 grid((unsigned)((N + kTile - 1) / kTile), (unsigned)p.nsplit);
-    row_norms<<<norms_grid(N), kBlock, 0, st>>>(X, ldx, N, D, xn);
+    const TsneStepArgs a = {{X, xn, ldx, N, p.split_rows, D}, beta, dmin, zsum, Y,
+                            (float)((double)exaggeration / (2.0 * (double)N)), exaggeration * 0x1p-52f, slab};
+    const dim3 grid = norms_and_grid(X, ldx, N, D, xn, p.nsplit, st);
     HAN_CHECK_LAUNCH();
     if (want_kl) tsne_step_tiles<true><<<grid, kBlock, 0, st>>>(a);
     else tsne_step_tiles<false><<<grid, kBlock, 0, st>>>(a);
     HAN_CHECK_LAUNCH();
     tsne_rowsum_parts<<<(unsigned)p.row_blocks, kBlock, 0, st>>>(slab, p.nsplit, ns, N, part);
     HAN_CHECK_LAUNCH();
-    tsne_total<<<1, kBlock, 0, st>>>(part, p.row_blocks, stats);
+    block_totals<<<1, kBlock, 0, st>>>(part, p.row_blocks, stats);
     HAN_CHECK_LAUNCH();
     TsneUpdateArgs u;
     u.slab = slab; u.zq = stats; u.nsplit = p.nsplit; u.ns = ns; u.N = N; u.nparts = p.row_blocks;
@@ -1205,7 +1201,7 @@ extern "C" int han_tsne_step(const float *X, int64_t ldx, const float *beta, con
     u.momentum = momentum; u.lr = lr; u.min_gain = min_gain; u.part = part;
     tsne_update<<<(unsigned)p.row_blocks, kBlock, 0, st>>>(u);
     HAN_CHECK_LAUNCH();
-    tsne_total<<<want_kl ? 2 : 1, kBlock, 0, st>>>(part, p.row_blocks, stats + 1);
+    block_totals<<<want_kl ? 2 : 1, kBlock, 0, st>>>(part, p.row_blocks, stats + 1);
     HAN_CHECK_LAUNCH();
     return 0;
 }
