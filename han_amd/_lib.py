@@ -82,6 +82,8 @@ SIGNATURES = {
     "han_sem_attn_bwd_rows_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
     "han_sem_attn_bwd_rows": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int,
                                       c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "han_sem_attn_bwd_rows_live": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P, I64, I64,
+                                           c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "han_classifier_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
     "han_classifier_loss": (c_int, [P, P, P, P, P, c_float, P, P, P, P, P, P, c_size_t, I64,
                                     c_int, c_int, c_int, P]),

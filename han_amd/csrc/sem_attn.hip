@@ -1986,8 +1986,10 @@ hipError_t launch_bwd_wave(K3Bwd &a) {
 }
 
 // shapes of the fold (han_sem_attn_bwd_rows): the one-wave bf16-pipe kernel with a node's rows inside a lane group
-bool k3_fold_ok(int64_t N, int P, int D, int A, int flags) {
-    return D == 64 && (A == 64 || A == 128) && (P == 1 || P == 2 || P == 4) && k3_b6(N, P, flags) &&
+// (the row list of han_sem_attn_bwd_rows_live has no least length: `any_count`)
+bool k3_fold_ok(int64_t N, int P, int D, int A, int flags, bool any_count = false) {
+    return D == 64 && (A == 64 || A == 128) && (P == 1 || P == 2 || P == 4) &&
+           (any_count ? !(flags & HAN_FLAG_K3_EXACT_PIPE) : k3_b6(N, P, flags)) &&
            !(flags & (HAN_FLAG_K3_PAIRS | HAN_FLAG_K3_G3_F32)) && N * kFoldRowBytes < ((int64_t)1 << 32);      // 32-bit table offsets
 }
 constexpr int k3_fold_slab_width(int P, int A) { return 64 * A + 2 * A + 64 * P; }
@@ -1999,6 +2001,17 @@ hipError_t launch_bwd_fold(K3Bwd &a, const K3FoldArgs &fa) {
     const size_t lds = B6BwdLds<64 * CA>::bytes + (size_t)a.P * 64 * sizeof(float);      // + c
     HAN_DISPATCH_P(a.P, if constexpr (PC <= 4) e = han_launch_lds(sem_attn_bwd_wave_b6_fold_kernel<CA, PC>, a.grid, 256, lds, a.st,
                                                                  a.M, a.w, a.b, a.u, a.beta, a.dZ, a.slab, a.N, fa));
+    return e;
+}
+
+// ... over a row list: a.N is the list's length, and the grid and the slab rows follow it
+template <int CA>
+hipError_t launch_bwd_fold_live(K3Bwd &a, const K3FoldLiveArgs &fa) {
+    hipError_t e = hipSuccess;
+    a.grid = bwd_wave_grid(a);
+    const size_t lds = B6BwdLds<64 * CA>::bytes + (size_t)a.P * 64 * sizeof(float) + kFoldRingBytes;      // + c + the id ring
+    HAN_DISPATCH_P(a.P, if constexpr (PC <= 4) e = han_launch_lds(sem_attn_bwd_wave_b6_live_kernel<CA, PC>, a.grid, 256, lds,
+                                                                 a.st, a.M, a.w, a.b, a.u, a.beta, a.dZ, a.slab, a.N, fa));
     return e;
 }
 
@@ -2124,4 +2137,49 @@ extern "C" int han_sem_attn_bwd_rows(const float *M, const float *w_omega, const
     o.seg_end[0] = D * A; o.seg_end[1] = D * A + A; o.seg_end[2] = wpar; o.seg_end[3] = width;
     o.nseg = 4;
     return (int)han_reduce_slabs(a.slab, a.grid, width, width, o, (hipStream_t)stream);
+}
+
+extern "C" int han_sem_attn_bwd_rows_live(const float *M, const float *w_omega, const float *b_omega, const float *u_omega,
+                                          const float *beta, const float *dZ, const float *const *aggp,
+                                          const float *const *tsum, const float *const *f1, const float *const *lse,
+                                          const float *c, void *const *gs, float *const *df1, float *dw_omega,
+                                          float *db_omega, float *du_omega, float *dc, void *workspace,
+                                          size_t workspace_bytes, const int32_t *live, int64_t n_live, int64_t N, int P,
+                                          int D, int A, int K, int FP, int table_dtype, int activation, int flags,
+                                          void *stream) {
+    if (!M || !w_omega || !b_omega || !u_omega || !beta || !dZ || !aggp || !tsum || !f1 || !lse || !c || !gs || !df1 ||
+        !dw_omega || !db_omega || !du_omega || !dc || !workspace || N < 0 || P <= 0 || n_live < 0 || n_live > N ||
+        (n_live > 0 && !live))
+        return HAN_E_BADARG;
+    if (!k3_fold_ok(N, P, D, A, flags, true) || K != 8 || FP != 8 || table_dtype != HAN_DTYPE_F32 ||
+        (activation != HAN_ACT_ELU && activation != HAN_ACT_IDENTITY))
+        return HAN_E_UNSUPPORTED;
+    K3FoldLiveArgs fa = {};
+    for (int p = 0; p < P; ++p) {
+        if (!aggp[p] || !tsum[p] || !f1[p] || !lse[p] || !gs[p] || !df1[p]) return HAN_E_BADARG;
+        fa.aggp[p] = aggp[p]; fa.tsum[p] = tsum[p]; fa.f1[p] = f1[p]; fa.lse[p] = lse[p];
+        fa.gs[p] = (char *)gs[p]; fa.df1[p] = df1[p];
+    }
+    fa.c = c;
+    fa.act = activation;
+    fa.live = live;
+    if (workspace_bytes < han_sem_attn_bwd_rows_workspace(N, P, D, A)) return HAN_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_live == 0) {      // no row, no launch: the sums over no rows
+        hipError_t e = hipMemsetAsync(dw_omega, 0, (size_t)D * A * sizeof(float), st);
+        if (e == hipSuccess) e = hipMemsetAsync(db_omega, 0, (size_t)A * sizeof(float), st);
+        if (e == hipSuccess) e = hipMemsetAsync(du_omega, 0, (size_t)A * sizeof(float), st);
+        if (e == hipSuccess) e = hipMemsetAsync(dc, 0, (size_t)P * 64 * sizeof(float), st);
+        return (int)e;
+    }
+    K3Bwd a = {M, w_omega, b_omega, u_omega, beta, dZ, nullptr, (float *)workspace, n_live, P, D, A, flags, st, 0};
+    hipError_t e = hipSuccess;
+    HAN_DISPATCH_CA(A, if constexpr (CA <= 2) e = launch_bwd_fold_live<CA>(a, fa));
+    if (e != hipSuccess) return (int)e;
+    const int wpar = D * A + 2 * A, width = k3_fold_slab_width(P, A);
+    HanReduceOut o = han_reduce_to(dw_omega, width);
+    o.ptr[1] = db_omega; o.ptr[2] = du_omega; o.ptr[3] = dc;
+    o.seg_end[0] = D * A; o.seg_end[1] = D * A + A; o.seg_end[2] = wpar; o.seg_end[3] = width;
+    o.nseg = 4;
+    return (int)han_reduce_slabs(a.slab, a.grid, width, width, o, st);
 }

@@ -92,6 +92,8 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         self.masked_bwd = None                # per-meta-path MaskedBackwardPlan list (HANTrainer(masked_backward=True))
         self.zero_rows = False                # set by HANTrainer: one node-attention layer and a loss mask of at most half of the rows, so most
                                               # backward rows g_i are zero and the backward gather is told to honour z (HAN_FLAG_K2_ZERO_ROWS)
+        self.live_bwd = None                  # layers.LiveBackwardPlan (HANTrainer(live_backward=...)): the backward of the single node-attention layer and
+                                              # of K3 visits only the rows of the train mask; masked_bwd, when set, wins
         self.path_streams = None              # one stream per meta-path (HANTrainer(use_graph=True)): layers._each_path
         self.path_order = "index"             # "heavy": the per-meta-path chains of a captured epoch are issued largest graph first (layers._path_order)
         self.overlap_branch = None            # HANTrainer(overlap_eval=True): the eval forward riding in the captured training step (trainer._EvalBranch)
@@ -291,6 +293,7 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
                 layer=layer, table_dtype=self.table_dtype, plans_f=self.halo_plans[0], plans_b=self.halo_plans[1],
                 xs_full=xs_full if first else None, masked_bwd=self.masked_bwd if (first and train) else None,
                 zero_rows=bool(self.zero_rows and first and train and not self.extra),
+                live_bwd=self.live_bwd if (first and train and not self.extra and self.masked_bwd is None) else None,
                 streams=self.path_streams, side_stream=self.side_stream, path_order=self.path_order,
                 overlap=self.overlap_branch if (first and train) else None, **kw)
 

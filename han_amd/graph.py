@@ -55,6 +55,7 @@ class CSRGraph:
         self._split = {}
         self._locality = None
         self.masked = False         # True: colidx holds -1 for skipped entries (with_masked_columns)
+        self.empty_rows_mid = False  # True: row_bins lists the empty rows with the mid rows (with_live_columns)
         if validate:
             self.validate()
 
@@ -105,6 +106,26 @@ class CSRGraph:
         g.masked = True
         return g
 
+    def with_live_columns(self, live_mask: torch.Tensor) -> "CSRGraph":
+        """The same rows and the same n_cols with only the entries whose column is live (live_mask (n_cols,), non-zero
+        = live): entry order inside a row kept, column ids unchanged -- they stay dropout keys and table indices --,
+        `values` filtered alike.  An ordinary graph (row_bins / row_split work and are cached): the transposed graph
+        of a backward whose dead destinations contribute exact zeros (HANTrainer(live_backward=...))."""
+        live_mask = live_mask.to(self.device)
+        if live_mask.shape != (self.n_cols,):
+            raise ValueError(f"live_mask: expected ({self.n_cols},), got {tuple(live_mask.shape)}")
+        keep = (live_mask != 0)[self.colidx.long()]
+        counts = torch.bincount(csr.row_ids(self.rowptr)[keep], minlength=self.n_rows)
+        g = CSRGraph(csr.scan(counts), self.colidx[keep].contiguous(), self.n_cols, validate=False,
+                     values=self.values[keep] if self.values is not None else None, row_base=self.row_base)
+        # In a four-rows-a-wave launch the slots of an EMPTY row have no entry of their own to fall back on and read the
+        # statistics record of table row 0 (times an exact zero -- for a finite record).  Here row 0 may be a row nobody
+        # writes, so the empty rows go with the wave-a-row launch, which reads nothing for them: the table rows outside
+        # the live set are then never read.  (Slots past the end of a non-empty row re-read the row's last entry.)
+        g.empty_rows_mid = True
+        g._locality = self.has_locality()      # a subset of the entries: as near to the row ids, or as far, as they were
+        return g
+
     def has_empty_rows(self) -> bool:
         return self.n_rows > 0 and bool((self.degrees() == 0).any())
 
@@ -130,14 +151,14 @@ class CSRGraph:
 
     def row_bins(self, short_deg: int = 16, split_deg: int = 1024):
         """Degree bins of the rows (han_row_split_t: short_rows / mid_rows): rows with fewer than `short_deg` entries
-        (incl. empty rows), ordered by ceil(deg / 4) and then id -- four of them share a wave, one 16-lane group
+        (incl. empty rows; a graph with empty_rows_mid lists those with the next bin), ordered by ceil(deg / 4) and then id -- four of them share a wave, one 16-lane group
         each, and should need the same number of 4-entry steps --, rows of short_deg .. split_deg entries in id order
         (a wave each), rows beyond split_deg (row_split's chunks).  Returns dict(n_short, short_rows, n_mid, mid_rows)
         with int32 device tensors; a list is None when its bin holds EVERY row (identity).  Cached."""
         key = ("bins", int(short_deg), int(split_deg))
         if key not in self._split:
             deg = self.degrees()
-            is_short = deg < short_deg
+            is_short = (deg < short_deg) & (deg > 0) if self.empty_rows_mid else deg < short_deg
             is_mid = (~is_short) & (deg <= split_deg)
             n_short, n_mid = int(is_short.sum()), int(is_mid.sum())
             short_rows = mid_rows = None

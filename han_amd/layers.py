@@ -182,6 +182,7 @@ class LayerRun:
     coef_sink: list | None = None     # receives per meta-path the coefficients of this call as data -- (E,K), or their
     coef_mean: bool = False           # head mean (E,) with coef_mean (return_coef of layers.py:43-44 / models/gat.py:143-172; single GPU only)
     fold_sink: list | None = None     # HeteGAT_multi.fold_k3: receives this call's FoldTail when its row-local backward may run in the K3 backward
+    live_bwd: object = None           # LiveBackwardPlan (HANTrainer(live_backward=...)): the backward visits only the rows the loss reaches
 
     @functools.cached_property
     def multi(self) -> bool:
@@ -221,7 +222,43 @@ class LayerRun:
         """(table source, kind of exchange tag) of meta-path p's backward table [g | stats]."""
         if masked and self.masked_bwd is not None and self.masked_bwd[p] is not None:
             return self.masked_bwd[p], "bm"      # opt-in: only the live rows are read / travel
+        if masked and self.live_bwd is not None:
+            return self.live_bwd.source(p, graph_t), "bl"      # the entries with a live destination, and no other
         return self._source(self.plans_b, p, graph_t), "b"
+
+
+class LiveBackwardPlan:
+    """Set-up-time plan of a backward that visits only the rows the loss reaches (HANTrainer(live_backward=...); single
+    process, one node-attention layer): with a row-local classifier and K3, dZ_i, dM_i and g_i are exactly zero for every
+    node i outside the train mask, which never changes.  `live`: the ascending int32 ids of the masked-in rows -- the row
+    list of the K3 backward (ops.sem_attn_bwd_rows(live=...)); `graphs_t`: per meta-path the transposed graph with only
+    the entries whose destination is live (CSRGraph.with_live_columns) -- the gather walks these and never meets a dead
+    entry, so rows of the [g | stats] tables outside `live` are never read and need not be written; df1(K): per
+    meta-path a persistent (N,K) buffer, zeroed once: the K3 backward writes its live rows, and the dead rows, which
+    the gather's write_src and score_param_bwd read for every source row, stay the zeros they are in the full backward."""
+
+    def __init__(self, graphs_t, train_mask):
+        mask = train_mask != 0
+        self.live = torch.nonzero(mask).flatten().to(torch.int32).contiguous()
+        self.full_t = tuple(graphs_t)
+        self.graphs_t = tuple(g.with_live_columns(mask) for g in graphs_t)
+        self._sources = tuple(LocalTable(g) for g in self.graphs_t)
+        self.n_rows = int(mask.numel())
+        self._df1 = {}
+
+    def source(self, p, graph_t):
+        """Table source of meta-path p's live graph; `graph_t` is the transposed graph the step would gather over, which
+        must be the one the plan was built from."""
+        if graph_t is not self.full_t[p]:
+            raise RuntimeError("live_backward: the model runs on other graphs than the trainer's; the live transposed "
+                               "graphs were built from those (HANTrainer(live_backward=False) for free-form use)")
+        return self._sources[p]
+
+    def df1(self, K):
+        if K not in self._df1:
+            self._df1[K] = [torch.zeros((self.n_rows, K), dtype=torch.float32, device=self.live.device)
+                            for _ in self.graphs_t]
+        return self._df1[K]
 
 
 class FoldTail:
@@ -231,10 +268,11 @@ class FoldTail:
     here for NodeLevelAttention.backward, which goes on from the exchange of the tables.  Valid only while M has no
     other consumer: NodeLevelAttention.backward raises when the gradient it receives is not the placeholder the K3
     backward returned (_no_grad_of) -- autograd has then added another consumer's gradient to it."""
-    __slots__ = ("saved", "c", "dc", "act", "K", "FP", "gs", "df1")
+    __slots__ = ("saved", "c", "dc", "act", "K", "FP", "gs", "df1", "live")
 
-    def __init__(self, saved, c, dc, act, K, FP):
+    def __init__(self, saved, c, dc, act, K, FP, live=None):
         self.saved, self.c, self.dc, self.act, self.K, self.FP = saved, c, dc, act, K, FP
+        self.live = live               # LiveBackwardPlan or None: the K3 backward runs over its row list
         self.gs = self.df1 = None      # filled by SemanticAttention.backward
 
 
@@ -418,7 +456,8 @@ class NodeLevelAttention(torch.autograd.Function):
         ctx.tail = None
         if (run.fold_sink is not None and train and W.is_cuda and Wr is None and run.streams is None
                 and tdt == torch.float32):
-            ctx.tail = FoldTail(saved, c, ctx.direct[5] if ctx.direct is not None else None, run.act, K, FP)
+            ctx.tail = FoldTail(saved, c, ctx.direct[5] if ctx.direct is not None else None, run.act, K, FP,
+                                live=run.live_bwd if run.masked_bwd is None else None)
             run.fold_sink.append(ctx.tail)
         # M, the output, is backward state too (the pre-activation is recovered from it): saved through autograd, so
         # that an in-place change of M between forward and backward raises instead of giving wrong gradients
@@ -493,7 +532,8 @@ class NodeLevelAttention(torch.autograd.Function):
             src = srcs[p][0]
             dH, df2 = ops.node_attn_bwd_cols(src.graph, gs_h.wait(), sv.H, sv.f2, df1, a1[p], a2[p], coef_drop=coef_drop,
                                              fts_drop=in_drop, seed=seed, src_offset=row_offset, dst_offset=0,
-                                             table_gid=src.gid, seed_dev=seed_dev, **({"zero_rows": True} if run.zero_rows else {}))
+                                             table_gid=src.gid, seed_dev=seed_dev,
+                                             **({"zero_rows": True} if run.zero_rows and srcs[p][1] != "bl" else {}))
             rows[p] = None
             ops.score_param_bwd(sv.H, df1, df2, K=K, FP=FP, out=(da1[p], da2[p], db1[p], db2[p]))
             if side is not None and dXin is None:
@@ -699,7 +739,8 @@ class SemanticAttention(torch.autograd.Function):
             r = ops.sem_attn_bwd_rows(M, w, b, u, beta, dZ.contiguous(),
                                       [(sv.aggp, sv.tsum, sv.f1, sv.lse) for sv in tail.saved], tail.c.contiguous(), dc,
                                       activation=tail.act, K=tail.K, FP=tail.FP, table_dtype=tail.saved[0].H.dtype,
-                                      out=ctx.direct)
+                                      out=ctx.direct, **({} if tail.live is None else
+                                                         {"live": tail.live.live, "df1_out": tail.live.df1(tail.K)}))
             if r is not None:
                 tail.gs, tail.df1, tail.dc = r[0], r[1], dc
                 if ctx.direct is not None:

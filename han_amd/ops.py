@@ -660,7 +660,9 @@ def node_attn_bwd_cols(graph_t: CSRGraph, gs_tab, H, f2, df1, a1, a2, coef_drop=
     fts_drop = _check_drop(fts_drop, "fts_drop")
     dH = torch.empty((NS, D), dtype=torch.float32, device=dev)
     df2 = torch.empty((NS, K), dtype=torch.float32, device=dev)
-    lean_b = not graph_t.masked and _use_lean(graph_t, H)
+    # (a live graph, CSRGraph.with_live_columns, stays on the row / chunk kernels: the lean kernels read the whole row 0 of
+    # the table for every slot past the end of a row piece, and row 0 may be a row nobody has written there)
+    lean_b = not graph_t.masked and not graph_t.empty_rows_mid and _use_lean(graph_t, H)
     split, _keep = _row_split_arg(graph_t, "b", bins=not lean_b, split=not lean_b)
     dense, _keep_d = _dense_arg(graph_t, False, "b") if (lean_b and table_gid is None and _use_dense(graph_t, H, K, FP)) else (None, None)
     with _k2_timed("bwd_cols", NS, graph_t.nnz):
@@ -745,14 +747,18 @@ def sem_attn_bwd(M, w_omega, b_omega, u_omega, beta, dZ, out=None, flags=0):
 
 
 def sem_attn_bwd_rows(M, w_omega, b_omega, u_omega, beta, dZ, paths, c, dc, activation=ACT_ELU, K=8, FP=8,
-                      table_dtype=torch.float32, out=None, flags=0, gs_out=None, df1_out=None):
+                      table_dtype=torch.float32, out=None, flags=0, gs_out=None, df1_out=None, live=None):
     """sem_attn_bwd with node_attn_bwd_rows of every meta-path in its epilogue, for an M (N,P,D) that is the K2 output
     of P node_attn_fwd calls and has no other consumer: no dM.  paths: per meta-path (aggp, tsum, f1, lse) as
     node_attn_bwd_rows takes them; c (P,D).  Returns (gs list, df1 list, dw, db, du) [dw, db, du written to the tensors
     of `out` when given] and writes dc (P,D) -- or None, with nothing launched, when the library does not take the shape
     (han_hip.h: han_sem_attn_bwd_rows decides, before any launch; the rule is written down there and nowhere else); the
     caller then runs the two ops.  gs_out / df1_out: optional lists of P
-    preallocated destinations (N, row_bytes) uint8 / (N,K)."""
+    preallocated destinations (N, row_bytes) uint8 / (N,K).
+    live: (n_live,) int32 ascending node ids (han_sem_attn_bwd_rows_live): only the rows of these nodes are read, and
+    only their rows of gs / df1 are written -- every other row of the destinations keeps what it held (pass df1_out
+    whose other rows are zero: the gather and score_param_bwd read df1 of every source row) --, and dw, db, du, dc are
+    the sums over them: what the full call gives when dZ is zero in every other row."""
     lib = _lib.load()
     N, P, Dm = M.shape
     A = w_omega.shape[1]
@@ -778,14 +784,23 @@ def sem_attn_bwd_rows(M, w_omega, b_omega, u_omega, beta, dZ, paths, c, dc, acti
     df1 = [_out(None if df1_out is None else df1_out[p], "df1_out", (N, K), dev) for p in range(P)]
     ws = _ws(lib.han_sem_attn_bwd_rows_workspace(N, P, Dm, A), dev, "semrows")
     arr = lambda ts: (ctypes.c_void_p * P)(*[t.data_ptr() for t in ts])
-    code = lib.han_sem_attn_bwd_rows(
-        M.data_ptr(), w_omega.data_ptr(), b_omega.data_ptr(), u_omega.data_ptr(), beta.data_ptr(), dZ.data_ptr(),
-        arr([p[0] for p in paths]), arr([p[1] for p in paths]), arr([p[2] for p in paths]), arr([p[3] for p in paths]),
-        c.data_ptr(), arr(gs), arr(df1), dw.data_ptr(), db.data_ptr(), du.data_ptr(), dc.data_ptr(), ws.data_ptr(),
-        ws.numel(), N, P, Dm, A, K, FP, DTYPE_CODE[table_dtype], int(activation), int(flags), _stream())
+    head = (M.data_ptr(), w_omega.data_ptr(), b_omega.data_ptr(), u_omega.data_ptr(), beta.data_ptr(), dZ.data_ptr(),
+            arr([p[0] for p in paths]), arr([p[1] for p in paths]), arr([p[2] for p in paths]), arr([p[3] for p in paths]),
+            c.data_ptr(), arr(gs), arr(df1), dw.data_ptr(), db.data_ptr(), du.data_ptr(), dc.data_ptr(), ws.data_ptr(),
+            ws.numel())
+    tail = (N, P, Dm, A, K, FP, DTYPE_CODE[table_dtype], int(activation), int(flags), _stream())
+    if live is None:
+        name = "han_sem_attn_bwd_rows"
+        code = lib.han_sem_attn_bwd_rows(*head, *tail)
+    else:
+        if live.dim() != 1 or live.numel() > N:
+            raise ValueError(f"live: expected at most {N} node ids, got {tuple(live.shape)}")
+        _chk(live, "live", (live.numel(),), dtype=torch.int32, device=dev)
+        name = "han_sem_attn_bwd_rows_live"
+        code = lib.han_sem_attn_bwd_rows_live(*head, _ptr_nonempty(live), live.numel(), *tail)
     if code == _lib.E_UNSUPPORTED:
         return None
-    _lib.check(code, "han_sem_attn_bwd_rows")
+    _lib.check(code, name)
     return gs, df1, dw, db, du
 
 

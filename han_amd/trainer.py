@@ -69,12 +69,19 @@ class _EvalBranch:
         self._run(fn)
 
 
+# HANTrainer(live_backward="auto") acts from this many rows on (the size from which side_stream="auto" acts).  The reason
+# is compatibility, not a measurement: the live backward adds its terms in another order, and the default trainer on
+# small graphs is what the existing parity tests pin to the bit (fold on against off, the fused entry's lower row bound,
+# the zero-rows hint on every gather).  live_backward=True has no such floor.
+LIVE_BACKWARD_MIN_ROWS = 262144
+
+
 class HANTrainer:
     def __init__(self, model: HeteGAT_multi, xs, graphs, labels, train_mask, val_mask=None,
                  lr=0.005, l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6,
                  part: NodePartition | None = None, patience=100, max_halo_fraction=0.6,
                  use_graph=False, graphs_local=False, xs_full=None, replicate="auto", masked_backward=False,
-                 side_stream=False, overlap_eval=False):
+                 side_stream=False, overlap_eval=False, live_backward="auto"):
         """xs: list of P (N_local,F) feature tensors (this rank's rows), or sparse features (SparseFeatures / torch
         sparse COO or CSR tensors; single process only);
         graphs: list of P CSRGraph (or dense masks / CSR tuples).  Under a partition (`part`) either
@@ -115,11 +122,21 @@ class HANTrainer:
         The trainer sets model.direct_grads(True) and model.fold_k3 = True and leaves them set: both describe ITS step
         (every parameter used once, M consumed by semantic() alone).  A model used free-form afterwards with another
         consumer of M raises in the backward (layers.FoldTail); set model.fold_k3 = False for that.
-        masked_backward: OPT-IN (never the default, never the headline measurement): with a single node-attention
-        layer the backward row g_i of every destination outside `train_mask` is identically zero, so the
-        transposed-graph pass skips those destinations in place (bit-identical results, dist.MaskedBackwardPlan)
-        and, under a partition, only the live rows of the backward table travel.  The reference evaluates every
-        row in every step (sess.run, ex_acm3025.py:190); this mode computes the same numbers with less work."""
+        live_backward ("auto" | True | False): the forward evaluates every row in every step, as the reference does (sess.run,
+        ex_acm3025.py:190); the backward computes exactly the terms that are not identically zero.  With a single
+        node-attention layer, a row-local K3 and classifier and a train mask that never changes, dZ_i, dM_i and g_i are
+        exactly zero for every row i outside the mask, so the set-up builds, once, the list of live rows and per
+        meta-path the transposed graph with only the entries whose destination is live (layers.LiveBackwardPlan); the
+        K3 backward then runs over the list and the gather over that graph.  Same terms, another summation order
+        (per-lane order of dH / df2, tile grouping of dw / db / du / dc): results agree to rounding, not to the bit.
+        "auto": on where all of these hold -- CUDA, no further node-attention layer, at most half of the rows in the
+        train mask, no node partition, masked_backward off -- and the graphs have at least LIVE_BACKWARD_MIN_ROWS rows
+        (below that the default keeps the bits of the full backward, which the small-graph parity tests pin; the gain
+        there has not been measured); True: on at any size (ValueError where one of the other conditions fails, masked_backward
+        still wins); False: every row in the backward too.
+        masked_backward: OPT-IN (never the default, never the headline measurement): the transposed-graph pass keeps
+        the dead entries in place and skips them one by one (bit-identical results, dist.MaskedBackwardPlan)
+        and, under a partition, only the live rows of the backward table travel.  Switches live_backward off."""
         if not model._built:
             raise RuntimeError("build the model first (model.build(...))")
         self.model = model
@@ -168,6 +185,17 @@ class HANTrainer:
         self.labels = labels.to(device=dev, dtype=torch.int32).contiguous()
         self.train_mask = train_mask.to(device=dev, dtype=torch.uint8).contiguous()
         self._masked_plans = None
+        if live_backward not in ("auto", True, False):
+            raise ValueError(f"live_backward = {live_backward!r}: expected 'auto', True or False")
+        self._live_plan = None
+        n_all = self._global_count(torch.ones_like(self.train_mask))
+        live_ok = (dev.type == "cuda" and not model.extra and self.part is None
+                   and 2 * self._global_count(self.train_mask) <= n_all)
+        if live_backward is True and not live_ok:
+            raise ValueError("live_backward=True needs a CUDA model with one node-attention layer, no node partition and "
+                             "a train mask of at most half of the rows")
+        if live_ok and (live_backward is True or (live_backward == "auto" and n_all >= LIVE_BACKWARD_MIN_ROWS)):
+            self._live_plan = layers.LiveBackwardPlan(self.graphs_t, self.train_mask)
         self.set_masked_backward(masked_backward)
         self.val_mask = (val_mask if val_mask is not None else train_mask).to(
             device=dev, dtype=torch.uint8).contiguous()
@@ -227,9 +255,15 @@ class HANTrainer:
                 if dev.type == "cuda":
                     self._eval_stream = torch.cuda.Stream(device=dev)
 
+    @property
+    def live_backward(self) -> bool:
+        """Whether the backward runs over the live rows only (the live_backward argument, as decided)."""
+        return self.model.live_bwd is not None
+
     def set_masked_backward(self, flag: bool):
         """Switch the opt-in masked backward on or off (plans are built on first use; collective under a partition)."""
         self.masked_backward = bool(flag)
+        self.model.live_bwd = None if self.masked_backward else self._live_plan      # the masked backward wins
         if not self.masked_backward:
             self.model.masked_bwd = None
             return

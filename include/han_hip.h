@@ -421,6 +421,25 @@ int han_sem_attn_bwd_rows(const float *M, const float *w_omega, const float *b_o
                           void *workspace, size_t workspace_bytes, int64_t N, int P, int D, int A, int K, int FP,
                           int table_dtype, int activation, int flags, void *stream);
 
+/* han_sem_attn_bwd_rows over a row list (added under ABI 15: a new entry point, nothing existing changed): `live` holds
+ * n_live ascending node ids (device, int32, each < N, none twice), and only rows (live[t], p) take part.  M, dZ, beta and
+ * the per-meta-path inputs are read at node live[t]; the [g | stats] row and df1 are written at node live[t] of the
+ * full-size (N-row) tables; rows of nodes that are not listed are neither read nor written.  dw / db / du / dc are the
+ * sums over the listed rows -- what the full entry gives when dZ is zero in every other row.  The grid and the
+ * reduction follow n_live * P; n_live == 0 launches no kernel and writes zeros to dw / db / du / dc.  With
+ * live = 0 .. N - 1 every output holds the bits of han_sem_attn_bwd_rows.
+ * HAN_E_UNSUPPORTED by the rule of han_sem_attn_bwd_rows WITHOUT its lower bound on the row count: the kernel's loops
+ * are correct for any count (the bound there only says from where the bf16 pipe is the form han_sem_attn_bwd runs), so
+ * D == 64, A in {64, 128}, P in {1, 2, 4}, K == 8, FP == 8, fp32 tables, ELU or identity, none of the three K3 flags.
+ * Workspace: han_sem_attn_bwd_rows_workspace(N, P, D, A).                                                          */
+int han_sem_attn_bwd_rows_live(const float *M, const float *w_omega, const float *b_omega, const float *u_omega,
+                               const float *beta, const float *dZ, const float *const *aggp, const float *const *tsum,
+                               const float *const *f1, const float *const *lse, const float *c, void *const *gs,
+                               float *const *df1, float *dw_omega, float *db_omega, float *du_omega, float *dc,
+                               void *workspace, size_t workspace_bytes, const int32_t *live, int64_t n_live, int64_t N,
+                               int P, int D, int A, int K, int FP, int table_dtype, int activation, int flags,
+                               void *stream);
+
 /* ---- classifier + masked loss ----------------------------------------------
  * models/gat.py:65-72: logits = (1/HC) sum_h (Z Wc[h] + bc[h]);  Wc (HC,D,C).
  * models/base_gattn.py:41-48,61-69: per-row masked softmax-CE and accuracy
