@@ -76,6 +76,7 @@ SIGNATURES = {
     "han_score_param_bwd_workspace": (c_size_t, [I64, c_int, c_int]),
     "han_score_param_bwd": (c_int, [P, c_int, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, P]),
     "han_sem_attn_fwd": (c_int, [P, P, P, P, P, P, I64, c_int, c_int, c_int, c_int, P]),
+    "han_sem_attn_fwd_live": (c_int, [P, P, P, P, P, P, P, I64, I64, c_int, c_int, c_int, c_int, P]),
     "han_sem_attn_bwd_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
     "han_sem_attn_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int,
                                  c_int, c_int, P]),
@@ -87,6 +88,8 @@ SIGNATURES = {
     "han_classifier_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
     "han_classifier_loss": (c_int, [P, P, P, P, P, c_float, P, P, P, P, P, P, c_size_t, I64,
                                     c_int, c_int, c_int, P]),
+    "han_classifier_loss_live": (c_int, [P, P, P, P, P, c_float, P, P, P, P, P, P, c_size_t, P, I64, I64,
+                                         c_int, c_int, c_int, P]),
     "han_classifier_bwd_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
     "han_classifier_bwd": (c_int, [P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, c_int, P]),
     "han_adam_step": (c_int, [P, P, P, P, I64, c_float, c_float, c_float, c_float, c_float, P, P]),

@@ -27,13 +27,13 @@ def group_by(keys: torch.Tensor, n_groups: int):
     return scan(torch.bincount(keys, minlength=n_groups)), order
 
 
-def chunk_table(ptr: torch.Tensor, longer_than: int, chunk: int):
-    """The segments of `ptr` with more than `longer_than` entries cut into chunks of `chunk` entries (a segment's last
-    may be shorter, none is empty): None without such a segment, else dict(n_long, n_chunks, long (n_long,) segment
+def chunk_table(ptr: torch.Tensor, longer_than: int, chunk: int, only: torch.Tensor | None = None):
+    """The segments of `ptr` with more than `longer_than` entries (`only` (n,) bool: among the segments it marks) cut into
+    chunks of `chunk` entries (a segment's last may be shorter, none is empty): None without such a segment, else dict(n_long, n_chunks, long (n_long,) segment
     ids, long_ptr (n_long + 1,) first chunk of each, chunk_long (n_chunks,) index into `long`, chunk_start / chunk_end
     (n_chunks,): chunk c covers entries [chunk_start[c], chunk_end[c])), int64.  One host read (n_chunks)."""
     lens = ptr[1:] - ptr[:-1]
-    long = torch.nonzero(lens > longer_than).flatten()
+    long = torch.nonzero(lens > longer_than if only is None else (lens > longer_than) & only).flatten()
     if long.numel() == 0:
         return None
     nch = (lens[long] + chunk - 1) // chunk

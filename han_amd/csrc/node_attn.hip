@@ -1869,9 +1869,11 @@ struct RowBins {
     const int32_t *short_rows, *mid_rows;
 };
 
-static RowBins bins_of(const han_row_split_t *sp) {
+// `subset` (HAN_FLAG_K2_ROW_SUBSET): the lists are all there is to do -- binned even when both bins are empty, so that
+// for_each_bin then launches nothing instead of every row
+static RowBins bins_of(const han_row_split_t *sp, bool subset = false) {
     RowBins b = {false, 0, 0, nullptr, nullptr};
-    if (sp && (sp->n_short > 0 || sp->n_mid > 0)) {
+    if (sp && (subset || sp->n_short > 0 || sp->n_mid > 0)) {
         b.binned = true;
         b.n_short = sp->n_short; b.n_mid = sp->n_mid;
         b.short_rows = sp->short_rows; b.mid_rows = sp->mid_rows;
@@ -2023,6 +2025,13 @@ extern "C" int han_node_attn_fwd(const int64_t *rowptr, const int32_t *colidx, c
     if (N == 0) return 0;   // nothing to do; row pointers of empty tensors may be null
     if (!rowptr || (!colidx && E > 0) || !H || !f1 || !a2 || !b2 || !c || !out || N < 0 || E < 0 || out_stride < HAN_D)
         return HAN_E_BADARG;
+    const bool subset = (flags & HAN_FLAG_K2_ROW_SUBSET) != 0;
+    if (subset) {      // the lists of `split` are the rows to compute: no whole-graph kernel form, no identity lists
+        if (!split) return HAN_E_BADARG;
+        if ((flags & HAN_FLAG_LEAN) || dense || (split->n_short > 0 && !split->short_rows) ||
+            (split->n_mid > 0 && !split->mid_rows))
+            return HAN_E_UNSUPPORTED;
+    }
     if (!split_ok(split, N)) return HAN_E_BADARG;
     if (!han_fp_supported(K, FP) || !dtype_ok(table_dtype)) return HAN_E_UNSUPPORTED;
     if ((flags & HAN_FLAG_LEAN) && !f2_src) return HAN_E_BADARG;      // the lean kernels read the scores from the table
@@ -2057,7 +2066,7 @@ extern "C" int han_node_attn_fwd(const int64_t *rowptr, const int32_t *colidx, c
         HAN_CHECK_LAUNCH();
         return 0;
     }
-    const RowBins bins = bins_of(split);
+    const RowBins bins = bins_of(split, subset);
     HAN_DISPATCH_BOOL(VAL, edge_val != nullptr,
                       HAN_DISPATCH_FP_BF(FP, table_dtype == HAN_DTYPE_BF16, launch_fwd_v<FPC, BF, VAL>(a, train, low, has_split, bins, st)));
     HAN_CHECK_LAUNCH();

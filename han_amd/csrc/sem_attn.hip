@@ -77,6 +77,41 @@ __device__ __forceinline__ float row_score(const f32x4 (&acc)[TA], int reg, cons
     return han_row16_sum(s);
 }
 
+// wave_node_softmax (below) over a row list (sem_attn_fwd_wave_b6_live_kernel, P <= 4): ids = the nodes of this lane
+// group's four rows, and Z / beta go to node ids[k * P].  The arithmetic is wave_node_softmax's, statement for statement
+// (a copy and not a shared helper: with one, the compiler schedules the P = 1 forms of the full kernels differently,
+// and tools/kernel_diff.py no longer calls them identical).
+template <int P>
+__device__ __forceinline__ void wave_node_softmax_live(const float (&sc)[4], const float4_t (&mz)[4], int64_t r0, int64_t R,
+                                                       int l15, int l4, float *Z, float *beta, const int (&ids)[4]) {
+    static_assert(P <= 4, "a node's rows inside one lane group");
+#pragma unroll
+    for (int k = 0; k < 4 / P; ++k) {       // the 4/P nodes of this lane group
+        const int64_t row = r0 + 4 * l4 + k * P;
+        if (row < R) {
+            float mx = sc[k * P];
+#pragma unroll
+            for (int p = 1; p < P; ++p) mx = fmaxf(mx, sc[k * P + p]);
+            float e[P], den = 0.f;
+#pragma unroll
+            for (int p = 0; p < P; ++p) { e[p] = __expf(sc[k * P + p] - mx); den += e[p]; }
+            const float inv = 1.f / den;
+            float4_t z = {0.f, 0.f, 0.f, 0.f};
+            float mine = 0.f;
+#pragma unroll
+            for (int p = 0; p < P; ++p) {
+                const float bp = e[p] * inv;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) z[c] += bp * mz[k * P + p][c];
+                mine = (l15 == p) ? bp : mine;
+            }
+            const int64_t node = ids[k * P];
+            *reinterpret_cast<float4_t *>(Z + node * 64 + 4 * l15) = z;
+            if (l15 < P) beta[node * P + l15] = mine;
+        }
+    }
+}
+
 // The end of the wave-local forward: softmax over the P scores of a node, Z = sum_p beta_p M_p, and the Z / beta
 // stores.  sc = the scores of this lane group's rows r0 + 4*l4 .. + 3, mz = those rows (lane = features 4*l15 .. + 3).
 template <int P>
@@ -358,58 +393,11 @@ struct B6FwdLds {
 template <int CA, int P>
 __global__ __launch_bounds__(256) void sem_attn_fwd_wave_b6_kernel(const float *__restrict__ M, const float *Wg,
                                                                    const float *bw, const float *uw, float *Z,
-                                                                   float *beta, int64_t N) {
-    constexpr int A = 64 * CA;
-    constexpr int TA = A / 16;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    // [3][A][128 B], XOR-swizzled: the 16-byte chunk g of row a sits at chunk g ^ ((a >> 1) & 7).  Two 128-B rows span
-    // the 64 banks, so the 16 lanes that read chunk g of 16 consecutive rows (8 of each parity) hit 64 different banks
-    // WITHOUT padding the rows to 144 B -- 48 KB instead of 54 KB at A = 128: three blocks per CU instead of two (round 3)
-    constexpr int FWLDB = B6FwdLds<A>::LDB;
-    unsigned char *Wt = reinterpret_cast<unsigned char *>(smem);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int l15 = lane & 15, l4 = lane >> 4;
-    stage_w_t<A, 256, FWLDB, true>(Wg, Wt);
-    __syncthreads();
-    float bcol[TA], ucol[TA];
-    load_bu<TA>(bw, uw, l15, bcol, ucol);
-    const int64_t R = N * P;
-    const int64_t ntiles = (R + 15) / 16;
-    const int64_t tstride = (int64_t)gridDim.x * 4;
-    float4_t araw[4];      // the contraction's A operand: this lane's 16 k-values of its row, one tile ahead
-    load_arow(M, (int64_t)blockIdx.x * 4 + w, R, l15, l4, araw);
-    for (int64_t tile = (int64_t)blockIdx.x * 4 + w; tile < ntiles; tile += tstride) {
-        const int64_t r0 = tile * 16;
-        f32x4 acc[TA];
-#pragma unroll
-        for (int t = 0; t < TA; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        i32x4 af[2][3];
-        split_arow(araw, af);
-        load_arow(M, tile + tstride, R, l15, l4, araw);      // next tile, in flight under the MFMAs
-        float4_t mz[4];
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int64_t row = r0 + 4 * l4 + rr;
-            mz[rr] = *reinterpret_cast<const float4_t *>(M + (row < R ? row : R - 1) * 64 + 4 * l15);
-        }
-#pragma unroll
-        for (int t = 0; t < TA; ++t) {
-            f32x4 c = acc[t];
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                i32x4 b[3];
-                load_b3(Wt + (16 * t + l15) * FWLDB + (((4 * s2 + l4) ^ ((l15 >> 1) & 7)) * 16), A * FWLDB, b);
-                c = han_b6_chain_k3(af[s2], b, c);
-            }
-            acc[t] = c;
-            __builtin_amdgcn_sched_barrier(0);      // keep one column tile's 6 fragment reads in flight, not all 48
-        }
-        float sc[4];
-#pragma unroll
-        for (int reg = 0; reg < 4; ++reg) sc[reg] = row_score<TA>(acc, reg, bcol, ucol);
-        wave_node_softmax<P>(sc, mz, r0, R, l15, l4, Z, beta);
-    }
-}
+                                                                   float *beta, int64_t N)
+#define K3_FWD_LIVE 0
+#include "sem_attn_fwd_b6_body.h"      // the body, shared with the row-list form
+#undef K3_FWD_LIVE
+#include "sem_attn_fwd_live.h"         // sem_attn_fwd_wave_b6_live_kernel (han_sem_attn_fwd_live)
 
 // The block-level backward at D = 64, A <= 128 for the meta-path counts the wave-local kernels do not take (P = 3 of
 // DBLP): a chunk of NB = 64/P whole nodes per block iteration.  It is sem_attn_bwd_gen_kernel<4> with the whole
@@ -2063,6 +2051,27 @@ extern "C" int han_sem_attn_fwd(const float *M, const float *w_omega, const floa
     } else {
         HAN_DISPATCH_CA(A, e = launch_fwd_gen<CA, 8>(a));
     }
+    return (int)e;
+}
+
+extern "C" int han_sem_attn_fwd_live(const float *M, const float *w_omega, const float *b_omega, const float *u_omega,
+                                     float *Z, float *beta, const int32_t *live, int64_t n_live, int64_t N, int P,
+                                     int D, int A, int flags, void *stream) {
+    if (!M || !w_omega || !b_omega || !u_omega || !Z || !beta || N < 0 || P <= 0 || n_live < 0 || n_live > N ||
+        (n_live > 0 && !live))
+        return HAN_E_BADARG;
+    // the shapes of the live backward (k3_fold_ok without its row bound and its table offsets): the kernel's loops are
+    // correct for any count
+    if (D != 64 || (A != 64 && A != 128) || (P != 1 && P != 2 && P != 4) || (flags & HAN_FLAG_K3_EXACT_PIPE))
+        return HAN_E_UNSUPPORTED;
+    if (n_live == 0) return 0;      // no row, no launch
+    const int grid = han_grid_for(n_live * P, 64, 256 * 3);      // the grid follows the list
+    hipError_t e = hipSuccess;
+    HAN_DISPATCH_CA(A, if constexpr (CA <= 2) {
+        HAN_DISPATCH_P(P, if constexpr (PC <= 4) e = han_launch_lds(sem_attn_fwd_wave_b6_live_kernel<CA, PC>, grid, 256,
+                                                                   B6FwdLds<64 * CA>::bytes + kFwdRingBytes, (hipStream_t)stream,
+                                                                   M, w_omega, b_omega, u_omega, Z, beta, n_live, live))
+    });
     return (int)e;
 }
 

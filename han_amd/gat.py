@@ -100,6 +100,8 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         self.fold_k3 = False                  # the K3 backward also runs the row-local half of the last layer's K2 backward (layers.FoldTail):
                                               # set by HANTrainer; off for free-form use, because it relies on M having no consumer but semantic()
         self._fold_handover = None            # (M, FoldTail) of the last node_level() call, taken by semantic(M)
+        self._live_handover = None            # (M or Z, layers.LiveForwardPlan) when the last node_level() computed only the plan's rows: semantic(M) hands
+                                              # it on with Z, classifier_loss(Z) takes the row list from it -- the stages of one forward agree on the rows
         self.side_stream = None               # second stream of the eager training step on large graphs (layers.NodeLevelAttention.backward):
                                               # dW of meta-path p runs beside the backward gather of meta-path p + 1
         self._graph_cache: dict = {}
@@ -255,7 +257,7 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         return out
 
     def node_level(self, xs, graphs, attn_drop, ffd_drop, train, act_code, graphs_t=None, coef_sink=None,
-                   post=None, xs_full=None):
+                   post=None, xs_full=None, live_fwd=None):
         """models/gat.py:39-60: every node-attention layer of every meta-path -> M (N,P,K*F').
         coef_sink: a list that receives, per meta-path, the head-mean coefficients of the
         FIRST layer (models/gat.py:143-172), or None.
@@ -264,10 +266,19 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         (N,P,K,F') so that an activation acting on the last axis sees what the reference's
         per-head (1,N,F') tensor gives it -- with its own autograd.
         xs_full: under a node partition, the features of ALL rows (P tensors (N,F)): the first layer
-        then projects the whole table on every rank instead of exchanging it (replicated projection)."""
+        then projects the whole table on every rank instead of exchanging it (replicated projection).
+        live_fwd: a layers.LiveForwardPlan (HANTrainer(live_forward=...)): the caller reads only the plan's rows of what
+        this forward gives, so K2 may compute only those rows of M -- the other rows are then uninitialised memory, and
+        semantic(M) / classifier_loss(Z) of this forward take the row list from the same plan.  Honoured for a single
+        layer of the reference head shape without `post`, a node partition or coefficients; a training call also
+        needs its backward to be the row-list fold (layers.NodeLevelAttention.forward decides); otherwise every row
+        is computed."""
         P = len(graphs)
         layers._no_sparse_under_partition(self.partition is not None or xs_full is not None, xs, xs_full)
-        self._fold_handover = None
+        self._fold_handover = self._live_handover = None
+        live_used = []
+        if self.extra or post is not None or self.partition is not None or coef_sink is not None or xs_full is not None:
+            live_fwd = None
         fold = [] if (self.fold_k3 and train and post is None) else None      # FoldTail of the LAST node-attention call
 
         def act(M, K, FP):
@@ -313,7 +324,8 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
                 fold.clear()
             if len(groups) == 1 and K * FP == GROUP:      # the reference shapes: no slicing, direct gradients
                 return layers.NodeLevelAttention.apply(Xin, W, a1, b1, a2, b2, c, Wr, br, xs_, tuple(graphs),
-                                                       run(layer, sd, coef_sink=sink, coef_mean=True, fold_sink=fold))
+                                                       run(layer, sd, coef_sink=sink, coef_mean=True, fold_sink=fold,
+                                                           live_fwd=live_fwd, live_sink=live_used))
             fn = layers.WideHeadAttention if wide else layers.NodeLevelAttention
             FPk = -(-FP // GROUP) * GROUP if wide else _kernel_head_width(FP)      # width a head runs at (zero-weight columns beyond FP)
             kg = max(GROUP // FPk, 1)                                              # head slots of a group
@@ -350,6 +362,8 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
             M = act(layer_fwd(i, M, None, Ki, FPi, None), Ki, FPi)
         if fold:
             self._fold_handover = (M, fold[0])
+        if live_used:
+            self._live_handover = (M, live_used[0])
         return M
 
     def semantic(self, M):
@@ -357,7 +371,15 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         (final_embed (N,D_out), att_val (N,P)); any width (layers.semantic_attention)."""
         h, self._fold_handover = self._fold_handover, None
         tail = h[1] if (h is not None and h[0] is M) else None      # M itself, straight from node_level()
-        return layers.semantic_attention(M, self.w_omega, self.b_omega, self.u_omega, tail=tail)
+        lv, self._live_handover = self._live_handover, None
+        if lv is None:
+            return layers.semantic_attention(M, self.w_omega, self.b_omega, self.u_omega, tail=tail)
+        # M holds only the plan's rows: K3 runs over the same list and writes only those rows of Z and att
+        if lv[0] is not M:
+            raise RuntimeError("live_forward: semantic() must take the M that node_level() returned")
+        Z, att = layers.semantic_attention(M, self.w_omega, self.b_omega, self.u_omega, tail=tail, live=lv[1])
+        self._live_handover = (Z, lv[1])
+        return Z, att
 
     def classify(self, Z):
         """models/gat.py:65-72: logits (N,C) = mean over the output heads of Z Wc[h] + bc[h]."""
@@ -365,8 +387,13 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
 
     def classifier_loss(self, Z, labels, mask, weight):
         """Fused classifier + masked softmax cross-entropy + accuracy (the trainer's step):
-        returns (loss, accuracy, logits)."""
-        return layers.classifier_loss_any(Z, self.Wc, self.bc, labels, mask, weight)
+        returns (loss, accuracy, logits).  After a forward over a row list (node_level(live_fwd=...)) the sums run over
+        that list, and only its rows of the logits are written."""
+        lv, self._live_handover = self._live_handover, None
+        if lv is not None and lv[0] is not Z:
+            raise RuntimeError("live_forward: classifier_loss() must take the Z that semantic() returned")
+        return layers.classifier_loss_any(Z, self.Wc, self.bc, labels, mask, weight,
+                                          live=lv[1].live if lv is not None else None)
 
     @_ClassOrInstance
     def inference(self, inputs_list, nb_classes, nb_nodes, training, attn_drop, ffd_drop,

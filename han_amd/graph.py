@@ -171,6 +171,32 @@ class CSRGraph:
             self._split[key] = dict(n_short=n_short, short_rows=short_rows, n_mid=n_mid, mid_rows=mid_rows)
         return self._split[key]
 
+    def row_subset(self, rows: torch.Tensor, short_deg: int = 16, split_deg: int = 1024, chunk: int = 512):
+        """row_bins and row_split restricted to the rows `rows` marks ((n_rows,) bool), for a launch that computes those
+        rows and no other (HAN_FLAG_K2_ROW_SUBSET): dict(n_rows, nnz -- the listed rows and their entries --, bins, split)
+        with `bins` as row_bins returns it, except that a list is always a tensor (the identity form would mean every
+        row of the graph; an empty bin has an empty list), and `split` as row_split returns it (None without a listed
+        long row).  Every listed row is in the set its length puts it in, the short bin in its order (ceil(deg / 4),
+        then id).  Not cached here: the caller's plan keeps it (layers.LiveForwardPlan)."""
+        rows = rows.to(self.device)
+        if rows.shape != (self.n_rows,) or rows.dtype != torch.bool:
+            raise ValueError(f"rows: expected a ({self.n_rows},) bool mask, got {tuple(rows.shape)} {rows.dtype}")
+        deg = self.degrees()
+        is_short = (deg < short_deg) & (deg > 0) if self.empty_rows_mid else deg < short_deg
+        is_mid = (~is_short) & (deg <= split_deg) & rows
+        is_short = is_short & rows
+        ids = torch.nonzero(is_short).flatten()
+        order = torch.sort((deg[ids] + 3) // 4, stable=True).indices
+        bins = dict(n_short=int(ids.numel()), short_rows=ids[order].to(torch.int32).contiguous(),
+                    mid_rows=torch.nonzero(is_mid).flatten().to(torch.int32).contiguous())
+        bins["n_mid"] = int(bins["mid_rows"].numel())
+        t = csr.chunk_table(self.rowptr, int(split_deg), int(chunk), only=rows)
+        if t is not None:
+            t = dict(split_deg=int(split_deg), n_long=t["n_long"], n_chunks=t["n_chunks"], long_rows=t["long"],
+                     long_ptr=t["long_ptr"], chunk_long=t["chunk_long"].to(torch.int32),
+                     chunk_start=t["chunk_start"], chunk_end=t["chunk_end"])
+        return dict(n_rows=int(rows.sum()), nnz=int(deg[rows].sum()), bins=bins, split=t)
+
     def bitmask(self):
         """Adjacency bit mask for the dense (matrix-pipe) K2 path: (n_rows, ceil(n_cols / 32)) int32 on the device, bit
         (j & 31) of word (j >> 5) of row i set iff the graph stores (i, j) -- or None when the graph holds repeated

@@ -183,6 +183,8 @@ class LayerRun:
     coef_mean: bool = False           # head mean (E,) with coef_mean (return_coef of layers.py:43-44 / models/gat.py:143-172; single GPU only)
     fold_sink: list | None = None     # HeteGAT_multi.fold_k3: receives this call's FoldTail when its row-local backward may run in the K3 backward
     live_bwd: object = None           # LiveBackwardPlan (HANTrainer(live_backward=...)): the backward visits only the rows the loss reaches
+    live_fwd: object = None           # LiveForwardPlan (HANTrainer(live_forward=...)): K2 computes only the rows the caller reads of M
+    live_sink: list | None = None     # receives live_fwd when this call ran over it (a training call may decline: NodeLevelAttention.forward)
 
     @functools.cached_property
     def multi(self) -> bool:
@@ -259,6 +261,39 @@ class LiveBackwardPlan:
             self._df1[K] = [torch.zeros((self.n_rows, K), dtype=torch.float32, device=self.live.device)
                             for _ in self.graphs_t]
         return self._df1[K]
+
+
+class LiveForwardPlan:
+    """Set-up-time plan of a forward that computes only the rows its caller reads (HANTrainer(live_forward=...); single
+    process, one node-attention layer): the loss and the metrics of a step are sums over a mask that never changes,
+    and K3 and the classifier are row-local, so row i of M, Z and the logits -- and of lse, aggp, tsum and beta, which
+    only the live backward reads, at live rows -- matters only for i in the mask.  K1 still projects every row (H is
+    the gather table).  `live`: the ascending int32 ids of the masked-in rows, the row list of the classifier
+    (ops.classifier_loss(live=...)); subset(graph): per graph the bins and the split restricted to the rows
+    (ops.RowSubset, computed on first use and kept); K3 runs over `live` too (ops.sem_attn_fwd(live=...)).  M, Z and the
+    logits stay full-size and node-indexed; their
+    other rows are uninitialised memory that nothing may sum over.  Whole-graph embeddings and logits remain what
+    inference / predict return: those paths never take a plan.  backward: the LiveBackwardPlan over the same rows, or
+    None -- a training forward runs over the list only in a step whose backward is that plan's row-list fold."""
+
+    def __init__(self, graphs, mask, backward=None):
+        self.mask = mask != 0
+        self.backward = backward
+        if backward is not None and not torch.equal(backward.live.to(self.mask.device), torch.nonzero(self.mask).flatten().to(torch.int32)):
+            raise ValueError("LiveForwardPlan: `backward` lists other rows than `mask`")
+        self.live = torch.nonzero(self.mask).flatten().to(torch.int32).contiguous()
+        self.graphs = tuple(graphs)
+        self.n_rows = int(self.mask.numel())
+        self._subsets = [None] * len(self.graphs)
+
+    def subset(self, graph):
+        for p, g in enumerate(self.graphs):
+            if g is graph:
+                if self._subsets[p] is None:
+                    self._subsets[p] = ops.RowSubset(g, self.mask, self.live)
+                return self._subsets[p]
+        raise RuntimeError("live_forward: the model runs on other graphs than the trainer's; the row lists were built "
+                           "from those (HANTrainer(live_forward=False) for free-form use)")
 
 
 class FoldTail:
@@ -369,6 +404,18 @@ class NodeLevelAttention(torch.autograd.Function):
         in_drop, coef_drop, row_offset, seed_dev, tdt = run.drop_in, run.drop_coef, run.row_offset, run.seed_dev, run.table_dtype
         N = xs[0].shape[0]
         M = torch.empty((N, P, D), dtype=torch.float32, device=W.device)
+        # THE place that decides whether this call's backward is the row-list fold (FoldTail with `live` set)
+        fold = (run.fold_sink is not None and train and W.is_cuda and Wr is None and run.streams is None
+                and tdt == torch.float32)
+        fold_live = run.live_bwd if (fold and run.masked_bwd is None) else None
+        # ... and whether K2 computes only the listed rows of M (LiveForwardPlan).  An eval call has no backward.  A
+        # training call does so only when its backward is that fold over the SAME rows: every other backward reads M
+        # and aggp of every row and sums dc over all of them, and one unwritten row would corrupt a gradient.
+        live_f = run.live_fwd if (W.is_cuda and not multi and Wr is None and run.coef_sink is None) else None
+        if live_f is not None and train and (fold_live is None or fold_live is not live_f.backward):
+            live_f = None
+        if live_f is not None and run.live_sink is not None:
+            run.live_sink.append(live_f)
         saved = [None] * P
         srcs = [run.source_f(p, graphs[p]) for p in range(P)]
         # all projections first, each table's exchange started as soon as it exists:
@@ -428,7 +475,7 @@ class NodeLevelAttention(torch.autograd.Function):
             _, sv = ops.node_attn_fwd(srcs[p].graph, handle.wait(), f1, a2[p], b2[p], c[p], out=M[:, p, :], train=train,
                                       coef_drop=coef_drop, fts_drop=in_drop, seed=int(run.seeds[p]), row_offset=row_offset,
                                       activation=run.act, table_gid=srcs[p].gid, res=R, seed_dev=seed_dev,
-                                      f2=None if multi else f2)
+                                      f2=None if multi else f2, **({} if live_f is None else {"rows": live_f}))
             if train:      # sv[0] is the OUTPUT view M[:, p, :]: kept through ctx.save_for_backward(M) below, not here
                 saved[p] = _SavedPath(H, f1, f2, *sv[1:], R, keep)
 
@@ -454,10 +501,10 @@ class NodeLevelAttention(torch.autograd.Function):
         plist = (W, a1, b1, a2, b2, c) + ((Wr, br) if Wr is not None else ())
         ctx.direct = tuple(p.grad for p in plist) if all(_direct(p) for p in plist) else None
         ctx.tail = None
-        if (run.fold_sink is not None and train and W.is_cuda and Wr is None and run.streams is None
-                and tdt == torch.float32):
+        ctx.live_fwd = live_f is not None
+        if fold:
             ctx.tail = FoldTail(saved, c, ctx.direct[5] if ctx.direct is not None else None, run.act, K, FP,
-                                live=run.live_bwd if run.masked_bwd is None else None)
+                                live=fold_live)
             run.fold_sink.append(ctx.tail)
         # M, the output, is backward state too (the pre-activation is recovered from it): saved through autograd, so
         # that an in-place change of M between forward and backward raises instead of giving wrong gradients
@@ -478,6 +525,10 @@ class NodeLevelAttention(torch.autograd.Function):
         K, FP = a1.shape[1], a1.shape[2]
         tail, ctx.tail = ctx.tail, None
         folded = tail is not None and tail.gs is not None      # the K3 backward has run the row-local half (FoldTail)
+        if ctx.live_fwd and not (folded and tail.live is not None):
+            raise RuntimeError("live_forward: M holds only the listed rows, and the backward that reached it is not the "
+                               "row-list fold (another consumer of M, or a K3 shape outside han_sem_attn_bwd_rows_live); "
+                               "HANTrainer(live_forward=False) for such a model")
         if folded:
             if dM.data_ptr() != _no_grad_of(dM).data_ptr() or any(dM.stride()):
                 raise RuntimeError("fold_k3: M has a consumer besides semantic(); its gradient cannot be folded into the K3 "
@@ -715,11 +766,13 @@ class SemanticAttention(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, M, w_omega, b_omega, u_omega, *tail):
-        """tail: nothing, or the FoldTail of the NodeLevelAttention call whose output M is (semantic_attention)."""
+        """tail: nothing, or the FoldTail of the NodeLevelAttention call whose output M is (semantic_attention), and / or
+        the LiveForwardPlan of a forward that computed only the plan's rows of M: K3 then runs over the same list."""
         M = M.contiguous()
-        Z, beta = ops.sem_attn_fwd(M, w_omega, b_omega, u_omega)
+        live = next((t for t in tail if isinstance(t, LiveForwardPlan)), None)
+        Z, beta = ops.sem_attn_fwd(M, w_omega, b_omega, u_omega, **({} if live is None else {"live": live.live}))
         ctx.n_tail = len(tail)
-        ctx.tail = tail[0] if tail else None
+        ctx.tail = next((t for t in tail if isinstance(t, FoldTail)), None)
         ctx.set_materialize_grads(False)      # no zero-filled gradient for beta (a fill launch per step)
         plist = (w_omega, b_omega, u_omega)
         ctx.direct = tuple(p.grad for p in plist) if all(_direct(p) for p in plist) else None
@@ -759,6 +812,8 @@ class ClassifierLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, Z, Wc, bc, labels, mask, row_weight, *grad_mode):
+        """grad_mode: nothing, or (grad enabled,), or (grad enabled, live): the int32 row list of a forward that
+        computed only those rows of Z (LiveForwardPlan.live; None: every row)."""
         # an eval forward under torch.no_grad() must neither pay for the gradient half of the kernel nor, in
         # direct-gradient mode, WRITE Wc.grad / bc.grad.  needs_input_grad reports requires_grad whatever the grad
         # mode and the grad mode is off inside every forward(), so the caller passes the one it was called under
@@ -771,7 +826,8 @@ class ClassifierLoss(torch.autograd.Function):
         ctx.direct = need and _direct(Wc) and _direct(bc)
         logits, loss_acc, grads = ops.classifier_loss(Z.contiguous(), Wc, bc, labels, mask,
                                                       row_weight, backward=need,
-                                                      grad_out=(Wc.grad, bc.grad) if ctx.direct else None)
+                                                      grad_out=(Wc.grad, bc.grad) if ctx.direct else None,
+                                                      **({"live": grad_mode[1]} if len(grad_mode) > 1 else {}))
         ctx.grads = grads
         if ctx.direct or not need:      # views of the kernel's output pair: no clone launches (eval forward: nothing to differentiate)
             loss, acc = loss_acc[0:1].view(()), loss_acc[1:2].view(())
@@ -825,7 +881,7 @@ def _pad_to(n: int) -> int:
     return 64 * ((n + 63) // 64)
 
 
-def semantic_attention(M, w_omega, b_omega, u_omega, tail=None):
+def semantic_attention(M, w_omega, b_omega, u_omega, tail=None, live=None):
     """utils/layers.py:152-159 for any embedding width D and attention size A, always on the K3 kernels.
     Widths that are not multiples of 64 are zero-padded -- padded columns of w_omega / u_omega contribute
     tanh(.) * 0 = 0 to the scores and padded embedding columns are 0 -- which is exact.  D in {64, 128} with
@@ -834,7 +890,8 @@ def semantic_attention(M, w_omega, b_omega, u_omega, tail=None):
     d, a = M.shape[2], w_omega.shape[1]
     dm, am = _pad_to(d), _pad_to(a)
     if dm == d and am == a:      # tail: M is the output of the NodeLevelAttention call that made it (FoldTail); padded, it is not
-        return SemanticAttention.apply(M.contiguous(), w_omega, b_omega, u_omega, *((tail,) if tail is not None else ()))
+        return SemanticAttention.apply(M.contiguous(), w_omega, b_omega, u_omega,
+                                       *(t for t in (tail, live) if t is not None))
     Z, att = SemanticAttention.apply(
         torch.nn.functional.pad(M, (0, dm - d)), torch.nn.functional.pad(w_omega, (0, am - a, 0, dm - d)),
         torch.nn.functional.pad(b_omega, (0, am - a)), torch.nn.functional.pad(u_omega, (0, am - a)))
@@ -851,11 +908,14 @@ def classifier_any(Z, Wc, bc):
     return classifier(Z, Wc, bc)
 
 
-def classifier_loss_any(Z, Wc, bc, labels, mask, weight):
+def classifier_loss_any(Z, Wc, bc, labels, mask, weight, live=None):
     """Classifier + masked softmax cross-entropy + accuracy (models/base_gattn.py:41-48,61-69) for any
-    embedding width / class count; returns (loss, accuracy, logits)."""
+    embedding width / class count; returns (loss, accuracy, logits).  live: the row list of a Z of which only those rows
+    were computed (ops.classifier_loss(live=...): widths of 64 / 128 columns, at most 64 classes)."""
     d = Z.shape[1]
     dm = _pad_to(d)
+    if live is not None:
+        return ClassifierLoss.apply(Z, Wc, bc, labels, mask, weight, torch.is_grad_enabled(), live)
     if dm != d:
         Z, Wc = torch.nn.functional.pad(Z, (0, dm - d)), torch.nn.functional.pad(Wc, (0, 0, 0, dm - d))
     return ClassifierLoss.apply(Z, Wc, bc, labels, mask, weight, torch.is_grad_enabled())

@@ -26,6 +26,7 @@ K2_FULL_GATHER = False     # tests / measurements: FLAG_K2_FULL_GATHER on every 
 FLAG_K2_FULL_GATHER = 2048 # HAN_FLAG_K2_FULL_GATHER: measurements only (the backward gather requests g rows whole, dropped heads included)
 FLAG_K2_ZERO_ROWS = 4096   # HAN_FLAG_K2_ZERO_ROWS: most rows of the gs table hold a zero gradient; the predicated backward gather honours z
 GS_Z_ALL_ZERO = 0x3F800000 # HAN_GS_Z_ALL_ZERO: fourth word of a head's statistics record when all g values of the head are +-0 (else 0)
+FLAG_K2_ROW_SUBSET = 8192  # HAN_FLAG_K2_ROW_SUBSET: the row lists of the split are all the rows han_node_attn_fwd computes
 FLAG_MASKED_EDGES = 64     # HAN_FLAG_MASKED_EDGES: negative entries of the transposed graph are skipped in place
 FLAG_K1_EXACT_PIPE = 2     # HAN_FLAG_K1_EXACT_PIPE / _MATRIX_PIPE: force one of the two K1 forward kernels (tests, measurements)
 FLAG_K1_MATRIX_PIPE = 4
@@ -207,6 +208,50 @@ def _row_split_arg(graph: CSRGraph, tag: str, bins: bool = True, split: bool = T
         st.n_short, st.n_mid = rb["n_short"], rb["n_mid"]
         st.short_rows, st.mid_rows = _ptr(rb["short_rows"]), _ptr(rb["mid_rows"])
     return st, (sp, rb, ws)
+
+
+class RowSubset:
+    """The rows of `graph` a forward is to compute (node_attn_fwd(rows=...), HAN_FLAG_K2_ROW_SUBSET): `mask` (n_rows,)
+    bool / uint8, non-zero = listed.  `live`: the ascending int32 ids; n_rows / nnz: the listed rows and their entries
+    (what a launch over them is priced by).  The bins and the split restricted to the rows (CSRGraph.row_subset) are
+    computed once per (SHORT_DEG, SPLIT_DEG, SPLIT_CHUNK) and kept."""
+
+    def __init__(self, graph: CSRGraph, mask: torch.Tensor, live: torch.Tensor | None = None):
+        self.graph = graph
+        self.mask = (mask != 0).to(graph.device)
+        self.live = live if live is not None else torch.nonzero(self.mask).flatten().to(torch.int32).contiguous()
+        self._parts = {}
+
+    def parts(self):
+        key = (SHORT_DEG, SPLIT_DEG, SPLIT_CHUNK)
+        if key not in self._parts:
+            self._parts[key] = self.graph.row_subset(self.mask, *key)
+        return self._parts[key]
+
+    @property
+    def n_rows(self) -> int:
+        return self.parts()["n_rows"]
+
+    @property
+    def nnz(self) -> int:
+        return self.parts()["nnz"]
+
+    def arg(self, tag: str):
+        """ctypes han_row_split_t of the listed rows (+ keepalive)."""
+        pt = self.parts()
+        sp, rb = pt["split"], pt["bins"]
+        ws = None
+        if sp is not None:
+            ws = _ws(_lib.load().han_row_split_workspace(sp["n_chunks"]), self.graph.device, "split" + tag)
+            st = _lib.HanRowSplit(sp["split_deg"], sp["n_long"], sp["n_chunks"], sp["long_rows"].data_ptr(),
+                                  sp["long_ptr"].data_ptr(), sp["chunk_long"].data_ptr(),
+                                  sp["chunk_start"].data_ptr(), sp["chunk_end"].data_ptr(), ws.data_ptr(),
+                                  ws.numel(), 0, 0, None, None)
+        else:
+            st = _lib.HanRowSplit(SPLIT_DEG, 0, 0, None, None, None, None, None, None, 0, 0, 0, None, None)
+        st.n_short, st.n_mid = rb["n_short"], rb["n_mid"]
+        st.short_rows, st.mid_rows = _ptr_nonempty(rb["short_rows"]), _ptr_nonempty(rb["mid_rows"])
+        return st, (pt, ws)
 
 
 LEAN = True                # tests / measurements: False keeps the classic gather kernels
@@ -482,7 +527,7 @@ def project_bwd_input(dH, W, K, FP, out=None, in_drop=0.0, seed=0, row_offset=0,
 # --------------------------------------------------------------------------- K2
 def node_attn_fwd(graph: CSRGraph, H_tab, f1, a2, b2, c, out=None, train=False, coef_drop=0.0,
                   fts_drop=0.0, seed=0, row_offset=0, activation=ACT_ELU, table_gid=None, res=None,
-                  seed_dev=None, f2_src=None, f2=None):
+                  seed_dev=None, f2_src=None, f2=None, rows=None):
     """utils/layers.py:26-35,46.  H_tab (NT,D): gather table of UNDROPPED projected
     rows indexed by graph.colidx (f2_j is recomputed from the gathered row with
     a2 (K,F'), b2 (K,)); with fts_drop > 0 bit 0 of each element is its keep bit
@@ -493,9 +538,17 @@ def node_attn_fwd(graph: CSRGraph, H_tab, f1, a2, b2, c, out=None, train=False, 
     this table instead of being recomputed (slices of a head wider than 64 columns: f1 / f2_src hold the head's
     totals).  f2 (NT,K): the table rows' scores as project_fwd returned them -- with them a small graph with long rows
     (_use_lean) runs on the lean kernels, which read the scores instead of recomputing them.
+    rows: None, or the rows to compute -- a RowSubset of `graph`, or a plan whose subset(graph) gives one
+    (layers.LiveForwardPlan).  Only the listed rows of out (and lse, aggp, tsum) are written, with the bits the full
+    call gives them; every other row keeps what the (full-size) tensors held.  Such a call never takes the lean or
+    dense form and records the listed rows and their entries in K2_TIMING.
     Returns out, saved where saved = (out, lse, aggp, tsum) if train else None: saved[0] is the OUTPUT view itself,
     which node_attn_bwd_rows reads (it must stay unmodified until then); the pre-activation is not stored."""
     lib = _lib.load()
+    if rows is not None and not isinstance(rows, RowSubset):
+        rows = rows.subset(graph)
+    if rows is not None and rows.graph is not graph:
+        raise ValueError("rows: the row subset was built for another graph")
     K, FP = a2.shape
     _check_heads(K, FP)
     N = graph.n_rows
@@ -515,7 +568,7 @@ def node_attn_fwd(graph: CSRGraph, H_tab, f1, a2, b2, c, out=None, train=False, 
             raise ValueError("f2_src: only for one head of 64 columns (K = 1, F' = 64)")
         _chk(f2_src, "f2_src", (graph.n_cols, 1), device=dev)
         f2 = f2_src
-    lean = f2 is not None and table_gid is None and _use_lean(graph, H_tab)
+    lean = rows is None and f2 is not None and table_gid is None and _use_lean(graph, H_tab)
     if lean:
         _chk(f2, "f2", (graph.n_cols, K), device=dev)
     if graph.device != dev:
@@ -540,9 +593,9 @@ def node_attn_fwd(graph: CSRGraph, H_tab, f1, a2, b2, c, out=None, train=False, 
         tsum = torch.empty((N, K), dtype=torch.float32, device=dev)
         saved = (out, lse, aggp, tsum)
         ptrs = [None, lse.data_ptr(), aggp.data_ptr(), tsum.data_ptr()]
-    split, _keep = _row_split_arg(graph, "f", bins=not lean, split=not lean)
+    split, _keep = _row_split_arg(graph, "f", bins=not lean, split=not lean) if rows is None else rows.arg("f")
     dense, _keep_d = _dense_arg(graph, train, "f") if (lean and f2_src is None and _use_dense(graph, H_tab, K, FP)) else (None, None)
-    with _k2_timed("train" if train else "eval", N, graph.nnz):
+    with _k2_timed("train" if train else "eval", *((N, graph.nnz) if rows is None else (rows.n_rows, rows.nnz))):
         _lib.check(lib.han_node_attn_fwd(
             graph.rowptr.data_ptr(), graph.colidx.data_ptr(),
             _ptr(graph.values), H_tab.data_ptr(), tcode, _ptr(table_gid), f1.data_ptr(),
@@ -552,7 +605,7 @@ def node_attn_fwd(graph: CSRGraph, H_tab, f1, a2, b2, c, out=None, train=False, 
             ptrs[0], ptrs[1], ptrs[2], ptrs[3], N, graph.nnz, K, FP, LEAKY_SLOPE, coef_drop, fts_drop,
             int(seed), _dev_word(seed_dev), int(row_offset), int(activation),
             (FLAG_XCD_ORDER if graph.has_locality() else 0) | (FLAG_LEAN if lean else 0) | (FLAG_K2_DEEP if K2_DEEP else 0)
-            | (FLAG_K2_SHARED_HASH if K2_SHARED_HASH else 0),
+            | (FLAG_K2_SHARED_HASH if K2_SHARED_HASH else 0) | (FLAG_K2_ROW_SUBSET if rows is not None else 0),
             ctypes.byref(split) if split is not None else None,
             ctypes.byref(dense) if dense is not None else None, _stream()), "han_node_attn_fwd")
     return out, saved
@@ -704,8 +757,12 @@ def score_param_bwd(H, df1, df2, K=8, FP=8, out=None):
 
 
 # --------------------------------------------------------------------------- K3
-def sem_attn_fwd(M, w_omega, b_omega, u_omega, flags=0):
-    """utils/layers.py:152-159.  M (N,P,D) -> Z (N,D), beta (N,P)."""
+def sem_attn_fwd(M, w_omega, b_omega, u_omega, flags=0, live=None, out=None):
+    """utils/layers.py:152-159.  M (N,P,D) -> Z (N,D), beta (N,P).
+    live: (n_live,) int32 ascending node ids (han_sem_attn_fwd_live): only the rows of these nodes of M are read and only
+    their rows of Z and beta are written -- the listed rows get the bits of the full call from 65 536 rows of M on --;
+    the other rows of the full-size outputs are uninitialised memory (or what `out` = (Z, beta) held).  Where the
+    library does not take the shape over a list (han_hip.h), the full entry runs: every row of M is then read."""
     lib = _lib.load()
     _chk(M, "M")
     if M.dim() != 3 or M.shape[2] % 64 != 0 or M.shape[2] == 0:
@@ -716,8 +773,18 @@ def sem_attn_fwd(M, w_omega, b_omega, u_omega, flags=0):
     _chk(w_omega, "w_omega", (Dm, A), device=dev)
     _chk(b_omega, "b_omega", (A,), device=dev)
     _chk(u_omega, "u_omega", (A,), device=dev)
-    Z = torch.empty((N, Dm), dtype=torch.float32, device=dev)
-    beta = torch.empty((N, P), dtype=torch.float32, device=dev)
+    Z = _out(None if out is None else out[0], "Z", (N, Dm), dev)
+    beta = _out(None if out is None else out[1], "beta", (N, P), dev)
+    if live is not None:
+        if live.dim() != 1 or live.numel() > N:
+            raise ValueError(f"live: expected at most {N} node ids, got {tuple(live.shape)}")
+        _chk(live, "live", (live.numel(),), dtype=torch.int32, device=dev)
+        code = lib.han_sem_attn_fwd_live(M.data_ptr(), w_omega.data_ptr(), b_omega.data_ptr(), u_omega.data_ptr(),
+                                         Z.data_ptr(), beta.data_ptr(), _ptr_nonempty(live), live.numel(), N, P, Dm, A,
+                                         int(flags), _stream())
+        if code != _lib.E_UNSUPPORTED:
+            _lib.check(code, "han_sem_attn_fwd_live")
+            return Z, beta
     _lib.check(lib.han_sem_attn_fwd(M.data_ptr(), w_omega.data_ptr(), b_omega.data_ptr(),
                                     u_omega.data_ptr(), Z.data_ptr(), beta.data_ptr(), N, P, Dm, A,
                                     int(flags), _stream()), "han_sem_attn_fwd")
@@ -818,11 +885,15 @@ def _classifier_args(Z, Wc, bc):
     return N, dev, HC, Dm, C
 
 
-def classifier_loss(Z, Wc, bc, labels, mask, row_weight, backward=False, grad_out=None):
+def classifier_loss(Z, Wc, bc, labels, mask, row_weight, backward=False, grad_out=None, live=None):
     """models/gat.py:65-72 + models/base_gattn.py:41-48,61-69.
     Z (N,D); Wc (HC,D,C); bc (HC,C); labels int32 (N,); mask uint8 (N,).
     Returns logits (N,C), loss_acc (2,) [masked CE, masked accuracy] and, if
-    backward, (dZ, dWc, dbc) [dWc, dbc written to the tensors of grad_out when given]."""
+    backward, (dZ, dWc, dbc) [dWc, dbc written to the tensors of grad_out when given].
+    live: (n_live,) int32 ascending node ids (han_classifier_loss_live): only these rows of Z are read -- the others may
+    hold anything --, only their rows of logits and dZ are written (the full call's bits; the other rows are
+    uninitialised memory), and the loss, the accuracy, dWc and dbc are sums over them, mask still applied per row.
+    The fused shapes only (D in {64, 128}, C <= 64): anything else raises."""
     lib = _lib.load()
     N, dev, HC, Dm, C = _classifier_args(Z, Wc, bc)
     _chk(labels, "labels", (N,), dtype=torch.int32, device=dev)
@@ -839,6 +910,16 @@ def classifier_loss(Z, Wc, bc, labels, mask, row_weight, backward=False, grad_ou
         grads = (dZ, dWc, dbc)
         ptrs = (dZ.data_ptr(), dWc.data_ptr(), dbc.data_ptr())
     ws = _ws(lib.han_classifier_workspace(N, Dm, C, HC), dev, "cls")
+    if live is not None:
+        if live.dim() != 1 or live.numel() > N:
+            raise ValueError(f"live: expected at most {N} node ids, got {tuple(live.shape)}")
+        _chk(live, "live", (live.numel(),), dtype=torch.int32, device=dev)
+        _lib.check(lib.han_classifier_loss_live(
+            Z.data_ptr(), Wc.data_ptr(), bc.data_ptr(), labels.data_ptr(), mask.data_ptr(),
+            float(row_weight), logits.data_ptr(), loss_acc.data_ptr(), ptrs[0], ptrs[1], ptrs[2],
+            ws.data_ptr(), ws.numel(), _ptr_nonempty(live), live.numel(), N, Dm, C, HC, _stream()),
+            "han_classifier_loss_live")
+        return logits, loss_acc, grads
     _lib.check(lib.han_classifier_loss(
         Z.data_ptr(), Wc.data_ptr(), bc.data_ptr(), labels.data_ptr(), mask.data_ptr(),
         float(row_weight), logits.data_ptr(), loss_acc.data_ptr(), ptrs[0], ptrs[1], ptrs[2],

@@ -76,12 +76,18 @@ class _EvalBranch:
 LIVE_BACKWARD_MIN_ROWS = 262144
 
 
+# HANTrainer(live_forward="auto") acts from this many rows on.  A constant of its own, so that patching the backward's
+# does not switch the forward on: below it the default trainer keeps the launches (and the whole-graph M, Z and logits)
+# that the small-graph tests look at.  live_forward=True has no such floor.
+LIVE_FORWARD_MIN_ROWS = 262144
+
+
 class HANTrainer:
     def __init__(self, model: HeteGAT_multi, xs, graphs, labels, train_mask, val_mask=None,
                  lr=0.005, l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6,
                  part: NodePartition | None = None, patience=100, max_halo_fraction=0.6,
                  use_graph=False, graphs_local=False, xs_full=None, replicate="auto", masked_backward=False,
-                 side_stream=False, overlap_eval=False, live_backward="auto"):
+                 side_stream=False, overlap_eval=False, live_backward="auto", live_forward="auto"):
         """xs: list of P (N_local,F) feature tensors (this rank's rows), or sparse features (SparseFeatures / torch
         sparse COO or CSR tensors; single process only);
         graphs: list of P CSRGraph (or dense masks / CSR tuples).  Under a partition (`part`) either
@@ -122,8 +128,22 @@ class HANTrainer:
         The trainer sets model.direct_grads(True) and model.fold_k3 = True and leaves them set: both describe ITS step
         (every parameter used once, M consumed by semantic() alone).  A model used free-form afterwards with another
         consumer of M raises in the backward (layers.FoldTail); set model.fold_k3 = False for that.
-        live_backward ("auto" | True | False): the forward evaluates every row in every step, as the reference does (sess.run,
-        ex_acm3025.py:190); the backward computes exactly the terms that are not identically zero.  With a single
+        live_forward ("auto" | True | False): epoch() returns four scalars -- the training loss and accuracy, sums over
+        the train mask, and the validation pair, a sum over the val mask -- and with one node-attention layer and a
+        row-local K3 and classifier, row i of M, Z and the logits influences them only when i is in the mask.  The
+        reference's sess.run([train_op, loss, accuracy]) (ex_acm3025.py:190) fetches the same scalars; TensorFlow
+        computes every row there only because its dense ops cannot do otherwise.  So K1 still projects every row (H is
+        the gather table), and the K2 gather, K3 and the classifier run over the masked rows only
+        (layers.LiveForwardPlan, one per mask, shared when both masks are one tensor), and so does K3.  A
+        listed row gets the bits the full forward gives it; the sums over the rows are taken in another order.  The eval
+        forward does so where all of these hold -- CUDA, one node-attention layer of the 8 x 8 head shape, at most 64
+        classes, no node partition, a mask of at most half of the rows -- and, for "auto", the graphs have at least
+        LIVE_FORWARD_MIN_ROWS rows; eval_step(mask=other) with any other mask runs the full forward.  The training
+        forward does so ONLY in a step whose backward is the row-list fold of live_backward (fp32 tables, no residual,
+        no per-meta-path streams, masked backward off, a K3 of han_sem_attn_bwd_rows_live's shapes): every other
+        backward reads M and aggp of every row.  True: ValueError where the eval conditions fail.  Whole-graph
+        embeddings and logits remain what inference / predict return: those paths are not touched.
+        live_backward ("auto" | True | False): the backward computes exactly the terms that are not identically zero.  With a single
         node-attention layer, a row-local K3 and classifier and a train mask that never changes, dZ_i, dM_i and g_i are
         exactly zero for every row i outside the mask, so the set-up builds, once, the list of live rows and per
         meta-path the transposed graph with only the entries whose destination is live (layers.LiveBackwardPlan); the
@@ -188,6 +208,7 @@ class HANTrainer:
         if live_backward not in ("auto", True, False):
             raise ValueError(f"live_backward = {live_backward!r}: expected 'auto', True or False")
         self._live_plan = None
+        self._live_fwd_train = None
         n_all = self._global_count(torch.ones_like(self.train_mask))
         live_ok = (dev.type == "cuda" and not model.extra and self.part is None
                    and 2 * self._global_count(self.train_mask) <= n_all)
@@ -197,8 +218,35 @@ class HANTrainer:
         if live_ok and (live_backward is True or (live_backward == "auto" and n_all >= LIVE_BACKWARD_MIN_ROWS)):
             self._live_plan = layers.LiveBackwardPlan(self.graphs_t, self.train_mask)
         self.set_masked_backward(masked_backward)
-        self.val_mask = (val_mask if val_mask is not None else train_mask).to(
-            device=dev, dtype=torch.uint8).contiguous()
+        # one tensor for both masks when the caller gave one: the plans below are looked up by the mask tensor's identity
+        # and built from its values once -- the masks are constructor arguments and must not be edited in place afterwards
+        # (an edit of the one would also be an edit of the other, and the row lists would go stale)
+        same_masks = val_mask is None or val_mask is train_mask
+        self.val_mask = self.train_mask if same_masks else val_mask.to(device=dev, dtype=torch.uint8).contiguous()
+        if live_forward not in ("auto", True, False):
+            raise ValueError(f"live_forward = {live_forward!r}: expected 'auto', True or False")
+        self._live_fwd = {}      # id(mask tensor) -> (mask, layers.LiveForwardPlan): train mask, val mask
+        shape_ok = (dev.type == "cuda" and not model.extra and self.part is None and model.K == 8 and model.FP == 8
+                    and model.Wc.shape[2] <= layers.MAX_CLASSES)
+
+        def fwd_ok(mask):
+            return shape_ok and 2 * self._global_count(mask) <= n_all
+        if live_forward is True and not fwd_ok(self.val_mask):
+            raise ValueError("live_forward=True needs a CUDA model with one node-attention layer of 8 x 8 heads, at most "
+                             "64 classes, no node partition and a val mask of at most half of the rows")
+        if live_forward is True or (live_forward == "auto" and n_all >= LIVE_FORWARD_MIN_ROWS):
+            if fwd_ok(self.val_mask):
+                self._live_fwd[id(self.val_mask)] = (self.val_mask, layers.LiveForwardPlan(self.graphs, self.val_mask))
+            # the training forward: only beside the row-list fold, whose K3 shapes are han_sem_attn_bwd_rows_live's
+            A, P = model.w_omega.shape[1], len(self.graphs)
+            if (self._live_plan is not None and shape_ok and A in (64, 128) and P in (1, 2, 4)
+                    and tuple(model.w_omega.shape) == (ops.D, A) and n_all * ops.gs_row_bytes() < (1 << 32)):
+                mine = self._live_fwd.get(id(self.train_mask))
+                plan = layers.LiveForwardPlan(self.graphs, self.train_mask, backward=self._live_plan)
+                if mine is not None:      # one mask for both: one plan, one set of row lists
+                    plan._subsets = mine[1]._subsets
+                self._live_fwd_train = plan
+
         # mean(loss * mask / mean(mask)) == sum(mask * loss) / count(mask): the
         # normaliser is a setup-time constant, summed over ranks once.
         self.w_train = 1.0 / max(self._global_count(self.train_mask), 1)
@@ -259,6 +307,11 @@ class HANTrainer:
     def live_backward(self) -> bool:
         """Whether the backward runs over the live rows only (the live_backward argument, as decided)."""
         return self.model.live_bwd is not None
+
+    @property
+    def live_forward(self) -> bool:
+        """Whether the eval forward of the val mask runs over its rows only (the live_forward argument, as decided)."""
+        return id(self.val_mask) in self._live_fwd
 
     def set_masked_backward(self, flag: bool):
         """Switch the opt-in masked backward on or off (plans are built on first use; collective under a partition)."""
@@ -342,11 +395,17 @@ class HANTrainer:
 
     def _forward(self, train: bool, mask, weight):
         m = self.model
+        if train:      # the train mask; NodeLevelAttention.forward declines where the backward is not the row-list fold
+            plan = self._live_fwd_train
+        else:          # the mask the plan was built for, and no other
+            plan = self._live_fwd.get(id(mask), (None, None))
+            plan = plan[1] if plan[0] is mask else None
         with torch.set_grad_enabled(train):
             M = m.node_level(self.xs, self.graphs, self.attn_drop if train else 0.0,
                              self.ffd_drop if train else 0.0, train, ops.ACT_ELU,
                              graphs_t=self.graphs_t,
-                             xs_full=self.xs_full if ("train" if train else "eval") in self.replicate else None)
+                             xs_full=self.xs_full if ("train" if train else "eval") in self.replicate else None,
+                             live_fwd=plan)
             Z, _ = m.semantic(M)
             loss, acc, _ = m.classifier_loss(Z, self.labels, mask, weight)
         return loss, acc

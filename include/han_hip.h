@@ -77,6 +77,15 @@ extern "C" {
                                   g row is identically zero -- a destination outside the loss mask of a one-layer model);
                                   the remaining terms are summed in the positions and order of the full pass, so the
                                   results are bit-identical to it.  Opt-in (HANTrainer(masked_backward=True)).          */
+#define HAN_FLAG_K2_ROW_SUBSET 8192 /* han_node_attn_fwd: `split` (required) lists exactly the rows to compute -- short_rows,
+                                  mid_rows and long_rows together, each row in the set its length puts it in; an empty set
+                                  launches nothing (no launch over all N rows).  Rows that are not listed are neither read
+                                  nor written in any output, and a listed row gets the bits the full launch gives it (the
+                                  same kernels, the same per-row arithmetic, dropout keyed by global ids).  For any head
+                                  shape and either table type.  HAN_E_UNSUPPORTED, before any launch, together with
+                                  HAN_FLAG_LEAN, with a han_dense_t, or with a non-empty set whose list pointer is NULL
+                                  (no identity lists).  For callers that read only some rows of the result: a trainer
+                                  whose loss and metrics are sums over a fixed mask (HANTrainer(live_forward=...)).      */
 /* `flags` of han_project_fwd: which matrix pipe runs the projection (default 0: the library chooses --
  * the bf16 x 6 kernel for training forwards and bf16 features, the exact-fp32 kernel otherwise).
  * Both have fp32-class accuracy; the switches exist for measurements and tests.                     */
@@ -231,7 +240,8 @@ int han_project_sparse_bwd(const int64_t *colptr, const int32_t *rowidx, const f
  *   mid_rows (n_mid): rows of HAN_SHORT_DEG .. split_deg entries -- a wave per row;
  *   rows beyond split_deg: the chunks below.
  * A list pointer may be NULL when its bin holds every row of the launch (n == N: identity).  Every row must be in
- * exactly one of the three sets; each row is processed by one fixed kernel in a fixed order (bitwise reproducible).
+ * exactly one of the three sets (under HAN_FLAG_K2_ROW_SUBSET of han_node_attn_fwd: every row TO COMPUTE, and no
+ * other); each row is processed by one fixed kernel in a fixed order (bitwise reproducible).
  * Splitting: rows (sources, in the backward) with more than split_deg stored entries are skipped by the main
  * launch; each is cut into chunks of consecutive edges [chunk_start, chunk_end),
  * one wave per chunk produces a partial state in `workspace`, and a finishing
@@ -440,6 +450,17 @@ int han_sem_attn_bwd_rows_live(const float *M, const float *w_omega, const float
                                int P, int D, int A, int K, int FP, int table_dtype, int activation, int flags,
                                void *stream);
 
+/* han_sem_attn_fwd over a row list (an addition under ABI 15): live (n_live) holds ascending int32 node ids, each below
+ * N, none twice.  Rows (live[t], p) of M are read; Z and beta are written at node live[t] of the full-size arrays;
+ * nothing else is read or written.  The kernel is the bf16-pipe wave kernel of han_sem_attn_fwd with a tile's 16 rows
+ * taken from the list (16 / P nodes per tile), at any count: with live = 0 .. N - 1 and N * P >= 65 536 every output
+ * holds the bits of han_sem_attn_fwd, and a listed row's bits do not depend on which other rows are listed.
+ * D == 64, A in {64, 128}, P in {1, 2, 4}, not HAN_FLAG_K3_EXACT_PIPE; anything else HAN_E_UNSUPPORTED before any
+ * launch (the caller then runs the full entry).  n_live == 0 launches nothing.                                    */
+int han_sem_attn_fwd_live(const float *M, const float *w_omega, const float *b_omega, const float *u_omega, float *Z,
+                          float *beta, const int32_t *live, int64_t n_live, int64_t N, int P, int D, int A, int flags,
+                          void *stream);
+
 /* ---- classifier + masked loss ----------------------------------------------
  * models/gat.py:65-72: logits = (1/HC) sum_h (Z Wc[h] + bc[h]);  Wc (HC,D,C).
  * models/base_gattn.py:41-48,61-69: per-row masked softmax-CE and accuracy
@@ -457,6 +478,19 @@ int han_classifier_loss(const float *Z, const float *Wc, const float *bc,
                         float *logits, float *loss_acc, float *dZ, float *dWc, float *dbc,
                         void *workspace, size_t workspace_bytes, int64_t N, int D, int C,
                         int HC, void *stream);
+
+/* han_classifier_loss over a row list (an addition under ABI 15): live (n_live) holds ascending int32 node ids, each
+ * below N, none twice.  Only the listed rows of Z, labels and mask are read; logits rows, and dZ rows when dZ != NULL,
+ * are written at the listed rows of the full-size arrays and nowhere else, with the bits han_classifier_loss gives
+ * them (the same kernel text and per-row arithmetic); loss_acc, dWc and dbc are the sums over the listed rows, mask
+ * still applied per row.  For callers whose Z holds no defined values outside the list (the full entry multiplies the
+ * loss of an unmasked row by a zero weight, and 0 x NaN is NaN).  The fused shapes only: D in {64, 128}, C <= 64,
+ * anything else HAN_E_UNSUPPORTED before any launch.  n_live == 0 launches no kernel and writes zeros to loss_acc (and
+ * dWc, dbc).  Workspace: han_classifier_workspace(N, D, C, HC).                                                      */
+int han_classifier_loss_live(const float *Z, const float *Wc, const float *bc, const int32_t *labels,
+                             const uint8_t *mask, float row_weight, float *logits, float *loss_acc, float *dZ,
+                             float *dWc, float *dbc, void *workspace, size_t workspace_bytes, const int32_t *live,
+                             int64_t n_live, int64_t N, int D, int C, int HC, void *stream);
 
 /* The backward of the logits alone (HeteGAT_multi.inference returns logits; a caller
  * that forms its own loss hands back dlogits (N,C)):  dZ = dlogits @ mean_h(Wc[h])^T,

@@ -15,11 +15,18 @@ KERNELS = {"k2_fwd_eval": "node_attn_fwd_kernel<8, false, 1,", "k2_fwd_train": "
 
 def main():
     vals = collections.defaultdict(lambda: collections.defaultdict(list))
+    short = collections.defaultdict(list)      # the four-rows-a-wave launches of the backward gather
     for f in glob.glob(os.path.join(ROOT, "gpurun_out", "pmc_traffic", "*_counter_collection.csv")):
         for r in csv.DictReader(open(f)):
             for tag, sub in KERNELS.items():
                 if sub in r["Kernel_Name"]:
                     vals[tag][r["Counter_Name"]].append(float(r["Counter_Value"]))
+            if "node_attn_bwd_cols_kernel<8, 4," in r["Kernel_Name"]:
+                short[r["Counter_Name"]].append(float(r["Counter_Value"]))
+    # the backward gather of a live graph (HANTrainer(live_backward=...)) runs four rows a wave, and its wave-a-row
+    # launch only visits the empty rows: price the row shape that moves the bytes
+    if short["FETCH_SIZE"] and sum(short["FETCH_SIZE"]) > sum(vals["k2_bwd_cols"]["FETCH_SIZE"]):
+        vals["k2_bwd_cols"] = short
     detail = {}
     for tag, d in vals.items():
         fetch = sum(d["FETCH_SIZE"]) / max(len(d["FETCH_SIZE"]), 1)
