@@ -51,6 +51,9 @@ SIGNATURES = {
                                 c_float, c_float, c_uint64, P, I64, P, c_int, P]),
     "han_project_fwd_multi": (c_int, [P, c_int, I64, P, P, P, P, P, P, c_int, P, P, P, c_size_t, I64, c_int, c_int, c_int,
                                       c_int, c_float, c_float, P, P, I64, P, c_int, P]),
+    "han_project_fwd_both_workspace": (c_size_t, [I64, c_int, c_int, c_int, c_int]),
+    "han_project_fwd_both": (c_int, [P, c_int, I64, P, P, P, P, P, P, c_int, P, P, P, P, P, P, c_size_t, I64, c_int, c_int,
+                                     c_int, c_int, c_float, c_float, P, P, I64, P, c_int, P]),
     "han_project_bwd_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
     "han_project_bwd": (c_int, [P, c_int, I64, P, P, P, c_size_t, I64, c_int, c_int, c_int, c_float,
                                 c_uint64, P, I64, P, P]),
@@ -127,6 +130,7 @@ SIGNATURES = {
 
 ABI_VERSION = 15
 E_UNSUPPORTED = -2      # HAN_E_UNSUPPORTED
+E_NOT_ELIGIBLE = -4     # HAN_E_NOT_ELIGIBLE (han_project_fwd_both: nothing was launched)
 _lib = None
 
 

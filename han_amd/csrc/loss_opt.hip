@@ -542,6 +542,7 @@ extern "C" const char *han_error_string(int code) {
         case HAN_E_BADARG: return "han: bad argument (null pointer, negative size or inconsistent shape)";
         case HAN_E_UNSUPPORTED: return "han: shape not supported by this build (K*FP == 64 with FP in {4,8,16,32,64}; D and A multiples of 64)";
         case HAN_E_WORKSPACE: return "han: workspace too small";
+        case HAN_E_NOT_ELIGIBLE: return "han: this call is outside the combined kernel's shapes; nothing was launched (use the separate entry points)";
         default: return code > 0 ? hipGetErrorString((hipError_t)code) : "han: unknown error";
     }
 }

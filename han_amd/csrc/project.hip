@@ -466,6 +466,189 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void project_fwd_b6_kerne
 }
 
 // ---------------------------------------------------------------------------------------------
+// Training forward AND eval forward of one meta-path in one pass over X (han_project_fwd_both): in a steady-state
+// epoch the eval forward projects X with the weights the next training forward projects it with again, and the
+// unmasked A fragments the eval product needs sit in the training kernel's registers before each head's mask is
+// applied.  The block is project_fwd_b6_kernel<true, false, true, 8>'s (128 rows, 8 waves x one 16-row tile, the keep
+// table collected in LDS); on top it issues the eval forward's six unmasked products per column tile, in the chain and
+// order of project_fwd_b6_multi_kernel, into a second 16 x 64 tile and writes a second row set without scale or stamp.
+//
+// Registers: 16 more accumulators do not fit beside one accumulator per HEAD (128 registers for four waves per SIMD).
+// The two heads of a 16-column tile therefore share ONE accumulator: head 2t is multiplied against B fragments whose
+// columns 8..15 are zero, head 2t + 1 against the complement.  A product with an exact zero adds +-0, and the
+// accumulator, which starts at +0 and so is never -0, keeps its bits: every column holds what its own head's
+// accumulator held, and the epilogue's select between two accumulators goes.  (X must be finite: a kept Inf of one
+// head meets the zero of its sibling's columns and leaves a NaN there; the per-head form discarded those columns.)
+// The zero halves cost no instruction and no second W image: a lane whose column belongs to the other head reads its
+// fragment 12 KB further on, from a zeroed mirror of the W tile (the same banks as the real fragment, so the reads
+// conflict as little as they always did; the lane's two base addresses are loop constants).  Zeroing the fragments in
+// registers instead -- a lane-constant AND on the full fragment, 12 vector instructions per head and no mirror -- was
+// built and measured: 40 spilled registers, 5.33 ms for four launches against 3.51 ms.
+// ---------------------------------------------------------------------------------------------
+struct ProjBothArgs {
+    ProjFwdArgs tr;          // the training half: what project_fwd_b6_kernel<true, false, true, 8> gets; wimg = K-step 0 of this meta-path
+    K1Epilogue ev;           // the eval rows: H / f1 / f2 and the score parameters; thr_fts = HAN_KEEP_ALL
+    int64_t wstep;           // bytes between two K-steps of the W image ([K-step][meta-path]: P * B6_WTILE)
+};
+
+__global__ __launch_bounds__(512, 4) void project_fwd_b6_both_kernel(const ProjBothArgs b_in) {
+    ProjFwdArgs a = b_in.tr;
+    han_resolve_seed(a.seed_lo, a.seed_hi, a.seed_dev);
+    constexpr int NT = 512;
+    constexpr int XV = 1024 / NT;             // float4 loads of X per thread per tile (128 rows x 32 k)
+    constexpr int WU = (B6_WTILE / 8) / NT;   // 8-byte pieces of the W image per thread per K-step
+    constexpr int ZB = B6_WTILE;              // the zeroed mirror of the W tile
+    __shared__ __attribute__((aligned(16))) unsigned char lds[3 * B6_XBYTES + B6_WTILE + ZB + B6_ROWS * 128];
+    unsigned char *Xs = lds;                                // [3][128][64 B, slots swizzled]
+    unsigned char *Ws = lds + 3 * B6_XBYTES;                // [3][64][64 B], then the mirror
+    unsigned char *Kacc = Ws + B6_WTILE + ZB;               // [128 rows][128 B]: the keep words of four K-steps
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, w = tid >> 6;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int64_t row0 = (int64_t)blockIdx.x * B6_ROWS;
+#pragma unroll
+    for (int i = 0; i < ZB / (8 * NT); ++i)                 // read only after the K loop's barriers
+        *reinterpret_cast<uint2 *>(Ws + B6_WTILE + 8 * (tid + NT * i)) = make_uint2(0u, 0u);
+    static_assert(ZB % (8 * NT) == 0, "the mirror is zeroed in whole 8-byte pieces per thread");
+    auto flush_keep = [&](int kbase) {                // rows x features [kbase, kbase + 128) of the table (as project_fwd_b6_kernel)
+#pragma unroll
+        for (int i = 0; i < 1024 / NT; ++i) {
+            const int c = tid + NT * i;
+            const int r = c >> 3, sg = c & 7;
+            const int64_t krow = row0 + r;
+            if (krow < a.N && kbase + 16 * sg < a.F) {
+                const uint4 raw = *reinterpret_cast<const uint4 *>(Kacc + r * 128 + 16 * (sg ^ ((r >> 1) & 7)));
+                const uint4 v = (r & 1) ? make_uint4(raw.z, raw.w, raw.x, raw.y) : raw;
+                uint8_t *dst = a.keep + krow * (int64_t)a.F + kbase + 16 * sg;
+                if (kbase + 16 * sg + 8 < a.F) *reinterpret_cast<uint4 *>(dst) = v;
+                else *reinterpret_cast<uint2 *>(dst) = make_uint2(v.x, v.y);
+            }
+        }
+    };
+
+    f32x4 acc[4], acc_e[4];      // per column tile: both heads' masked products / the unmasked products
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = acc_e[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    float4_t xr[XV];
+    uint2 wq[WU];
+    const int ktiles = (a.F + 31) >> 5;
+    auto load_tile = [&](int k0) {      // unconditional loads from clamped addresses (see project_fwd_b6_kernel)
+#pragma unroll
+        for (int i = 0; i < XV; ++i) {
+            const int idx = tid + NT * i;
+            const int r = idx >> 3, c4 = (idx & 7) * 4;
+            const int64_t row = row0 + r;
+            const int64_t rc = row < a.N ? row : a.N - 1;
+            const int kc = k0 + c4 < a.F ? k0 + c4 : a.F - 4;
+            xr[i] = load_x4(a.X, false, rc * a.ldx + kc);
+        }
+        const int kt = (k0 >> 5) < ktiles ? (k0 >> 5) : ktiles - 1;
+        const unsigned char *src = a.wimg + (int64_t)kt * b_in.wstep;
+#pragma unroll
+        for (int i = 0; i < WU; ++i) wq[i] = *reinterpret_cast<const uint2 *>(src + 8 * (tid + NT * i));
+    };
+    const uint32_t thr2 = (a.thr_in & 0xFFFFu) * 0x00010001u, one2 = 0x00010001u;   // keep iff field < thr_in
+    const int fro = l15 * B6_LDB + ((l4 ^ b6_swz(l15)) << 4);      // this lane's fragment inside a 16-row tile
+    // head parity hh owns the columns 8 hh .. 8 hh + 7 of its tile: the other lanes read the mirror's zeros
+    const int frz0 = fro + (l15 < 8 ? 0 : ZB), frz1 = fro + (l15 < 8 ? ZB : 0);
+    load_tile(0);
+    for (int k0 = 0; k0 < a.F; k0 += 32) {
+        __syncthreads();   // the previous tile's fragment reads are done
+        if (k0 > 0 && (k0 & 96) == 0) flush_keep(k0 - 128);      // the four K-steps before this one are complete
+#pragma unroll
+        for (int i = 0; i < XV; ++i) {
+            const int idx = tid + NT * i;
+            b6_stage_x4<false>(Xs, B6_XBYTES, idx, row0 + (idx >> 3) < a.N && k0 + (idx & 7) * 4 < a.F, xr[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < WU; ++i) *reinterpret_cast<uint2 *>(Ws + 8 * (tid + NT * i)) = wq[i];      // straight copy
+        __syncthreads();
+        load_tile(k0 + 32);   // in flight under the MFMAs
+        auto bfrag = [&](int t, int s3, int off) {        // B[k = 8*l4 + j][col = 16t + l15]
+            return *reinterpret_cast<const i32x4 *>(Ws + s3 * B6_WBYTES + 16 * t * B6_LDB + off);
+        };
+        const int lr = 16 * w + l15;
+        i32x4 af[3];
+#pragma unroll
+        for (int s3 = 0; s3 < 3; ++s3)
+            af[s3] = *reinterpret_cast<const i32x4 *>(Xs + s3 * B6_XBYTES + 16 * w * B6_LDB + fro);
+        // keep masks of this lane's 8 elements, four heads per call, and the keep words: project_fwd_b6_kernel's
+        const uint32_t nglob = (uint32_t)(row0 + lr + a.row_offset);
+        uint32_t kw[2] = {0u, 0u};
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            uint32_t mk[8][2];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t kglob = (uint32_t)(k0 + 8 * l4 + j);
+                const HanRand64 rn = han_rand64(a.seed_lo, a.seed_hi, HAN_STREAM_SEQ, nglob, kglob * 2u + (uint32_t)c);
+                mk[j][0] = b6_keep_masks(rn.x, thr2, one2);
+                mk[j][1] = b6_keep_masks(rn.y, thr2, one2);
+#pragma unroll
+                for (int wd = 0; wd < 2; ++wd)
+                    kw[j >> 2] |= mk[j][wd] & (0x00010001u << (4 * (2 * c + wd) + (j & 3)));
+            }
+#pragma unroll
+            for (int hq = 0; hq < 4; ++hq) {
+                const int head = 4 * c + hq;
+                const int t = head >> 1, hh = head & 1, wd = hq >> 1;
+                const uint32_t sel = (head & 1) ? 0x07060302u : 0x05040100u;
+                i32x4 am[3];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t pm = __builtin_amdgcn_perm(mk[2 * i + 1][wd], mk[2 * i][wd], sel);
+#pragma unroll
+                    for (int s3 = 0; s3 < 3; ++s3) am[s3][i] = af[s3][i] & (int)pm;
+                }
+                if (hh == 0) {      // the tile's unmasked products: the eval forward's
+                    const i32x4 b0 = bfrag(t, 0, fro), b1 = bfrag(t, 1, fro), b2 = bfrag(t, 2, fro);
+                    acc_e[t] = han_b6_chain_k1<false>(af, b0, b1, b2, acc_e[t]);
+                }
+                const int fz = hh ? frz1 : frz0;
+                const i32x4 z0 = bfrag(t, 0, fz), z1 = bfrag(t, 1, fz), z2 = bfrag(t, 2, fz);
+                acc[t] = han_b6_chain_k1<false>(am, z0, z1, z2, acc[t]);
+            }
+        }
+        *reinterpret_cast<uint2 *>(Kacc + lr * 128 + 8 * ((((k0 & 96) >> 3) + l4) ^ (lr & 15))) = make_uint2(kw[0], kw[1]);
+    }
+    __syncthreads();
+    flush_keep(((a.F - 1) >> 7) << 7);      // the last (possibly partial) group of K-steps
+    // epilogue: C/D layout col = lane & 15, row = (lane >> 4) * 4 + reg; the training rows, then the eval rows
+    float a1c[4], a2c[4];
+    k1_tile_coeffs(a, l15, a1c, a2c);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int64_t row = row0 + 16 * w + l4 * 4 + r;
+        float vst[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) vst[t] = k1_store_elem(a, row, t, l15, acc[t][r] * a.inv_keep_in);
+        tile_scores<8>(a, row, row < a.N, vst, a1c, a2c, l15);
+    }
+    const K1Epilogue &e = b_in.ev;
+    k1_tile_coeffs(e, l15, a1c, a2c);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int64_t row = row0 + 16 * w + l4 * 4 + r;
+        float vst[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {      // nothing is stamped: the plain stores of project_fwd_b6_multi_kernel
+            const float v = acc_e[t][r];
+            const int64_t o = row * HAN_D + 16 * t + l15;
+            if (e.h_bf16) {
+                const uint32_t b = han_f32_to_bf16_bits(v);
+                if (row < a.N) reinterpret_cast<uint16_t *>(e.H)[o] = (uint16_t)b;
+                vst[t] = __uint_as_float(b << 16);
+            } else {
+                if (row < a.N) reinterpret_cast<float *>(e.H)[o] = v;
+                vst[t] = v;
+            }
+        }
+        tile_scores<8>(e, row, row < a.N, vst, a1c, a2c, l15);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Eval forward of SEVERAL meta-paths that share one feature matrix (the reference feeds ONE matrix to every
 // meta-path: ex_acm3025.py:86, models/gat.py:39), on the bf16 x 6 matrix pipe: the X tile is read from HBM,
 // split into its three bf16 terms and staged ONCE for NP x 64 output columns (round 2 read, split and staged
@@ -1315,6 +1498,55 @@ extern "C" int han_project_fwd_multi(const void *X, int x_dtype, int64_t ldx, co
                                        workspace, workspace_bytes, N, F, K, FP, in_drop, fts_drop,
                                        seeds ? seeds[p] : 0, seed_dev, row_offset, q.keep, flags, stream);
         if (rc != 0) return rc;
+    }
+    return 0;
+}
+
+extern "C" size_t han_project_fwd_both_workspace(int64_t N, int F, int K, int FP, int P) {
+    return k1_plan(N, F, F, K, FP, P).fwd_bytes;      // the W images of P meta-paths, as the fused eval forward's
+}
+
+// Training and eval forward in one pass over X per meta-path (project_fwd_b6_both_kernel), only where BOTH separate
+// routes would run the bf16 x 6 kernels for EVERY meta-path -- the training forward project_fwd_b6_kernel<true, false,
+// true, 8> (use_b6 with a keep table), the eval forward project_fwd_b6_multi_kernel (use_fused, P even: an odd last
+// meta-path takes the exact-fp32 kernel) -- so that both row sets keep the bits of the separate calls.
+extern "C" int han_project_fwd_both(const void *X, int x_dtype, int64_t ldx, const float *W, const float *a1,
+                                    const float *a2, const float *b1, const float *b2, void *H, int table_dtype,
+                                    float *f1, float *f2, void *H_eval, float *f1_eval, float *f2_eval, void *workspace,
+                                    size_t workspace_bytes, int64_t N, int F, int K, int FP, int P, float in_drop,
+                                    float fts_drop, const uint64_t *seeds, const uint64_t *seed_dev, int64_t row_offset,
+                                    uint8_t *keep, int flags, void *stream) {
+    if (P <= 0 || (in_drop > 0.f && !seeds)) return HAN_E_BADARG;
+    if (N == 0) return 0;
+    const K1Path all = {W, a1, a2, b1, b2, H, f1, f2, keep};
+    const int bad = han_k1_check_fwd(X, all, N, F, ldx >= F && H_eval && f1_eval && f2_eval, true, K, FP, x_dtype,
+                                     table_dtype, in_drop, fts_drop);
+    if (bad != 0) return bad;
+    if ((flags & HAN_FLAG_K1_EXACT_PIPE) && (flags & HAN_FLAG_K1_MATRIX_PIPE)) return HAN_E_BADARG;
+    const K1Plan plan = k1_plan(N, F, ldx, K, FP, P);
+    const bool vec = x_vec(X, ldx, F, false);
+    const bool fp32 = x_dtype == HAN_DTYPE_F32 && table_dtype == HAN_DTYPE_F32;      // the forms built and tested
+    if (!(fp32 && in_drop > 0.f && keep && plan.keep_table && P % 2 == 0 && !(flags & HAN_FLAG_K1_4WAVE) &&
+          use_b6(plan, vec, false, in_drop, K, FP, flags) && use_fused(plan, vec, P, 0.f, 0.f, flags)))
+        return HAN_E_NOT_ELIGIBLE;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = launch_wimage(W, workspace, workspace_bytes, F, P, st);
+    if (rc != 0) return rc;
+    const size_t hb = (size_t)N * HAN_D * sizeof(float), kb = (size_t)N * (size_t)F + 128;
+    const K1Path all_e = {W, a1, a2, b1, b2, H_eval, f1_eval, f2_eval, nullptr};
+    const dim3 grid((unsigned)((N + B6_ROWS - 1) / B6_ROWS));
+    for (int p = 0; p < P; ++p) {
+        const K1Path q = path_of(all, p, N, F, K, hb, kb);
+        ProjBothArgs b;
+        static_cast<K1Epilogue &>(b.tr) = han_k1_epilogue(q, true, table_dtype, N, seeds[p], seed_dev, fts_drop, flags, row_offset);
+        b.tr.X = X; b.tr.ldx = ldx; b.tr.W = q.W; b.tr.F = F; b.tr.x_bf16 = 0;
+        b.tr.thr_in = han_drop_threshold(in_drop); b.tr.inv_keep_in = 1.f / (1.f - in_drop);
+        b.tr.keep = q.keep; b.tr.f_chunk = plan.f_chunk; b.tr.partial = nullptr;
+        b.tr.wimg = (const unsigned char *)workspace + (size_t)p * B6_WTILE;
+        b.wstep = (int64_t)P * B6_WTILE;
+        b.ev = han_k1_epilogue(path_of(all_e, p, N, F, K, hb, 0), true, table_dtype, N, 0, nullptr, 0.f, 0, 0);
+        project_fwd_b6_both_kernel<<<grid, 512, 0, st>>>(b);
+        HAN_CHECK_LAUNCH();
     }
     return 0;
 }

@@ -104,6 +104,8 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
                                               # it on with Z, classifier_loss(Z) takes the row list from it -- the stages of one forward agree on the rows
         self.side_stream = None               # second stream of the eager training step on large graphs (layers.NodeLevelAttention.backward):
                                               # dW of meta-path p runs beside the backward gather of meta-path p + 1
+        self.shared_proj = None               # layers.SharedProjection (HANTrainer(shared_projection=...)): the eval forward of an epoch
+                                              # projects for the next training forward too
         self._graph_cache: dict = {}
         # captured-step mode (HANTrainer(use_graph=True)): a device seed word that the trainer
         # bumps between replays + fixed per-(layer, meta-path) seed constants (han_hip.h "Seeds")
@@ -217,6 +219,12 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         self._graph_cache.clear()
         return self
 
+    def load_state_dict(self, *args, **kw):
+        """nn.Module.load_state_dict; a stashed training projection (layers.SharedProjection) belongs to the old parameters."""
+        if self.shared_proj is not None:
+            self.shared_proj.drop()
+        return super().load_state_dict(*args, **kw)
+
     def param_shapes(self):
         return _param_shapes(self.P, self.F, self.K, self.FP, self.A, self.C, self.HC, self.extra,
                              self.residual)
@@ -306,7 +314,8 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
                 zero_rows=bool(self.zero_rows and first and train and not self.extra),
                 live_bwd=self.live_bwd if (first and train and not self.extra and self.masked_bwd is None) else None,
                 streams=self.path_streams, side_stream=self.side_stream, path_order=self.path_order,
-                overlap=self.overlap_branch if (first and train) else None, **kw)
+                overlap=self.overlap_branch if (first and train) else None,
+                shared_proj=self.shared_proj if (first and not self.extra) else None, **kw)
 
         def layer_fwd(layer, Xin, xs_, K, FP, sink):
             """One node-attention layer: its K heads run through the 64-column K1/K2 kernels in groups of

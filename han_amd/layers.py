@@ -156,6 +156,65 @@ class AllGatherTable(LocalTable):
         return self.part.all_gather_rows_async(table, tag)
 
 
+def stash_key(step, flat):
+    """What must not have changed between the eval forward that stashed a training projection and the training forward
+    that takes it: Adam's step count (the native Adam step writes `flat` without touching its version counter), the
+    version counter of the flat parameter buffer (every torch-side write bumps it, through any view), and the
+    buffer's address (nn.Module.to() and friends re-create it)."""
+    return (int(step), int(flat._version), int(flat.data_ptr()))
+
+
+class SharedProjection:
+    """HANTrainer(shared_projection=...): inside epoch() the eval forward projects X with the parameters the NEXT
+    training forward projects it with again, so its K1 runs as ops.project_fwd_both -- the eval tables plus, under the
+    next step's seeds (rng.peek_seeds) and dropout rates, the training tables H / f1 / f2 / keep of every meta-path --
+    and the training tables wait here.  The next training forward draws its seeds as always and takes them in place of
+    its own ops.project_fwd_multi iff everything they depend on is what it would use itself (take()); they are
+    byte for byte what that call computes.  A stash that is not taken is freed, and the ordinary call runs.
+    The stash holds P x (N x 64 x 4 B + 2 x N x 8 x 4 B + N x F B): 4 x (256 + 64 + 256) MB at N = 1M, P = 4, F = 256."""
+
+    def __init__(self, flat_of, step_of):
+        self._flat_of, self._step_of = flat_of, step_of      # callables: the model's flat buffer, Adam's step count
+        self.armed = None      # the training dropout rate while epoch() runs its eval forward, else None
+        self._stash = None
+        self.taken = 0         # training forwards that ran from a stash (tests, bench diagnostics)
+
+    def key(self):
+        return stash_key(self._step_of(), self._flat_of())
+
+    @staticmethod
+    def stash_bytes(N, F, P):
+        return P * (N * D * 4 + 2 * N * 8 * 4 + N * F + 128)
+
+    def drop(self):
+        self._stash = None
+
+    def eval_forward(self, X, W, a1, a2, b1, b2, row_offset, tdt):
+        """The eval tables (H, f1, f2) of all meta-paths, the next step's training tables stashed -- or None where
+        the combined kernel does not apply (nothing ran: the caller makes the ordinary eval call)."""
+        self._stash = None
+        P = W.shape[0]
+        seeds = rng.peek_seeds(P)
+        got = ops.project_fwd_both(X, W, a1, a2, b1, b2, self.armed, self.armed, seeds, row_offset=row_offset,
+                                   table_dtype=tdt)
+        if got is None:
+            return None
+        self._stash = (self.key(), X, float(self.armed), tuple(seeds), int(row_offset), tdt, got[0])
+        return got[1]
+
+    def take(self, X, in_drop, seeds, row_offset, tdt):
+        """The stashed (H, f1, f2, keeps) for exactly this training projection, or None; the stash is gone either way."""
+        st, self._stash = self._stash, None
+        if st is None:
+            return None
+        key, Xs, drop, sds, off, tdt_s, tables = st
+        if (Xs is X and drop == float(in_drop) and sds == tuple(int(v) for v in seeds) and off == int(row_offset)
+                and tdt_s == tdt and key == self.key()):
+            self.taken += 1
+            return tables
+        return None
+
+
 @dataclasses.dataclass(frozen=True, eq=False)
 class LayerRun:
     """How one call of NodeLevelAttention / WideHeadAttention is to run (built by gat.HeteGAT_multi.node_level)."""
@@ -185,6 +244,7 @@ class LayerRun:
     live_bwd: object = None           # LiveBackwardPlan (HANTrainer(live_backward=...)): the backward visits only the rows the loss reaches
     live_fwd: object = None           # LiveForwardPlan (HANTrainer(live_forward=...)): K2 computes only the rows the caller reads of M
     live_sink: list | None = None     # receives live_fwd when this call ran over it (a training call may decline: NodeLevelAttention.forward)
+    shared_proj: object = None        # SharedProjection (HANTrainer(shared_projection=...)): the eval forward's K1 also projects for the next training forward
 
     @functools.cached_property
     def multi(self) -> bool:
@@ -438,10 +498,18 @@ class NodeLevelAttention(torch.autograd.Function):
             overlap.node_level()
         if streams is None and P > 1 and shared is not None and _same_tensor(shared) and W.is_contiguous() and _unit_stride(shared[0]):
             full = all(replicated)
-            Hs, f1s, f2s, keeps = ops.project_fwd_multi(shared[0], W, a1, a2, b1, b2, in_drop=in_drop, fts_drop=in_drop,
-                                                        seeds=[int(v) for v in run.seeds],
-                                                        row_offset=0 if full else row_offset, table_dtype=tdt,
-                                                        seed_dev=seed_dev, want_keep=True)
+            off = 0 if full else row_offset
+            # HANTrainer(shared_projection=...): the eval forward of an epoch also projects for the next training
+            # forward, which then finds its tables waiting (SharedProjection; the same bytes either way)
+            sp, got = run.shared_proj if seed_dev is None else None, None
+            if sp is not None and train:
+                got = sp.take(shared[0], in_drop, run.seeds, off, tdt)
+            elif sp is not None and sp.armed is not None:
+                ev = sp.eval_forward(shared[0], W, a1, a2, b1, b2, off, tdt)
+                got = ev + ([None] * P,) if ev is not None else None
+            Hs, f1s, f2s, keeps = got if got is not None else ops.project_fwd_multi(
+                shared[0], W, a1, a2, b1, b2, in_drop=in_drop, fts_drop=in_drop, seeds=[int(v) for v in run.seeds],
+                row_offset=off, table_dtype=tdt, seed_dev=seed_dev, want_keep=True)
             pj = [(Hs[p], f1s[p], f2s[p], keeps[p]) for p in range(P)]
 
         def project_path(p):

@@ -473,6 +473,35 @@ def project_fwd_multi(X, W, a1, a2, b1, b2, in_drop=0.0, fts_drop=0.0, seeds=Non
     return H, f1, f2
 
 
+def project_fwd_both(X, W, a1, a2, b1, b2, in_drop, fts_drop, seeds, row_offset=0, table_dtype=torch.float32,
+                     seed_dev=None, flags=0):
+    """han_project_fwd_both: the TRAINING forward (in_drop / fts_drop / seeds, keep tables) and the EVAL forward (no
+    dropout) of all P meta-paths of one dense feature matrix in one pass over X per meta-path.  Returns
+    ((H, f1, f2, [keep tables]), (H_eval, f1_eval, f2_eval)) -- byte for byte what project_fwd_multi(..., in_drop,
+    fts_drop, seeds, want_keep=True) and project_fwd_multi(...) without dropout return -- or None, with nothing
+    launched, where the library's one combined kernel does not apply (han_hip.h lists the conditions: fp32 X and
+    tables, input dropout with a keep table, P even, ...): the caller then makes those two calls.  X must be finite."""
+    lib = _lib.load()
+    if isinstance(X, SparseFeatures) or X.dim() != 2 or W.dim() != 3:
+        return None
+    P = a1.shape[0]
+    xcode, ldx, N, F, K, FP, in_drop, fts_drop, H, f1, f2, ws, keep = _project_fwd_setup(
+        X, W, a1, a2, b1, b2, (P,), in_drop, fts_drop, table_dtype, flags, True, lib.han_project_fwd_both_workspace)
+    if seeds is None or len(seeds) != P:
+        raise ValueError("one seed per meta-path")
+    He, f1e, f2e = torch.empty_like(H), torch.empty_like(f1), torch.empty_like(f2)
+    seed_arr = (ctypes.c_uint64 * P)(*[int(x) & ((1 << 64) - 1) for x in seeds])
+    code = lib.han_project_fwd_both(
+        X.data_ptr(), xcode, ldx, W.data_ptr(), a1.data_ptr(), a2.data_ptr(), b1.data_ptr(), b2.data_ptr(),
+        H.data_ptr(), DTYPE_CODE[table_dtype], f1.data_ptr(), f2.data_ptr(), He.data_ptr(), f1e.data_ptr(), f2e.data_ptr(),
+        _ptr(ws), ws.numel() if ws is not None else 0, N, F, K, FP, P, in_drop, fts_drop, seed_arr, _dev_word(seed_dev),
+        int(row_offset), _ptr(keep), int(flags), _stream())
+    if code == _lib.E_NOT_ELIGIBLE:
+        return None
+    _lib.check(code, "han_project_fwd_both")
+    return (H, f1, f2, [keep[p] for p in range(P)]), (He, f1e, f2e)
+
+
 def project_bwd(X, dH, K, FP, in_drop=0.0, seed=0, row_offset=0, seed_dev=None, out=None, keep=None):
     """dW (F,D) = dropout_k(X)^T dH (written to `out` when given).  keep: the table project_fwd(want_keep=True)
     returned for the same X / seed (the draws are then read, not regenerated), or None.

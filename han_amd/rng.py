@@ -28,3 +28,9 @@ def next_seed() -> int:
     the same number of draws."""
     _state["counter"] += 1
     return _splitmix64(_state["seed"] ^ _splitmix64(_state["counter"]))
+
+
+def peek_seeds(n: int) -> tuple:
+    """The next `n` values next_seed() will return, without advancing the counter."""
+    c = _state["counter"]
+    return tuple(_splitmix64(_state["seed"] ^ _splitmix64(c + i)) for i in range(1, int(n) + 1))

@@ -87,7 +87,8 @@ class HANTrainer:
                  lr=0.005, l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6,
                  part: NodePartition | None = None, patience=100, max_halo_fraction=0.6,
                  use_graph=False, graphs_local=False, xs_full=None, replicate="auto", masked_backward=False,
-                 side_stream=False, overlap_eval=False, live_backward="auto", live_forward="auto"):
+                 side_stream=False, overlap_eval=False, live_backward="auto", live_forward="auto",
+                 shared_projection="auto"):
         """xs: list of P (N_local,F) feature tensors (this rank's rows), or sparse features (SparseFeatures / torch
         sparse COO or CSR tensors; single process only);
         graphs: list of P CSRGraph (or dense masks / CSR tuples).  Under a partition (`part`) either
@@ -154,6 +155,19 @@ class HANTrainer:
         (below that the default keeps the bits of the full backward, which the small-graph parity tests pin; the gain
         there has not been measured); True: on at any size (ValueError where one of the other conditions fails, masked_backward
         still wins); False: every row in the backward too.
+        shared_projection ("auto" | True | False): inside epoch() the eval forward projects X with the parameters the next
+        training forward projects it with again, under dropout.  Its K1 then runs as ops.project_fwd_both -- one pass
+        over X per meta-path that gives the eval tables and, under the next step's seeds (rng.peek_seeds), the
+        training tables -- and the next training forward takes those in place of its own K1 (layers.SharedProjection:
+        only when seeds, dropout rates, features and parameters are what it would use itself; every public path that
+        writes parameters drops them).  Byte for byte the same tables, so the same epochs.  A bare eval_step() is
+        not touched.  The waiting tables hold P x (N x 64 x 4 + 2 x N x 8 x 4 + N x F) bytes: 4 x (256 + 64 + 256) MB
+        at N = 1M, P = 4, F = 256.  It acts where all of these hold: CUDA, one node-attention layer of 8 x 8 heads on
+        fp32 tables, ONE dense fp32 feature tensor with finite values for every meta-path, an even number of them,
+        at least 32 768 rows (the row count from which K1 writes a keep table), input dropout, no node partition, no
+        captured epoch.  "auto" also declines when the waiting tables would take more than a quarter of the device
+        memory that is free at construction; True raises ValueError where it cannot act; False is the two separate
+        calls.
         masked_backward: OPT-IN (never the default, never the headline measurement): the transposed-graph pass keeps
         the dead entries in place and skips them one by one (bit-identical results, dist.MaskedBackwardPlan)
         and, under a partition, only the live rows of the backward table travel.  Switches live_backward off."""
@@ -247,6 +261,27 @@ class HANTrainer:
                     plan._subsets = mine[1]._subsets
                 self._live_fwd_train = plan
 
+        if shared_projection not in ("auto", True, False):
+            raise ValueError(f"shared_projection = {shared_projection!r}: expected 'auto', True or False")
+        model.shared_proj = None
+        x0 = self.xs[0] if self.xs else None
+        P_ = len(self.graphs)
+        share_ok = (dev.type == "cuda" and not model.extra and self.part is None and not use_graph and not overlap_eval
+                    and model.K == 8 and model.FP == 8 and model.table_dtype == torch.float32 and P_ >= 2 and P_ % 2 == 0
+                    and float(ffd_drop) > 0 and isinstance(x0, torch.Tensor) and x0.dtype == torch.float32
+                    and all(x is x0 for x in self.xs)
+                    and ops.keep_bytes(x0.shape[0], x0.shape[1], x0.stride(0), 8, 8) > 0
+                    and bool(torch.isfinite(x0).all()))      # (the combined kernel's one condition on the VALUES: han_hip.h)
+        if shared_projection is True and not share_ok:
+            raise ValueError("shared_projection=True needs a CUDA model with one node-attention layer of 8 x 8 heads and fp32 "
+                             "tables, one dense fp32 feature tensor of at least 32 768 rows shared by an even number of "
+                             "meta-paths, input dropout, no node partition, no captured epoch and no overlap_eval")
+        if share_ok and shared_projection == "auto":
+            need = layers.SharedProjection.stash_bytes(x0.shape[0], x0.shape[1], P_)
+            share_ok = 4 * need <= torch.cuda.mem_get_info(dev)[0]
+        if share_ok and shared_projection is not False:
+            model.shared_proj = layers.SharedProjection(lambda: model.flat, lambda: self.opt.t)
+
         # mean(loss * mask / mean(mask)) == sum(mask * loss) / count(mask): the
         # normaliser is a setup-time constant, summed over ranks once.
         self.w_train = 1.0 / max(self._global_count(self.train_mask), 1)
@@ -307,6 +342,15 @@ class HANTrainer:
     def live_backward(self) -> bool:
         """Whether the backward runs over the live rows only (the live_backward argument, as decided)."""
         return self.model.live_bwd is not None
+
+    @property
+    def shared_projection(self) -> bool:
+        """Whether epoch()'s eval forward also projects for the next training forward (the shared_projection argument, as decided)."""
+        return self.model.shared_proj is not None
+
+    def _drop_shared(self):
+        if self.model.shared_proj is not None:
+            self.model.shared_proj.drop()
 
     @property
     def live_forward(self) -> bool:
@@ -434,7 +478,15 @@ class HANTrainer:
         if self.use_graph:
             return self._epoch_graph()
         tl, ta = self.train_step()
-        vl, va = self.eval_step()
+        sp = self.model.shared_proj
+        if sp is None:
+            vl, va = self.eval_step()
+            return tl, ta, vl, va
+        sp.armed = float(self.ffd_drop)      # this eval forward's K1 also projects for the next training forward
+        try:
+            vl, va = self.eval_step()
+        finally:
+            sp.armed = None
         return tl, ta, vl, va
 
     def _epoch_body(self):
@@ -571,6 +623,7 @@ class HANTrainer:
             raise ValueError("checkpoint was written for a different model / trainer configuration: "
                              f"{ck.get('signature')} vs {sig}")
         m = self.model
+        self._drop_shared()
         m.flat.copy_(ck["flat"])
         self.opt.load_state_dict(ck["opt"])
         rng._state.update(ck["rng"])
@@ -589,4 +642,5 @@ class HANTrainer:
     def restore_best(self):
         """saver.restore(sess, checkpt_file) (ex_acm3025.py:247)."""
         if self.best_state is not None:
+            self._drop_shared()
             self.model.flat.copy_(self.best_state)

@@ -34,6 +34,8 @@ extern "C" {
                               * carry null data pointers)                                  */
 #define HAN_E_UNSUPPORTED (-2) /* shape outside this build (e.g. K*FP != 64)     */
 #define HAN_E_WORKSPACE (-3)  /* workspace too small                            */
+#define HAN_E_NOT_ELIGIBLE (-4) /* han_project_fwd_both only: valid arguments, but outside the shapes of its one kernel;
+                                 * nothing was launched or written, the caller makes the two separate calls instead */
 
 #define HAN_ACT_IDENTITY 0
 #define HAN_ACT_ELU      1
@@ -176,6 +178,30 @@ int han_project_fwd_multi(const void *X, int x_dtype, int64_t ldx, const float *
                           int F, int K, int FP, int P, float in_drop, float fts_drop,
                           const uint64_t *seeds, const uint64_t *seed_dev, int64_t row_offset,
                           uint8_t *keep, int flags, void *stream);
+
+/* The training forward AND the eval forward of P meta-paths in ONE pass over X per meta-path (added under ABI 15: new
+ * entry points only, nothing existing changed).  For a trainer whose eval forward of epoch t and training forward of
+ * epoch t + 1 project the same X with the same parameters: the training kernel already holds the unmasked X fragments
+ * in registers, so the eval products ride along and the eval forward's own read, split and staging of X goes.
+ * Arguments as han_project_fwd_multi (in_drop / fts_drop / seeds / keep are the TRAINING forward's) plus the eval
+ * outputs H_eval (P,N,D), f1_eval / f2_eval (P,N,K).  On return 0
+ *   H, f1, f2, keep      hold the bytes han_project_fwd_multi writes with the same seeds and dropout rates,
+ *   H_eval, f1_eval, f2_eval   the bytes it writes with in_drop == fts_drop == 0.
+ * It runs only where both of those calls would take the matrix-pipe kernels for every meta-path -- fp32 X and fp32
+ * tables, in_drop > 0, a keep table (han_project_keep_bytes() != 0 and keep != NULL), P even, 16-byte aligned rows
+ * with F % 4 == 0, neither HAN_FLAG_K1_EXACT_PIPE nor HAN_FLAG_K1_4WAVE -- and returns HAN_E_NOT_ELIGIBLE everywhere
+ * else, after the argument checks of han_project_fwd_multi (same order, same codes) and before any launch.
+ * X MUST BE FINITE: the two heads of a 16-column tile share an accumulator (each multiplied against zeros in the
+ * other's columns), so a kept Inf / NaN of one head turns its sibling's columns of that row into NaN, where the
+ * separate training forward keeps a non-finite value inside its own head.
+ * workspace: han_project_fwd_both_workspace() bytes (the W images of the P meta-paths).  N == 0 returns 0.   */
+size_t han_project_fwd_both_workspace(int64_t N, int F, int K, int FP, int P);
+int han_project_fwd_both(const void *X, int x_dtype, int64_t ldx, const float *W, const float *a1,
+                         const float *a2, const float *b1, const float *b2, void *H, int table_dtype,
+                         float *f1, float *f2, void *H_eval, float *f1_eval, float *f2_eval, void *workspace,
+                         size_t workspace_bytes, int64_t N, int F, int K, int FP, int P, float in_drop,
+                         float fts_drop, const uint64_t *seeds, const uint64_t *seed_dev, int64_t row_offset,
+                         uint8_t *keep, int flags, void *stream);
 
 /* dW = Xk^T dH.  keep: the table the forward of the SAME seed wrote (then no draw is regenerated), or
  * NULL: per head dropout masks regenerated from the seed.
