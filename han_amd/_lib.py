@@ -55,6 +55,7 @@ SIGNATURES = {
     "han_project_fwd_both": (c_int, [P, c_int, I64, P, P, P, P, P, P, c_int, P, P, P, P, P, P, c_size_t, I64, c_int, c_int,
                                      c_int, c_int, c_float, c_float, P, P, I64, P, c_int, P]),
     "han_project_bwd_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
+    "han_project_bwd_keep_last_byte": (c_int64, [I64, c_int]),
     "han_project_bwd": (c_int, [P, c_int, I64, P, P, P, c_size_t, I64, c_int, c_int, c_int, c_float,
                                 c_uint64, P, I64, P, P]),
     "han_project_bwd_input": (c_int, [P, P, P, I64, I64, c_int, c_int, c_int, c_float, c_uint64, P, I64, P]),

@@ -1070,18 +1070,47 @@ __global__ __launch_bounds__(256) void project_bwd_input_kernel(const ProjBwdInA
 // so a block can carry ONE head: block b = (q, b') takes the 4 features f = oct + 4q + i (q = lane / 32) of
 // head k(b') = 2 (b' % 4) + b' / 4 against 4 of that head's columns.  The A operand of lane l is then
 // X[n][oct + 4q + i] if bit l of the row's 64-bit keep word is set (han_hip.h: the forward wrote the table
-// in exactly this bit order): one v_bfe_i32 + one v_and_b32, no hash, no wasted column, and each masked A
-// register serves two MFMAs (column quads 0-3 and 4-7 of every head).  Same fp32 pipe, same 64 flop / clk /
-// SIMD, but 1024 useful flop per 16 cycles of issue instead of 1024 useful out of 2048 per 32.
-// Block: 128 features (4 waves x 4 octets) x all 64 columns over a chunk of rows; X, dH and the keep words
-// of 32 rows are staged through LDS one tile ahead, laid out so that a row costs a wave three LDS reads:
+// in exactly this bit order).  The word is the same for the whole wave, so it lives in a scalar register pair
+// and masks an A register with one v_cndmask_b32 (a dropped element is +0, a kept one keeps its bits): no
+// hash, no wasted column, and each masked A register serves two MFMAs (column quads 0-3 and 4-7 of every
+// head).  Same fp32 pipe, same 64 flop / clk / SIMD, but 1024 useful flop per 16 cycles of issue instead of
+// 1024 useful out of 2048 per 32.
+// Block: 128 features (4 waves x 4 octets) x all 64 columns over a chunk of rows; X and dH of 32 rows are
+// staged through LDS one tile ahead, laid out so that a row costs a wave two LDS reads:
 //   Xs[n][wave][q][i][octet]      one ds_read_b128 = the lane's 4 A values
 //   Gs[n][b'][j][parity]          one ds_read_b64  = its 2 B values
-//   Ks[n][wave][q][octet]         one ds_read_b128 = the 4 half keep words holding its bits
+// and the wave's four keep words of a row (32 bytes at keep[n][f0 + 32 wave]) come by one scalar load, DW_KG rows
+// per group and one group ahead (see dw_keep_offset for why every such address lies inside the table).
 // Partial tiles go to a slab (fixed-order second stage, no float atomics).
 // ---------------------------------------------------------------------------------------------
 constexpr int DW_BN = 32;            // rows per staged tile
 constexpr int DW_FB = 128;           // dW rows (features) per block
+constexpr int DW_KG = 4;             // rows per group of keep-word loads (two groups = 16 DW_KG scalar registers)
+static_assert(DW_KG >= 2 && DW_BN % (2 * DW_KG) == 0, "a tile holds an even number of groups: its first group is always buffer 0");
+
+// Byte offset into the keep table of the 32 bytes (four 64-bit words) that wave w of the block at features f0 reads
+// for row n_begin + rel of the chunk that begins at row n_begin < N (rel in 32 bits, like every other row offset inside a
+// chunk: the clamp is then one scalar min, where a 64-bit compare would be a vector instruction).  A scalar load has no
+// descriptor and no range check, so the offset itself must be inside the table:
+//   * rows: a tile may run past the end of its chunk, the group requested ahead lies one tile further, and in the last
+//     chunk both pass N.  The row is clamped to N - 1; X and dH of those rows are zero from the buffer range check, so
+//     the bits read for them do not reach a result;
+//   * features: a wave whose 32 features begin at or beyond F (f0 + 32 w >= F, e.g. waves 1-3 at F = 8) reads into the
+//     next row and, from row N - 1, beyond N F.  f0 is a multiple of 128 below F and F % 8 == 0, so f0 <= F - 8 and the
+//     last byte is at most (N - 1) F + (F - 8) + 96 + 31 = N F + 119: inside the 128 bytes of slack that
+//     han_project_keep_bytes() adds.  X of those features is zero as well.
+// F % 8 == 0 and the 8-byte alignment han_project_bwd asks of the table make the offset a multiple of 8.
+__host__ __device__ inline int64_t dw_keep_offset(int64_t n_begin, uint32_t rel, int64_t N, int F, int f0, int w) {
+    const int64_t left = N - 1 - n_begin;
+    const uint32_t last = left < 0xFFFFFFFFll ? (uint32_t)left : 0xFFFFFFFFu;
+    return n_begin * (int64_t)F + (int64_t)((uint64_t)(rel < last ? rel : last) * (uint32_t)F) + f0 + 32 * w;
+}
+// the last byte of the table that any wave of the dW grid of an (N, F) input may touch: row N - 1 (whatever the chunk,
+// no clamped row lies beyond it), the last feature block, wave 3
+static int64_t dw_keep_last_byte(int64_t N, int F) {
+    const int f0_last = (F - 1) / DW_FB * DW_FB;
+    return dw_keep_offset(N - 1, 0xFFFFFFFFu, N, F, f0_last, 3) + 31;
+}
 
 struct ProjBwdBlkArgs {
     const void *X;
@@ -1099,7 +1128,6 @@ template <bool DROP, bool XBF>
 __global__ __launch_bounds__(256, 4) void project_bwd_blk_kernel(const ProjBwdBlkArgs a) {
     __shared__ __attribute__((aligned(16))) float Xs[DW_BN * DW_FB];
     __shared__ __attribute__((aligned(16))) float Gs[DW_BN * HAN_D];
-    __shared__ __attribute__((aligned(16))) uint32_t Ks[DROP ? DW_BN * 32 : 4];
     const int tid = threadIdx.x;
     const int lane = tid & 63, w = tid >> 6;
     const int f0 = blockIdx.x * DW_FB;
@@ -1114,7 +1142,7 @@ __global__ __launch_bounds__(256, 4) void project_bwd_blk_kernel(const ProjBwdBl
 #pragma unroll
         for (int h = 0; h < 2; ++h) acc[o][h] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    // staging registers: X tile 32 x 128 (4 x 16 B per thread), dH tile 32 x 64 (2 x 16 B), keep tile 32 x 128 B (2 x 8 B).
+    // staging registers: X tile 32 x 128 (4 x 16 B per thread), dH tile 32 x 64 (2 x 16 B).
     // Buffer loads: the range check of the descriptor returns 0 for rows beyond the chunk, a thread whose
     // columns lie beyond F carries an out-of-range offset for good, and the step advance is a scalar offset --
     // the tile costs no vector ALU work (the selects and 64-bit address arithmetic of plain loads were 58 % of
@@ -1127,17 +1155,22 @@ __global__ __launch_bounds__(256, 4) void project_bwd_blk_kernel(const ProjBwdBl
         (void *)(reinterpret_cast<const char *>(a.X) + (n_begin * a.ldx + f0) * XE), 0,
         (int)(((nrows - 1) * a.ldx + (a.F - f0 < DW_FB ? a.F - f0 : DW_FB)) * XE), 0x00020000);
     const auto rs_g = __builtin_amdgcn_make_buffer_rsrc((void *)(a.dH + n_begin * HAN_D), 0, (int)(nrows * HAN_D * 4), 0x00020000);
-    const auto rs_k = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)(DROP ? a.keep + n_begin * (int64_t)a.F + f0 : (const uint8_t *)a.X), 0,
-        DROP ? (int)((nrows - 1) * a.F + (a.F - f0 < DW_FB ? a.F - f0 : DW_FB)) : 0, 0x00020000);
     const int xc4 = (tid & 31) * 4;
     const uint32_t vx = f0 + xc4 < a.F ? (uint32_t)(((tid >> 5) * a.ldx + xc4) * XE) : OOB;      // + 8 i rows
     const uint32_t vg = (uint32_t)((tid >> 3) * (HAN_D * 4) + (tid & 7) * 32);                // (row, head): 8 columns = 2 x 16 B
-    const uint32_t vk = f0 + 16 * (tid & 7) < a.F ? (uint32_t)((tid >> 3) * a.F + 16 * (tid & 7)) : OOB;
+    // The keep words themselves come by scalar loads (below), whose miss would go all the way to memory: a table of N F
+    // bytes is read once and is in no cache.  Wave 0 therefore touches the first and the last dword of every row's
+    // bytes of the next tile with a range-checked buffer load (at most two lines per row): when the scalar loads of
+    // those rows go out, a tile later, they stop at the L2.  The loaded value is not used.
+    const int kspan = a.F - f0 < DW_FB ? a.F - f0 : DW_FB;
+    const auto rs_k = __builtin_amdgcn_make_buffer_rsrc(
+        (void *)(DROP ? a.keep + n_begin * (int64_t)a.F + f0 : (const uint8_t *)a.X), 0,
+        DROP ? (int)((nrows - 1) * a.F + kspan) : 0, 0x00020000);
+    const uint32_t vk = tid < 64 ? (uint32_t)((tid >> 1) * a.F + (tid & 1) * (kspan - 4)) : OOB;
+    uint32_t ktouch = 0;
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     float4_t xr[4], gr[2];
-    u32x2 kr[2];
     // The whole offset travels in the VECTOR offset: the descriptor's range check covers inst_offset + voffset only
     // (an SGPR offset is added after the check), and the check is what zeroes the rows beyond the chunk.
     auto load_tile = [&](int64_t n0) {
@@ -1160,21 +1193,31 @@ __global__ __launch_bounds__(256, 4) void project_bwd_blk_kernel(const ProjBwdBl
 #pragma unroll
         for (int i = 0; i < 2; ++i)      // the 8 columns of this thread's (row, head): parity 0 and parity 1 quads
             gr[i] = __builtin_bit_cast(float4_t, __builtin_amdgcn_raw_buffer_load_b128(rs_g, vg + step * (HAN_D * 4) + 16 * i, 0, 0));
-        if (DROP) {      // features beyond F meet X == 0, so their (arbitrary) keep bits do not matter
-            const uint32_t vo = vk == OOB ? OOB : vk + step * (uint32_t)a.F;
-            kr[0] = __builtin_amdgcn_raw_buffer_load_b64(rs_k, vo, 0, 0);
-            kr[1] = __builtin_amdgcn_raw_buffer_load_b64(rs_k, vo == OOB ? OOB : vo + 8, 0, 0);
+        if (DROP) ktouch = __builtin_amdgcn_raw_buffer_load_b32(rs_k, vk == OOB ? OOB : vk + step * (uint32_t)a.F, 0, 0);
+    };
+    // Keep words: two groups of DW_KG rows x 4 octets, each word a scalar register pair.  Features beyond F meet
+    // X == 0, so their (arbitrary) keep bits do not matter.
+    const int ws = __builtin_amdgcn_readfirstlane(w);
+    uint64_t km[2][DW_KG][4];
+    // (the constant address space says what is true of the table while this kernel runs, and makes the loads scalar
+    //  whatever else the compiler has to assume about the memory operations around them)
+    typedef const __attribute__((address_space(4))) uint64_t *keep_words_t;
+    auto load_keep = [&](uint32_t rel0, int buf) {
+#pragma unroll
+        for (int r = 0; r < DW_KG; ++r) {
+            const keep_words_t kw = (keep_words_t)(uintptr_t)(a.keep + dw_keep_offset(n_begin, rel0 + r, a.N, a.F, f0, ws));
+#pragma unroll
+            for (int o = 0; o < 4; ++o) km[buf][r][o] = kw[o];
         }
     };
-    // dword offsets of this lane's operands inside a row of the three LDS images
+    // dword offsets of this lane's operands inside a row of the two LDS images
     // (the wave's 32 dwords of a row are rotated by 4 w: with it the staging stores of the four waves' features fall
     //  on 32 different banks -- without, 4-way conflicts on every store made LDS co-critical with the matrix pipe)
     const int a_off = 32 * w + ((16 * q + 4 * i4 + 4 * w) & 31);
     const int b_off = 8 * bq + 2 * i4;
-    const int k_off = 8 * w + 4 * q;
-    const uint32_t my_bit = (uint32_t)(lane & 31);
 
     load_tile(n_begin);
+    if (DROP) load_keep(0u, 0);
     for (int64_t n0 = n_begin; n0 < n_end; n0 += DW_BN) {
         __syncthreads();      // the previous tile's operand reads are done
 #pragma unroll
@@ -1193,30 +1236,28 @@ __global__ __launch_bounds__(256, 4) void project_bwd_blk_kernel(const ProjBwdBl
             *reinterpret_cast<float4_t *>(dst) = (float4_t){gr[0][0], gr[1][0], gr[0][1], gr[1][1]};
             *reinterpret_cast<float4_t *>(dst + 4) = (float4_t){gr[0][2], gr[1][2], gr[0][3], gr[1][3]};
         }
-        if (DROP) {
-            const int seg = tid & 7;                                   // octets 2 seg, 2 seg + 1 of the tile's 16
-            uint32_t *dst = Ks + (tid >> 3) * 32 + 8 * (seg >> 1) + 2 * (seg & 1);
-            *reinterpret_cast<uint2 *>(dst) = make_uint2(kr[0].x, kr[1].x);         // q = 0 halves of the two octets
-            *reinterpret_cast<uint2 *>(dst + 4) = make_uint2(kr[0].y, kr[1].y);     // q = 1 halves
-        }
+        if (DROP) asm volatile("" ::"v"(ktouch));      // the touch of the keep lines is a load to be issued, not a value
         __syncthreads();
         load_tile(n0 + DW_BN);     // in flight under the MFMAs (unconditional: beyond the chunk the descriptor returns 0)
         // Three-stage software pipeline over the 32 rows of the tile, spelled out because hipcc's own schedule
         // (reads of two rows, then a wait right behind them, one temporary through every mask / and / MFMA chain)
         // exposes the LDS latency every other row: row n + 2 is being read, row n + 1's A operands are being
-        // masked, row n's eight MFMAs issue; sched_group_barrier pins that interleave (2 MFMA : 2 VALU).
+        // masked, row n's eight MFMAs issue; sched_group_barrier pins that interleave (2 MFMA : 1 VALU).
+        // The keep words of rows g DW_KG .. of this tile sit in km[g & 1]; group g + 1 (after the last group: the first
+        // group of the next tile) is requested when row g DW_KG + 1 issues: row g DW_KG, the last user of that buffer's
+        // previous group, has been masked by then, and the tile's first rows, which wait for their LDS reads at once,
+        // have none in flight.  Scalar loads return out of order, so the next wait for an LDS read after a request is a
+        // full lgkmcnt(0): per group one in front of the request and one a row behind it, none in the other rows.
         float4_t xa[3];
         float2 bb[3];
-        uint4 kk[3];
         auto fetch = [&](int n, int slot) {
             xa[slot] = *reinterpret_cast<const float4_t *>(Xs + n * DW_FB + a_off);
             bb[slot] = *reinterpret_cast<const float2 *>(Gs + n * HAN_D + b_off);
-            if (DROP) kk[slot] = *reinterpret_cast<const uint4 *>(Ks + n * 32 + k_off);
         };
-        auto masked = [&](int slot, int o) -> float {
-            if (!DROP) return xa[slot][o];
-            const uint32_t kwd = o == 0 ? kk[slot].x : o == 1 ? kk[slot].y : o == 2 ? kk[slot].z : kk[slot].w;
-            return __int_as_float(__float_as_int(xa[slot][o]) & __builtin_amdgcn_sbfe((int)kwd, my_bit, 1u));
+        auto masked = [&](int n, int o) -> float {
+            const float x = xa[n % 3][o];
+            if (!DROP) return x;
+            return __builtin_amdgcn_inverse_ballot_w64(km[(n / DW_KG) & 1][n % DW_KG][o]) ? x : 0.f;
         };
         float am[2][4];
         fetch(0, 0);
@@ -1226,18 +1267,24 @@ __global__ __launch_bounds__(256, 4) void project_bwd_blk_kernel(const ProjBwdBl
 #pragma unroll
         for (int n = 0; n < DW_BN; ++n) {
             const int cur = n & 1;
+            if (DROP && n % DW_KG == 1) {
+                // Row n + 1's operands, read a row ago, are awaited HERE, in front of the request: this row then has no
+                // LDS wait behind it, and the full wait falls a whole row later (row n + 2's operands), not at once.
+                __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0)
+                load_keep((uint32_t)(n0 - n_begin) + n - 1 + DW_KG, (n / DW_KG + 1) & 1);
+            }
             if (n + 2 < DW_BN) fetch(n + 2, (n + 2) % 3);
             __builtin_amdgcn_sched_barrier(0);      // the reads of row n + 2 go out BEFORE row n's MFMAs, and stay there
 #pragma unroll
             for (int o = 0; o < 4; ++o) {
                 acc[o][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(am[cur][o], bb[n % 3].x, acc[o][0], 0, 0, 0);
                 acc[o][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(am[cur][o], bb[n % 3].y, acc[o][1], 0, 0, 0);
-                if (n + 1 < DW_BN) am[cur ^ 1][o] = masked((n + 1) % 3, o);
+                if (n + 1 < DW_BN) am[cur ^ 1][o] = masked(n + 1, o);
             }
 #pragma unroll
             for (int o = 0; o < 4; ++o) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                              // 2 MFMA
-                if (DROP && n + 1 < DW_BN) __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // 2 VALU (bfe, and)
+                if (DROP && n + 1 < DW_BN) __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // 1 VALU (cndmask)
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -1555,6 +1602,10 @@ extern "C" size_t han_project_bwd_workspace(int64_t N, int F, int, int) {
     int ftiles; int64_t rpc, nch;
     bwd_geometry(N, F, &ftiles, &rpc, &nch);
     return (size_t)nch * (size_t)F * HAN_D * sizeof(float);
+}
+
+extern "C" int64_t han_project_bwd_keep_last_byte(int64_t N, int F) {
+    return N > 0 && F > 0 ? dw_keep_last_byte(N, F) : -1;
 }
 
 extern "C" int han_project_bwd(const void *X, int x_dtype, int64_t ldx, const float *dH, float *dW, void *workspace,

@@ -153,11 +153,18 @@ size_t han_project_fwd_multi_workspace(int64_t N, int F, int K, int FP, int P);
  * the 8 bytes of features 8o .. 8o+7 of row n form one little-endian 64-bit word whose bit
  *     32*q + 16*(k % 2) + 4*(k / 2) + i        (q = 0,1; i = 0..3; head k = 0..7)
  * is 1 iff head k keeps feature f = 8o + 4q + i of row n -- i.e. the word IS the 64-lane mask of the
- * dW kernel's v_mfma_f32_4x4x1_16B_f32 A operand.  han_project_keep_bytes() returns the size the
- * caller allocates (N*F + 128 B of slack for the kernel's whole-tile mask loads), or 0 when this
- * shape has no table (then pass NULL and the backward regenerates the draws from the seed):
+ * dW kernel's v_mfma_f32_4x4x1_16B_f32 A operand, and dW reads it as such: every wave fetches the
+ * four words of its 32 features of a row with one scalar load, which has no range check.  A wave whose
+ * features begin beyond F reads on into the next row and, from the last row, beyond N*F: the 128 B of
+ * slack are what those loads may touch there (at most N*F + 119, han_project_bwd_keep_last_byte();
+ * nothing read beyond F reaches a result).  han_project_keep_bytes() returns the size the caller
+ * allocates (N*F + 128 B), or 0 when this shape has no table (then pass NULL and the backward
+ * regenerates the draws from the seed):
  * built for K == 8, FP == 8, F % 8 == 0, ldx % 4 == 0, N >= 32768 (the matrix-pipe forward).        */
 size_t han_project_keep_bytes(int64_t N, int F, int64_t ldx, int K, int FP);
+/* Index of the last byte of the keep table that han_project_bwd's scalar loads may touch for an (N, F)
+ * input (host-side arithmetic shared with the kernel; added under ABI 15); -1 when N <= 0 or F <= 0.  */
+int64_t han_project_bwd_keep_last_byte(int64_t N, int F);
 int han_project_fwd(const void *X, int x_dtype, int64_t ldx, const float *W, const float *a1,
                     const float *a2, const float *b1, const float *b2, void *H,
                     int table_dtype, float *f1, float *f2, void *workspace,
