@@ -77,6 +77,10 @@ SIGNATURES = {
                                        c_int, c_int, c_int, P]),
     "han_node_attn_bwd_cols": (c_int, [P, P, P, P, P, P, c_int, P, P, P, P, P, P, I64, I64, c_int, c_int,
                                        c_float, c_float, c_float, c_uint64, P, I64, I64, c_int, P, P, P]),
+    "han_node_attn_bwd_cols_scores_workspace": (c_size_t, [I64, c_int, c_int]),
+    "han_node_attn_bwd_cols_scores": (c_int, [P, P, P, P, P, P, c_int, P, P, P, P, P, P, I64, I64, c_int, c_int,
+                                              c_float, c_float, c_float, c_uint64, P, I64, I64, c_int, P, P, P, P, P, P,
+                                              P, c_size_t, P]),
     "han_score_param_bwd_workspace": (c_size_t, [I64, c_int, c_int]),
     "han_score_param_bwd": (c_int, [P, c_int, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, P]),
     "han_sem_attn_fwd": (c_int, [P, P, P, P, P, P, I64, c_int, c_int, c_int, c_int, P]),
@@ -131,7 +135,7 @@ SIGNATURES = {
 
 ABI_VERSION = 15
 E_UNSUPPORTED = -2      # HAN_E_UNSUPPORTED
-E_NOT_ELIGIBLE = -4     # HAN_E_NOT_ELIGIBLE (han_project_fwd_both: nothing was launched)
+E_NOT_ELIGIBLE = -4     # HAN_E_NOT_ELIGIBLE (han_project_fwd_both, han_node_attn_bwd_cols_scores: nothing was launched)
 _lib = None
 
 

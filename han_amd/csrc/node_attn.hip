@@ -1081,7 +1081,7 @@ struct BwdColsArgs {
     int64_t n_long, n_chunks;
     const int64_t *long_rows, *long_ptr, *chunk_start, *chunk_end;
     const int32_t *chunk_long;
-    float *split_ws;
+    float *split_ws;     // (SCORE launches, which never have long rows: this launch's rows of the score-gradient slab, one per block)
 };
 
 // per source row: the dropped projected row H~_j (layers.py:32) and its mask/keep factors
@@ -1272,9 +1272,22 @@ __device__ __forceinline__ void write_src(const BwdColsArgs &a, const int64_t sr
     if ((4 * q) % FP == 0) a.df2[src * K + head] = dfacc;
 }
 
-// MODE: 0 = bwd_consume, 1 / 2 / 3 = bwd_consume_pred (the FAST fp32 launches: bwd_gather_mode)
-template <int FP, int RPW, int U, bool BF, bool VAL, bool FAST, bool MASKED = false, bool DEDUP = false, int MODE = 0>
+// MODE_IN & 3, the gather MODE: 0 = bwd_consume, 1 / 2 / 3 = bwd_consume_pred (the FAST fp32 launches: bwd_gather_mode).
+// MODE_IN & 4, SCORE (han_node_attn_bwd_cols_scores): the launch also takes the score-parameter gradients of its rows, which
+// score_param_bwd_kernel forms from a second pass over H, df1 and df2:  da1[k][d] = sum_j df1[j][k] H[j][FP k + d],  da2
+// likewise with df2,  db1 / db2 the plain sums.  A lane that writes a source row holds all three operands -- the row AS
+// STORED (keep bit included, not masked, not scaled: load_src overwrites hd, so the loaded row is kept beside it), df1_j
+// and the df2_j it is about to write -- and adds the row's terms to per-lane sums it carries across the grid-stride loop.
+// At the end the block's 16 lane groups are summed through LDS in a fixed order (score_param_bwd_kernel's red[][]) and
+// the block writes ONE slab row; no float atomics, so the sums are the same bits from call to call.
+// It is the 4 of MODE (MODE_IN = 4 + gather mode) and not a template parameter of its own: one more parameter would
+// rename every kernel of the family, and the kernels without it are the parent's, instruction for instruction
+// (tools/kernel_diff.py pairs kernels by name).
+template <int FP, int RPW, int U, bool BF, bool VAL, bool FAST, bool MASKED = false, bool DEDUP = false, int MODE_IN = 0>
 __global__ __launch_bounds__(256) void node_attn_bwd_cols_kernel(const BwdColsArgs a_in) {
+    constexpr bool SCORE = MODE_IN >= 4;
+    constexpr int MODE = MODE_IN & 3;
+    static_assert(!SCORE || (U == 4 && !MASKED && !DEDUP), "SCORE: the forms launch_bwd_rows dispatches");
     BwdColsArgs a = a_in;
     han_resolve_seed(a.seed_lo, a.seed_hi, a.seed_dev);
     const int lane = threadIdx.x & 63;
@@ -1286,6 +1299,8 @@ __global__ __launch_bounds__(256) void node_attn_bwd_cols_kernel(const BwdColsAr
     const float4_t a14 = *reinterpret_cast<const float4_t *>(a.a1 + 4 * q);
     const float4_t a24 = *reinterpret_cast<const float4_t *>(a.a2 + 4 * q);
     const int64_t nunits = (a.n_work + RPW - 1) / RPW;
+    float sd1[4] = {0.f, 0.f, 0.f, 0.f}, sd2[4] = {0.f, 0.f, 0.f, 0.f};      // SCORE: this lane's part of da1 / da2 ...
+    float ss1 = 0.f, ss2 = 0.f;                                              // ... and of db1 / db2
 
     for (int64_t unit = wave0; unit < nunits; unit += nwaves) {
         const int64_t idx_raw = (RPW == 1) ? unit : unit * 4 + g;
@@ -1297,6 +1312,8 @@ __global__ __launch_bounds__(256) void node_attn_bwd_cols_kernel(const BwdColsAr
         const bool is_long = e_raw - s > a.split_deg;
         const int64_t e = is_long ? s : e_raw;
         const SrcRow sr = load_src<FP, BF>(a, src, q, head);
+        float4_t hraw = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (SCORE) hraw = han_load_row4<BF>(a.H, src, q);      // the row as stored (load_src's own load)
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         float dfacc = 0.f;
         const int64_t len = e - s;
@@ -1375,7 +1392,42 @@ __global__ __launch_bounds__(256) void node_attn_bwd_cols_kernel(const BwdColsAr
                 for (int t = 0; t < 4; ++t) acc[t] += __shfl_xor(acc[t], off, 64);
             }
         }
+        if constexpr (SCORE) {
+            if (src_ok && !is_long && (RPW == 4 || g == 0)) {
+                const float d1 = a.df1[src * (HAN_D / FP) + head];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    sd1[t] += d1 * hraw[t];
+                    sd2[t] += dfacc * hraw[t];
+                }
+                ss1 += d1;
+                ss2 += dfacc;
+            }
+        }
         if (src_ok && !is_long && (RPW == 4 || g == 0)) write_src<FP>(a, src, sr, acc, dfacc, q, head, a14, a24);
+    }
+    if constexpr (SCORE) {
+        // slab row layout: score_param_bwd_kernel's.  (RPW == 1: the lane groups g > 0 of a wave hold zeros.)
+        constexpr int K = HAN_D / FP;
+        constexpr int WIDTH = 128 + 2 * K;
+        __shared__ float red[16][WIDTH];
+        const int r = threadIdx.x >> 4;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            red[r][4 * q + t] = sd1[t];
+            red[r][64 + 4 * q + t] = sd2[t];
+        }
+        if ((4 * q) % FP == 0) {
+            red[r][128 + head] = ss1;
+            red[r][128 + K + head] = ss2;
+        }
+        __syncthreads();
+        if (threadIdx.x < WIDTH) {
+            float sacc = 0.f;
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) sacc += red[rr][threadIdx.x];
+            a.split_ws[(int64_t)blockIdx.x * WIDTH + threadIdx.x] = sacc;
+        }
     }
 }
 
@@ -1926,14 +1978,23 @@ static int bwd_gather_mode(const BwdColsArgs &a, bool bf) {
     return a.full_gather ? 2 : (a.zero_rows ? 3 : 1);
 }
 
-template <int FPC, bool BF, bool VAL>
-static void launch_bwd_rows(const BwdColsArgs &a, bool short_rows, hipStream_t st) {
+// SCORE: the same forms with the score-parameter gradients (MODE + 4; never the masked backward).
+// Returns the grid: a SCORE launch writes that many rows of its slab.
+template <int FPC, bool BF, bool VAL, bool SCORE = false>
+static int launch_bwd_rows(const BwdColsArgs &a, bool short_rows, hipStream_t st) {
     const bool fast = a.thr_coef < HAN_KEEP_ALL && !a.gid;
     const int grid = attn_grid(short_rows ? (a.n_work + 3) / 4 : a.n_work);
     HAN_DISPATCH_BOOL(SHORT, short_rows, {
         constexpr int RPW = SHORT ? 4 : 1;
         const int mode = bwd_gather_mode(a, BF);      // 1 / 2: attention dropout on and no id table, i.e. `fast`
-        if (a.masked)      // opt-in masked backward: the general instantiations, dead entries skipped in place
+        if constexpr (SCORE) {
+            if (mode == 0) HAN_DISPATCH_BOOL(FAST, fast, node_attn_bwd_cols_kernel<FPC, RPW, 4, BF, VAL, FAST, false, false, 4><<<grid, 256, 0, st>>>(a));
+            else if constexpr (!BF) {
+                if (mode == 1) node_attn_bwd_cols_kernel<FPC, RPW, 4, false, VAL, true, false, false, 5><<<grid, 256, 0, st>>>(a);
+                else if (mode == 3) node_attn_bwd_cols_kernel<FPC, RPW, 4, false, VAL, true, false, false, 7><<<grid, 256, 0, st>>>(a);
+                else node_attn_bwd_cols_kernel<FPC, RPW, 4, false, VAL, true, false, false, 6><<<grid, 256, 0, st>>>(a);
+            }
+        } else if (a.masked)      // opt-in masked backward: the general instantiations, dead entries skipped in place
             node_attn_bwd_cols_kernel<FPC, RPW, 4, BF, VAL, false, true><<<grid, 256, 0, st>>>(a);
         else if (mode == 0) HAN_DISPATCH_BOOL(FAST, fast, node_attn_bwd_cols_kernel<FPC, RPW, 4, BF, VAL, FAST><<<grid, 256, 0, st>>>(a));
         else if constexpr (!BF) {
@@ -1942,6 +2003,21 @@ static void launch_bwd_rows(const BwdColsArgs &a, bool short_rows, hipStream_t s
             else node_attn_bwd_cols_kernel<FPC, RPW, 4, false, VAL, true, false, false, 2><<<grid, 256, 0, st>>>(a);
         }
     });
+    return grid;
+}
+
+// The row launches of han_node_attn_bwd_cols_scores: one, or one per bin; launch after launch takes the next rows of the
+// slab.  Returns the slab rows written.
+template <int FPC, bool BF, bool VAL>
+static int launch_bwd_cols_scores_v(const BwdColsArgs &a_in, bool low, const RowBins &bins, float *slab, hipStream_t st) {
+    BwdColsArgs a = a_in;
+    int rows = 0;
+    for_each_bin(a, a.NS, low, bins, [&](const BwdColsArgs &b_in, bool short_rows) {
+        BwdColsArgs b = b_in;
+        b.split_ws = slab + (size_t)rows * (size_t)(128 + 2 * (HAN_D / FPC));
+        rows += launch_bwd_rows<FPC, BF, VAL, true>(b, short_rows, st);
+    });
+    return rows;
 }
 
 template <int FPC, bool BF, bool VAL>
@@ -2112,19 +2188,48 @@ extern "C" int han_node_attn_bwd_rows(const float *dOut, int64_t dout_stride, co
     return 0;
 }
 
-extern "C" int han_node_attn_bwd_cols(const int64_t *colptr, const int32_t *rowidx, const float *edge_val,
-                                      const void *gs, const int32_t *table_gid, const void *H,
-                                      int table_dtype, const float *f2,
-                                      const float *df1, const float *a1, const float *a2,
-                                      float *dH, float *df2, int64_t NS, int64_t E, int K, int FP, float slope,
-                                      float coef_drop, float fts_drop, uint64_t seed, const uint64_t *seed_dev,
-                                      int64_t src_offset, int64_t dst_offset, int flags,
-                                      const han_row_split_t *split, const han_dense_t *dense, void *stream) {
+// the slab of han_node_attn_bwd_cols_scores: one row per block of at most two row launches, then kScoreFold rows
+constexpr int kScoreFold = 256;
+static size_t score_slab_rows() { return 2 * (size_t)attn_grid(INT64_MAX / 8); }
+
+// First stage of the sum over the gather's slab rows (up to 16 384 of them: han_reduce_slabs alone, whose nine blocks
+// would walk them in 64-byte pieces, takes longer than the pass over H this entry removes): block j adds the rows
+// j, j + kScoreFold, ... in that order, a thread per column, and writes row j of `out`.
+static __global__ __launch_bounds__(256) void score_slab_fold_kernel(const float *slab, int nrows, int width, float *out) {
+    if ((int)threadIdx.x >= width) return;
+    float sacc = 0.f;
+#pragma unroll 8
+    for (int r = blockIdx.x; r < nrows; r += kScoreFold) sacc += slab[(int64_t)r * width + threadIdx.x];
+    out[(int64_t)blockIdx.x * width + threadIdx.x] = sacc;
+}
+
+struct ScoreGrads {
+    float *da1, *da2, *db1, *db2;
+    void *workspace;
+    size_t workspace_bytes;
+};
+
+// han_node_attn_bwd_cols (sg null) and han_node_attn_bwd_cols_scores
+static int bwd_cols_entry(const int64_t *colptr, const int32_t *rowidx, const float *edge_val, const void *gs,
+                          const int32_t *table_gid, const void *H, int table_dtype, const float *f2, const float *df1,
+                          const float *a1, const float *a2, float *dH, float *df2, int64_t NS, int64_t E, int K, int FP,
+                          float slope, float coef_drop, float fts_drop, uint64_t seed, const uint64_t *seed_dev,
+                          int64_t src_offset, int64_t dst_offset, int flags, const han_row_split_t *split,
+                          const han_dense_t *dense, void *stream, const ScoreGrads *sg) {
     if (!colptr || (!rowidx && E > 0) || !gs || !H || !f2 || !df1 || !a1 || !a2 || !dH || !df2 || NS < 0 || E < 0)
         return HAN_E_BADARG;
+    if (sg && (!sg->da1 || !sg->da2 || !sg->db1 || !sg->db2 || !sg->workspace)) return HAN_E_BADARG;
     if (!split_ok(split, NS)) return HAN_E_BADARG;
     if (!han_fp_supported(K, FP) || !dtype_ok(table_dtype)) return HAN_E_UNSUPPORTED;
     if (coef_drop < 0.f || coef_drop >= 1.f || fts_drop < 0.f || fts_drop >= 1.f) return HAN_E_BADARG;
+    if (sg) {
+        if (sg->workspace_bytes < han_node_attn_bwd_cols_scores_workspace(NS, K, FP)) return HAN_E_WORKSPACE;
+        // the forms that are built: the row kernels over every source row, no long rows behind them
+        const bool all_rows = !split || (split->n_short <= 0 && split->n_mid <= 0) || split->n_short + split->n_mid == NS;
+        if (NS == 0 || (flags & (HAN_FLAG_LEAN | HAN_FLAG_MASKED_EDGES)) || (dense && dense->bits) ||
+            (split && split->n_long > 0) || !all_rows)
+            return HAN_E_NOT_ELIGIBLE;
+    }
     if (NS == 0) return 0;
     BwdColsArgs a;
     a.colptr = colptr; a.rowidx = rowidx; a.edge_val = edge_val; a.gs = gs; a.gid = table_gid; a.H = H; a.lsb_mask = fts_drop > 0.f; a.f2 = f2;
@@ -2140,6 +2245,29 @@ extern "C" int han_node_attn_bwd_cols(const int64_t *colptr, const int32_t *rowi
     const bool has_split = fill_split(a, split);
     hipStream_t st = (hipStream_t)stream;
     const bool low = (double)E < kLowDegree * (double)NS;
+    const RowBins bins = bins_of(split);
+    if (sg) {
+        const int width = 128 + 2 * K;
+        float *slab = (float *)sg->workspace;
+        int rows = 0;
+        HAN_DISPATCH_BOOL(VAL, edge_val != nullptr,
+                          HAN_DISPATCH_FP_BF(FP, table_dtype == HAN_DTYPE_BF16,
+                                             rows = launch_bwd_cols_scores_v<FPC, BF, VAL>(a, low, bins, slab, st)));
+        HAN_CHECK_LAUNCH();
+        if (rows > kReduceBlocks) {      // two stages; few rows go to han_reduce_slabs as they are
+            float *folded = slab + score_slab_rows() * (size_t)width;
+            score_slab_fold_kernel<<<kScoreFold, 256, 0, st>>>(slab, rows, width, folded);
+            HAN_CHECK_LAUNCH();
+            slab = folded;
+            rows = kScoreFold;
+        }
+        HanReduceOut o = han_reduce_to(sg->da1, width);
+        o.ptr[1] = sg->da2; o.ptr[2] = sg->db1; o.ptr[3] = sg->db2;
+        o.seg_end[0] = 64; o.seg_end[1] = 128; o.seg_end[2] = 128 + K; o.seg_end[3] = 128 + 2 * K;
+        o.nseg = 4;
+        const hipError_t e = han_reduce_slabs(slab, rows, width, width, o, st);
+        return e == hipSuccess ? 0 : (int)e;
+    }
     if (dense && dense->bits) {
         // the transposed bit mask
         if (!a.lean || a.masked || low || table_dtype != HAN_DTYPE_F32 || table_gid || edge_val || K != 8 || FP != 8)
@@ -2150,11 +2278,44 @@ extern "C" int han_node_attn_bwd_cols(const int64_t *colptr, const int32_t *rowi
         });
         if (err) return err;
     }
-    const RowBins bins = bins_of(split);
     HAN_DISPATCH_BOOL(VAL, edge_val != nullptr,
                       HAN_DISPATCH_FP_BF(FP, table_dtype == HAN_DTYPE_BF16, launch_bwd_cols_v<FPC, BF, VAL>(a, low, has_split, bins, st)));
     HAN_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int han_node_attn_bwd_cols(const int64_t *colptr, const int32_t *rowidx, const float *edge_val,
+                                      const void *gs, const int32_t *table_gid, const void *H,
+                                      int table_dtype, const float *f2,
+                                      const float *df1, const float *a1, const float *a2,
+                                      float *dH, float *df2, int64_t NS, int64_t E, int K, int FP, float slope,
+                                      float coef_drop, float fts_drop, uint64_t seed, const uint64_t *seed_dev,
+                                      int64_t src_offset, int64_t dst_offset, int flags,
+                                      const han_row_split_t *split, const han_dense_t *dense, void *stream) {
+    return bwd_cols_entry(colptr, rowidx, edge_val, gs, table_gid, H, table_dtype, f2, df1, a1, a2, dH, df2, NS, E, K, FP,
+                          slope, coef_drop, fts_drop, seed, seed_dev, src_offset, dst_offset, flags, split, dense, stream,
+                          nullptr);
+}
+
+extern "C" size_t han_node_attn_bwd_cols_scores_workspace(int64_t NS, int K, int FP) {
+    (void)NS; (void)FP;
+    return (score_slab_rows() + kScoreFold) * (size_t)(128 + 2 * K) * sizeof(float);
+}
+
+extern "C" int han_node_attn_bwd_cols_scores(const int64_t *colptr, const int32_t *rowidx, const float *edge_val,
+                                             const void *gs, const int32_t *table_gid, const void *H,
+                                             int table_dtype, const float *f2,
+                                             const float *df1, const float *a1, const float *a2,
+                                             float *dH, float *df2, int64_t NS, int64_t E, int K, int FP, float slope,
+                                             float coef_drop, float fts_drop, uint64_t seed, const uint64_t *seed_dev,
+                                             int64_t src_offset, int64_t dst_offset, int flags,
+                                             const han_row_split_t *split, const han_dense_t *dense, float *da1,
+                                             float *da2, float *db1, float *db2, void *workspace, size_t workspace_bytes,
+                                             void *stream) {
+    const ScoreGrads sg = {da1, da2, db1, db2, workspace, workspace_bytes};
+    return bwd_cols_entry(colptr, rowidx, edge_val, gs, table_gid, H, table_dtype, f2, df1, a1, a2, dH, df2, NS, E, K, FP,
+                          slope, coef_drop, fts_drop, seed, seed_dev, src_offset, dst_offset, flags, split, dense, stream,
+                          &sg);
 }
 
 extern "C" size_t han_score_param_bwd_workspace(int64_t N, int K, int FP) {

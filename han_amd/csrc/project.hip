@@ -491,7 +491,28 @@ struct ProjBothArgs {
     int64_t wstep;           // bytes between two K-steps of the W image ([K-step][meta-path]: P * B6_WTILE)
 };
 
-__global__ __launch_bounds__(512, 4) void project_fwd_b6_both_kernel(const ProjBothArgs b_in) {
+// One launch serves up to kBothMaxP meta-paths (the argument sets travel by value; a block reads its own through scalar
+// loads at a uniform index).  Block b works on row tile 8 (r / P) + b % 8 of meta-path r % P, r = b / 8: consecutive block
+// ids go round the 8 XCDs, so the P blocks of a row tile fall on ONE XCD, next to each other in its dispatch order, and
+// all but the first of their reads of the X tile can stop at that XCD's L2.  The grid is 8 ceil(tiles / 8) P blocks; the
+// blocks of a tile past the last return at once.  What a block computes for its (row tile, meta-path) is what the
+// launch per meta-path computed.  (Measured at SYN-1M, P = 4: 3.30-3.34 ms against 3.50-3.52 ms for four launches; with
+// the meta-path slowest instead -- the four launches back to back without tails -- 3.50-3.52 ms, so the gain is the
+// shared X tile and not the tails.  DESIGN.md section 5, round 25.)
+constexpr int kBothMaxP = 8;
+struct ProjBothMultiArgs {
+    ProjBothArgs path[kBothMaxP];
+    int P;                   // meta-paths of this launch
+    unsigned tiles;          // row tiles of 128 rows
+};
+static_assert(sizeof(ProjBothMultiArgs) <= 4096, "the argument sets of a launch must fit the 4 KB kernel-argument segment");
+
+__global__ __launch_bounds__(512, 4) void project_fwd_b6_both_kernel(const ProjBothMultiArgs m) {
+    const unsigned rr = blockIdx.x >> 3;
+    const unsigned tile = 8u * (rr / (unsigned)m.P) + (blockIdx.x & 7u);
+    const unsigned pi = rr % (unsigned)m.P;
+    if (tile >= m.tiles) return;
+    const ProjBothArgs &b_in = m.path[pi];
     ProjFwdArgs a = b_in.tr;
     han_resolve_seed(a.seed_lo, a.seed_hi, a.seed_dev);
     constexpr int NT = 512;
@@ -505,7 +526,7 @@ __global__ __launch_bounds__(512, 4) void project_fwd_b6_both_kernel(const ProjB
     const int tid = threadIdx.x;
     const int lane = tid & 63, w = tid >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
-    const int64_t row0 = (int64_t)blockIdx.x * B6_ROWS;
+    const int64_t row0 = (int64_t)tile * B6_ROWS;
 #pragma unroll
     for (int i = 0; i < ZB / (8 * NT); ++i)                 // read only after the K loop's barriers
         *reinterpret_cast<uint2 *>(Ws + B6_WTILE + 8 * (tid + NT * i)) = make_uint2(0u, 0u);
@@ -1581,18 +1602,26 @@ extern "C" int han_project_fwd_both(const void *X, int x_dtype, int64_t ldx, con
     if (rc != 0) return rc;
     const size_t hb = (size_t)N * HAN_D * sizeof(float), kb = (size_t)N * (size_t)F + 128;
     const K1Path all_e = {W, a1, a2, b1, b2, H_eval, f1_eval, f2_eval, nullptr};
-    const dim3 grid((unsigned)((N + B6_ROWS - 1) / B6_ROWS));
-    for (int p = 0; p < P; ++p) {
-        const K1Path q = path_of(all, p, N, F, K, hb, kb);
-        ProjBothArgs b;
-        static_cast<K1Epilogue &>(b.tr) = han_k1_epilogue(q, true, table_dtype, N, seeds[p], seed_dev, fts_drop, flags, row_offset);
-        b.tr.X = X; b.tr.ldx = ldx; b.tr.W = q.W; b.tr.F = F; b.tr.x_bf16 = 0;
-        b.tr.thr_in = han_drop_threshold(in_drop); b.tr.inv_keep_in = 1.f / (1.f - in_drop);
-        b.tr.keep = q.keep; b.tr.f_chunk = plan.f_chunk; b.tr.partial = nullptr;
-        b.tr.wimg = (const unsigned char *)workspace + (size_t)p * B6_WTILE;
-        b.wstep = (int64_t)P * B6_WTILE;
-        b.ev = han_k1_epilogue(path_of(all_e, p, N, F, K, hb, 0), true, table_dtype, N, 0, nullptr, 0.f, 0, 0);
-        project_fwd_b6_both_kernel<<<grid, 512, 0, st>>>(b);
+    const unsigned tiles = (unsigned)((N + B6_ROWS - 1) / B6_ROWS);
+    for (int p0 = 0; p0 < P; p0 += kBothMaxP) {      // one launch per group of at most kBothMaxP meta-paths
+        ProjBothMultiArgs m;
+        m.P = P - p0 < kBothMaxP ? P - p0 : kBothMaxP;
+        m.tiles = tiles;
+        for (int i = 0; i < m.P; ++i) {
+            const int p = p0 + i;
+            const K1Path q = path_of(all, p, N, F, K, hb, kb);
+            ProjBothArgs &b = m.path[i];
+            static_cast<K1Epilogue &>(b.tr) = han_k1_epilogue(q, true, table_dtype, N, seeds[p], seed_dev, fts_drop, flags, row_offset);
+            b.tr.X = X; b.tr.ldx = ldx; b.tr.W = q.W; b.tr.F = F; b.tr.x_bf16 = 0;
+            b.tr.thr_in = han_drop_threshold(in_drop); b.tr.inv_keep_in = 1.f / (1.f - in_drop);
+            b.tr.keep = q.keep; b.tr.f_chunk = plan.f_chunk; b.tr.partial = nullptr;
+            b.tr.wimg = (const unsigned char *)workspace + (size_t)p * B6_WTILE;
+            b.wstep = (int64_t)P * B6_WTILE;
+            b.ev = han_k1_epilogue(path_of(all_e, p, N, F, K, hb, 0), true, table_dtype, N, 0, nullptr, 0.f, 0, 0);
+        }
+        for (int i = m.P; i < kBothMaxP; ++i) m.path[i] = m.path[0];      // never read: defined bytes in the argument segment
+        const unsigned grid = 8u * ((tiles + 7u) / 8u) * (unsigned)m.P;
+        project_fwd_b6_both_kernel<<<dim3(grid), 512, 0, st>>>(m);
         HAN_CHECK_LAUNCH();
     }
     return 0;

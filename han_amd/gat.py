@@ -106,6 +106,9 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
                                               # dW of meta-path p runs beside the backward gather of meta-path p + 1
         self.shared_proj = None               # layers.SharedProjection (HANTrainer(shared_projection=...)): the eval forward of an epoch
                                               # projects for the next training forward too
+        self.fused_scores = "auto"            # "auto" | True | False: the backward gather of a K-head layer also sums da1, da2, db1, db2
+                                              # (ops.node_attn_bwd_cols_scores) instead of a second pass over H; "auto": for CUDA tensors.
+                                              # Where the library declines (small, masked or skewed graphs) the two calls run as before
         self._graph_cache: dict = {}
         # captured-step mode (HANTrainer(use_graph=True)): a device seed word that the trainer
         # bumps between replays + fixed per-(layer, meta-path) seed constants (han_hip.h "Seeds")
@@ -315,7 +318,8 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
                 live_bwd=self.live_bwd if (first and train and not self.extra and self.masked_bwd is None) else None,
                 streams=self.path_streams, side_stream=self.side_stream, path_order=self.path_order,
                 overlap=self.overlap_branch if (first and train) else None,
-                shared_proj=self.shared_proj if (first and not self.extra) else None, **kw)
+                shared_proj=self.shared_proj if (first and not self.extra) else None,
+                fused_scores=self.fused_scores, **kw)
 
         def layer_fwd(layer, Xin, xs_, K, FP, sink):
             """One node-attention layer: its K heads run through the 64-column K1/K2 kernels in groups of

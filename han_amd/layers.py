@@ -244,6 +244,7 @@ class LayerRun:
     live_bwd: object = None           # LiveBackwardPlan (HANTrainer(live_backward=...)): the backward visits only the rows the loss reaches
     live_fwd: object = None           # LiveForwardPlan (HANTrainer(live_forward=...)): K2 computes only the rows the caller reads of M
     live_sink: list | None = None     # receives live_fwd when this call ran over it (a training call may decline: NodeLevelAttention.forward)
+    fused_scores: object = "auto"     # HeteGAT_multi.fused_scores: the backward gather also takes the score-parameter gradients (ops.node_attn_bwd_cols_scores)
     shared_proj: object = None        # SharedProjection (HANTrainer(shared_projection=...)): the eval forward's K1 also projects for the next training forward
 
     @functools.cached_property
@@ -649,12 +650,21 @@ class NodeLevelAttention(torch.autograd.Function):
             seed = int(run.seeds[p])
             gs_h, df1 = rows[p]
             src = srcs[p][0]
-            dH, df2 = ops.node_attn_bwd_cols(src.graph, gs_h.wait(), sv.H, sv.f2, df1, a1[p], a2[p], coef_drop=coef_drop,
-                                             fts_drop=in_drop, seed=seed, src_offset=row_offset, dst_offset=0,
-                                             table_gid=src.gid, seed_dev=seed_dev,
-                                             **({"zero_rows": True} if run.zero_rows and srcs[p][1] != "bl" else {}))
+            cols_kw = dict(coef_drop=coef_drop, fts_drop=in_drop, seed=seed, src_offset=row_offset, dst_offset=0,
+                           table_gid=src.gid, seed_dev=seed_dev,
+                           **({"zero_rows": True} if run.zero_rows and srcs[p][1] != "bl" else {}))
+            score_out = (da1[p], da2[p], db1[p], db2[p])
+            if run.fused_scores is True or (run.fused_scores == "auto" and sv.H.is_cuda):
+                # the gather also takes da1, da2, db1, db2 where the library has that form (ops.node_attn_bwd_cols_scores):
+                # no second pass over H
+                dH, df2, scored = ops.node_attn_bwd_cols(src.graph, gs_h.wait(), sv.H, sv.f2, df1, a1[p], a2[p],
+                                                         scores_out=score_out, **cols_kw)
+            else:
+                dH, df2 = ops.node_attn_bwd_cols(src.graph, gs_h.wait(), sv.H, sv.f2, df1, a1[p], a2[p], **cols_kw)
+                scored = False
+            if not scored:
+                ops.score_param_bwd(sv.H, df1, df2, K=K, FP=FP, out=score_out)
             rows[p] = None
-            ops.score_param_bwd(sv.H, df1, df2, K=K, FP=FP, out=(da1[p], da2[p], db1[p], db2[p]))
             if side is not None and dXin is None:
                 # dW(p) on the side stream (single GPU, eager training step on large graphs) beside the transposed-graph
                 # gather of meta-path p + 1: the gather is bound by the memory fabric and leaves vector / matrix issue

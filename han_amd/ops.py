@@ -719,12 +719,20 @@ def node_attn_bwd_rows(dOut, out, aggp, tsum, f1, lse, c, activation=ACT_ELU, K=
 
 
 def node_attn_bwd_cols(graph_t: CSRGraph, gs_tab, H, f2, df1, a1, a2, coef_drop=0.0,
-                       fts_drop=0.0, seed=0, src_offset=0, dst_offset=0, table_gid=None, seed_dev=None, zero_rows=False):
+                       fts_drop=0.0, seed=0, src_offset=0, dst_offset=0, table_gid=None, seed_dev=None, zero_rows=False,
+                       scores_out=None):
     """Transposed-graph half of the K2 backward.  graph_t rows = local sources j,
     its colidx = destinations i indexing the fused table gs_tab (NT, row_bytes) uint8.
     H (NS,D) undropped local rows (keep bits in bit 0 when fts_drop > 0),
     f2/df1 (NS,K).  zero_rows: a hint that most rows of gs_tab hold a zero gradient (HAN_FLAG_K2_ZERO_ROWS: the
-    g piece of a head whose record says so is not requested; same bits).  Returns dH (NS,D), df2 (NS,K)."""
+    g piece of a head whose record says so is not requested; same bits).  Returns dH (NS,D), df2 (NS,K).
+    scores_out = (da1, da2, db1, db2): the call goes through node_attn_bwd_cols_scores where the library has that form,
+    and returns (dH, df2, done) -- done False: the four tensors are untouched, score_param_bwd is still to be called."""
+    if scores_out is not None:
+        got = node_attn_bwd_cols_scores(graph_t, gs_tab, H, f2, df1, a1, a2, coef_drop, fts_drop, seed, src_offset,
+                                        dst_offset, table_gid, seed_dev, zero_rows, out=scores_out)
+        if got is not None:
+            return got + (True,)
     lib = _lib.load()
     K, FP = a1.shape
     _check_heads(K, FP)
@@ -759,6 +767,56 @@ def node_attn_bwd_cols(graph_t: CSRGraph, gs_tab, H, f2, df1, a1, a2, coef_drop=
             | (FLAG_K2_ZERO_ROWS if zero_rows else 0),
             ctypes.byref(split) if split is not None else None,
             ctypes.byref(dense) if dense is not None else None, _stream()), "han_node_attn_bwd_cols")
+    return (dH, df2, False) if scores_out is not None else (dH, df2)
+
+
+def node_attn_bwd_cols_scores(graph_t: CSRGraph, gs_tab, H, f2, df1, a1, a2, coef_drop=0.0, fts_drop=0.0, seed=0,
+                              src_offset=0, dst_offset=0, table_gid=None, seed_dev=None, zero_rows=False, *, out):
+    """node_attn_bwd_cols and score_param_bwd in one pass (han_node_attn_bwd_cols_scores): the gather also sums
+    da1, da2 (K,F'), db1, db2 (K,) over all source rows, into the 4 tensors of `out`, from the H rows, df1 and df2 it
+    holds anyway.  Returns (dH, df2) -- the bytes of node_attn_bwd_cols -- or None, with nothing launched and
+    `out` untouched, where the library has no such form (small graphs on the lean / dense kernels, the masked backward,
+    graphs with rows beyond the split length; han_hip.h): the caller then makes the two calls."""
+    lib = _lib.load()
+    K, FP = a1.shape
+    _check_heads(K, FP)
+    NS = graph_t.n_rows
+    dev = H.device
+    _chk(H, "H", (NS, D), dtype=H.dtype)
+    tcode = _dtype_code(H, "H")
+    _chk(gs_tab, "gs", (graph_t.n_cols, gs_row_bytes(K, FP, H.dtype)), device=dev, dtype=torch.uint8)
+    if table_gid is not None:
+        _chk(table_gid, "table_gid", (graph_t.n_cols,), dtype=torch.int32, device=dev)
+    _chk(f2, "f2", (NS, K), device=dev)
+    _chk(df1, "df1", (NS, K), device=dev)
+    _chk(a1, "a1", (K, FP), device=dev)
+    _chk(a2, "a2", (K, FP), device=dev)
+    fts_drop = _check_drop(fts_drop, "fts_drop")
+    coef_drop = _check_drop(coef_drop, "coef_drop")
+    da1 = _out(out[0], "da1", (K, FP), dev)
+    da2 = _out(out[1], "da2", (K, FP), dev)
+    db1 = _out(out[2], "db1", (K,), dev)
+    db2 = _out(out[3], "db2", (K,), dev)
+    lean_b = not graph_t.masked and not graph_t.empty_rows_mid and _use_lean(graph_t, H)      # as node_attn_bwd_cols: declined
+    split, _keep = _row_split_arg(graph_t, "b", bins=not lean_b, split=not lean_b)
+    dH = torch.empty((NS, D), dtype=torch.float32, device=dev)
+    df2 = torch.empty((NS, K), dtype=torch.float32, device=dev)
+    ws = _ws(lib.han_node_attn_bwd_cols_scores_workspace(NS, K, FP), dev, "score_cols")
+    with _k2_timed("bwd_cols", NS, graph_t.nnz):
+        code = lib.han_node_attn_bwd_cols_scores(
+            graph_t.rowptr.data_ptr(), graph_t.colidx.data_ptr(),
+            _ptr(graph_t.values), gs_tab.data_ptr(), _ptr(table_gid), H.data_ptr(),
+            tcode, f2.data_ptr(), df1.data_ptr(), a1.data_ptr(), a2.data_ptr(), dH.data_ptr(), df2.data_ptr(),
+            NS, graph_t.nnz, K, FP, LEAKY_SLOPE, coef_drop, fts_drop,
+            int(seed), _dev_word(seed_dev), int(src_offset), int(dst_offset),
+            (FLAG_XCD_ORDER if graph_t.has_locality() else 0) | (FLAG_MASKED_EDGES if graph_t.masked else 0)
+            | (FLAG_LEAN if lean_b else 0) | (FLAG_K2_FULL_GATHER if K2_FULL_GATHER else 0)
+            | (FLAG_K2_ZERO_ROWS if zero_rows else 0),
+            ctypes.byref(split) if split is not None else None, None,
+            da1.data_ptr(), da2.data_ptr(), db1.data_ptr(), db2.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    if code == _lib.E_NOT_ELIGIBLE:
+        return None
+    _lib.check(code, "han_node_attn_bwd_cols_scores")
     return dH, df2
 
 

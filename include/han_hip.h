@@ -34,8 +34,9 @@ extern "C" {
                               * carry null data pointers)                                  */
 #define HAN_E_UNSUPPORTED (-2) /* shape outside this build (e.g. K*FP != 64)     */
 #define HAN_E_WORKSPACE (-3)  /* workspace too small                            */
-#define HAN_E_NOT_ELIGIBLE (-4) /* han_project_fwd_both only: valid arguments, but outside the shapes of its one kernel;
-                                 * nothing was launched or written, the caller makes the two separate calls instead */
+#define HAN_E_NOT_ELIGIBLE (-4) /* han_project_fwd_both and han_node_attn_bwd_cols_scores only: valid arguments, but outside
+                                 * the forms of the combined kernels; nothing was launched or written, the caller makes the
+                                 * two separate calls instead */
 
 #define HAN_ACT_IDENTITY 0
 #define HAN_ACT_ELU      1
@@ -419,6 +420,27 @@ int han_node_attn_bwd_cols(const int64_t *colptr, const int32_t *rowidx, const f
                            float coef_drop, float fts_drop, uint64_t seed, const uint64_t *seed_dev,
                            int64_t src_offset, int64_t dst_offset, int flags,
                            const han_row_split_t *split, const han_dense_t *dense, void *stream);
+
+/* Backward, steps 2 AND 3 in one pass: han_node_attn_bwd_cols, and the gather also takes
+ * han_score_param_bwd's sums over ALL NS source rows -- da1, da2 (K,FP), db1, db2 (K) from H as stored (keep bit
+ * included, not masked, not scaled), df1 and the df2 it writes -- instead of a second pass over H, df1 and df2.
+ * dH and df2 are the BYTES of han_node_attn_bwd_cols.  The sums are taken per block and then over the blocks in a fixed
+ * order (no float atomics): the same bits from call to call, within rounding of han_score_param_bwd's, whose order
+ * differs.  Only the row kernels have this form.  Returns, after every argument check and with nothing launched or
+ * written, HAN_E_NOT_ELIGIBLE for: NS == 0; HAN_FLAG_LEAN or HAN_FLAG_MASKED_EDGES; `dense` with a bit mask; a `split`
+ * with long rows (n_long > 0) or whose bins do not list every source row.  The caller then makes the two calls.
+ * Check order: null pointers and sizes (HAN_E_BADARG), shapes and dtypes (HAN_E_UNSUPPORTED), dropout rates
+ * (HAN_E_BADARG), workspace_bytes (HAN_E_WORKSPACE), eligibility.                                             */
+size_t han_node_attn_bwd_cols_scores_workspace(int64_t NS, int K, int FP);
+int han_node_attn_bwd_cols_scores(const int64_t *colptr, const int32_t *rowidx, const float *edge_val,
+                                  const void *gs, const int32_t *table_gid, const void *H,
+                                  int table_dtype, const float *f2,
+                                  const float *df1, const float *a1, const float *a2,
+                                  float *dH, float *df2, int64_t NS, int64_t E, int K, int FP, float slope,
+                                  float coef_drop, float fts_drop, uint64_t seed, const uint64_t *seed_dev,
+                                  int64_t src_offset, int64_t dst_offset, int flags,
+                                  const han_row_split_t *split, const han_dense_t *dense, float *da1, float *da2,
+                                  float *db1, float *db2, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Backward, step 3: gradients of the score parameters
  *   da1[k,f] = sum_n df1[n,k] H[n,k,f]   da2 likewise with df2

@@ -112,7 +112,8 @@ def main():
         t = timeit(lambda: [ops.project_fwd(X, Wp[i], ap1[i], ap2[i], bp1[i], bp2[i]) for i in range(p)])
         print(json.dumps({"kernel": f"project_fwd eval x{p} (one launch per meta-path)", "ms": round(t, 4)}))
         # round 23: what an epoch's eval forward and next training forward cost as separate calls (P training launches with
-        # keep tables + the fused eval launch), and as han_project_fwd_both's P combined launches
+        # keep tables + the fused eval launch), and as han_project_fwd_both's combined launch (round 25: one for up to 8 meta-paths;
+        # before: one per meta-path)
         if kv.get("xbf") != "1" and p % 2 == 0:
             seeds = list(range(11, 11 + p))
             sep = lambda: (ops.project_fwd_multi(X, Wp, ap1, ap2, bp1, bp2, in_drop=0.6, fts_drop=0.6, seeds=seeds, want_keep=True),
@@ -124,7 +125,7 @@ def main():
                 if both() is None:
                     raise SystemExit("project_fwd_both: not eligible at this shape")
                 t = timeit(both)
-                print(json.dumps({"kernel": f"k1 combined: {p} launches", "ms": round(t, 4)}))
+                print(json.dumps({"kernel": f"k1 combined: {p} meta-paths", "ms": round(t, 4)}))
         # round 3: the forward writes the keep table, dW reads it (4x4x1 16-block MFMA kernel)
         t = timeit(lambda: ops.project_fwd(X, W, a1, a2, b1, b2, in_drop=0.6, fts_drop=0.6, seed=5, want_keep=True, flags=fl_))
         print(json.dumps({"kernel": f"project_fwd drop=0.6 + keep table flags={fl_}", "ms": round(t, 4)}))
