@@ -5,7 +5,7 @@ full-graph with early stopping, restore the best weights, report the test metric
 KNN / KMeans scores of ``final_embed``.
 
     python examples/ex_acm3025.py [--mat ACM3025.mat] [--epochs 200] [--graph] [--eval-device gpu] [--sparse-features]
-                                  [--batch-size B [--fanout 10 | --fanout 10,5]]
+                                  [--batch-size B [--fanout 10 | --fanout 10,5]] [--multilabel]
 
 Hyper-parameters are the reference's (ex_acm3025.py:16-31): lr 0.005, l2 0.001,
 hid_units [8], n_heads [8, 1], dropout 0.6/0.6, patience 100, mp_att_size 128.
@@ -45,6 +45,10 @@ def main():
     ap.add_argument("--fanout", default=None, metavar="F[,F...]",
                     help="with --batch-size: sample every step's block afresh, at most F neighbours per row and "
                          "meta-path (one number, or one per node-attention layer: the seeds' rows first)")
+    ap.add_argument("--multilabel", action="store_true",
+                    help="the reference's multi-label pair (masked sigmoid cross-entropy, micro-F1; "
+                         "models/base_gattn.py:50-59,71-94) on the synthetic planted task: every node carries several "
+                         "of 5 label planes (synth.multilabel_labels); reports micro-F1 per epoch and at the end")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eval-device", choices=("cpu", "gpu"), default="cpu",
                     help="where final_embed is scored: cpu = scikit-learn on the host, as the reference; gpu = the "
@@ -58,6 +62,9 @@ def main():
     dev = torch.device("cuda:0")
     torch.manual_seed(args.seed)
 
+    if args.multilabel and args.mat:
+        ap.error("--multilabel runs on synthetic data (the ACM3025 file carries one label per node)")
+    metric = "micro-F1" if args.multilabel else "acc"
     if args.mat:
         adj_list, fea_list, y_train, y_val, y_test, train_mask, val_mask, test_mask = process.load_data_mat(args.mat)
         graphs = [process.adj_to_graph(a, nhood=1, device=dev) for a in adj_list]      # == adj_to_bias's edge set
@@ -72,7 +79,7 @@ def main():
         labels = torch.tensor(y.argmax(1), dtype=torch.int32, device=dev)
         masks = [torch.tensor(m, device=dev) for m in (train_mask, val_mask, test_mask)]
         nb_classes = y.shape[1]
-    elif args.planted:
+    elif args.planted or args.multilabel:
         wl = synth.planted_partition(3025, 3, 2, 64, deg_in=8, deg_out=2, noise=1.0, seed=args.seed, device=dev)
         graphs, xs = wl["graphs"], [wl["x"]] * wl["p"]
         labels, nb_classes = wl["labels"], wl["c"]
@@ -85,6 +92,10 @@ def main():
         masks = [wl["train_mask"], wl["val_mask"], test]
         if args.sparse_features:      # ~1 % of the 1870 columns per row, a few words in most documents
             xs = [synth.bag_of_words(wl["n"], wl["f"], 20, seed=args.seed, device=dev)] * wl["p"]
+    classes, n_groups = labels, nb_classes      # what the embeddings are scored against: one id per node
+    if args.multilabel:
+        labels, nb_classes = synth.multilabel_labels(classes, 5, seed=args.seed), 5
+    objective = dict(objective="sigmoid" if args.multilabel else "softmax")
     n, ft = xs[0].shape
     print(f"nodes {n}, features {ft}, classes {nb_classes}, meta-paths {len(graphs)}, "
           f"edges {[g.nnz for g in graphs]}")
@@ -104,21 +115,21 @@ def main():
             ap.error("--batch-size: the block shapes change per batch, there is no epoch to capture (--graph)")
         tr = MiniBatchTrainer(model, xs, graphs, labels, masks[0], masks[1], batch_size=args.batch_size, lr=0.005,
                               l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6, seed=args.seed, patience=args.patience,
-                              fanout=fanout)
+                              fanout=fanout, **objective)
         tr.overlap_eval = False
     else:
         tr = HANTrainer(model, xs, graphs, labels, masks[0], masks[1], lr=0.005, l2_coef=0.001,
                         attn_drop=0.6, ffd_drop=0.6, patience=args.patience, use_graph=args.graph,
-                        overlap_eval=args.graph and args.overlap_eval)
+                        overlap_eval=args.graph and args.overlap_eval, **objective)
     t0 = time.perf_counter()
     for epoch in range(args.epochs):
         tl, ta, vl, va = (float(v) for v in tr.epoch())
         if tr.overlap_eval and epoch == 0:
             continue                         # that pair belongs to the initial parameters (ex_acm3025.py has no such line)
         if epoch % 10 == 0:
-            print(f"epoch {epoch:4d}  train loss {tl:.5f} acc {ta:.5f} | val loss {vl:.5f} acc {va:.5f}")
+            print(f"epoch {epoch:4d}  train loss {tl:.5f} {metric} {ta:.5f} | val loss {vl:.5f} {metric} {va:.5f}")
         if tr.early_stopping(vl, va):
-            print(f"early stop at epoch {epoch}: min val loss {tr.vlss_mn:.5f}, max val acc {tr.vacc_mx:.5f}")
+            print(f"early stop at epoch {epoch}: min val loss {tr.vlss_mn:.5f}, max val {metric} {tr.vacc_mx:.5f}")
             break
     else:
         if tr.overlap_eval:                  # the validation pair of the last epoch
@@ -132,18 +143,18 @@ def main():
     else:
         w_test = 1.0 / max(int(masks[2].sum()), 1)
         tl, ta = tr.eval_step(masks[2].to(torch.uint8).contiguous(), w_test)
-    print(f"test loss {float(tl):.5f}  test accuracy {float(ta):.5f}")
+    print(f"test loss {float(tl):.5f}  test {'micro-F1' if args.multilabel else 'accuracy'} {float(ta):.5f}")
     with torch.no_grad():
         _, final_embed, att = model.inference(xs, nb_classes, n, False, 0.0, 0.0, graphs, [8], [8, 1])
     print("mean meta-path attention:", att.mean(0).tolist())
     if args.eval_device == "gpu":
         sel = masks[2].bool()
-        emb, lab, eval_dev = final_embed[sel], labels[sel], dev
+        emb, lab, eval_dev = final_embed[sel], classes[sel], dev
     else:
         sel = masks[2].bool().cpu().numpy()
-        emb, lab, eval_dev = final_embed.cpu().numpy()[sel], labels.cpu().numpy()[sel], None
+        emb, lab, eval_dev = final_embed.cpu().numpy()[sel], classes.cpu().numpy()[sel], None
     evaluate.my_KNN(emb, lab, seed=args.seed, device=eval_dev)                     # ex_acm3025.py:288
-    evaluate.my_Kmeans(emb, lab, k=nb_classes, seed=args.seed, device=eval_dev, silhouette=args.silhouette)    # :289
+    evaluate.my_Kmeans(emb, lab, k=n_groups, seed=args.seed, device=eval_dev, silhouette=args.silhouette)    # :289
     if args.tsne:                                                                  # the picture of jhyexp.py:16
         import numpy as np
         coords, info = evaluate.tsne(emb, seed=args.seed, device=eval_dev, return_info=True)

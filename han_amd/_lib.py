@@ -98,6 +98,9 @@ SIGNATURES = {
                                     c_int, c_int, c_int, P]),
     "han_classifier_loss_live": (c_int, [P, P, P, P, P, c_float, P, P, P, P, P, P, c_size_t, P, I64, I64,
                                          c_int, c_int, c_int, P]),
+    "han_classifier_multilabel_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
+    "han_classifier_multilabel": (c_int, [P, P, P, P, P, c_float, P, P, P, P, P, P, P, c_size_t, P, I64, I64,
+                                          c_int, c_int, c_int, P]),
     "han_classifier_bwd_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
     "han_classifier_bwd": (c_int, [P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, c_int, P]),
     "han_adam_step": (c_int, [P, P, P, P, I64, c_float, c_float, c_float, c_float, c_float, P, P]),

@@ -2,13 +2,21 @@
 
 * :meth:`BaseGAttN.masked_softmax_cross_entropy` -- models/base_gattn.py:41-48
 * :meth:`BaseGAttN.masked_accuracy`              -- models/base_gattn.py:61-69
+* :meth:`BaseGAttN.masked_sigmoid_cross_entropy` -- models/base_gattn.py:50-59
+* :meth:`BaseGAttN.micro_f1`                     -- models/base_gattn.py:71-94
 * :meth:`BaseGAttN.training`                     -- models/base_gattn.py:12-24
 
 The standalone loss / metric functions are O(N*C) host-side torch expressions on
 whatever device the logits live on ("host-side
 PyTorch, no custom kernel").  The training loop (han_amd/trainer.py) does not
-use them: it calls the fused classifier+loss kernel and the fused L2+Adam
-kernel (han_classifier_loss / han_adam_step).
+use them: it calls the fused classifier+loss kernel of its objective --
+han_classifier_loss (softmax cross-entropy + accuracy) or
+han_classifier_multilabel (sigmoid cross-entropy + micro-F1,
+HANTrainer(objective="sigmoid")) -- and the fused L2+Adam kernel
+(han_adam_step).  One documented difference: the kernel predicts a label
+where the logit is > 0, which is round(sigmoid(x)) in exact arithmetic;
+micro_f1 below rounds an fp32 sigmoid, which maps tiny positive logits to 0
+-- a difference inside the logits' own rounding error.
 """
 from __future__ import annotations
 

@@ -546,3 +546,279 @@ extern "C" const char *han_error_string(int code) {
         default: return code > 0 ? hipGetErrorString((hipError_t)code) : "han: unknown error";
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Multi-label objective (han_classifier_multilabel): models/base_gattn.py:50-59 (masked sigmoid cross-entropy, TF's
+// stable form, mean over the C classes of a row) and :71-94 (micro-F1).  Per class, with e = exp(-|x|):
+//   loss term   max(x, 0) - x y + log(1 + e)
+//   sigma       1 / (1 + e) for x >= 0, e / (1 + e) otherwise        dlogits = (w / C) (sigma - y)
+//   prediction  x > 0                                                (round(sigmoid(x)), half to even)
+// Labels are bit words: class c of a row is bit c % 64 of word c / 64.  The counts tp | fp | fn of the masked rows are
+// integers from the lane to the slab to the finishing kernel, which also forms micro-F1 = 2 tp / (2 tp + fp + fn) in
+// double (NaN for tp == 0, the reference's 0 / 0).  The softmax kernels above are not touched: the fused forms are
+// their thread maps with another objective (multilabel_body.h), the any-shape form is a row kernel that writes the dL
+// table for cls_dw_kernel.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct MlArgs {
+    const float *Z, *Wc, *bc;
+    const unsigned long long *bits;
+    const uint8_t *mask;
+    float row_weight;
+    float *logits, *dZ, *slab;
+    unsigned long long *cslab;      // [gridDim.x][3] tp | fp | fn
+    int64_t N;
+    int C, HC;
+};
+
+__device__ __forceinline__ float ml_exp(float x) { return __expf(-fabsf(x)); }
+
+__device__ __forceinline__ float ml_loss(float x, unsigned y, float e) {
+    return (fmaxf(x, 0.f) - (y ? x : 0.f)) + __logf(1.f + e);
+}
+
+__device__ __forceinline__ float ml_sigma(float x, float e) { return (x >= 0.f ? 1.f : e) / (1.f + e); }
+
+#define ML_KERNEL multilabel_kernel
+#define ML_WIDE_KERNEL multilabel_wide_kernel
+#define ML_PARAMS const MlArgs a
+#define ML_ROW(it) (it)
+#include "multilabel_body.h"
+#undef ML_KERNEL
+#undef ML_WIDE_KERNEL
+#undef ML_PARAMS
+#undef ML_ROW
+// the row list: the rows live[0 .. a.N)
+#define ML_KERNEL multilabel_live_kernel
+#define ML_WIDE_KERNEL multilabel_wide_live_kernel
+#define ML_PARAMS const MlArgs a, const int32_t *live
+#define ML_ROW(it) ((int64_t)live[it])
+#include "multilabel_body.h"
+#undef ML_KERNEL
+#undef ML_WIDE_KERNEL
+#undef ML_PARAMS
+#undef ML_ROW
+
+template <int NV>
+static void launch_multilabel(const MlArgs &a, const int32_t *live, bool bwd, int grid, hipStream_t st) {
+    const int cm = a.C <= 4 ? 4 : a.C <= 8 ? 8 : a.C <= MAXC ? 16 : 0;
+    HAN_DISPATCH_BOOL(BWD, bwd, {
+        if (live) {
+            switch (cm) {
+                case 4: multilabel_live_kernel<BWD, 4, NV><<<grid, 256, 0, st>>>(a, live); break;
+                case 8: multilabel_live_kernel<BWD, 8, NV><<<grid, 256, 0, st>>>(a, live); break;
+                case 16: multilabel_live_kernel<BWD, 16, NV><<<grid, 256, 0, st>>>(a, live); break;
+                default: multilabel_wide_live_kernel<BWD, NV><<<grid, 256, 0, st>>>(a, live); break;
+            }
+        } else {
+            switch (cm) {
+                case 4: multilabel_kernel<BWD, 4, NV><<<grid, 256, 0, st>>>(a); break;
+                case 8: multilabel_kernel<BWD, 8, NV><<<grid, 256, 0, st>>>(a); break;
+                case 16: multilabel_kernel<BWD, 16, NV><<<grid, 256, 0, st>>>(a); break;
+                default: multilabel_wide_kernel<BWD, NV><<<grid, 256, 0, st>>>(a); break;
+            }
+        }
+    });
+}
+
+struct MlGenArgs {
+    const float *Z, *WmT, *bm;
+    const unsigned long long *bits;
+    const uint8_t *mask;
+    float row_weight;
+    float *logits, *dZ, *dL, *slab;    // slab: [gridDim.x] loss
+    unsigned long long *cslab;
+    int64_t N;
+    int D, C, NW;                      // NW = label words per row
+};
+
+// Any width / class count: one wave per row, lane = feature, class by class as cls_gen_kernel -- but the sigmoid
+// objective needs no statistics of the row, so one pass over the classes gives logit, loss term, count, dl and the dZ
+// update.  Rows outside the mask get a dZ row of zeros and no dL row (cls_dw_kernel skips them by the same predicate).
+template <bool BWD, int NV>
+__global__ __launch_bounds__(256) void ml_gen_kernel(const MlGenArgs a) {
+    constexpr int NR = NV > 0 ? NV : 1;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int D = a.D, C = a.C, nv = D / 64;
+    const float invc = 1.f / (float)C;
+    float loss_acc = 0.f;
+    unsigned long long tp = 0, fp = 0, fn = 0;
+    const int64_t wave0 = (int64_t)blockIdx.x * 4 + w, nwaves = (int64_t)gridDim.x * 4;
+    for (int64_t row = wave0; row < a.N; row += nwaves) {
+        const float *zrow = a.Z + row * D + lane;
+        float z[NR];
+        if (NV > 0) {
+#pragma unroll
+            for (int v = 0; v < NR; ++v) z[v] = v < nv ? zrow[64 * v] : 0.f;
+        }
+        const bool live = __builtin_amdgcn_readfirstlane((int)a.mask[row]) != 0;      // the same byte in every lane
+        const float wgt = live ? a.row_weight : 0.f;
+        const float wc = wgt * invc;
+        const unsigned long long *yrow = a.bits + row * a.NW;
+        unsigned long long yw = 0;
+        float rs = 0.f;
+        float dz[NR];
+#pragma unroll
+        for (int v = 0; v < NR; ++v) dz[v] = 0.f;
+        if (BWD && NV == 0)
+            for (int v = 0; v < nv; ++v) a.dZ[row * D + 64 * v + lane] = 0.f;
+        for (int c = 0; c < C; ++c) {
+            if ((c & 63) == 0) yw = yrow[c >> 6];
+            const unsigned y = (unsigned)(yw >> (c & 63)) & 1u;
+            const float *wr = a.WmT + (int64_t)c * D + lane;
+            float part = 0.f;
+            if (NV > 0) {
+#pragma unroll
+                for (int v = 0; v < NR; ++v) part += v < nv ? z[v] * wr[64 * v] : 0.f;
+            } else {
+                for (int v = 0; v < nv; ++v) part += zrow[64 * v] * wr[64 * v];
+            }
+            const float lg = han_wave_sum(part) + a.bm[c];
+            if (lane == 0) a.logits[row * C + c] = lg;
+            if (live) {                 // wave-uniform; a row outside the mask: its logits and nothing else
+                const float e = ml_exp(lg);
+                rs += ml_loss(lg, y, e);
+                const unsigned p = lg > 0.f ? 1u : 0u;
+                tp += p & y;
+                fp += p & (y ^ 1u);
+                fn += (p ^ 1u) & y;
+                if (BWD) {
+                    const float dl = wc * (ml_sigma(lg, e) - (float)y);
+                    if (lane == 0) a.dL[row * C + c] = dl;
+                    if (NV > 0) {
+#pragma unroll
+                        for (int v = 0; v < NR; ++v) dz[v] += v < nv ? dl * wr[64 * v] : 0.f;
+                    } else {
+                        for (int v = 0; v < nv; ++v) a.dZ[row * D + 64 * v + lane] += dl * wr[64 * v];
+                    }
+                }
+            }
+        }
+        if (lane == 0 && live) loss_acc += wgt * (rs * invc);
+        if (BWD && NV > 0) {
+#pragma unroll
+            for (int v = 0; v < NR; ++v)
+                if (v < nv) a.dZ[row * D + 64 * v + lane] = dz[v];
+        }
+    }
+    __shared__ float red[4];
+    __shared__ unsigned long long cnt[4][3];
+    if (lane == 0) { red[w] = loss_acc; cnt[w][0] = tp; cnt[w][1] = fp; cnt[w][2] = fn; }
+    __syncthreads();
+    if (threadIdx.x == 0) a.slab[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    if (threadIdx.x < 3)
+        a.cslab[(int64_t)blockIdx.x * 3 + threadIdx.x] =
+            cnt[0][threadIdx.x] + cnt[1][threadIdx.x] + cnt[2][threadIdx.x] + cnt[3][threadIdx.x];
+}
+
+// the counts of the blocks -> counts[3] (int64) and loss_acc[1] = micro-F1; one block of 192 threads
+__global__ __launch_bounds__(192) void ml_finish_kernel(const unsigned long long *cslab, int nblocks, float *loss_acc,
+                                                        long long *counts) {
+    __shared__ unsigned long long part[3][64];
+    __shared__ unsigned long long tot[3];
+    const int k = threadIdx.x >> 6, j = threadIdx.x & 63;
+    unsigned long long s = 0;
+    for (int b = j; b < nblocks; b += 64) s += cslab[(int64_t)b * 3 + k];
+    part[k][j] = s;
+    __syncthreads();
+    if (j == 0) {
+        unsigned long long t = 0;
+        for (int i = 0; i < 64; ++i) t += part[k][i];
+        tot[k] = t;
+        counts[k] = (long long)t;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double tp = (double)tot[0], rest = (double)tot[1] + (double)tot[2];
+        loss_acc[1] = tot[0] == 0 ? __int_as_float(0x7FC00000) : (float)(2.0 * tp / (2.0 * tp + rest));
+    }
+}
+
+// workspace: the float part (the slabs of the fused kernels, or the three-kernel layout of cls_gen_ws with ONE loss
+// column used), then, 8-byte aligned, the count slab [blocks][3]
+struct MlWs { size_t counts, bytes; };
+
+static MlWs ml_ws(int64_t N, int D, int C) {
+    MlWs w;
+    const size_t floats = cls_tuned(D, C) ? (size_t)kClsBlocks * (size_t)(D * C + C + 1) : cls_gen_ws(N, D, C, true).floats;
+    w.counts = (floats * sizeof(float) + 7) / 8 * 8;
+    w.bytes = w.counts + (size_t)(cls_tuned(D, C) ? kClsBlocks : kClsGenBlocks) * 3 * sizeof(unsigned long long);
+    return w;
+}
+
+}  // namespace
+
+extern "C" size_t han_classifier_multilabel_workspace(int64_t N, int D, int C, int) {
+    if (!cls_shape(D, C) || N < 0) return 0;
+    return ml_ws(N, D, C).bytes;
+}
+
+extern "C" int han_classifier_multilabel(const float *Z, const float *Wc, const float *bc, const uint64_t *label_bits,
+                                         const uint8_t *mask, float row_weight, float *logits, float *loss_acc,
+                                         int64_t *counts, float *dZ, float *dWc, float *dbc, void *workspace,
+                                         size_t workspace_bytes, const int32_t *live, int64_t n_live, int64_t N, int D,
+                                         int C, int HC, void *stream) {
+    if (!Z || !Wc || !bc || !label_bits || !mask || !logits || !loss_acc || !counts || !workspace || N < 0 || HC <= 0)
+        return HAN_E_BADARG;
+    if (live && (n_live < 0 || n_live > N)) return HAN_E_BADARG;
+    const bool bwd = dZ != nullptr;
+    if (bwd && (!dWc || !dbc)) return HAN_E_BADARG;
+    if (!cls_shape(D, C)) return HAN_E_UNSUPPORTED;
+    const bool tuned = cls_tuned(D, C);
+    if (live && !tuned) return HAN_E_UNSUPPORTED;      // the row list: the fused kernels only
+    const MlWs mw = ml_ws(N, D, C);
+    if (workspace_bytes < mw.bytes) return HAN_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    float *ws = (float *)workspace;
+    unsigned long long *cslab = (unsigned long long *)((char *)workspace + mw.counts);
+    const unsigned long long *bits = (const unsigned long long *)label_bits;
+    if (live && n_live == 0) {      // no row, no launch: the sums over no rows, and 0 / 0 for the metric (all-ones is a NaN)
+        hipError_t e = hipMemsetAsync(loss_acc, 0, sizeof(float), st);
+        if (e == hipSuccess) e = hipMemsetAsync(loss_acc + 1, 0xFF, sizeof(float), st);
+        if (e == hipSuccess) e = hipMemsetAsync(counts, 0, 3 * sizeof(int64_t), st);
+        if (e == hipSuccess && bwd) e = hipMemsetAsync(dWc, 0, (size_t)HC * D * C * sizeof(float), st);
+        if (e == hipSuccess && bwd) e = hipMemsetAsync(dbc, 0, (size_t)HC * C * sizeof(float), st);
+        return (int)e;
+    }
+    if (!tuned) {       // head average -> row kernel -> Z^T dL over the masked rows
+        const ClsGenWs w = cls_gen_ws(N, D, C, true);
+        MlGenArgs g;
+        g.Z = Z; g.WmT = ws; g.bm = ws + w.bm; g.bits = bits; g.mask = mask; g.row_weight = row_weight;
+        g.logits = logits; g.dZ = dZ; g.dL = ws + w.dL; g.slab = ws + w.la; g.cslab = cslab; g.N = N; g.D = D; g.C = C;
+        g.NW = (C + 63) / 64;
+        const int rc = launch_cls_mean(Wc, bc, ws, w, D, C, HC, st);
+        if (rc != 0) return rc;
+        const int grid = han_grid_for(N > 0 ? N : 1, 4, kClsGenBlocks);
+        HAN_DISPATCH_BOOL(BWD, bwd, {
+            switch (D <= 256 ? 4 : D <= 512 ? 8 : D <= 1024 ? 16 : 0) {
+                case 4: ml_gen_kernel<BWD, 4><<<grid, 256, 0, st>>>(g); break;
+                case 8: ml_gen_kernel<BWD, 8><<<grid, 256, 0, st>>>(g); break;
+                case 16: ml_gen_kernel<BWD, 16><<<grid, 256, 0, st>>>(g); break;
+                default: ml_gen_kernel<BWD, 0><<<grid, 256, 0, st>>>(g); break;
+            }
+        });
+        HAN_CHECK_LAUNCH();
+        const hipError_t e = han_reduce_slabs(g.slab, grid, 1, 1, han_reduce_to(loss_acc, 1), st);
+        if (e != hipSuccess) return (int)e;
+        ml_finish_kernel<<<1, 192, 0, st>>>(cslab, grid, loss_acc, (long long *)counts);
+        HAN_CHECK_LAUNCH();
+        return bwd ? launch_cls_dw(Z, g.dL, mask, ws + w.dws, dWc, dbc, N, D, C, HC, st) : 0;
+    }
+    const int64_t rows = live ? n_live : N;
+    MlArgs a;
+    a.Z = Z; a.Wc = Wc; a.bc = bc; a.bits = bits; a.mask = mask; a.row_weight = row_weight;
+    a.logits = logits; a.dZ = dZ; a.slab = ws; a.cslab = cslab; a.N = rows; a.C = C; a.HC = HC;
+    const int grid = han_grid_for(rows > 0 ? rows : 1, C > MAXC ? 4 : 16, kClsBlocks);
+    if (D == 128) launch_multilabel<2>(a, live, bwd, grid, st);
+    else launch_multilabel<1>(a, live, bwd, grid, st);
+    HAN_CHECK_LAUNCH();
+    // one second-stage launch: the head gradients and the loss (the last slab column); then the counts
+    const int width = D * C + C + 1;
+    const hipError_t e = bwd ? han_reduce_slabs(ws, grid, width, width, cls_head_grads(dWc, dbc, loss_acc, D, C, HC), st)
+                             : han_reduce_slabs(ws + D * C + C, grid, width, 1, han_reduce_to(loss_acc, 1), st);
+    if (e != hipSuccess) return (int)e;
+    ml_finish_kernel<<<1, 192, 0, st>>>(cslab, grid, loss_acc, (long long *)counts);
+    HAN_CHECK_LAUNCH();
+    return 0;
+}

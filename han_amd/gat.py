@@ -401,12 +401,20 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
     def classifier_loss(self, Z, labels, mask, weight):
         """Fused classifier + masked softmax cross-entropy + accuracy (the trainer's step):
         returns (loss, accuracy, logits).  After a forward over a row list (node_level(live_fwd=...)) the sums run over
-        that list, and only its rows of the logits are written."""
+        that list, and only its rows of the logits are written.
+        The kind of `labels` selects the objective: (N,) int32 class ids the softmax one; (N, ceil(C/64)) int64 words
+        from ops.pack_label_bits the multi-label one (masked sigmoid cross-entropy, models/base_gattn.py:50-59), whose
+        second result is micro-F1 (:71-94) and whose result also carries .counts = [tp, fp, fn]."""
         lv, self._live_handover = self._live_handover, None
         if lv is not None and lv[0] is not Z:
             raise RuntimeError("live_forward: classifier_loss() must take the Z that semantic() returned")
-        return layers.classifier_loss_any(Z, self.Wc, self.bc, labels, mask, weight,
-                                          live=lv[1].live if lv is not None else None)
+        live = lv[1].live if lv is not None else None
+        if labels.dim() == 2:
+            if labels.dtype != torch.int64:
+                raise ValueError(f"labels: a 2-D label tensor must hold packed words (ops.pack_label_bits, int64), "
+                                 f"got {labels.dtype}")
+            return layers.classifier_multilabel_any(Z, self.Wc, self.bc, labels, mask, weight, live=live)
+        return layers.classifier_loss_any(Z, self.Wc, self.bc, labels, mask, weight, live=live)
 
     @_ClassOrInstance
     def inference(self, inputs_list, nb_classes, nb_nodes, training, attn_drop, ffd_drop,

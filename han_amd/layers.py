@@ -926,6 +926,66 @@ class ClassifierLoss(torch.autograd.Function):
         return (dZ * dloss, dWc * dloss, dbc * dloss) + tail
 
 
+class MultiLabelResult(tuple):
+    """What classifier_multilabel_any returns: the 3-tuple (loss, micro_f1, logits) -- the shape of
+    classifier_loss_any's result, in length, indexing and unpacking -- with one attribute more: `counts`, the int64
+    device tensor [tp, fp, fn] the metric was formed from (sums over ranks or batches, which micro-F1 itself is not:
+    micro_f1_of_counts forms it from summed counts)."""
+
+    def __new__(cls, loss, micro_f1, logits, counts):
+        r = super().__new__(cls, (loss, micro_f1, logits))
+        r.counts = counts
+        return r
+
+    loss = property(lambda self: self[0])
+    micro_f1 = property(lambda self: self[1])
+    logits = property(lambda self: self[2])
+
+
+def micro_f1_of_counts(counts):
+    """2 tp / (2 tp + fp + fn) in double, rounded to fp32, of an int64 tensor [tp, fp, fn] (models/base_gattn.py:90-92,
+    algebraically); NaN for tp == 0, the reference's 0 / 0.  A few scalar torch ops on the device of `counts`."""
+    c = counts.to(torch.float64)
+    f1 = 2.0 * c[0] / (2.0 * c[0] + c[1] + c[2])
+    return torch.where(counts[0] == 0, torch.full_like(f1, float("nan")), f1).to(torch.float32)
+
+
+class MultiLabelClassifierLoss(torch.autograd.Function):
+    """Fused classifier + masked sigmoid cross-entropy (+ micro-F1 and its counts).
+    models/gat.py:65-72, models/base_gattn.py:50-59,71-94.
+    Returns (loss, micro_f1, logits (N,C), counts (3,) int64); only `loss` is differentiable."""
+
+    @staticmethod
+    def forward(ctx, Z, Wc, bc, label_bits, mask, row_weight, *grad_mode):
+        """grad_mode: as ClassifierLoss.forward -- nothing, (grad enabled,) or (grad enabled, live)."""
+        need = any(ctx.needs_input_grad[:3]) and (not grad_mode or bool(grad_mode[0]))
+        ctx.n_opt = len(grad_mode)
+        ctx.set_materialize_grads(False)
+        ctx.direct = need and _direct(Wc) and _direct(bc)
+        logits, loss_acc, counts, grads = ops.classifier_multilabel(
+            Z.contiguous(), Wc, bc, label_bits, mask, row_weight, backward=need,
+            grad_out=(Wc.grad, bc.grad) if ctx.direct else None,
+            **({"live": grad_mode[1]} if len(grad_mode) > 1 else {}))
+        ctx.grads = grads
+        if ctx.direct or not need:
+            loss, f1 = loss_acc[0:1].view(()), loss_acc[1:2].view(())
+        else:
+            loss, f1 = loss_acc[0].clone(), loss_acc[1].clone()
+        ctx.mark_non_differentiable(f1, logits, counts)
+        return loss, f1, logits, counts
+
+    @staticmethod
+    def backward(ctx, dloss, _df1, _dlogits, _dcounts):
+        dZ, dWc, dbc = ctx.grads
+        ctx.grads = None
+        tail = (None,) * (3 + ctx.n_opt)
+        if ctx.direct:
+            return (dZ, None, None) + tail
+        if dloss is None:
+            return (None, None, None) + tail
+        return (dZ * dloss, dWc * dloss, dbc * dloss) + tail
+
+
 class _ClassifierForward(torch.autograd.Function):
     """logits = (1/HC) sum_h (Z Wc[h] + bc[h]) (models/gat.py:65-72) by the HIP kernels, forward and backward
     (han_classifier_loss with an empty mask; han_classifier_bwd for a caller-supplied dlogits)."""
@@ -997,6 +1057,20 @@ def classifier_loss_any(Z, Wc, bc, labels, mask, weight, live=None):
     if dm != d:
         Z, Wc = torch.nn.functional.pad(Z, (0, dm - d)), torch.nn.functional.pad(Wc, (0, 0, 0, dm - d))
     return ClassifierLoss.apply(Z, Wc, bc, labels, mask, weight, torch.is_grad_enabled())
+
+
+def classifier_multilabel_any(Z, Wc, bc, label_bits, mask, weight, live=None):
+    """Classifier + masked sigmoid cross-entropy + micro-F1 (models/base_gattn.py:50-59,71-94) for any embedding
+    width / class count; label_bits: ops.pack_label_bits of the (N, C) multi-hot labels.  Returns a MultiLabelResult
+    (loss, micro_f1, logits; .counts = [tp, fp, fn]).  live: as classifier_loss_any."""
+    d = Z.shape[1]
+    dm = _pad_to(d)
+    if live is not None:
+        return MultiLabelResult(*MultiLabelClassifierLoss.apply(Z, Wc, bc, label_bits, mask, weight,
+                                                                torch.is_grad_enabled(), live))
+    if dm != d:
+        Z, Wc = torch.nn.functional.pad(Z, (0, dm - d)), torch.nn.functional.pad(Wc, (0, 0, 0, dm - d))
+    return MultiLabelResult(*MultiLabelClassifierLoss.apply(Z, Wc, bc, label_bits, mask, weight, torch.is_grad_enabled()))
 
 
 # ---------------------------------------------------------------------------

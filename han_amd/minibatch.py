@@ -302,14 +302,21 @@ class MiniBatchTrainer:
     evaluate() stays exact (unsampled blocks)."""
 
     def __init__(self, model, xs, graphs, labels, train_mask, val_mask=None, batch_size: int = 1024, lr=0.005,
-                 l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6, seed: int = 0, patience: int = 100, fanout=None):
+                 l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6, seed: int = 0, patience: int = 100, fanout=None,
+                 objective="softmax"):
+        """objective: HANTrainer's -- "sigmoid" takes (N, C) multi-hot labels, packed once (EgoBlock.take gathers the
+        packed words like any dense row table), trains on the masked sigmoid cross-entropy and reports micro-F1 where
+        "softmax" reports the accuracy."""
+        from .trainer import check_objective, device_labels
+        check_objective(objective, labels, model.Wc.shape[2])
+        self.objective = objective
         self.model = model
         self.xs, self.graphs = _inputs(model, xs, graphs)
         model.direct_grads(True)
         dev = model.flat.device
         self.hops = _model_hops(model)
         self.fanout, self.steps_done = _check_fanout(fanout, self.hops), 0
-        self.labels = labels.to(device=dev, dtype=torch.int32).contiguous()
+        self.labels = device_labels(objective, labels, dev)
         self.train_mask = train_mask.to(device=dev, dtype=torch.uint8).contiguous()
         self.val_mask = (val_mask if val_mask is not None else train_mask).to(device=dev, dtype=torch.uint8).contiguous()
         self.train_ids = torch.nonzero(self.train_mask).flatten().cpu().numpy()
@@ -325,6 +332,7 @@ class MiniBatchTrainer:
         self.patience = patience
         self.vlss_mn, self.vacc_mx, self.curr_step = float("inf"), 0.0, 0
         self.best_state = None
+        self.last_counts = None
 
     def batches(self):
         """The seed batches of the next epoch (host arrays)."""
@@ -346,7 +354,9 @@ class MiniBatchTrainer:
             with torch.enable_grad():
                 M = m.node_level(xs, blk.graphs, self.attn_drop, self.ffd_drop, True, ops.ACT_ELU)
                 Z, _ = m.semantic(M)
-                loss, acc, _ = m.classifier_loss(Z, labels, mask, 1.0 / blk.seed_pos.numel())
+                res = m.classifier_loss(Z, labels, mask, 1.0 / blk.seed_pos.numel())
+                loss, acc, _ = res
+            self.last_counts = getattr(res, "counts", None)      # objective="sigmoid": [tp, fp, fn] of this batch
             loss.backward(self._one)
         finally:
             self._rng = dict(rng._state)
@@ -361,28 +371,44 @@ class MiniBatchTrainer:
         ids = torch.nonzero(mask.to(self.labels.device)).flatten()
         if ids.numel() == 0:
             raise ValueError("the mask selects no node")
-        logits, _, _ = predict(self.model, self.xs, self.graphs, ids, self.batch_size)
+        logits, embed, _ = predict(self.model, self.xs, self.graphs, ids, self.batch_size)
+        if self.objective == "sigmoid":      # the masked sigmoid cross-entropy and micro-F1 of the rows, by the kernel
+            with torch.no_grad():
+                ones = torch.ones(ids.numel(), dtype=torch.uint8, device=embed.device)
+                loss, f1, _ = layers.classifier_multilabel_any(embed.contiguous(), self.model.Wc, self.model.bc,
+                                                               self.labels[ids].contiguous(), ones, 1.0 / ids.numel())
+            return loss, f1
         labels = self.labels[ids].long()
         loss = torch.nn.functional.cross_entropy(logits, labels)
         return loss, (logits.argmax(1) == labels).to(torch.float32).mean()
 
     def epoch(self):
         """One pass over the training nodes, then the validation pair: (train loss, train accuracy -- the batch
-        figures averaged over the training nodes --, val loss, val accuracy), device scalars."""
+        figures averaged over the training nodes --, val loss, val accuracy), device scalars.  With
+        objective="sigmoid" the second and fourth are micro-F1, and the training one is formed ONCE from the counts
+        tp / fp / fn summed over the batches: micro-F1 is a ratio of sums, not a mean of the batches' ratios (and one
+        batch without a true positive must not turn the epoch's figure into NaN)."""
         tl = ta = 0.0
+        counts = None
         for b in self.batches():
             loss, acc = self.train_step(b)
             tl, ta = tl + loss * (b.size / self.train_ids.size), ta + acc * (b.size / self.train_ids.size)
+            if self.last_counts is not None:
+                counts = self.last_counts.clone() if counts is None else counts + self.last_counts
+        if counts is not None:
+            ta = layers.micro_f1_of_counts(counts)
         self.epochs_done += 1
         vl, va = self.evaluate()
         return tl, ta, vl, va
 
     def early_stopping(self, val_loss: float, val_acc: float) -> bool:
         """HANTrainer.early_stopping (ex_acm3025.py:225-240): True to stop."""
-        if val_acc >= self.vacc_mx or val_loss <= self.vlss_mn:
-            if val_acc >= self.vacc_mx and val_loss <= self.vlss_mn:
+        from .trainer import metric_improved
+        acc_ok = metric_improved(val_acc, self.vacc_mx)      # a NaN micro-F1 is no improvement and is never stored
+        if acc_ok or val_loss <= self.vlss_mn:
+            if acc_ok and val_loss <= self.vlss_mn:
                 self.best_state = self.model.flat.detach().clone()
-            self.vacc_mx, self.vlss_mn = max(val_acc, self.vacc_mx), min(val_loss, self.vlss_mn)
+            self.vacc_mx, self.vlss_mn = (val_acc if acc_ok else self.vacc_mx), min(val_loss, self.vlss_mn)
             self.curr_step = 0
             return False
         self.curr_step += 1

@@ -1014,6 +1014,83 @@ def classifier_loss(Z, Wc, bc, labels, mask, row_weight, backward=False, grad_ou
     return logits, loss_acc, grads
 
 
+def label_words(C: int) -> int:
+    """64-bit words per row of a packed (N, C) multi-hot label matrix."""
+    return (int(C) + 63) // 64
+
+
+PACK_ROWS = 65536      # rows per step of pack_label_bits
+
+
+def pack_label_bits(y):
+    """(N, C) bool / 0-1 labels -> (N, ceil(C/64)) packed words, class c of a row at bit c % 64 of word c / 64: the
+    `label_bits` of han_classifier_multilabel.  The words are stored as int64 (torch has no arithmetic on uint64); the
+    kernels read the same 8 bytes as uint64.  Plain torch on the device of `y`: it runs once per data set."""
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise ValueError(f"labels: expected an (N, C) multi-hot tensor, got {type(y).__name__} "
+                         f"{tuple(y.shape) if isinstance(y, torch.Tensor) else ''}")
+    N, C = y.shape
+    if C < 1:
+        raise ValueError("labels: at least one class")
+    if not bool(((y == 0) | (y == 1)).all()):
+        raise ValueError("labels: a multi-hot matrix holds only 0 and 1")
+    nw = label_words(C)
+    out = torch.empty((N, nw), dtype=torch.int64, device=y.device)
+    # bit 63 is the sign bit of the stored word: 1 << 63 wraps to the most negative int64, which is that bit pattern
+    shifts = torch.arange(64, dtype=torch.int64, device=y.device)
+    # in row chunks, so that the transient (rows, nw * 64) int64 image stays at about 32 MB per word whatever N is
+    for r0 in range(0, N, PACK_ROWS):
+        yc = y[r0:r0 + PACK_ROWS]
+        b = torch.zeros((yc.shape[0], nw * 64), dtype=torch.int64, device=y.device)
+        b[:, :C] = yc.to(torch.int64)
+        out[r0:r0 + PACK_ROWS] = b.view(-1, nw, 64).bitwise_left_shift_(shifts).sum(-1)
+    return out
+
+
+def unpack_label_bits(words, C: int):
+    """The (N, C) uint8 multi-hot matrix of packed label words (pack_label_bits)."""
+    N, nw = words.shape
+    shifts = torch.arange(64, dtype=torch.int64, device=words.device)
+    return ((words.view(N, nw, 1) >> shifts) & 1).view(N, nw * 64)[:, :C].to(torch.uint8)
+
+
+def classifier_multilabel(Z, Wc, bc, label_bits, mask, row_weight, backward=False, grad_out=None, live=None):
+    """models/gat.py:65-72 + models/base_gattn.py:50-59,71-94: the multi-label objective (han_classifier_multilabel).
+    Z (N,D); Wc (HC,D,C); bc (HC,C); label_bits int64 (N, ceil(C/64)) from pack_label_bits; mask uint8 (N,).
+    Returns logits (N,C), loss_acc (2,) [masked sigmoid cross-entropy, micro-F1], counts (3,) int64 [tp, fp, fn] and, if
+    backward, (dZ, dWc, dbc) [dWc, dbc written to the tensors of grad_out when given].  live: as classifier_loss --
+    only these rows are read and written, the sums and counts run over them; the fused shapes only."""
+    lib = _lib.load()
+    N, dev, HC, Dm, C = _classifier_args(Z, Wc, bc)
+    _chk(label_bits, "label_bits", (N, label_words(C)), dtype=torch.int64, device=dev)
+    _chk(mask, "mask", (N,), dtype=torch.uint8, device=dev)
+    logits = torch.empty((N, C), dtype=torch.float32, device=dev)
+    loss_acc = torch.empty((2,), dtype=torch.float32, device=dev)
+    counts = torch.empty((3,), dtype=torch.int64, device=dev)
+    grads = None
+    ptrs = (None, None, None)
+    if backward:
+        dZ = torch.empty((N, Dm), dtype=torch.float32, device=dev)
+        go = grad_out if grad_out is not None else (None, None)
+        dWc = _out(go[0], "dWc", tuple(Wc.shape), dev)
+        dbc = _out(go[1], "dbc", tuple(bc.shape), dev)
+        grads = (dZ, dWc, dbc)
+        ptrs = (dZ.data_ptr(), dWc.data_ptr(), dbc.data_ptr())
+    ws = _ws(lib.han_classifier_multilabel_workspace(N, Dm, C, HC), dev, "clsml")
+    live_ptr, n_live = None, 0
+    if live is not None:
+        if live.dim() != 1 or live.numel() > N:
+            raise ValueError(f"live: expected at most {N} node ids, got {tuple(live.shape)}")
+        _chk(live, "live", (live.numel(),), dtype=torch.int32, device=dev)
+        # an empty list still means "no row": the C ABI tells a list from "every row" by the pointer
+        live_ptr, n_live = (live.data_ptr() if live.numel() else ws.data_ptr()), live.numel()
+    _lib.check(lib.han_classifier_multilabel(
+        Z.data_ptr(), Wc.data_ptr(), bc.data_ptr(), label_bits.data_ptr(), mask.data_ptr(), float(row_weight),
+        logits.data_ptr(), loss_acc.data_ptr(), counts.data_ptr(), ptrs[0], ptrs[1], ptrs[2], ws.data_ptr(), ws.numel(),
+        live_ptr, n_live, N, Dm, C, HC, _stream()), "han_classifier_multilabel")
+    return logits, loss_acc, counts, grads
+
+
 def classifier_bwd(Z, Wc, bc, dlogits):
     """Backward of logits = (1/HC) sum_h (Z Wc[h] + bc[h]) (models/gat.py:65-72) for a given dlogits (N,C):
     returns (dZ, dWc, dbc)."""

@@ -188,6 +188,30 @@ def planted_partition(n: int, c: int, p_metapaths: int, f: int, deg_in: int, deg
                 test_mask=t(u >= 0.4, torch.uint8), n=n, f=f, c=c, p=p_metapaths, name="planted")
 
 
+def multilabel_labels(communities, n_labels: int, seed: int, flip: float = 0.05):
+    """Seeded multi-hot labels (N, n_labels) uint8 for a workload whose nodes carry a community id (`labels` of
+    planted_partition / make_workload): every community owns a seeded subset of the label planes -- about a third of
+    them, never none and never all when n_labels > 1 -- a node carries the planes of its community, and each entry is
+    then flipped with probability `flip`.  The planes are so correlated with the planted communities (a model that
+    finds the community finds the labels up to the flips) while a node still carries several labels at once, as the
+    IMDB genres and the PPI functions of the reference's data do.  On the device of `communities`."""
+    com = communities.detach().cpu().numpy().astype(np.int64)
+    if com.ndim != 1:
+        raise ValueError(f"communities: expected (N,) ids, got shape {com.shape}")
+    if n_labels < 1 or not 0.0 <= flip < 0.5:
+        raise ValueError("multilabel_labels: n_labels >= 1 and 0 <= flip < 0.5")
+    k = int(com.max()) + 1 if com.size else 1
+    rng = np.random.default_rng([int(seed), int(n_labels), 0x4D4C])
+    own = rng.random((k, n_labels)) < 1.0 / 3.0
+    for q in range(k):          # every community differs from "nothing" and from "everything"
+        if not own[q].any():
+            own[q, (q * 7 + 1) % n_labels] = True
+        if own[q].all() and n_labels > 1:
+            own[q, (q * 5) % n_labels] = False
+    y = own[com] ^ (rng.random((com.size, n_labels)) < flip)
+    return torch.as_tensor(y.astype(np.uint8), device=communities.device)
+
+
 CONFIGS = {
     # name: (N, P, F, C, per-meta-path graph spec)
     # the data sets' entry counts incl. self-loops (SURVEY.md section 8: PAP / PSP; APA / APCPA / APTPA), exactly

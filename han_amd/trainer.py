@@ -82,14 +82,51 @@ LIVE_BACKWARD_MIN_ROWS = 262144
 LIVE_FORWARD_MIN_ROWS = 262144
 
 
+OBJECTIVES = ("softmax", "sigmoid")
+
+
+def check_objective(objective, labels, n_classes: int, partitioned: bool = False):
+    """The constructor checks of HANTrainer / MiniBatchTrainer(objective=...); host-side, before anything is built."""
+    if objective not in OBJECTIVES:
+        raise ValueError(f"objective = {objective!r}: expected one of {OBJECTIVES}")
+    if objective != "sigmoid":
+        return
+    if partitioned:
+        raise NotImplementedError("objective='sigmoid' under a node partition is not supported: micro-F1 is not a sum "
+                                  "over ranks (its counts tp / fp / fn are, and are not exchanged yet)")
+    if labels.dim() != 2 or labels.shape[1] != n_classes:
+        raise ValueError(f"objective='sigmoid': labels must be an (N, {n_classes}) multi-hot matrix, got "
+                         f"{tuple(labels.shape)}")
+
+
+def metric_improved(value: float, best: float) -> bool:
+    """value >= best for the early-stopping rule of both trainers; a NaN value never is."""
+    return value == value and value >= best
+
+
+def device_labels(objective, labels, dev):
+    """The label tensor the classifier kernels read: (N,) int32 class ids, or the packed words of a multi-hot matrix."""
+    if objective == "sigmoid":
+        return ops.pack_label_bits(labels.to(dev)).contiguous()
+    return labels.to(device=dev, dtype=torch.int32).contiguous()
+
+
 class HANTrainer:
     def __init__(self, model: HeteGAT_multi, xs, graphs, labels, train_mask, val_mask=None,
                  lr=0.005, l2_coef=0.001, attn_drop=0.6, ffd_drop=0.6,
                  part: NodePartition | None = None, patience=100, max_halo_fraction=0.6,
                  use_graph=False, graphs_local=False, xs_full=None, replicate="auto", masked_backward=False,
                  side_stream=False, overlap_eval=False, live_backward="auto", live_forward="auto",
-                 shared_projection="auto"):
-        """xs: list of P (N_local,F) feature tensors (this rank's rows), or sparse features (SparseFeatures / torch
+                 shared_projection="auto", objective="softmax"):
+        """objective ("softmax" | "sigmoid"): "softmax" is the single-label step (labels (N,) class ids; the second
+        scalar of train_step / eval_step / epoch is the masked accuracy).  "sigmoid" is the reference's multi-label
+        pair, models/base_gattn.py:50-59,71-94: labels is an (N, C) multi-hot matrix, packed once
+        (ops.pack_label_bits), the loss is the masked sigmoid cross-entropy and the second scalar is micro-F1, on which
+        early_stopping, checkpoints and resume then work as they do on the accuracy (NaN -- no true positive yet --
+        never counts as an improvement).  Everything below or beside the classifier (live_forward, live_backward,
+        fold_k3, the captured epoch, overlap_eval) is unchanged.  Not under a node partition: micro-F1 is not a sum
+        over ranks (its counts are; exchanging them is left open), so that raises here.
+        xs: list of P (N_local,F) feature tensors (this rank's rows), or sparse features (SparseFeatures / torch
         sparse COO or CSR tensors; single process only);
         graphs: list of P CSRGraph (or dense masks / CSR tuples).  Under a partition (`part`) either
         the GLOBAL graphs (graphs_local=False: each rank keeps its row block; small data sets) or --
@@ -173,6 +210,8 @@ class HANTrainer:
         and, under a partition, only the live rows of the backward table travel.  Switches live_backward off."""
         if not model._built:
             raise RuntimeError("build the model first (model.build(...))")
+        self.objective = objective
+        check_objective(objective, labels, model.Wc.shape[2], part is not None and part.active)
         self.model = model
         model.direct_grads(True)      # gradients land in model.flat_grad without copy/accumulate launches
         model.fold_k3 = True          # M goes from node_level() straight into semantic(): the K3 backward runs the row-local K2 backward too
@@ -216,7 +255,7 @@ class HANTrainer:
             model.halo_plans = (None, None)
         if self.xs_full is not None and self._replicate_arg == "auto" and "HAN_REPLICATE" not in os.environ:
             self._calibrate_replication(ffd_drop)
-        self.labels = labels.to(device=dev, dtype=torch.int32).contiguous()
+        self.labels = device_labels(objective, labels, dev)
         self.train_mask = train_mask.to(device=dev, dtype=torch.uint8).contiguous()
         self._masked_plans = None
         if live_backward not in ("auto", True, False):
@@ -584,13 +623,16 @@ class HANTrainer:
 
     def early_stopping(self, val_loss: float, val_acc: float) -> bool:
         """ex_acm3025.py:225-240: checkpoint when val acc >= best AND val loss <= best;
-        stop after `patience` epochs without either improving.  Returns True to stop."""
-        if val_acc >= self.vacc_mx or val_loss <= self.vlss_mn:
-            if val_acc >= self.vacc_mx and val_loss <= self.vlss_mn:
+        stop after `patience` epochs without either improving.  Returns True to stop.
+        A NaN metric (micro-F1 of objective="sigmoid" while nothing is predicted correctly: tp == 0) is no improvement
+        and is never stored: max(nan, x) is nan, and every later comparison against a stored nan would be False."""
+        acc_ok = metric_improved(val_acc, self.vacc_mx)
+        if acc_ok or val_loss <= self.vlss_mn:
+            if acc_ok and val_loss <= self.vlss_mn:
                 # overlap_eval: the pair belongs to the parameters before the step that ran beside it
                 src = self._flat_prev if self.overlap_eval else self.model.flat
                 self.best_state = src.detach().clone()
-            self.vacc_mx = max(val_acc, self.vacc_mx)
+            self.vacc_mx = max(val_acc, self.vacc_mx) if acc_ok else self.vacc_mx
             self.vlss_mn = min(val_loss, self.vlss_mn)
             self.curr_step = 0
             return False

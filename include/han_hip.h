@@ -547,6 +547,36 @@ int han_classifier_loss_live(const float *Z, const float *Wc, const float *bc, c
                              float *dWc, float *dbc, void *workspace, size_t workspace_bytes, const int32_t *live,
                              int64_t n_live, int64_t N, int D, int C, int HC, void *stream);
 
+/* The multi-label objective (added under ABI 15: two new entry points, nothing existing changed): models/base_gattn.py:50-59,71-94 -- masked sigmoid cross-entropy and micro-F1 --
+ * on the logits of han_classifier_loss.  label_bits (N, ceil(C/64)) uint64: class c of a row is bit c % 64 of word
+ * c / 64 (8 B per row up to 64 classes).  Per row i with logits x, labels y in {0,1}^C, w_i = mask_i ? row_weight : 0:
+ *   loss      = sum_i w_i (1/C) sum_c [ max(x_c, 0) - x_c y_c + log(1 + exp(-|x_c|)) ]     (TF's stable form, then
+ *               reduce_mean(axis=1), then the mask weighting of :56-59)
+ *   dlogits   = (w_i / C) (sigma(x_c) - y_c), sigma from the same e = exp(-|x_c|): 1 / (1 + e) for x_c >= 0, e / (1 + e)
+ *               otherwise -- no overflow for any finite logit; rows outside the mask get exact zeros
+ *   predicted = (x_c > 0): round(sigmoid(x)) with half-to-even in exact arithmetic (sigma(0) = 1/2 rounds to 0); an fp32
+ *               sigmoid followed by round maps tiny positive logits to 0 -- a difference inside the logits' own
+ *               rounding error
+ *   tp, fp, fn  over the rows with mask_i != 0 and all classes, exact integers (accumulated as integers throughout);
+ *               micro_f1 = 2 tp / (2 tp + fp + fn) in double (algebraically :90-92), NaN when tp == 0 (the reference's 0/0)
+ * Writes logits (N,C), loss_acc[0] = loss, loss_acc[1] = micro_f1 (float), counts[3] = {tp, fp, fn} (int64), all on the
+ * device; with dZ != NULL also dZ (N,D), dWc (HC,D,C), dbc (HC,C).  Cross-block sums are slabs reduced in a fixed
+ * order: bitwise reproducible, no atomics.  D in {64,128} with C <= 64: fused single-launch kernels (16 lanes per row
+ * up to 16 classes, class-per-lane beyond); any other multiple of 64 / class count: head average -> row kernel ->
+ * Z^T dlogits over the masked rows.
+ * live (NULL: every row): n_live ascending int32 node ids, each below N, none twice -- the contract of
+ * han_classifier_loss_live: only the listed rows of Z, label_bits and mask are read, only the listed rows of logits
+ * and dZ are written, with the bits of the full call; the sums run over the list.  The fused shapes only.  n_live == 0
+ * launches no kernel and writes zeros (loss, counts, dWc, dbc) and NaN for micro_f1.
+ * HAN_E_BADARG: a null pointer, a negative size, n_live > N, dZ without dWc / dbc; HAN_E_UNSUPPORTED, before any launch:
+ * D % 64 != 0, or `live` outside the fused shapes; HAN_E_WORKSPACE: workspace_bytes below
+ * han_classifier_multilabel_workspace(N, D, C, HC).                                                               */
+size_t han_classifier_multilabel_workspace(int64_t N, int D, int C, int HC);
+int han_classifier_multilabel(const float *Z, const float *Wc, const float *bc, const uint64_t *label_bits,
+                              const uint8_t *mask, float row_weight, float *logits, float *loss_acc, int64_t *counts,
+                              float *dZ, float *dWc, float *dbc, void *workspace, size_t workspace_bytes,
+                              const int32_t *live, int64_t n_live, int64_t N, int D, int C, int HC, void *stream);
+
 /* The backward of the logits alone (HeteGAT_multi.inference returns logits; a caller
  * that forms its own loss hands back dlogits (N,C)):  dZ = dlogits @ mean_h(Wc[h])^T,
  * dWc[h] = Z^T dlogits / HC, dbc[h] = sum_n dlogits / HC.  Same shape rules.      */
