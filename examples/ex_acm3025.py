@@ -49,6 +49,10 @@ def main():
                     help="the reference's multi-label pair (masked sigmoid cross-entropy, micro-F1; "
                          "models/base_gattn.py:50-59,71-94) on the synthetic planted task: every node carries several "
                          "of 5 label planes (synth.multilabel_labels); reports micro-F1 per epoch and at the end")
+    ap.add_argument("--semantic", choices=("node", "metapath"), default="node",
+                    help="semantic attention: node = the softmax over the meta-paths per node (utils/layers.py:156); "
+                         "metapath = the published form, one weight per meta-path from the node means of the scores "
+                         "(han.pdf eq. 7-9): the P weights are printed with every reported epoch")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eval-device", choices=("cpu", "gpu"), default="cpu",
                     help="where final_embed is scored: cpu = scikit-learn on the host, as the reference; gpu = the "
@@ -100,7 +104,7 @@ def main():
     print(f"nodes {n}, features {ft}, classes {nb_classes}, meta-paths {len(graphs)}, "
           f"edges {[g.nnz for g in graphs]}")
 
-    model = HeteGAT_multi().build(len(graphs), ft, nb_classes, (8,), (8, 1), 128, device=dev)
+    model = HeteGAT_multi().build(len(graphs), ft, nb_classes, (8,), (8, 1), 128, device=dev, semantic=args.semantic)
     fanout = None
     if args.fanout is not None:
         if args.batch_size is None:
@@ -111,6 +115,8 @@ def main():
             ap.error(f"--fanout {args.fanout}: expected F or F,F,...")
         fanout = fanout[0] if len(fanout) == 1 else fanout
     if args.batch_size is not None:
+        if args.semantic == "metapath":
+            ap.error("--batch-size: a block's mean score is not the graph's, --semantic metapath needs the whole graph")
         if args.graph:
             ap.error("--batch-size: the block shapes change per batch, there is no epoch to capture (--graph)")
         tr = MiniBatchTrainer(model, xs, graphs, labels, masks[0], masks[1], batch_size=args.batch_size, lr=0.005,
@@ -128,6 +134,8 @@ def main():
             continue                         # that pair belongs to the initial parameters (ex_acm3025.py has no such line)
         if epoch % 10 == 0:
             print(f"epoch {epoch:4d}  train loss {tl:.5f} {metric} {ta:.5f} | val loss {vl:.5f} {metric} {va:.5f}")
+            if args.semantic == "metapath":      # the weights of the epoch's last forward (the validation one)
+                print("            meta-path weights:", [round(v, 5) for v in model.metapath_weights.tolist()])
         if tr.early_stopping(vl, va):
             print(f"early stop at epoch {epoch}: min val loss {tr.vlss_mn:.5f}, max val {metric} {tr.vacc_mx:.5f}")
             break
@@ -145,7 +153,8 @@ def main():
         tl, ta = tr.eval_step(masks[2].to(torch.uint8).contiguous(), w_test)
     print(f"test loss {float(tl):.5f}  test {'micro-F1' if args.multilabel else 'accuracy'} {float(ta):.5f}")
     with torch.no_grad():
-        _, final_embed, att = model.inference(xs, nb_classes, n, False, 0.0, 0.0, graphs, [8], [8, 1])
+        _, final_embed, att = model.inference(xs, nb_classes, n, False, 0.0, 0.0, graphs, [8], [8, 1],
+                                              semantic=args.semantic)
     print("mean meta-path attention:", att.mean(0).tolist())
     if args.eval_device == "gpu":
         sel = masks[2].bool()

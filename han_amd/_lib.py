@@ -14,8 +14,8 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_size_t, c_uint64, c_void
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libhan_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ("node_attn.hip", "project.hip", "project_sparse.hip", "sem_attn.hip", "loss_opt.hip", "metapath.hip", "evaluate.hip",
-           "ego_block.hip")
+SOURCES = ("node_attn.hip", "project.hip", "project_sparse.hip", "sem_attn.hip", "sem_attn_mean.hip", "loss_opt.hip", "metapath.hip",
+           "evaluate.hip", "ego_block.hip")
 # node_attn.hip: the dense K2 kernels (node_attn_dense.h) keep 8-16 fp32 MFMA accumulators in a rolled loop; with the
 # default AGPR form hipcc shuffles them through v_accvgpr_read / _mov / _write every iteration (each a wait for the
 # matrix pipe); the VGPR form of the MFMA destination has no such traffic
@@ -93,6 +93,9 @@ SIGNATURES = {
                                       c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "han_sem_attn_bwd_rows_live": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_size_t, P, I64, I64,
                                            c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "han_sem_attn_mean_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
+    "han_sem_attn_mean_fwd": (c_int, [P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, c_int, c_int, P]),
+    "han_sem_attn_mean_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_size_t, I64, c_int, c_int, c_int, c_int, P]),
     "han_classifier_workspace": (c_size_t, [I64, c_int, c_int, c_int]),
     "han_classifier_loss": (c_int, [P, P, P, P, P, c_float, P, P, P, P, P, P, c_size_t, I64,
                                     c_int, c_int, c_int, P]),

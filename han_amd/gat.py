@@ -106,6 +106,9 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
                                               # dW of meta-path p runs beside the backward gather of meta-path p + 1
         self.shared_proj = None               # layers.SharedProjection (HANTrainer(shared_projection=...)): the eval forward of an epoch
                                               # projects for the next training forward too
+        self.semantic_mode = "node"           # "node": the softmax over the meta-paths per node (utils/layers.py:156); "metapath": one weight per
+                                              # meta-path from the node means of the scores (han.pdf eq. 7-9); chosen by build(semantic=...)
+        self.metapath_weights = None          # semantic="metapath": beta (P,) of the last semantic() call, on the device
         self.fused_scores = "auto"            # "auto" | True | False: the backward gather of a K-head layer also sums da1, da2, db1, db2
                                               # (ops.node_attn_bwd_cols_scores) instead of a second pass over H; "auto": for CUDA tensors.
                                               # Where the library declines (small, masked or skewed graphs) the two calls run as before
@@ -129,10 +132,13 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
     # ------------------------------------------------------------------ params
     def build(self, n_metapaths, ft_size, nb_classes, hid_units=(8,), n_heads=(8, 1),
               mp_att_size=128, device=None, generator: torch.Generator | None = None,
-              table_dtype=torch.float32, residual=False):
+              table_dtype=torch.float32, residual=False, semantic="node"):
         """Create the variables the reference's first inference() call creates
         (SURVEY.md 8a): glorot-uniform conv1d/dense kernels, zero biases,
-        N(0, 0.1^2) semantic-attention variables."""
+        N(0, 0.1^2) semantic-attention variables.
+        semantic: "node" (utils/layers.py:156, the default) or "metapath" (han.pdf eq. 7-9: one weight per meta-path);
+        the variables are the same, the mode is part of state_dict() and of a trainer's checkpoints."""
+        self.semantic_mode = layers.check_semantic(semantic)
         if len(n_heads) != len(hid_units) + 1:
             raise ValueError("n_heads needs one entry per hidden layer plus the output entry "
                              "(ex_acm3025.py:27)")
@@ -222,11 +228,27 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         self._graph_cache.clear()
         return self
 
-    def load_state_dict(self, *args, **kw):
-        """nn.Module.load_state_dict; a stashed training projection (layers.SharedProjection) belongs to the old parameters."""
+    SEMANTIC_KEY = "semantic"      # state_dict() entry of a model that is not in "node" mode (a "node" state is as it always was)
+
+    def state_dict(self, *args, **kw):
+        """nn.Module.state_dict plus the semantic mode where it is not "node": a state is not silently evaluated in the
+        other mode."""
+        sd = super().state_dict(*args, **kw)
+        if self.semantic_mode != "node":
+            sd[kw.get("prefix", "") + self.SEMANTIC_KEY] = self.semantic_mode
+        return sd
+
+    def load_state_dict(self, state_dict, *args, **kw):
+        """nn.Module.load_state_dict; a stashed training projection (layers.SharedProjection) belongs to the old parameters.
+        The semantic mode the state was written in ("node" where it names none) must be this model's."""
+        state_dict = dict(state_dict)
+        mode = state_dict.pop(self.SEMANTIC_KEY, "node")
+        if mode != self.semantic_mode:
+            raise ValueError(f"state_dict was written with semantic={mode!r}, this model was built with "
+                             f"semantic={self.semantic_mode!r}")
         if self.shared_proj is not None:
             self.shared_proj.drop()
-        return super().load_state_dict(*args, **kw)
+        return super().load_state_dict(state_dict, *args, **kw)
 
     def param_shapes(self):
         return _param_shapes(self.P, self.F, self.K, self.FP, self.A, self.C, self.HC, self.extra,
@@ -288,9 +310,14 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         layers._no_sparse_under_partition(self.partition is not None or xs_full is not None, xs, xs_full)
         self._fold_handover = self._live_handover = None
         live_used = []
-        if self.extra or post is not None or self.partition is not None or coef_sink is not None or xs_full is not None:
+        row_local = self.semantic_mode == "node"      # "metapath": the mean needs every row of M, and dM has no zero rows
+        if self.partition is not None and not row_local:
+            raise NotImplementedError('semantic="metapath" under a node partition is not supported: the mean of a '
+                                      "meta-path's scores is a sum over ranks (two all-reduces of P doubles per step)")
+        if (self.extra or post is not None or self.partition is not None or coef_sink is not None or xs_full is not None
+                or not row_local):
             live_fwd = None
-        fold = [] if (self.fold_k3 and train and post is None) else None      # FoldTail of the LAST node-attention call
+        fold = [] if (self.fold_k3 and train and post is None and row_local) else None      # FoldTail of the LAST node-attention call
 
         def act(M, K, FP):
             if post is None:
@@ -314,8 +341,8 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
                 seed_dev=self.step_seed_dev if train else None, act=act_code, part=self.partition, graphs_t=graphs_t,
                 layer=layer, table_dtype=self.table_dtype, plans_f=self.halo_plans[0], plans_b=self.halo_plans[1],
                 xs_full=xs_full if first else None, masked_bwd=self.masked_bwd if (first and train) else None,
-                zero_rows=bool(self.zero_rows and first and train and not self.extra),
-                live_bwd=self.live_bwd if (first and train and not self.extra and self.masked_bwd is None) else None,
+                zero_rows=bool(self.zero_rows and first and train and not self.extra and row_local),
+                live_bwd=self.live_bwd if (first and train and not self.extra and self.masked_bwd is None and row_local) else None,
                 streams=self.path_streams, side_stream=self.side_stream, path_order=self.path_order,
                 overlap=self.overlap_branch if (first and train) else None,
                 shared_proj=self.shared_proj if (first and not self.extra) else None,
@@ -385,6 +412,10 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         h, self._fold_handover = self._fold_handover, None
         tail = h[1] if (h is not None and h[0] is M) else None      # M itself, straight from node_level()
         lv, self._live_handover = self._live_handover, None
+        if self.semantic_mode == "metapath":      # (node_level() hands over neither a FoldTail nor a row list in this mode)
+            Z, att = layers.semantic_attention(M, self.w_omega, self.b_omega, self.u_omega, mode="metapath")
+            self.metapath_weights = att.detach()[0] if att.shape[0] else None      # (P,) device floats of the last call; a captured epoch rewrites them in place
+            return Z, att
         if lv is None:
             return layers.semantic_attention(M, self.w_omega, self.b_omega, self.u_omega, tail=tail)
         # M holds only the plan's rows: K3 runs over the same list and writes only those rows of Z and att
@@ -419,20 +450,23 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
     @_ClassOrInstance
     def inference(self, inputs_list, nb_classes, nb_nodes, training, attn_drop, ffd_drop,
                   bias_mat_list, hid_units, n_heads, activation=F_torch.elu, residual=False,
-                  mp_att_size=128):
+                  mp_att_size=128, semantic="node"):
         return self._inference(inputs_list, nb_classes, nb_nodes, training, attn_drop, ffd_drop,
-                               bias_mat_list, hid_units, n_heads, activation, residual, mp_att_size)
+                               bias_mat_list, hid_units, n_heads, activation, residual, mp_att_size, semantic=semantic)
 
     def _inference(self, inputs_list, nb_classes, nb_nodes, training, attn_drop, ffd_drop,
                    bias_mat_list, hid_units, n_heads, activation=F_torch.elu, residual=False,
-                   mp_att_size=128, coef_sink=None):
-        """Same positional arguments as models/gat.py:35-37.  `inputs_list[p]`:
+                   mp_att_size=128, coef_sink=None, semantic="node"):
+        """Same positional arguments as models/gat.py:35-37; `semantic` as in build().  `inputs_list[p]`:
         (1,N,F) or (N,F) fp32 GPU tensor, or sparse features (a SparseFeatures, or a torch sparse COO / CSR
         tensor (N,F) / (1,N,F), converted once per tensor) -- dense and sparse may be mixed; `bias_mat_list[p]`: (1,N,N) additive
         mask, CSRGraph or (rowptr, colidx).  Lists are zipped, shorter wins
         (gat.py:39).  `training` and `nb_nodes` are accepted and ignored, as in
         the reference; dropout is driven by attn_drop / ffd_drop alone.
         Returns (logits (1,N,C), final_embed (N,K*F'), att_val (N,P))."""
+        if layers.check_semantic(semantic) != self.semantic_mode and self._built:
+            raise ValueError(f"semantic={semantic!r} does not match the model, which was built with "
+                             f"semantic={self.semantic_mode!r}")
         n = min(len(inputs_list), len(bias_mat_list))
         xs = [layers._squeeze_batch(x, f"inputs_list[{i}]") for i, x in enumerate(inputs_list[:n])]
         for x in xs:
@@ -441,7 +475,7 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
         dev = xs[0].device
         if not self._built:
             self.build(n, xs[0].shape[1], nb_classes, hid_units, n_heads, mp_att_size, device=dev,
-                       residual=residual)
+                       residual=residual, semantic=semantic)
         if bool(residual) != self.residual:
             raise ValueError("residual does not match the variables created by the first call")
         if n != self.P or xs[0].shape[1] != self.F or nb_classes != self.C:
@@ -468,7 +502,8 @@ class HeteGAT_multi(BaseGAttN, torch.nn.Module):
             raise RuntimeError("call build(...) or inference(...) first")
         return self.inference(inputs_list, self.C, None, None, attn_drop, ffd_drop, bias_mat_list,
                               [self.FP] + [e[1] for e in self.extra],
-                              [self.K] + [e[0] for e in self.extra] + [self.HC], mp_att_size=self.A)
+                              [self.K] + [e[0] for e in self.extra] + [self.HC], mp_att_size=self.A,
+                              semantic=self.semantic_mode)
 
 
 class HeteGAT(HeteGAT_multi):
@@ -480,7 +515,7 @@ class HeteGAT(HeteGAT_multi):
     @_ClassOrInstance
     def inference(self, inputs, nb_classes, nb_nodes, training, attn_drop, ffd_drop,
                   bias_mat_list, hid_units, n_heads, activation=F_torch.elu, residual=False,
-                  mp_att_size=128, return_coef=False):
+                  mp_att_size=128, return_coef=False, semantic="node"):
         """Returns (logits, final_embed, att_val[, coef_list]).  coef_list[p] (gat.py:170-172):
         the first layer's coefficients averaged over its heads, as a torch sparse CSR
         tensor (N,N) over the stored neighbours of meta-path p (the reference's dense
@@ -488,7 +523,7 @@ class HeteGAT(HeteGAT_multi):
         sink = [] if return_coef else None
         out = self._inference([inputs] * len(bias_mat_list), nb_classes, nb_nodes, training, attn_drop,
                               ffd_drop, bias_mat_list, hid_units, n_heads, activation, residual,
-                              mp_att_size, coef_sink=sink)
+                              mp_att_size, coef_sink=sink, semantic=semantic)
         return out + (sink,) if return_coef else out
 
 
@@ -502,7 +537,7 @@ class HeteGAT_no_coef(HeteGAT):
     @_ClassOrInstance
     def inference(self, inputs, nb_classes, nb_nodes, training, attn_drop, ffd_drop,
                   bias_mat_list, hid_units, n_heads, activation=F_torch.elu, residual=False,
-                  mp_att_size=128):
+                  mp_att_size=128, semantic="node"):
         return self._inference([inputs] * len(bias_mat_list), nb_classes, nb_nodes, training, attn_drop,
                                ffd_drop, bias_mat_list, hid_units, n_heads, activation, residual,
-                               mp_att_size)
+                               mp_att_size, semantic=semantic)

@@ -883,6 +883,33 @@ class SemanticAttention(torch.autograd.Function):
         return (dM, dw, db, du) + none
 
 
+class SemanticAttentionMean(torch.autograd.Function):
+    """K3 as published (han.pdf eq. 7-9): M (N,P,D) -> (Z (N,D), beta (P,)), one weight per meta-path from the node
+    means of the scores.  Every row of dM depends on every row of dZ, so nothing row-local (FoldTail, row lists)
+    applies here."""
+
+    @staticmethod
+    def forward(ctx, M, w_omega, b_omega, u_omega):
+        M = M.contiguous()
+        Z, beta = ops.sem_attn_mean_fwd(M, w_omega, b_omega, u_omega)
+        ctx.set_materialize_grads(False)
+        plist = (w_omega, b_omega, u_omega)
+        ctx.direct = tuple(p.grad for p in plist) if all(_direct(p) for p in plist) else None
+        ctx.save_for_backward(M, w_omega, b_omega, u_omega, beta)
+        ctx.mark_non_differentiable(beta)
+        return Z, beta
+
+    @staticmethod
+    def backward(ctx, dZ, _dbeta):
+        M, w, b, u, beta = ctx.saved_tensors
+        if dZ is None:
+            dZ = torch.zeros((M.shape[0], M.shape[2]), dtype=M.dtype, device=M.device)
+        dM, dw, db, du = ops.sem_attn_mean_bwd(M, w, b, u, beta, dZ.contiguous(), out=ctx.direct)
+        if ctx.direct is not None:
+            return dM, None, None, None
+        return dM, dw, db, du
+
+
 class ClassifierLoss(torch.autograd.Function):
     """Fused classifier + masked softmax-CE (+ accuracy).
     models/gat.py:65-72, models/base_gattn.py:41-48,61-69.
@@ -1019,12 +1046,48 @@ def _pad_to(n: int) -> int:
     return 64 * ((n + 63) // 64)
 
 
-def semantic_attention(M, w_omega, b_omega, u_omega, tail=None, live=None):
+SEMANTIC_MODES = ("node", "metapath")
+
+
+def check_semantic(mode):
+    if mode not in SEMANTIC_MODES:
+        raise ValueError(f"semantic: expected one of {SEMANTIC_MODES}, got {mode!r}")
+    return mode
+
+
+def _semantic_attention_mean(M, w_omega, b_omega, u_omega):
+    """mode="metapath" of semantic_attention: han.pdf eq. 7-9 on the kernels of sem_attn_mean.hip.  The zero-padding is
+    exact here too (a padded column adds tanh(.) * 0 to every score, hence 0 to every mean)."""
+    d, a = M.shape[2], w_omega.shape[1]
+    dm, am = _pad_to(d), _pad_to(a)
+    if dm not in ops.SEM_MEAN_D or am not in ops.SEM_MEAN_A or not 1 <= M.shape[1] <= ops.SEM_MEAN_MAX_P:
+        raise NotImplementedError(
+            f'semantic="metapath": D = {d}, A = {a}, P = {M.shape[1]} is outside the kernels\' shapes: D (padded to a '
+            f"multiple of 64) in {ops.SEM_MEAN_D}, A (padded) in {ops.SEM_MEAN_A}, 1 <= P <= {ops.SEM_MEAN_MAX_P}")
+    if dm == d and am == a:
+        Z, beta = SemanticAttentionMean.apply(M.contiguous(), w_omega, b_omega, u_omega)
+    else:
+        Z, beta = SemanticAttentionMean.apply(
+            torch.nn.functional.pad(M, (0, dm - d)), torch.nn.functional.pad(w_omega, (0, am - a, 0, dm - d)),
+            torch.nn.functional.pad(b_omega, (0, am - a)), torch.nn.functional.pad(u_omega, (0, am - a)))
+        Z = Z[:, :d]
+    return Z, beta.expand(M.shape[0], -1)      # (N,P), stride 0 over the P device floats: every node's row is beta
+
+
+def semantic_attention(M, w_omega, b_omega, u_omega, tail=None, live=None, mode="node"):
     """utils/layers.py:152-159 for any embedding width D and attention size A, always on the K3 kernels.
     Widths that are not multiples of 64 are zero-padded -- padded columns of w_omega / u_omega contribute
     tanh(.) * 0 = 0 to the scores and padded embedding columns are 0 -- which is exact.  D in {64, 128} with
     A <= 256 run the tuned kernels; anything wider (a last layer of 8 heads x 32, hid_units = [128],
-    mp_att_size = 512, ...) the run-time-width kernels of sem_attn.hip (round 3: no torch branch is left)."""
+    mp_att_size = 512, ...) the run-time-width kernels of sem_attn.hip (round 3: no torch branch is left).
+    mode="metapath": the published form, one weight per meta-path (han.pdf eq. 7-9) -- the softmax is taken once, over the
+    node means of the scores; the returned attention is that (P,) vector expanded to (N,P).  It needs every row of M,
+    so it takes neither a FoldTail nor a row list."""
+    if check_semantic(mode) == "metapath":
+        if tail is not None or live is not None:
+            raise ValueError('semantic="metapath" is not row-local: the mean runs over every node, and every row of dM '
+                             "depends on every row of dZ; it takes no FoldTail and no row list")
+        return _semantic_attention_mean(M, w_omega, b_omega, u_omega)
     d, a = M.shape[2], w_omega.shape[1]
     dm, am = _pad_to(d), _pad_to(a)
     if dm == d and am == a:      # tail: M is the output of the NodeLevelAttention call that made it (FoldTail); padded, it is not
@@ -1189,10 +1252,10 @@ def sp_attn_head(seq, out_sz, adj_mat, activation, nb_nodes, in_drop=0.0, coef_d
                         seed)
 
 
-def SimpleAttLayer(inputs, attention_size, time_major=False, return_alphas=False, *, params):
+def SimpleAttLayer(inputs, attention_size, time_major=False, return_alphas=False, *, params, semantic="node"):
     """utils/layers.py:132-164.  inputs (N,P,D) [or (P,N,D) if time_major, or a
     tuple to be concatenated on the last axis]; params: w_omega (D,A),
-    b_omega (A,), u_omega (A,)."""
+    b_omega (A,), u_omega (A,).  semantic="metapath": one weight per meta-path (han.pdf eq. 7-9)."""
     if isinstance(inputs, tuple):
         inputs = torch.cat(inputs, 2)                    # :134-136
     if time_major:
@@ -1200,7 +1263,7 @@ def SimpleAttLayer(inputs, attention_size, time_major=False, return_alphas=False
     if params["w_omega"].shape != (inputs.shape[2], attention_size):
         raise ValueError("w_omega must be (hidden_size, attention_size)")
     out, alphas = semantic_attention(inputs.contiguous(), params["w_omega"], params["b_omega"],
-                                     params["u_omega"])
+                                     params["u_omega"], mode=semantic)
     if not return_alphas:
         return out
     return out, alphas

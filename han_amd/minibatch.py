@@ -219,6 +219,9 @@ def _inputs(model, xs, graphs):
         raise RuntimeError("build the model first (model.build(...))")
     if model.partition is not None:
         raise NotImplementedError("ego blocks under a node partition are not supported")
+    if model.semantic_mode == "metapath":
+        raise ValueError('semantic="metapath": the weight of a meta-path is the mean of its scores over every node of the '
+                         "graph; the mean over an ego block is another number, so blocks cannot answer for the full graph")
     dev = model.flat.device
     xs = [layers._squeeze_batch(x, f"xs[{i}]") for i, x in enumerate(xs)]
     xs = [x if isinstance(x, SparseFeatures) else x.contiguous() for x in xs]

@@ -900,6 +900,67 @@ def sem_attn_bwd(M, w_omega, b_omega, u_omega, beta, dZ, out=None, flags=0):
     return dM, dw, db, du
 
 
+SEM_MEAN_GRID_CAP = 1024        # most blocks of any kernel of sem_attn_mean.hip (kMeanStreamBlocks)
+SEM_MEAN_ROWS_PER_BLOCK = 64    # rows of M per block iteration (ROWS there); the combine kernel takes 16 or 8 NODES
+SEM_MEAN_D = (64, 128)          # shapes of han_sem_attn_mean_fwd / _bwd (after zero-padding to multiples of 64)
+SEM_MEAN_A = (64, 128, 192, 256)
+SEM_MEAN_MAX_P = 64
+
+
+def _sem_mean_args(M, w_omega, b_omega, u_omega):
+    _chk(M, "M")
+    if M.dim() != 3 or M.shape[2] % 64 != 0 or M.shape[2] == 0:
+        raise ValueError(f"M: expected (N,P,D) with D a multiple of 64, got {tuple(M.shape)}")
+    N, P, Dm = M.shape
+    dev = M.device
+    if w_omega.dim() != 2:
+        raise ValueError(f"w_omega: expected (D,A), got {tuple(w_omega.shape)}")
+    A = w_omega.shape[1]
+    _chk(w_omega, "w_omega", (Dm, A), device=dev)
+    _chk(b_omega, "b_omega", (A,), device=dev)
+    _chk(u_omega, "u_omega", (A,), device=dev)
+    return N, P, Dm, A, dev
+
+
+def sem_attn_mean_fwd(M, w_omega, b_omega, u_omega, flags=0, out=None, want_mean=False):
+    """han.pdf eq. 7-9: one weight per meta-path.  M (N,P,D) -> Z (N,D), beta (P,) [, the node means of the scores
+    (P,) float64].  out = (Z, beta) destinations.  D in SEM_MEAN_D, A in SEM_MEAN_A, P <= SEM_MEAN_MAX_P."""
+    lib = _lib.load()
+    N, P, Dm, A, dev = _sem_mean_args(M, w_omega, b_omega, u_omega)
+    Z = _out(None if out is None else out[0], "Z", (N, Dm), dev)
+    beta = _out(None if out is None else out[1], "beta", (P,), dev)
+    wmean = torch.empty((P,), dtype=torch.float64, device=dev) if want_mean else None
+    ws = _ws(lib.han_sem_attn_mean_workspace(N, P, Dm, A), dev, "semmean")
+    _lib.check(lib.han_sem_attn_mean_fwd(
+        M.data_ptr(), w_omega.data_ptr(), b_omega.data_ptr(), u_omega.data_ptr(), Z.data_ptr(), beta.data_ptr(),
+        None if wmean is None else wmean.data_ptr(), ws.data_ptr(), ws.numel(), N, P, Dm, A, int(flags), _stream()),
+        "han_sem_attn_mean_fwd")
+    return (Z, beta, wmean) if want_mean else (Z, beta)
+
+
+def sem_attn_mean_bwd(M, w_omega, b_omega, u_omega, beta, dZ, out=None, flags=0):
+    """dM, dw, db, du of sem_attn_mean_fwd [the last three written to the tensors of `out` when given]."""
+    lib = _lib.load()
+    N, P, Dm, A, dev = _sem_mean_args(M, w_omega, b_omega, u_omega)
+    _chk(beta, "beta", (P,), device=dev)
+    _chk(dZ, "dZ", (N, Dm), device=dev)
+    dM = torch.empty_like(M)
+    o = out if out is not None else (None,) * 3
+    dw = _out(o[0], "dw", tuple(w_omega.shape), dev)
+    db = _out(o[1], "db", tuple(b_omega.shape), dev)
+    du = _out(o[2], "du", tuple(u_omega.shape), dev)
+    if N == 0:      # the entry launches nothing
+        for g in (dw, db, du):
+            g.zero_()
+        return dM, dw, db, du
+    ws = _ws(lib.han_sem_attn_mean_workspace(N, P, Dm, A), dev, "semmean")
+    _lib.check(lib.han_sem_attn_mean_bwd(
+        M.data_ptr(), w_omega.data_ptr(), b_omega.data_ptr(), u_omega.data_ptr(), beta.data_ptr(),
+        dZ.data_ptr(), dM.data_ptr(), dw.data_ptr(), db.data_ptr(), du.data_ptr(), ws.data_ptr(),
+        ws.numel(), N, P, Dm, A, int(flags), _stream()), "han_sem_attn_mean_bwd")
+    return dM, dw, db, du
+
+
 def sem_attn_bwd_rows(M, w_omega, b_omega, u_omega, beta, dZ, paths, c, dc, activation=ACT_ELU, K=8, FP=8,
                       table_dtype=torch.float32, out=None, flags=0, gs_out=None, df1_out=None, live=None):
     """sem_attn_bwd with node_attn_bwd_rows of every meta-path in its epilogue, for an M (N,P,D) that is the K2 output

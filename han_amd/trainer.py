@@ -207,7 +207,11 @@ class HANTrainer:
         calls.
         masked_backward: OPT-IN (never the default, never the headline measurement): the transposed-graph pass keeps
         the dead entries in place and skips them one by one (bit-identical results, dist.MaskedBackwardPlan)
-        and, under a partition, only the live rows of the backward table travel.  Switches live_backward off."""
+        and, under a partition, only the live rows of the backward table travel.  Switches live_backward off.
+        A model built with semantic="metapath" (one weight per meta-path, han.pdf eq. 7-9) is not row-local: live_forward
+        and live_backward "auto" resolve to off and True raises ValueError, masked_backward=True raises ValueError, a
+        node partition raises NotImplementedError, fold_k3 has no effect; shared_projection, side_stream, use_graph and
+        overlap_eval work as in the node mode."""
         if not model._built:
             raise RuntimeError("build the model first (model.build(...))")
         self.objective = objective
@@ -216,6 +220,21 @@ class HANTrainer:
         model.direct_grads(True)      # gradients land in model.flat_grad without copy/accumulate launches
         model.fold_k3 = True          # M goes from node_level() straight into semantic(): the K3 backward runs the row-local K2 backward too
         self.part = part if (part is not None and part.active) else None
+        # semantic="metapath" (han.pdf eq. 7-9): the mean of a meta-path's scores runs over EVERY node and dM has no zero
+        # rows, so nothing that relies on row-locality applies -- "auto" resolves to off, an explicit request raises
+        metapath = model.semantic_mode == "metapath"
+        if metapath:
+            why = ('semantic="metapath": the weight of a meta-path is the mean of its scores over every node, and every '
+                   "row of dM depends on every row of dZ; ")
+            if self.part is not None:
+                raise NotImplementedError(why + "under a node partition the mean is a sum over ranks (two all-reduces of "
+                                          "P doubles per step), which is not built")
+            if live_forward is True or live_backward is True:
+                raise ValueError(why + "live_forward / live_backward visit only the rows of a mask")
+            if masked_backward:
+                raise ValueError(why + "masked_backward drops the rows outside the train mask")
+            live_forward = False if live_forward == "auto" else live_forward
+            live_backward = False if live_backward == "auto" else live_backward
         layers._no_sparse_under_partition(self.part is not None or xs_full is not None, xs, xs_full)
         model.partition = self.part
         dev = model.flat.device
@@ -398,6 +417,9 @@ class HANTrainer:
 
     def set_masked_backward(self, flag: bool):
         """Switch the opt-in masked backward on or off (plans are built on first use; collective under a partition)."""
+        if flag and self.model.semantic_mode == "metapath":
+            raise ValueError('semantic="metapath": every row of dM depends on every row of dZ; masked_backward drops the '
+                             "rows outside the train mask")
         self.masked_backward = bool(flag)
         self.model.live_bwd = None if self.masked_backward else self._live_plan      # the masked backward wins
         if not self.masked_backward:
@@ -641,8 +663,11 @@ class HANTrainer:
 
     def _signature(self):
         m = self.model
-        return {"param_shapes": [(n, list(s)) for n, s in m.param_shapes()], "residual": bool(m.residual),
-                "table_dtype": str(m.table_dtype), "use_graph": self.use_graph}
+        sig = {"param_shapes": [(n, list(s)) for n, s in m.param_shapes()], "residual": bool(m.residual),
+               "table_dtype": str(m.table_dtype), "use_graph": self.use_graph}
+        if m.semantic_mode != "node":      # a "node" signature is as it always was: earlier checkpoints still load
+            sig["semantic"] = m.semantic_mode
+        return sig
 
     def save_checkpoint(self, path):
         """saver.save(sess, checkpt_file) (ex_acm3025.py:229) -- plus what the reference does not keep

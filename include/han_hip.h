@@ -469,6 +469,35 @@ int han_sem_attn_bwd(const float *M, const float *w_omega, const float *b_omega,
                      float *dw_omega, float *db_omega, float *du_omega, void *workspace,
                      size_t workspace_bytes, int64_t N, int P, int D, int A, int flags, void *stream);
 
+/* ---- K3 as published: one weight per meta-path (added under ABI 15: three new entry points, nothing existing
+ * changed) ----
+ * han.pdf sec. 4.2, eq. 7-9: s_ip = u . tanh(W^T M_ip + b); w_p = (1/N) sum_i s_ip; beta = softmax over P of w;
+ * Z_i = sum_p beta_p M_ip.  The difference from utils/layers.py:156 (han_sem_attn_fwd): the softmax is taken ONCE, over
+ * the node means of the scores, not per node -- beta is P floats shared by every node, and wmean (may be null) receives
+ * the P means in double.  M (N,P,D); Womega (D,A); bomega, uomega (A); Z (N,D).
+ * Shapes: D in {64, 128}, A in {64, 128, 192, 256}, 1 <= P <= 64, any N >= 1; anything else HAN_E_UNSUPPORTED before any
+ * launch (zero-pad narrower D / A to a multiple of 64: exact).  HAN_E_BADARG: a null pointer other than wmean, a
+ * workspace not 8-byte aligned, N < 0, P <= 0; HAN_E_WORKSPACE: workspace_bytes below
+ * han_sem_attn_mean_workspace(N, P, D, A), which serves both entries.  N == 0 returns 0 with nothing launched.  Neither
+ * entry allocates or synchronises; no value travels through the host; results are bit-identical from run to run.
+ * `flags` is reserved (pass 0).                                                                                    */
+size_t han_sem_attn_mean_workspace(int64_t N, int P, int D, int A);
+int han_sem_attn_mean_fwd(const float *M, const float *w_omega, const float *b_omega, const float *u_omega,
+                          float *Z, float *beta /* P floats */, double *wmean /* P doubles, may be null */,
+                          void *workspace, size_t workspace_bytes, int64_t N, int P, int D, int A, int flags,
+                          void *stream);
+
+/* Backward of han_sem_attn_mean_fwd (han.pdf eq. 7-9; unlike utils/layers.py:156 every row of dM depends on every row of
+ * dZ, through the P scalars d w_p): dZ (N,D) -> dM (N,P,D), dWomega (D,A), dbomega (A), duomega (A).
+ *   dbeta_p = sum_i <dZ_i, M_ip>;  dw_p = beta_p (dbeta_p - sum_q beta_q dbeta_q);  ds_ip = dw_p / N;
+ *   dpre_ip = ds_ip u (1 - v_ip^2);  dM_ip = beta_p dZ_i + W dpre_ip;  dW = sum M_ip (x) dpre_ip; db = sum dpre_ip;
+ *   du = sum ds_ip v_ip.
+ * beta (P floats) is the forward's output.  Shapes, return codes and workspace as for the forward.                  */
+int han_sem_attn_mean_bwd(const float *M, const float *w_omega, const float *b_omega, const float *u_omega,
+                          const float *beta /* P floats */, const float *dZ, float *dM, float *dw_omega,
+                          float *db_omega, float *du_omega, void *workspace, size_t workspace_bytes, int64_t N, int P,
+                          int D, int A, int flags, void *stream);
+
 /* han_sem_attn_bwd with the row-local step of the K2 backward (han_node_attn_bwd_rows) of all P meta-paths in its
  * epilogue, for an M that is the K2 output itself: row (n, p) of M is the output row n of meta-path p's
  * han_node_attn_fwd, and nothing else consumes M.  dM is not written.  aggp, tsum, f1, lse, gs and df1 are HOST
